@@ -8,13 +8,18 @@ primary detector + start-peak scan + boundary validation, minibatches of 1000 re
 over one HBM-resident batch of --reads reads per GPU (default 96 000: sized for the 288 GB HBM); inputs are generated on the device
 before the timed region (bit-identical host twin: adapted_amd/synth.py).
 
-    python bench.py --gpus 1 --steps 8 --warmup 1
+    python bench.py --gpus 1 --steps 8 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 8 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 N > 1: one process per GPU, each owns a contiguous block of whole minibatches (weak scaling,
 no data-path collective); the fixed-width result rows are gathered to rank 0 over RCCL at the
 end of every step (inside the timed region).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps (with the per-kernel HIP events behind `kernel_ms` and `roofline`) and prints
+the line; --dump-outputs DIR also writes the last step's rows as .npy files.  --full adds what the headline does not need:
+the CPU baselines, the secondary workloads, the PCIe-inclusive host-pipeline runs and the per-workload kernel times file.
 """
 from __future__ import annotations
 
@@ -42,6 +47,48 @@ def make_spc(max_obs_trace: int, primary: str = "llr"):
     spc.update_primary_method()
     spc.update_sig_preload_size()
     return spc
+
+
+DUMP_BUDGET = 63 * 1000 * 1000  # bytes of array data --dump-outputs may write (under 64 MB in all with the .npy headers)
+
+
+def dump_outputs(rows, primary: str, ddir: str, seed: int = 0):
+    """--dump-outputs: the rows the timed path delivered in its last step as DIR/<name>.npy, float64 throughout (every integer
+    field is below 2**53) and every value finite: read_index, one file per result column, success, fail_code, mvs_fail_mask,
+    start_peak_type, n_cand, n_open_pores, present (bit i: the row carries column i), nonfinite (bit i: column i is carried
+    but not finite), polya_candidates and open_pores ([n, 16], -1 past n_cand / n_open_pores).  A column the row does not
+    carry reads 0; a carried value that is not finite reads 0 for NaN, +1 / -1 for +inf / -inf, with its nonfinite bit set.
+    open_pores_more (an arena offset handed out in any order) and the reserved word are left out.  More rows than the budget
+    holds: a fixed, seeded sample of them, in read order."""
+    from adapted_amd import lib
+
+    n = rows.shape[0]
+    per_row = 8 * (1 + lib.NCOL + 8 + lib.MAX_CAND + lib.MAX_OPEN_PORES)
+    keep = min(n, DUMP_BUDGET // per_row)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    r = rows[idx]
+    os.makedirs(ddir, exist_ok=True)
+    out = {"read_index": idx.astype(np.float64)}
+    present = r["present"]
+    nonfinite = np.zeros(len(idx), dtype=np.uint64)
+    for i, name in enumerate(lib.COLS):
+        v = r["col"][:, i].astype(np.float64)
+        carried = (present >> np.uint64(i)) & np.uint64(1) == 1
+        bad = carried & ~np.isfinite(v)
+        nonfinite |= bad.astype(np.uint64) << np.uint64(i)
+        v[bad] = np.nan_to_num(v[bad], nan=0.0, posinf=1.0, neginf=-1.0)
+        v[~carried] = 0.0
+        out[name.format(primary=primary)] = v
+    for name in ("success", "fail_code", "mvs_fail_mask", "start_peak_type", "n_cand", "n_open_pores", "present"):
+        out[name] = r[name].astype(np.float64)
+    out["nonfinite"] = nonfinite.astype(np.float64)
+    for name, field, count in (("polya_candidates", "cand", "n_cand"), ("open_pores", "open_pores", "n_open_pores")):
+        v = r[field].astype(np.float64)
+        v[np.arange(v.shape[1])[None, :] >= r[count][:, None]] = -1.0
+        out[name] = v
+    for name, v in out.items():
+        np.save(os.path.join(ddir, name + ".npy"), v)
+    return len(idx)
 
 
 # ---------------------------------------------------------------------------------------------- CPU baseline (the checker, timed)
@@ -597,7 +644,11 @@ def run_workload(w, rank, world, local, dist, backend, cpu_pool=None, cpu_procs=
                                       "mad_not_predicted": int(c[3]), "mad_bracket_overflow": int(c[4]),
                                       "n1_fused_minibatches": int(c[5]), "n1_fused_fallbacks": int(c[6]) + int(c[7]),
                                       "n1_heavy_keys": int(c[22]), "n1_heavy_samples": int(c[23])}
-        if world == 1 and not multi and w.cpu_sample > 0 and w.primary == "llr" and w.lens == "full" and w.adc_step == 0 and raw_t is None:
+        if w.dump_outputs:  # (several ranks: every rank's block, as the gather delivered it)
+            drows = np.concatenate([g.cpu().numpy().reshape(-1) for g in gathered]).view(lib.ROW_DTYPE) if multi else rows
+            dump_outputs(drows, w.primary, w.dump_outputs, seed=w.seed)
+            del drows
+        if w.full and world == 1 and not multi and w.cpu_sample > 0 and w.primary == "llr" and w.lens == "full" and w.adc_step == 0 and raw_t is None:
             n_s = min(w.cpu_sample, R)
             n_all = min(w.cpu_sample_all, R // max(cpu_procs, 1)) if cpu_procs > 1 else 0
             out["cpu_baseline"] = cpu_baseline(eng, spc, sig_t.data_ptr(), n_s, m, rows, lens_host, cpu_pool, cpu_procs if n_all > 0 else 0,
@@ -689,7 +740,19 @@ def main():
     ap.add_argument("--fill-threads", type=int, default=1, help="with --host-pipeline: host threads copying a slot's reads (the stand-in reader)")
     ap.add_argument("--int16", action="store_true", help="the resident workload as RAW int16 ADC samples + per-read calibration (every kernel reads them "
                                                          "natively: adp_detect_llr_i16); with --host-pipeline: stream raw int16 samples from host memory")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baselines (--cpu-sample, --cpu-sample-all, --cpu-procs), the secondary "
+                         "workloads and the PCIe-inclusive host-pipeline runs (--no-secondary, --with-grouped) and the per-workload kernel "
+                         "times file; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows of the last step as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.host_pipeline > 0:
+        ap.error("--dump-outputs writes the resident workload's rows; --host-pipeline has none to write")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     world_env = int(os.environ.get("WORLD_SIZE", "0"))
     if args.gpus > 1 and world_env == 0:  # no launcher around us: be the launcher (before anything touches the GPU)
@@ -706,7 +769,7 @@ def main():
 
     # the all-cores CPU baseline runs in worker processes: start them before this process initialises the GPU
     cpu_pool, cpu_procs = None, 0
-    if world == 1 and args.cpu_sample > 0 and args.cpu_sample_all > 0 and default_run and os.environ.get("ADP_BENCH_FORCE_DIST", "0") != "1":
+    if args.full and world == 1 and args.cpu_sample > 0 and args.cpu_sample_all > 0 and default_run and os.environ.get("ADP_BENCH_FORCE_DIST", "0") != "1":
         global _CPU_WHY
         cpu_procs, _CPU_WHY = cpu_worker_count(args.cpu_procs)
         if cpu_procs > 1:
@@ -767,7 +830,7 @@ def main():
 
         out["dist"] = {"backend": backend, "world_size": world, "forced_group_of_one": bool(force_dist and world == 1),
                        "hip_runtimes": _lib.hip_runtimes(), "row_gather": "dist.gather of %d-byte rows, double-buffered" % _lib.ROW_DTYPE.itemsize}
-    if rank == 0 and world == 1 and dist is None and default_run and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and dist is None and default_run and not args.no_secondary:
         # the other single-GPU configurations of BASELINE.json, driver-run with the headline (each its own roofline)
         sec = {}
         detail = {"headline": {"kernel_ms": out["kernel_ms"], "ms_per_step": out["ms_per_step"]}}
@@ -788,6 +851,7 @@ def main():
         for name, kw in plan:
             w = argparse.Namespace(**vars(args))
             w.cpu_sample = 0
+            w.dump_outputs = None  # (the headline's rows only)
             env = kw.pop("env", {})
             for k, v in kw.items():
                 setattr(w, k, v)

@@ -6,6 +6,7 @@ vectors can be regenerated, never shipped to or run on the GPU box.
     /usr/local/bin/python3   oracle/gen_golden.py cnn        # CNN cases (needs torch)
     /usr/local/bin/python3   oracle/gen_golden.py cnn rna004_cnn_200k   # just the named case(s)
     /usr/local/bin/python3   oracle/gen_golden.py preds      # cnn_detect over thousands of reads: positions + the scores there
+    /usr/local/bin/python3   oracle/gen_golden.py presets    # the reference's preset TOML files as parsed data
 
 Inputs are regenerated from seeds by adapted_amd/synth.py (host twin of the device
 generator), so only the reference's OUTPUTS are stored.
@@ -350,6 +351,21 @@ def export_weights():
     np.savez(dst, **{k: v.numpy() for k, v in sd.items()})
 
 
+def gen_presets():
+    """The reference's two chemistry presets (adapted/config/config_files/*.toml) as parsed TOML data, section by section:
+    the presets of adapted_amd.config are checked against these values without the reference at hand."""
+    sys.path.insert(0, ROOT)
+    from adapted_amd.config import toml_io
+
+    src = os.path.join(ref_harness.REF_ROOT, "adapted", "config", "config_files")
+    out = {}
+    for chem, fn in (("RNA004", "rna004_130bps@v0.2.4.toml"), ("RNA002", "rna002_70bps@v0.2.4.toml")):
+        out[chem] = {"file": "adapted/config/config_files/" + fn, "sections": toml_io.load(os.path.join(src, fn))}
+    with open(os.path.join(GOLD, "reference_presets.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else "llr"
     only = set(sys.argv[2].split(",")) if len(sys.argv) > 2 else None  # e.g. llr rna004_llr_mvs_overwrite: just these cases
@@ -357,6 +373,9 @@ def main():
     if what == "bottleneck":
         gen_bottleneck()
         gen_bottleneck_nan()
+        return
+    if what == "presets":
+        gen_presets()
         return
     ref_harness.install(need_torch=(what in ("cnn", "preds")))
     if what == "preds":

@@ -1,5 +1,6 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric/value/unit/n_gpus/steps/warmup/ms_per_step/
-higher_is_better/scaling/vs_baseline/dtype/data/config) plus the roofline and cpu_baseline objects."""
+higher_is_better/scaling/vs_baseline/dtype/data/config) plus the roofline object; with --full also the cpu_baseline object,
+the secondary workloads and the summary.  --dump-outputs writes the last step's rows, the same from run to run."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2000", "--steps", "2", "--warmup", "1",
-                          "--cpu-sample", "40"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-sample", "40", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -55,3 +56,37 @@ def test_bench_json_contract():
         assert d["secondary"]["host_pipeline"][k]["minibatches"] == 12
     assert hp["f32_padded"][0] < sm["headline"][0]  # (never the headline)
     assert len(json.dumps(sm)) < 1400 and "grouped" not in d["secondary"] and "int16" not in sm
+
+
+def _plain(extra):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2000", "--steps", "3", "--warmup", "1"] + extra,
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_same_rows(tmp_path):
+    """without --full: the headline line (no CPU baseline, no secondaries); --dump-outputs writes the last step's rows as finite
+    float64 .npy files, under 64 MB, identical between two runs with the same arguments"""
+    import numpy as np
+
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    lines = [_plain(["--dump-outputs", str(d)]) for d in dumps]
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "rows_sha256"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "reads/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2000 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    assert d["cpu_baseline"] is None and "secondary" not in d and "summary" not in d
+    assert lines[1]["rows_sha256"] == d["rows_sha256"]
+    names = sorted(p.name for p in dumps[0].iterdir())
+    assert names == sorted(p.name for p in dumps[1].iterdir())
+    assert {"read_index.npy", "success.npy", "adapter_end.npy", "polya_end.npy", "polya_candidates.npy"} <= set(names)
+    assert sum(p.stat().st_size for p in dumps[0].iterdir()) <= 64 * 1000 * 1000
+    for name in names:
+        a, b = np.load(dumps[0] / name), np.load(dumps[1] / name)
+        assert a.dtype == np.float64 and a.shape[0] == 2000 and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+    assert np.load(dumps[0] / "success.npy").mean() == d["config"]["pass_rate"]

@@ -68,16 +68,17 @@ def test_toml_roundtrip_and_unknown_keys(tmp_path):
         load_nested_config_from_file(str(bad))
 
 
-@pytest.mark.reference
 def test_presets_equal_reference_tomls():
-    ref = "/root/reference/adapted/config/config_files"
-    if not os.path.isdir(ref):
-        pytest.skip("reference not present")
-    from adapted_amd.config import get_chemistry_specific_config, load_nested_config_from_file
+    # the reference's preset TOML files as parsed data (oracle/gen_golden.py presets)
+    from adapted_amd.config import get_chemistry_specific_config
+    from adapted_amd.config.sig_proc import nested_config_from_dict
 
-    for chem, fn in (("RNA004", "rna004_130bps@v0.2.4.toml"), ("RNA002", "rna002_70bps@v0.2.4.toml")):
+    with open(os.path.join(GOLD, "reference_presets.json")) as fh:
+        ref = json.load(fh)
+    assert sorted(ref) == ["RNA002", "RNA004"]
+    for chem in ("RNA004", "RNA002"):
         a = get_chemistry_specific_config(chem)
-        b = load_nested_config_from_file(os.path.join(ref, fn))
+        b = nested_config_from_dict(ref[chem]["sections"])
         for sec in ("core", "llr_boundaries", "mvs_polya", "real_range", "cnn_boundaries", "med_shift", "rna_start_peak"):
             assert getattr(a, sec).typed_dict() == getattr(b, sec).typed_dict(), (chem, sec)
 
@@ -617,6 +618,42 @@ def test_bench_finds_a_kernels_traffic_whatever_its_template_arguments():
     assert bench._traffic_of(t, "k_gains<2>", 96000) == 2.0
     assert bench._traffic_of(t, "k_gains", 96000) is None          # ambiguous: two instantiations
     assert bench._traffic_of(t, "k_norm_pool", 96000) is None and bench._traffic_of(None, "k_validate", 1) is None
+
+
+def test_bench_dump_outputs_masks_absent_values_and_samples_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: finite float64 arrays (absent values 0, carried NaN / +inf / -inf as 0 / 1 / -1 with their
+    bit in `nonfinite`), and past the budget a seeded sample of the rows that is the same every time"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from adapted_amd import lib
+
+    rows = np.zeros(6, dtype=lib.ROW_DTYPE)
+    rows["col"][:] = np.arange(lib.NCOL)
+    rows["present"][:] = 0b101                   # signal_len and adapter_start
+    rows["present"][3:] |= 1 << 27                # adapter_rna_median_shift: NaN, +inf, -inf
+    rows["col"][3:, 27] = [np.nan, np.inf, -np.inf]
+    rows["n_cand"] = [-1, 0, 2, 16, 3, 1]
+    rows["cand"][:] = 7
+    rows["n_open_pores"] = [0, 20, 1, 0, 0, 0]    # (more than a row holds: the row's 16 are written)
+    rows["open_pores"][:] = 9
+    rows["success"] = [1, 0, 1, 1, 0, 1]
+    rows["open_pores_more"] = 12345
+    assert bench.dump_outputs(rows, "llr", str(tmp_path / "all")) == 6
+    d = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert "open_pores_more" not in d and "reserved_" not in d and "llr_adapter_end" in d
+    assert all(v.dtype == np.float64 and v.shape[0] == 6 and np.isfinite(v).all() for v in d.values())
+    assert (d["signal_len"] == 0).all() and (d["adapter_start"] == 2).all() and (d["preloaded"] == 0).all()
+    assert np.array_equal(d["adapter_rna_median_shift"], [0, 0, 0, 0, 1, -1])
+    assert np.array_equal(d["nonfinite"], [0, 0, 0, 1 << 27, 1 << 27, 1 << 27])
+    assert np.array_equal(d["success"], [1, 0, 1, 1, 0, 1]) and np.array_equal(d["read_index"], np.arange(6))
+    assert np.array_equal((d["polya_candidates"] == -1).sum(1), [16, 16, 14, 0, 13, 15])
+    assert np.array_equal((d["open_pores"] == -1).sum(1), [16, 0, 15, 16, 16, 16])
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8 * (1 + lib.NCOL + 8 + lib.MAX_CAND + lib.MAX_OPEN_PORES) * 4)
+    assert bench.dump_outputs(rows, "llr", str(tmp_path / "s1")) == 4
+    assert bench.dump_outputs(rows, "llr", str(tmp_path / "s2")) == 4
+    i1, i2 = np.load(tmp_path / "s1" / "read_index.npy"), np.load(tmp_path / "s2" / "read_index.npy")
+    assert np.array_equal(i1, i2) and (np.diff(i1) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "success.npy"), rows["success"][i1.astype(int)])
 
 
 def test_every_lds_array_of_the_library_is_declared_16_byte_aligned():

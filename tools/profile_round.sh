@@ -22,7 +22,7 @@ pmc() { # pmc <name> <reads per launch> <T> <bench arguments ...>: FETCH_SIZE an
 }
 case $PART in
 a)
-  BENCH="python3 bench.py --steps 6 --warmup 2"
+  BENCH="python3 bench.py --steps 6 --warmup 2 --full"
   $BENCH > $S/bench.json 2> $OUT/${TAG}_bench.err
   rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o run -- $BENCH --cpu-sample 0 > $S/bench_under_rocprof.json 2> $OUT/${TAG}_bench_under_rocprof.err
   python3 profiles/summarize_phases.py $OUT/${TAG}_stats/run_results.db $S/kernel_stats_by_workload.csv > $S/kernel_stats_by_workload.txt
