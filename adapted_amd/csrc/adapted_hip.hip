@@ -28,6 +28,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_conv.h"
 #include "cnn_conv_split.h"
 #include "trace_api.h"
+#include "llr_detect_api.h"
 #include "wave_stats.h"
 
 static thread_local std::string g_err;
@@ -86,6 +87,7 @@ struct adp_handle {
     // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
     DevBuf tr_buf, tr_meta; // adp_c_llr_trace: staging of host arrays
+    DevBuf cd_buf, cd_meta; // adp_c_llr_detect / adp_c_llr_best_split: sums and staging; segments, chunk winners, per-read state
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
@@ -277,7 +279,7 @@ int adp_destroy(adp_handle *h)
     for (hipEvent_t e : h->ev_sync) (void)hipEventDestroy(e);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     h->mbstat.release(); h->mbparams.release(); h->sphead.release();
-    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
+    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
                      &h->t1, &h->adapter_idx, &h->polya_idx, &h->bounds, &h->topk_none, &h->rows, &h->preq, &h->series, &h->have_series, &h->vscratch, &h->pk, &h->pkv, &h->npk,
                      &h->mk, &h->st, &h->sp, &h->any_none, &h->sig_stage, &h->len_stage, &h->bounds_stage};
     for (DevBuf *b : all) b->release();
@@ -1019,7 +1021,7 @@ int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const 
         if (!in_dev) { double *t = take(); HIPCHK(hipMemcpyAsync(t, raw, mat, hipMemcpyHostToDevice, h->stream)); draw = t; }
         if (c_io && out_dev) { dc_w = c_io; dc2_w = c2_io; } else { dc_w = take(); dc2_w = take(); }
         { Scope s(h, "k_trace_cumsum");
-          hipLaunchKernelGGL(k_trace_cumsum, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, dc_w, dc2_w); }
+          hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, dc_w, dc2_w); }
         dc = dc_w; dc2 = dc2_w;
     }
     double *dg = out_dev ? gain_out : take();
@@ -1036,6 +1038,142 @@ int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const 
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// the split searches of one level: chunk winners, then per segment (llr_detect_api.h)
+static void cd_splits(adp_handle *h, const double *dc, const double *dc2, int L, const CdSeg *segs, int n_seg, double *part_g,
+                      int32_t *part_x, int32_t *st_x, double *st_g)
+{
+    const int nck = (L + CD_CHUNK - 1) / CD_CHUNK;
+    { Scope s(h, "k_split_part");
+      hipLaunchKernelGGL(k_split_part, dim3(n_seg, nck), dim3(CD_BLOCK), 0, h->stream, dc, dc2, L, segs, nck, part_g, part_x); }
+    { Scope s(h, "k_split_reduce");
+      hipLaunchKernelGGL(k_split_reduce, dim3(n_seg), dim3(64), 0, h->stream, segs, nck, part_g, part_x, st_x, st_g); }
+}
+
+// the small per-call arrays of a detect / best-split call in cd_meta: segments (2 per read), chunk winners, state, rows
+struct CdMeta { CdSeg *segs, *psegs; double *part_g, *st_g, *med; int32_t *part_x, *st_x, *res, *len; };
+static int cd_meta(adp_handle *h, int n_reads, int L, CdMeta &m)
+{
+    const size_t nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK, n = (size_t)n_reads;
+    const size_t sz[] = {2 * n * sizeof(CdSeg), n * sizeof(CdSeg), 2 * n * nck * 8, 4 * n * 8, 4 * n * 8, 2 * n * nck * 4, 4 * n * 4, 4 * n * 4, n * 4};
+    size_t tot = 0;
+    for (size_t b : sz) tot += (b + 255) & ~(size_t)255;
+    if (h->cd_meta.ensure(tot)) return -1;
+    char *p = h->cd_meta.as<char>();
+    void *out[9];
+    for (int i = 0; i < 9; i++) { out[i] = p; p += (sz[i] + 255) & ~(size_t)255; }
+    m.segs = (CdSeg *)out[0]; m.psegs = (CdSeg *)out[1]; m.part_g = (double *)out[2]; m.st_g = (double *)out[3]; m.med = (double *)out[4];
+    m.part_x = (int32_t *)out[5]; m.st_x = (int32_t *)out[6]; m.res = (int32_t *)out[7]; m.len = (int32_t *)out[8];
+    return 0;
+}
+
+// _best_split (_c_llr.pyx:40-64) for a batch of rows of given sums: one segment per row
+int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const int32_t *len, const int32_t *start, const int32_t *end,
+                         const int32_t *offset_head, const int32_t *offset_tail, int n_reads, int L, int flags, int64_t *x_out, double *gain_out)
+{
+    if (!h || !c || !c2 || !len || !start || !end || !offset_head || !offset_tail || !x_out || !gain_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    for (int r = 0; r < n_reads; r++)
+        if (len[r] < 0 || len[r] > L || start[r] < 0 || start[r] > end[r] || end[r] > len[r] || offset_head[r] < 0 || offset_tail[r] < 0) {
+            g_err = "need 0 <= start <= end <= len <= L and offsets >= 0 for every row"; return ADP_ERR_INVALID;
+        }
+    const bool in_dev = (flags & ADP_IN_DEVICE) != 0;
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    CdMeta m;
+    if (cd_meta(h, n_reads, L, m)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    const size_t mat = (size_t)L * 8 * n_reads;
+    const double *dc = c, *dc2 = c2;
+    if (!in_dev) {
+        if (h->cd_buf.ensure(2 * mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        double *t0 = h->cd_buf.as<double>(), *t1 = t0 + (size_t)L * n_reads;
+        HIPCHK(hipMemcpyAsync(t0, c, mat, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(t1, c2, mat, hipMemcpyHostToDevice, h->stream));
+        dc = t0; dc2 = t1;
+    }
+    std::vector<CdSeg> segs(n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        long lo = (long)start[r] + offset_head[r], hi = (long)end[r] - offset_tail[r];
+        if (lo > end[r]) lo = end[r];
+        if (hi < lo) hi = lo; // (an empty range: the reference's loop does not run)
+        segs[r] = CdSeg{r, start[r], end[r], (int32_t)lo, (int32_t)hi, r};
+    }
+    HIPCHK(hipMemcpyAsync(m.segs, segs.data(), segs.size() * sizeof(CdSeg), hipMemcpyHostToDevice, h->stream));
+    cd_splits(h, dc, dc2, L, m.segs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> x(n_reads);
+    HIPCHK(hipMemcpyAsync(x.data(), m.st_x, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(gain_out, m.st_g, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int r = 0; r < n_reads; r++) x_out[r] = x[r];
+    return ADP_OK;
+}
+
+// c_llr_detect_adapter (_c_llr.pyx:239-287) / c_llr_detect_adapter_polya (:290-365) for a batch (llr_detect_api.h)
+int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_reads, int L, int32_t min_obs_adapter, int32_t border_trim,
+                     int32_t min_obs_polya, int flags, int64_t *rows_out, int64_t *splits_out, double *stats_out)
+{
+    if (!h || !raw || !len || !rows_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (min_obs_adapter < 0 || border_trim < 0 || min_obs_polya < 0) { g_err = "offsets must be >= 0"; return ADP_ERR_INVALID; }
+    for (int r = 0; r < n_reads; r++)
+        if (len[r] < 1 || len[r] > L) { g_err = "need 1 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const bool in_dev = (flags & ADP_IN_DEVICE) != 0, f32 = (flags & ADP_CLLR_F32) != 0, polya = (flags & ADP_CLLR_POLYA) != 0;
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    CdMeta m;
+    if (cd_meta(h, n_reads, L, m)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    const size_t cells = (size_t)L * n_reads, esz = f32 ? 4 : 8;
+    // [c | c2 | raw staging]
+    const size_t need = 2 * cells * 8 + (in_dev ? 0 : ((cells * esz + 255) & ~(size_t)255));
+    if (h->cd_buf.ensure(need)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    double *dc = h->cd_buf.as<double>(), *dc2 = dc + cells;
+    const void *draw = raw;
+    if (!in_dev) {
+        void *t = dc2 + cells;
+        HIPCHK(hipMemcpyAsync(t, raw, cells * esz, hipMemcpyHostToDevice, h->stream));
+        draw = t;
+    }
+    HIPCHK(hipMemcpyAsync(m.len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+    const CdArgs a = {min_obs_adapter, border_trim, min_obs_polya, polya ? 1 : 0};
+    const int rb = (n_reads + 255) / 256;
+    { Scope s(h, "k_trace_cumsum");
+      if (f32) hipLaunchKernelGGL(k_trace_cumsum<float>, dim3(n_reads), dim3(64), 0, h->stream, (const float *)draw, m.len, L, n_reads, dc, dc2);
+      else hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, (const double *)draw, m.len, L, n_reads, dc, dc2); }
+    { Scope s(h, "k_cd_plan");
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 0, m.len, n_reads, a, m.st_x, m.segs); }
+    cd_splits(h, dc, dc2, L, m.segs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+    { Scope s(h, "k_cd_plan");
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 1, m.len, n_reads, a, m.st_x, m.segs); }
+    cd_splits(h, dc, dc2, L, m.segs, 2 * n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+    { Scope s(h, "k_cd_medians");
+      if (f32) hipLaunchKernelGGL(k_cd_medians<float>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const float *)draw, m.len, L, a, m.st_x, m.st_g, m.res, m.med, m.psegs);
+      else hipLaunchKernelGGL(k_cd_medians<double>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const double *)draw, m.len, L, a, m.st_x, m.st_g, m.res, m.med, m.psegs); }
+    if (polya) {
+        cd_splits(h, dc, dc2, L, m.psegs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+        { Scope s(h, "k_cd_finish");
+          hipLaunchKernelGGL(k_cd_finish, dim3(rb), dim3(256), 0, h->stream, n_reads, m.st_x, m.res); }
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> res((size_t)n_reads * 4), sx;
+    std::vector<double> sg, med;
+    HIPCHK(hipMemcpyAsync(res.data(), m.res, res.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    if (splits_out) { sx.resize((size_t)n_reads * 4); HIPCHK(hipMemcpyAsync(sx.data(), m.st_x, sx.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
+    if (stats_out) {
+        sg.resize((size_t)n_reads * 4); med.resize((size_t)n_reads * 4);
+        HIPCHK(hipMemcpyAsync(sg.data(), m.st_g, sg.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(med.data(), m.med, med.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < res.size(); i++) rows_out[i] = res[i];
+    for (int r = 0; r < n_reads; r++) {
+        const bool searched = res[r * 4 + 3] == 3 && res[r * 4 + 1] != 0;
+        if (splits_out) for (int k = 0; k < 4; k++) splits_out[r * 4 + k] = (k == 3 && !searched) ? -1 : sx[r * 4 + k];
+        if (stats_out) for (int k = 0; k < 4; k++) {
+            stats_out[r * 8 + k] = (k == 3 && !searched) ? 0.0 : sg[r * 4 + k];
+            stats_out[r * 8 + 4 + k] = med[r * 4 + k];
+        }
+    }
     return ADP_OK;
 }
 

@@ -18,21 +18,44 @@
 
 struct TraceArgs { int min_obs, border_trim, stride, a_es, a_w, a_s, p_es, p_w, p_s; };
 
+// var_c (_c_llr.pyx:23-37): 0 for an empty segment; the sums before `lo` are 0 for lo = 0 (x - 0.0 = x: the same bits as
+// the reference's branch without the subtraction)
+static __device__ __forceinline__ double llr_var_c(const double *cr, const double *c2r, long lo, long hi)
+{
+    if (lo == hi) return 0.0;
+    const double d = (double)(hi - lo);
+    const double cl = lo > 0 ? cr[lo - 1] : 0.0, c2l = lo > 0 ? c2r[lo - 1] : 0.0;
+    const double mu = (cr[hi - 1] - cl) / d;
+    return (c2r[hi - 1] - c2l) / d - mu * mu;
+}
+
+// the gain of split point i of [start, end) (_c_llr.pyx:58-60), vs = (end - start) log var_c(start, end): shared by the trace
+// (k_trace_gains) and the best-split search (llr_detect_api.h)
+template <class Log>
+static __device__ __forceinline__ double llr_gain_at(const double *cr, const double *c2r, long start, long end, long i, double vs, Log flog)
+{
+    const double h = (double)(i - start) * flog(llr_var_c(cr, c2r, start, i));
+    const double t = (double)(end - i) * flog(llr_var_c(cr, c2r, i, end));
+    return vs - (h + t);
+}
+
 // np.cumsum(raw), np.cumsum(raw * raw): one wave per read; tiles of 512 samples through LDS (coalesced loads and stores),
-// the two chains run by lane 0.  grid = n_reads, block = 64.
-__global__ void __launch_bounds__(64) k_trace_cumsum(const double *__restrict__ raw, const int32_t *__restrict__ len, int L, int n_reads,
+// the two chains run by lane 0.  grid = n_reads, block = 64.  T = float: the rows widened to float64 first (exact), the sums of
+// x.astype(float64).
+template <class T>
+__global__ void __launch_bounds__(64) k_trace_cumsum(const T *__restrict__ raw, const int32_t *__restrict__ len, int L, int n_reads,
                                                      double *__restrict__ c, double *__restrict__ c2)
 {
     constexpr int TILE = 512;
     __shared__ __attribute__((aligned(16))) double sx[TILE], sc[TILE], sq[TILE];
     const int r = blockIdx.x, ln = threadIdx.x;
     const int n = len[r];
-    const double *x = raw + (size_t)r * L;
+    const T *x = raw + (size_t)r * L;
     double *co = c + (size_t)r * L, *c2o = c2 + (size_t)r * L;
     double a = 0.0, b = 0.0;
     for (int tb = 0; tb < n; tb += TILE) {
         const int cnt = min(TILE, n - tb);
-        for (int k = ln; k < cnt; k += 64) sx[k] = x[tb + k];
+        for (int k = ln; k < cnt; k += 64) sx[k] = (double)x[tb + k];
         __syncthreads();
         if (ln == 0) {
 #pragma unroll 8
@@ -120,23 +143,10 @@ __global__ void __launch_bounds__(64) k_trace_gains(const double *__restrict__ c
     const LDS double *lt = (const LDS double *)lt_;
     auto flog = [&](double v) { return log_cr_impl(v, lt, [](double u) { return log(u); }); };
     const double *cr = c + (size_t)r * L, *c2r = c2 + (size_t)r * L;
-    // var_c (_c_llr.pyx:23-37): 0 for an empty segment; the sums before `lo` are 0 for lo = 0 (x - 0.0 = x: the same bits as
-    // the reference's branch without the subtraction)
-    auto var_c = [&](long lo, long hi) {
-        if (lo == hi) return 0.0;
-        const double d = (double)(hi - lo);
-        const double cl = lo > 0 ? cr[lo - 1] : 0.0, c2l = lo > 0 ? c2r[lo - 1] : 0.0;
-        const double mu = (cr[hi - 1] - cl) / d;
-        return (c2r[hi - 1] - c2l) / d - mu * mu;
-    };
     const long s0 = start + a.min_obs, stop = end - a.border_trim, s = a.stride;
     if (n > 0 && s0 < stop) {
-        const double vs = (double)(end - start) * flog(var_c(start, end));
-        for (long i = s0 + (long)ln * s; i < stop; i += 64 * s) {
-            const double h = (double)(i - start) * flog(var_c(start, i));
-            const double t = (double)(end - i) * flog(var_c(i, end));
-            g[i] = vs - (h + t);
-        }
+        const double vs = (double)(end - start) * flog(llr_var_c(cr, c2r, start, end));
+        for (long i = s0 + (long)ln * s; i < stop; i += 64 * s) g[i] = llr_gain_at(cr, c2r, start, end, i, vs, flog);
     }
     if (!(a.p_es > 0 || a.a_es > 0) || !(n > 0 && s0 < stop)) return;
     __syncthreads();

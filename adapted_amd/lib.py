@@ -270,7 +270,7 @@ EXPORTS = ["adp_abi_version", "adp_sizeof_cfg", "adp_sizeof_row", "adp_last_erro
            "adp_debug_llr_upto", "adp_debug_log", "adp_cnn_topk", "adp_host_alloc", "adp_host_free", "adp_memcpy_h2d_async",
            "adp_copy_mark", "adp_copy_wait", "adp_debug_divcheck", "adp_calibrate_i16", "adp_expand_ragged", "adp_set_layout",
            "adp_cnn_set_weights", "adp_cnn_forward", "adp_cnn_predict", "adp_detect_cnn", "adp_open_pores_arena", "adp_detect_llr_i16", "adp_expand_ragged_i16",
-           "adp_c_llr_trace"]
+           "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect"]
 
 
 class AdpTraceArgs(C.Structure):
@@ -281,6 +281,8 @@ class AdpTraceArgs(C.Structure):
 
 
 ADP_TRACE_FROM_SUMS = 64
+ADP_CLLR_POLYA = 128
+ADP_CLLR_F32 = 256
 
 
 class MinibatchDropped(RuntimeError):
@@ -645,6 +647,52 @@ class Engine:
                                              g.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p) if c is not None else None,
                                              c2.ctypes.data_as(C.c_void_p) if c2 is not None else None))
         return (g, c, c2) if return_c_c2 else g
+
+    def c_llr_best_split(self, c, c2, lens, starts, ends, offset_heads, offset_tails):
+        """adp_c_llr_best_split: the reference's `_best_split` for a batch -- sums float64 [n, L], per-row lens / starts / ends /
+        offsets -> (x int64 [n], gain float64 [n])"""
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        c2 = np.ascontiguousarray(c2, dtype=np.float64)
+        n, L = c.shape
+        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (lens, starts, ends, offset_heads, offset_tails)]
+        if c2.shape != c.shape or any(a.size != n for a in arrs):
+            raise ValueError("c, c2 [n, L] and one entry per row of lens / starts / ends / offsets")
+        x = np.zeros(n, dtype=np.int64)
+        g = np.zeros(n)
+        self._check(self.lib.adp_c_llr_best_split(self._h, c.ctypes.data_as(C.c_void_p), c2.ctypes.data_as(C.c_void_p),
+                                                  *[a.ctypes.data_as(C.c_void_p) for a in arrs], int(n), int(L), 0,
+                                                  x.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p)))
+        return x, g
+
+    def c_llr_detect(self, raw, lens, min_obs_adapter: int, border_trim: int, min_obs_polya: int = 0, polya: bool = False,
+                     n: Optional[int] = None, L: Optional[int] = None, float32: bool = False, details: bool = False):
+        """adp_c_llr_detect: `c_llr_detect_adapter` / `c_llr_detect_adapter_polya` for a batch.  raw: float64 or float32 [n, L]
+        host array, or a device pointer (int) with n, L and ``float32`` given.  -> rows int64 [n, 4] (adapter_start, adapter_end,
+        polya_end, tuple length 2 or 3); with ``details`` also (splits int64 [n, 4], stats float64 [n, 8])"""
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        flags = ADP_CLLR_POLYA if polya else 0
+        if isinstance(raw, int):
+            rawp = C.c_void_p(raw)
+            flags |= ADP_IN_DEVICE
+        else:
+            raw = np.ascontiguousarray(raw)
+            if raw.dtype not in (np.float32, np.float64):
+                raw = raw.astype(np.float64)
+            float32 = raw.dtype == np.float32
+            n, L = raw.shape
+            rawp = raw.ctypes.data_as(C.c_void_p)
+        if float32:
+            flags |= ADP_CLLR_F32
+        if lens.size != n:
+            raise ValueError("lens needs one entry per read")
+        rows = np.zeros((n, 4), dtype=np.int64)
+        splits = np.zeros((n, 4), dtype=np.int64) if details else None
+        stats = np.zeros((n, 8)) if details else None
+        self._check(self.lib.adp_c_llr_detect(self._h, rawp, lens.ctypes.data_as(C.c_void_p), int(n), int(L), int(min_obs_adapter),
+                                              int(border_trim), int(min_obs_polya), flags, rows.ctypes.data_as(C.c_void_p),
+                                              splits.ctypes.data_as(C.c_void_p) if details else None,
+                                              stats.ctypes.data_as(C.c_void_p) if details else None))
+        return (rows, splits, stats) if details else rows
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

@@ -322,6 +322,28 @@ typedef struct adp_trace_args {
 int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const int32_t *start, const int32_t *end, int n_reads,
                     int L, const adp_trace_args *args, int flags, double *gain_out, double *c_io, double *c2_io);
 
+/* The rest of the reference's native module: `_best_split` (_c_llr.pyx:40-64) and the unnormalised 3-split segmenters
+ * `c_llr_detect_adapter` (:239-287) / `c_llr_detect_adapter_polya` (:290-365), batched (adapted_amd/csrc/llr_detect_api.h).
+ *
+ * adp_c_llr_best_split: per row r of the cumulative sums c, c2 [n_reads, L] (row r valid in [0, len[r])), the best split of
+ *   [start[r], end[r]) over the points [start + offset_head, end - offset_tail) -> x_out (int64, -1 when no gain is > 0) and
+ *   gain_out (0.0 then).  len, start, end, offset_head, offset_tail: HOST int32 [n_reads], checked here (0 <= start <= end <= len
+ *   <= L, offsets >= 0).  flags: ADP_IN_DEVICE -- c, c2 are device pointers.  x_out / gain_out: host.
+ * adp_c_llr_detect: raw [n_reads, L] float64 (float32 with ADP_CLLR_F32: widened on the device, the rows of x.astype(float64)),
+ *   read r valid in [0, len[r]), len HOST int32 [n_reads] with 1 <= len <= L; offsets >= 0.  flags: ADP_IN_DEVICE -- raw is a
+ *   device pointer; ADP_CLLR_POLYA -- c_llr_detect_adapter_polya (else c_llr_detect_adapter).  Host outputs:
+ *     rows_out   int64 [n_reads, 4]  adapter_start, adapter_end, polya_end, and the LENGTH of the tuple the reference returns:
+ *                2 for c_llr_detect_adapter, and for c_llr_detect_adapter_polya when the first split finds nothing (its
+ *                `return 0,0`, :310-312); 3 otherwise (polya_end 0 in a 2-tuple row)
+ *     splits_out int64 [n_reads, 4] or NULL: x_first, x_head, x_tail, x_polya as the searches returned them (-1: none / not searched)
+ *     stats_out  double [n_reads, 8] or NULL: the gains of those four searches, then the four medians (0.0 where not computed) */
+#define ADP_CLLR_POLYA 128
+#define ADP_CLLR_F32 256
+int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const int32_t *len, const int32_t *start, const int32_t *end,
+                         const int32_t *offset_head, const int32_t *offset_tail, int n_reads, int L, int flags, int64_t *x_out, double *gain_out);
+int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_reads, int L, int32_t min_obs_adapter, int32_t border_trim,
+                     int32_t min_obs_polya, int flags, int64_t *rows_out, int64_t *splits_out, double *stats_out);
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
