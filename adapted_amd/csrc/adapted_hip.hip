@@ -29,6 +29,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_conv_split.h"
 #include "trace_api.h"
 #include "llr_detect_api.h"
+#include "trace_peaks_api.h"
 #include "wave_stats.h"
 
 static thread_local std::string g_err;
@@ -88,6 +89,7 @@ struct adp_handle {
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
     DevBuf tr_buf, tr_meta; // adp_c_llr_trace: staging of host arrays
     DevBuf cd_buf, cd_meta; // adp_c_llr_detect / adp_c_llr_best_split: sums and staging; segments, chunk winners, per-read state
+    DevBuf lp_buf, lp_meta, lp_sum, lp_pk; // adp_llr_trace_*: trace staging; per-read arrays; block summaries; maxima + work lists
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
@@ -239,6 +241,8 @@ extern "C" {
 int adp_abi_version(void) { return ADP_ABI_VERSION; }
 int adp_sizeof_cfg(void) { return (int)sizeof(adp_cfg); }
 int adp_sizeof_row(void) { return (int)sizeof(adp_row); }
+int adp_sizeof_peak_args(void) { return (int)sizeof(adp_peak_args); }
+int adp_sizeof_spike_args(void) { return (int)sizeof(adp_spike_args); }
 const char *adp_last_error(void) { return g_err.c_str(); }
 
 int adp_device_count(void)
@@ -279,7 +283,7 @@ int adp_destroy(adp_handle *h)
     for (hipEvent_t e : h->ev_sync) (void)hipEventDestroy(e);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     h->mbstat.release(); h->mbparams.release(); h->sphead.release();
-    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
+    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->lp_buf, &h->lp_meta, &h->lp_sum, &h->lp_pk, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
                      &h->t1, &h->adapter_idx, &h->polya_idx, &h->bounds, &h->topk_none, &h->rows, &h->preq, &h->series, &h->have_series, &h->vscratch, &h->pk, &h->pkv, &h->npk,
                      &h->mk, &h->st, &h->sp, &h->any_none, &h->sig_stage, &h->len_stage, &h->bounds_stage};
     for (DevBuf *b : all) b->release();
@@ -1174,6 +1178,128 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
             stats_out[r * 8 + 4 + k] = med[r * 4 + k];
         }
     }
+    return ADP_OK;
+}
+
+// ---- the reference's Python LLR module (adapted/detect/llr.py) on device traces (trace_peaks_api.h)
+
+// the trace rows on the device (staged when they are host memory) and the per-read int32 arrays copied to lp_meta
+static int lp_stage(adp_handle *h, const double *trace, int n_reads, int L, int flags, std::initializer_list<const int32_t *> ints,
+                    size_t out_bytes, const double **dtr, std::vector<int32_t *> &dints, void **dout)
+{
+    const size_t mat = (size_t)L * 8 * n_reads;
+    if (!(flags & ADP_IN_DEVICE)) {
+        if (h->lp_buf.ensure(mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        HIPCHK(hipMemcpyAsync(h->lp_buf.p, trace, mat, hipMemcpyHostToDevice, h->stream));
+        *dtr = h->lp_buf.as<double>();
+    } else *dtr = trace;
+    const size_t isz = ((size_t)n_reads * 4 + 255) & ~(size_t)255;
+    if (h->lp_meta.ensure(isz * ints.size() + out_bytes)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    char *p = h->lp_meta.as<char>();
+    for (const int32_t *a : ints) {
+        HIPCHK(hipMemcpyAsync(p, a, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+        dints.push_back((int32_t *)p);
+        p += isz;
+    }
+    *dout = p;
+    return ADP_OK;
+}
+
+static int lp_blocksum(adp_handle *h, const double *dtr, const int32_t *dlen, int n_reads, int L, int sanitize, double **bx, double **bn, int *nsum)
+{
+    *nsum = (L + SUMBLK - 1) / SUMBLK;
+    if (h->lp_sum.ensure((size_t)*nsum * n_reads * 16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    *bx = h->lp_sum.as<double>(); *bn = *bx + (size_t)*nsum * n_reads;
+    { Scope s(h, "k_trace_blocksum");
+      hipLaunchKernelGGL(k_trace_blocksum, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, *nsum, sanitize, *bx, *bn); }
+    return ADP_OK;
+}
+
+static bool lp_lens_ok(const int32_t *len, int n_reads, int L)
+{
+    for (int r = 0; r < n_reads; r++) if (len[r] < 0 || len[r] > L) return false;
+    return true;
+}
+
+int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const int32_t *min_obs, const int32_t *tail_trim, int stride,
+                         int n_reads, int L, int flags, int32_t *start_out, int32_t *end_out, int32_t *early_stop_out)
+{
+    if (!h || !trace || !len || !min_obs || !tail_trim || !start_out || !end_out || !early_stop_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (stride < 1) { g_err = "stride must be >= 1"; return ADP_ERR_INVALID; }
+    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const double *dtr; std::vector<int32_t *> di; void *dout;
+    int rc = lp_stage(h, trace, n_reads, L, flags, {len, min_obs, tail_trim}, (size_t)n_reads * 12, &dtr, di, &dout);
+    if (rc) return rc;
+    int32_t *ds = (int32_t *)dout, *de = ds + n_reads, *des = de + n_reads;
+    const int interp = (flags & ADP_LLR_INTERP) && stride > 1;
+    { Scope s(h, "k_trace_bounds");
+      hipLaunchKernelGGL(k_trace_bounds, dim3(n_reads), dim3(64), 0, h->stream, const_cast<double *>(dtr), di[0], L, di[1], di[2], stride, interp, ds, de, des); }
+    HIPCHK(hipGetLastError());
+    if (interp && !(flags & ADP_IN_DEVICE))
+        HIPCHK(hipMemcpyAsync(trace, dtr, (size_t)L * 8 * n_reads, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(start_out, ds, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(end_out, de, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(early_stop_out, des, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, const int32_t *clip_lo, const int32_t *clip_hi, int n_reads,
+                        int L, const adp_peak_args *args, int flags, int cap, int64_t *peaks_out, int64_t *count_out)
+{
+    if (!h || !trace || !len || !clip_lo || !clip_hi || !args || !peaks_out || !count_out || n_reads < 1 || L < 1 || cap < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const int given = (flags & ADP_LLR_GIVEN_PEAK) != 0;
+    for (int r = 0; r < n_reads; r++)
+        if (given ? (clip_lo[r] < 0 || clip_lo[r] >= len[r]) : (clip_lo[r] < 0 || clip_lo[r] > clip_hi[r] || clip_hi[r] > len[r])) {
+            g_err = "need 0 <= clip_lo <= clip_hi <= len (with ADP_LLR_GIVEN_PEAK: 0 <= clip_lo < len) for every read"; return ADP_ERR_INVALID;
+        }
+    const adp_peak_args &a = *args;
+    if ((a.plateau_on && a.plateau_s < 1) || (a.split_on && a.split_s < 0)) { g_err = "plateau s must be >= 1, split s >= 0"; return ADP_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const double *dtr; std::vector<int32_t *> di; void *dout;
+    int rc = lp_stage(h, trace, n_reads, L, flags, {len, clip_lo, clip_hi}, (size_t)n_reads * 8 * (cap + 1), &dtr, di, &dout);
+    if (rc) return rc;
+    int64_t *dcnt = (int64_t *)dout, *dpk = dcnt + n_reads;
+    double *bx, *bn; int nsum;
+    if ((rc = lp_blocksum(h, dtr, di[0], n_reads, L, 0, &bx, &bn, &nsum))) return rc;
+    { Scope s(h, "k_trace_peaks");
+      hipLaunchKernelGGL(k_trace_peaks, dim3(n_reads), dim3(64), 0, h->stream, dtr, di[0], L, di[1], di[2], bx, bn, nsum, a, given, cap, dpk, dcnt); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(count_out, dcnt, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(peaks_out, dpk, (size_t)n_reads * 8 * cap, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, int n_reads, int L, const adp_spike_args *args, int flags,
+                       int64_t *out)
+{
+    if (!h || !trace || !len || !args || !out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const adp_spike_args &a = *args;
+    if (!(a.min_peak_distance >= 1.0)) { g_err = "min_peak_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
+    const double dd = ceil(a.min_peak_distance);
+    const int dist = dd > (double)L ? L + 1 : (int)dd; // (beyond the row: every pair of maxima is within it)
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const double *dtr; std::vector<int32_t *> di; void *dout;
+    int rc = lp_stage(h, trace, n_reads, L, flags, {len}, (size_t)n_reads * 8, &dtr, di, &dout);
+    if (rc) return rc;
+    int64_t *dres = (int64_t *)dout;
+    double *bx, *bn; int nsum;
+    if ((rc = lp_blocksum(h, dtr, di[0], n_reads, L, 1, &bx, &bn, &nsum))) return rc;
+    const int half = L / 2 + 1;
+    if (h->lp_pk.ensure((size_t)half * n_reads * 8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    uint32_t *pk = h->lp_pk.as<uint32_t>(), *wl = pk + (size_t)half * n_reads;
+    { Scope s(h, "k_trace_spike");
+      hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, di[0], L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dres, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
 

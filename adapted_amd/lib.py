@@ -255,7 +255,8 @@ def load():
     except Exception as e:  # no CPU fallback by design
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
-    if lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize:
+    if (lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize
+            or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     lib.adp_last_error.restype = C.c_char_p
     lib.adp_stream.restype = C.c_void_p
@@ -270,7 +271,8 @@ EXPORTS = ["adp_abi_version", "adp_sizeof_cfg", "adp_sizeof_row", "adp_last_erro
            "adp_debug_llr_upto", "adp_debug_log", "adp_cnn_topk", "adp_host_alloc", "adp_host_free", "adp_memcpy_h2d_async",
            "adp_copy_mark", "adp_copy_wait", "adp_debug_divcheck", "adp_calibrate_i16", "adp_expand_ragged", "adp_set_layout",
            "adp_cnn_set_weights", "adp_cnn_forward", "adp_cnn_predict", "adp_detect_cnn", "adp_open_pores_arena", "adp_detect_llr_i16", "adp_expand_ragged_i16",
-           "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect"]
+           "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect", "adp_sizeof_peak_args", "adp_sizeof_spike_args",
+           "adp_llr_trace_bounds", "adp_llr_trace_peaks", "adp_llr_spike_peak"]
 
 
 class AdpTraceArgs(C.Structure):
@@ -280,7 +282,21 @@ class AdpTraceArgs(C.Structure):
                                          "polya_early_stop_stride")]
 
 
+class AdpPeakArgs(C.Structure):
+    """struct adp_peak_args (include/adapted_hip.h): find_peaks_in_trace's and the two corrections' parameters"""
+    _fields_ = [(k, C.c_double) for k in ("prominence", "width", "rel_height", "plateau_t", "split_t", "split_prominence")] + \
+               [(k, C.c_int32) for k in ("plateau_on", "plateau_s", "plateau_window", "split_on", "split_s", "split_window")]
+
+
+class AdpSpikeArgs(C.Structure):
+    """struct adp_spike_args (include/adapted_hip.h): detect_full_polya_trace_peak_with_spike's parameters"""
+    _fields_ = [(k, C.c_double) for k in ("min_peak_distance", "prominence_threshold", "min_width", "threshold_prominence_ratio",
+                                          "threshold_r_squared")]
+
+
 ADP_TRACE_FROM_SUMS = 64
+ADP_LLR_INTERP = 512
+ADP_LLR_GIVEN_PEAK = 1024
 ADP_CLLR_POLYA = 128
 ADP_CLLR_F32 = 256
 
@@ -693,6 +709,61 @@ class Engine:
                                               splits.ctypes.data_as(C.c_void_p) if details else None,
                                               stats.ctypes.data_as(C.c_void_p) if details else None))
         return (rows, splits, stats) if details else rows
+
+    # -- the reference's Python LLR module (adp_llr_trace_*) ---------------------------------------------------------------
+    def _trace_in(self, trace, n, L):
+        """a host float64 [n, L] array or a device pointer (int) with n, L -> (pointer, flags, n, L, host array or None)"""
+        if isinstance(trace, int):
+            if n is None or L is None:
+                raise ValueError("a device pointer needs n and L")
+            return C.c_void_p(trace), ADP_IN_DEVICE, int(n), int(L), None
+        a = np.asarray(trace)
+        if a.dtype != np.float64 or not a.flags.c_contiguous or a.ndim != 2:
+            raise ValueError("traces: a C-contiguous float64 [n, L] array")
+        return a.ctypes.data_as(C.c_void_p), 0, a.shape[0], a.shape[1], a
+
+    @staticmethod
+    def _i32(a, n, what):
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        if a.size != n:
+            raise ValueError("%s needs one entry per read" % what)
+        return a
+
+    def llr_trace_bounds(self, trace, lens, min_obs, tail_trim, stride: int, interp: bool, n: Optional[int] = None, L: Optional[int] = None):
+        """adp_llr_trace_bounds: LLRTrace's start / end / early_stop, and with ``interp`` interp_stride IN PLACE (trace: a writable
+        host float64 [n, L] array, or a device pointer with n, L) -> (start, end, early_stop) int32 [n] (early_stop bit 1: the
+        knot set was empty)"""
+        p, flags, n, L, _ = self._trace_in(trace, n, L)
+        lens, mo, tt = (self._i32(a, n, w) for a, w in ((lens, "lens"), (min_obs, "min_obs"), (tail_trim, "tail_trim")))
+        st, en, es = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        if interp:
+            flags |= ADP_LLR_INTERP
+        self._check(self.lib.adp_llr_trace_bounds(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, mo, tt)), int(stride), int(n),
+                                                  int(L), flags, *(a.ctypes.data_as(C.c_void_p) for a in (st, en, es))))
+        return st, en, es
+
+    def llr_trace_peaks(self, trace, lens, clip_lo, clip_hi, args: "AdpPeakArgs", cap: int = 16, n: Optional[int] = None,
+                        L: Optional[int] = None, given_peak: bool = False):
+        """adp_llr_trace_peaks -> (peaks int64 [n, cap] padded with -1, counts int64 [n]: the true counts, also past cap).
+        ``given_peak``: clip_lo holds one peak per read, only corrected (ADP_LLR_GIVEN_PEAK)"""
+        p, flags, n, L, _ = self._trace_in(trace, n, L)
+        if given_peak:
+            flags |= ADP_LLR_GIVEN_PEAK
+        lens, lo, hi = (self._i32(a, n, w) for a, w in ((lens, "lens"), (clip_lo, "clip_lo"), (clip_hi, "clip_hi")))
+        pk = np.zeros((n, int(cap)), dtype=np.int64)
+        cnt = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.adp_llr_trace_peaks(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, lo, hi)), int(n), int(L),
+                                                 C.byref(args), flags, int(cap), pk.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+        return pk, cnt
+
+    def llr_spike_peak(self, trace, lens, args: "AdpSpikeArgs", n: Optional[int] = None, L: Optional[int] = None):
+        """adp_llr_spike_peak -> int64 [n]"""
+        p, flags, n, L, _ = self._trace_in(trace, n, L)
+        lens = self._i32(lens, n, "lens")
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.adp_llr_spike_peak(self._h, p, lens.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
+                                                out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

@@ -344,6 +344,50 @@ int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const
 int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_reads, int L, int32_t min_obs_adapter, int32_t border_trim,
                      int32_t min_obs_polya, int flags, int64_t *rows_out, int64_t *splits_out, double *stats_out);
 
+/* The reference's Python LLR module (adapted/detect/llr.py) above its native one, batched on traces [n_reads, L] float64 (read r
+ * valid in [0, len[r])), one wave per read (adapted_amd/csrc/trace_peaks_api.h).  len and every other per-read array: HOST int32
+ * [n_reads], checked here (0 <= len <= L).  flags: ADP_IN_DEVICE -- `trace` is a device pointer (resident traces never cross
+ * PCIe).  Outputs: host memory.
+ *
+ * adp_llr_trace_bounds: the derived state of `LLRTrace` (llr.py:53-132) -- `_trace_start_end` (:135-142: the first and last index
+ *   whose value is not <= 0, NaN counting as positive; 0 and len - 1 when there is none), `early_stop` (:86: end <
+ *   `max_len_no_early_stop` :72-84, np.arange(min_obs, len - 1 - tail_trim, stride)[-1], len - 1 - tail_trim for an empty
+ *   range) and, with ADP_LLR_INTERP and stride > 1, `interp_stride` (:116-132) IN PLACE (a host trace is copied back): np.interp
+ *   of the knots -- the indices in [start, end) whose value is != 0, NaN included -- bit for bit, left = right = 0.
+ *   min_obs, tail_trim: per read (calc_polya_trace derives both from adapter_end, :375-381).  early_stop_out: bit 0 the flag,
+ *   bit 1 set when interpolation was asked for and the knot set is empty (numpy raises ValueError; the trace is unchanged).
+ * adp_llr_trace_peaks: `find_peaks_in_trace` (:204-224) on trace[clip_lo:clip_hi] -- scipy's find_peaks with prominence
+ *   args->prominence * np.nanstd(clip) (numpy's summation order), width and rel_height -- then for EVERY peak, in index order,
+ *   `correct_for_plateau` (:145-177) and `correct_for_split_peak` (:180-201) as `adapter_end_from_trace` (:227-263) applies them
+ *   (each when its `*_on` is set, with its own s / t / window; the split test's find_peaks uses width = split_s, the absolute
+ *   split_prominence and rel_height 0.5).  peaks_out int64 [n_reads, cap]: full-trace indices, -1 padding; count_out int64
+ *   [n_reads]: the true number of peaks, also when it exceeds cap.  0 <= clip_lo <= clip_hi <= len; plateau_s >= 1.
+ *   With ADP_LLR_GIVEN_PEAK, clip_lo[r] is a peak (0 <= clip_lo < len) that only the corrections are applied to (the reference's
+ *   correct_for_plateau / correct_for_split_peak on their own; clip_hi is not read, count_out is 1).
+ * adp_llr_spike_peak: `detect_full_polya_trace_peak_with_spike` (:406-479) with all five parameters -> out int64 [n_reads] (0: no
+ *   peak).  scipy's find_peaks(np.nan_to_num(trace, nan=0), distance, prominence, width, rel_height=0.5): the distance selection
+ *   over ALL local maxima first (ties: the later index wins), then prominence and width; the heights, np.argmin and
+ *   linregress's r on the trace as given.  min_peak_distance >= 1 (scipy's ValueError otherwise). */
+typedef struct adp_peak_args {
+    double prominence, width, rel_height;             /* find_peaks_in_trace; prominence relative to np.nanstd(clip) */
+    double plateau_t, split_t, split_prominence;
+    int32_t plateau_on, plateau_s, plateau_window;    /* correct_for_plateau(trace, peak, s, t, window) */
+    int32_t split_on, split_s, split_window;          /* correct_for_split_peak(trace, peak, s, t, window, prominence) */
+} adp_peak_args;
+typedef struct adp_spike_args {
+    double min_peak_distance, prominence_threshold, min_width, threshold_prominence_ratio, threshold_r_squared;
+} adp_spike_args;
+#define ADP_LLR_INTERP 512
+#define ADP_LLR_GIVEN_PEAK 1024
+int adp_sizeof_peak_args(void);
+int adp_sizeof_spike_args(void);
+int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const int32_t *min_obs, const int32_t *tail_trim, int stride,
+                         int n_reads, int L, int flags, int32_t *start_out, int32_t *end_out, int32_t *early_stop_out);
+int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, const int32_t *clip_lo, const int32_t *clip_hi, int n_reads,
+                        int L, const adp_peak_args *args, int flags, int cap, int64_t *peaks_out, int64_t *count_out);
+int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, int n_reads, int L, const adp_spike_args *args, int flags,
+                       int64_t *out);
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
