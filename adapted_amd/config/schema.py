@@ -44,7 +44,7 @@ SECTIONS: Dict[str, list] = {
         ("max_obs_local_range", int, 5000), ("local_range", Range, (10.0, 30.0)),
         ("adapter_mad_range", Range, (3.0, 12.0)),
     ],
-    "streaming": [  # accepted for TOML compatibility; unused by the detect path
+    "streaming": [  # mean_var_shift_polyA_detect's parameters (adapted_amd/detect/mvs.py); the detect pipeline does not read them
         ("min_obs_adapter", int, 2500), ("min_obs_post_loc", int, 300), ("search_increment_step", int, 100),
         ("pA_mean_window", int, 20), ("pA_mean_range", Range, (90.0, 130.0)), ("pA_var_window", int, 100),
         ("pA_var_range", Range, (None, 20.0)), ("median_shift_window", int, 2000),

@@ -90,6 +90,7 @@ struct adp_handle {
     DevBuf tr_buf, tr_meta; // adp_c_llr_trace: staging of host arrays
     DevBuf cd_buf, cd_meta; // adp_c_llr_detect / adp_c_llr_best_split: sums and staging; segments, chunk winners, per-read state
     DevBuf lp_buf, lp_meta, lp_sum, lp_pk; // adp_llr_trace_*: trace staging; per-read arrays; block summaries; maxima + work lists
+    DevBuf mv_buf, mv_meta, mv_scr; // adp_mvs_*: signal staging; per-read inputs and outputs; per-slot series scratch
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
@@ -243,6 +244,7 @@ int adp_sizeof_cfg(void) { return (int)sizeof(adp_cfg); }
 int adp_sizeof_row(void) { return (int)sizeof(adp_row); }
 int adp_sizeof_peak_args(void) { return (int)sizeof(adp_peak_args); }
 int adp_sizeof_spike_args(void) { return (int)sizeof(adp_spike_args); }
+int adp_sizeof_mvs_args(void) { return (int)sizeof(adp_mvs_args); }
 const char *adp_last_error(void) { return g_err.c_str(); }
 
 int adp_device_count(void)
@@ -283,7 +285,7 @@ int adp_destroy(adp_handle *h)
     for (hipEvent_t e : h->ev_sync) (void)hipEventDestroy(e);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     h->mbstat.release(); h->mbparams.release(); h->sphead.release();
-    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->lp_buf, &h->lp_meta, &h->lp_sum, &h->lp_pk, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
+    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->lp_buf, &h->lp_meta, &h->lp_sum, &h->lp_pk, &h->mv_buf, &h->mv_meta, &h->mv_scr, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
                      &h->t1, &h->adapter_idx, &h->polya_idx, &h->bounds, &h->topk_none, &h->rows, &h->preq, &h->series, &h->have_series, &h->vscratch, &h->pk, &h->pkv, &h->npk,
                      &h->mk, &h->st, &h->sp, &h->any_none, &h->sig_stage, &h->len_stage, &h->bounds_stage};
     for (DevBuf *b : all) b->release();
@@ -1298,6 +1300,141 @@ int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, i
     { Scope s(h, "k_trace_spike");
       hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, di[0], L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
     HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dres, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// ---- the reference's MVS poly(A) module (adapted/detect/mvs.py) on batched signals (mvs_api.h, compiled in mvs_kernels.hip)
+__attribute__((visibility("hidden"))) int mvs_launch_check(bool f64, int grid, hipStream_t st, const void *sig, const int32_t *len, int n, int L, const int64_t *ae,
+                     const int64_t *pe, const adp_mvs_args &a, void *scr, int32_t *info, double *vals);
+__attribute__((visibility("hidden"))) int mvs_launch_at_loc(bool f64, int grid, hipStream_t st, const void *sig, const int32_t *len, int n, int L, const int64_t *loc,
+                      const adp_mvs_args &a, void *scr, int32_t *info, int64_t *idx, double *vals);
+__attribute__((visibility("hidden"))) int mvs_launch_stream(bool f64, int grid, hipStream_t st, const void *sig, const int32_t *len, int n, int L, const adp_mvs_args &a,
+                      int64_t *out);
+
+// the signal rows on the device (staged when they are host memory), the per-read inputs and the outputs in mv_meta
+static int mv_stage(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags, std::initializer_list<const int64_t *> pos,
+                    size_t out_bytes, const void **dsig, const int32_t **dlen, std::vector<const int64_t *> &dpos, void **dout)
+{
+    const size_t esz = (flags & ADP_MVS_F64) ? 8 : 4, mat = (size_t)L * esz * n_reads;
+    if (!(flags & ADP_IN_DEVICE)) {
+        if (h->mv_buf.ensure(mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        HIPCHK(hipMemcpyAsync(h->mv_buf.p, sig, mat, hipMemcpyHostToDevice, h->stream));
+        *dsig = h->mv_buf.p;
+    } else *dsig = sig;
+    const size_t isz = ((size_t)n_reads * 8 + 255) & ~(size_t)255;
+    if (h->mv_meta.ensure(isz * (1 + pos.size()) + out_bytes)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    char *p = h->mv_meta.as<char>();
+    HIPCHK(hipMemcpyAsync(p, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+    *dlen = (const int32_t *)p;
+    p += isz;
+    for (const int64_t *a : pos) {
+        HIPCHK(hipMemcpyAsync(p, a, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
+        dpos.push_back((const int64_t *)p);
+        p += isz;
+    }
+    *dout = p;
+    return ADP_OK;
+}
+
+static int mv_check_args(const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *a, std::initializer_list<const int64_t *> pos)
+{
+    if (!sig || !len || !a || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    for (int r = 0; r < n_reads; r++) if (len[r] < 0 || len[r] > L) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    for (const int64_t *p : pos) {
+        if (!p) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+        for (int r = 0; r < n_reads; r++) if (p[r] < 0 || p[r] > ((int64_t)1 << 40)) { g_err = "positions must lie in [0, 2^40]"; return ADP_ERR_INVALID; }
+    }
+    if (a->pA_mean_window < 1 || a->pA_var_window < 1 || a->s_pA_mean_window < 1 || a->s_pA_var_window < 1) {
+        g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID;
+    }
+    if (a->search_increment_step < 1) { g_err = "search_increment_step must be >= 1"; return ADP_ERR_INVALID; }
+    return ADP_OK;
+}
+
+// slots of the series kernels: one wave each, [2, L] elements of scratch per slot (at most ~512 MiB in all)
+static int mv_slots(adp_handle *h, int n_reads, int L, size_t esz, void **scr)
+{
+    const size_t per = (size_t)2 * L * esz;
+    size_t slots = ((size_t)512 << 20) / per;
+    if (slots < 64) slots = 64;
+    if (slots > (size_t)n_reads) slots = n_reads;
+    if (slots > 8192) slots = 8192;
+    if (h->mv_scr.ensure(per * slots)) { g_err = "device allocation failed"; return -1; }
+    *scr = h->mv_scr.p;
+    return (int)slots;
+}
+
+int adp_mvs_check(adp_handle *h, const void *sig, const int32_t *len, const int64_t *adapter_end, const int64_t *polya_end, int n_reads,
+                  int L, const adp_mvs_args *args, int flags, int32_t *info_out, double *vals_out)
+{
+    if (!h || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    int rc = mv_check_args(sig, len, n_reads, L, args, {adapter_end, polya_end});
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
+    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {adapter_end, polya_end}, (size_t)n_reads * (32 + 40), &ds, &dl, dp, &dout))) return rc;
+    int32_t *dinfo = (int32_t *)dout;
+    double *dvals = (double *)(dinfo + (size_t)n_reads * 8);
+    void *scr;
+    const int slots = mv_slots(h, n_reads, L, f64 ? 8 : 4, &scr);
+    if (slots < 1) return ADP_ERR_HIP;
+    { Scope s(h, "k_mvs_check");
+      HIPCHK((hipError_t)mvs_launch_check(f64, slots, h->stream, ds, dl, n_reads, L, dp[0], dp[1], *args, scr, dinfo, dvals)); }
+    HIPCHK(hipMemcpyAsync(info_out, dinfo, (size_t)n_reads * 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(vals_out, dvals, (size_t)n_reads * 40, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, const int64_t *loc, int n_reads, int L,
+                          const adp_mvs_args *args, int flags, int32_t *info_out, int64_t *idx_out, double *vals_out)
+{
+    if (!h || !info_out || !idx_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    int rc = mv_check_args(sig, len, n_reads, L, args, {loc});
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
+    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {loc}, (size_t)n_reads * (32 + 8 + 40), &ds, &dl, dp, &dout))) return rc;
+    int32_t *dinfo = (int32_t *)dout;
+    int64_t *didx = (int64_t *)(dinfo + (size_t)n_reads * 8);
+    double *dvals = (double *)(didx + n_reads);
+    void *scr;
+    const int slots = mv_slots(h, n_reads, L, f64 ? 8 : 4, &scr);
+    if (slots < 1) return ADP_ERR_HIP;
+    { Scope s(h, "k_mvs_at_loc");
+      HIPCHK((hipError_t)mvs_launch_at_loc(f64, slots, h->stream, ds, dl, n_reads, L, dp[0], *args, scr, dinfo, didx, dvals)); }
+    HIPCHK(hipMemcpyAsync(info_out, dinfo, (size_t)n_reads * 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(idx_out, didx, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(vals_out, dvals, (size_t)n_reads * 40, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *args, int flags,
+                   int64_t *out)
+{
+    if (!h || !out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    int rc = mv_check_args(sig, len, n_reads, L, args, {});
+    if (rc) return rc;
+    if (args->min_obs_adapter < 0 || args->min_obs_post_loc < 0 || args->s_median_shift_window < 0 || args->s_polyA_window < 0) {
+        g_err = "min_obs_adapter, min_obs_post_loc and the windows must be >= 0"; return ADP_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
+    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {}, (size_t)n_reads * 8, &ds, &dl, dp, &dout))) return rc;
+    int64_t *dres = (int64_t *)dout;
+    // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
+    const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
+    { Scope s(h, "k_mvs_stream");
+      HIPCHK((hipError_t)mvs_launch_stream(f64, grid, h->stream, ds, dl, n_reads, L, *args, dres)); }
     HIPCHK(hipMemcpyAsync(out, dres, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;

@@ -256,7 +256,8 @@ def load():
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
     if (lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize
-            or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)):
+            or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)
+            or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     lib.adp_last_error.restype = C.c_char_p
     lib.adp_stream.restype = C.c_void_p
@@ -272,7 +273,8 @@ EXPORTS = ["adp_abi_version", "adp_sizeof_cfg", "adp_sizeof_row", "adp_last_erro
            "adp_copy_mark", "adp_copy_wait", "adp_debug_divcheck", "adp_calibrate_i16", "adp_expand_ragged", "adp_set_layout",
            "adp_cnn_set_weights", "adp_cnn_forward", "adp_cnn_predict", "adp_detect_cnn", "adp_open_pores_arena", "adp_detect_llr_i16", "adp_expand_ragged_i16",
            "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect", "adp_sizeof_peak_args", "adp_sizeof_spike_args",
-           "adp_llr_trace_bounds", "adp_llr_trace_peaks", "adp_llr_spike_peak"]
+           "adp_llr_trace_bounds", "adp_llr_trace_peaks", "adp_llr_spike_peak", "adp_sizeof_mvs_args", "adp_mvs_check",
+           "adp_mvs_detect_at_loc", "adp_mvs_detect"]
 
 
 class AdpTraceArgs(C.Structure):
@@ -294,11 +296,22 @@ class AdpSpikeArgs(C.Structure):
                                           "threshold_r_squared")]
 
 
+class AdpMvsArgs(C.Structure):
+    """struct adp_mvs_args (include/adapted_hip.h): the [mvs_polya] and [streaming] parameters of the MVS module, plus its flags"""
+    _fields_ = [(k, C.c_double * 2) for k in ("pA_mean_range", "pA_var_range", "median_shift_range", "polyA_med_range", "polyA_local_range")] + \
+               [(k, C.c_int32) for k in ("search_window", "pA_mean_window", "pA_var_window", "median_shift_window", "polyA_window",
+                                         "less_signal_ok", "windowed_stats", "min_obs_adapter", "min_obs_post_loc", "search_increment_step",
+                                         "s_pA_mean_window", "s_pA_var_window", "s_median_shift_window", "s_polyA_window", "pad")] + \
+               [(k, C.c_double * 2) for k in ("s_pA_mean_range", "s_pA_var_range", "s_median_shift_range", "s_polyA_med_range",
+                                              "s_polyA_local_range")]
+
+
 ADP_TRACE_FROM_SUMS = 64
 ADP_LLR_INTERP = 512
 ADP_LLR_GIVEN_PEAK = 1024
 ADP_CLLR_POLYA = 128
 ADP_CLLR_F32 = 256
+ADP_MVS_F64 = 2048
 
 
 class MinibatchDropped(RuntimeError):
@@ -763,6 +776,59 @@ class Engine:
         out = np.zeros(n, dtype=np.int64)
         self._check(self.lib.adp_llr_spike_peak(self._h, p, lens.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
                                                 out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # -- the reference's MVS poly(A) module (adp_mvs_*) --------------------------------------------------------------------
+    def _mvs_in(self, sig, n, L, f64):
+        """a host float32 / float64 [n, L] array or a device pointer (int) with n, L (and f64 for its dtype) -> (pointer, flags, n, L)"""
+        if isinstance(sig, int):
+            if n is None or L is None:
+                raise ValueError("a device pointer needs n and L")
+            return C.c_void_p(sig), ADP_IN_DEVICE | (ADP_MVS_F64 if f64 else 0), int(n), int(L)
+        a = np.asarray(sig)
+        if a.dtype not in (np.float32, np.float64) or not a.flags.c_contiguous or a.ndim != 2:
+            raise ValueError("signals: a C-contiguous float32 or float64 [n, L] array")
+        return a.ctypes.data_as(C.c_void_p), ADP_MVS_F64 if a.dtype == np.float64 else 0, a.shape[0], a.shape[1]
+
+    @staticmethod
+    def _i64(a, n, what):
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        if a.size != n:
+            raise ValueError("%s needs one entry per read" % what)
+        return a
+
+    def mvs_check(self, sig, lens, adapter_ends, polya_ends, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None,
+                  f64: bool = False):
+        """adp_mvs_check -> (info int32 [n, 8], vals float64 [n, 5])"""
+        p, flags, n, L = self._mvs_in(sig, n, L, f64)
+        lens = self._i32(lens, n, "lens")
+        ae, pe = self._i64(adapter_ends, n, "adapter_ends"), self._i64(polya_ends, n, "polya_ends")
+        info = np.zeros((n, 8), dtype=np.int32)
+        vals = np.zeros((n, 5), dtype=np.float64)
+        self._check(self.lib.adp_mvs_check(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, ae, pe)), int(n), int(L), C.byref(args),
+                                           flags, info.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p)))
+        return info, vals
+
+    def mvs_detect_at_loc(self, sig, lens, locs, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
+        """adp_mvs_detect_at_loc -> (info int32 [n, 8], idx int64 [n], vals float64 [n, 5])"""
+        p, flags, n, L = self._mvs_in(sig, n, L, f64)
+        lens = self._i32(lens, n, "lens")
+        lo = self._i64(locs, n, "locs")
+        info = np.zeros((n, 8), dtype=np.int32)
+        idx = np.zeros(n, dtype=np.int64)
+        vals = np.zeros((n, 5), dtype=np.float64)
+        self._check(self.lib.adp_mvs_detect_at_loc(self._h, p, lens.ctypes.data_as(C.c_void_p), lo.ctypes.data_as(C.c_void_p), int(n), int(L),
+                                                   C.byref(args), flags, info.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                   vals.ctypes.data_as(C.c_void_p)))
+        return info, idx, vals
+
+    def mvs_detect(self, sig, lens, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
+        """adp_mvs_detect -> int64 [n] (0: no poly(A) found)"""
+        p, flags, n, L = self._mvs_in(sig, n, L, f64)
+        lens = self._i32(lens, n, "lens")
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.adp_mvs_detect(self._h, p, lens.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
+                                            out.ctypes.data_as(C.c_void_p)))
         return out
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):

@@ -388,6 +388,39 @@ int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, 
 int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, int n_reads, int L, const adp_spike_args *args, int flags,
                        int64_t *out);
 
+/* The reference's MVS poly(A) module (adapted/detect/mvs.py), batched on signals [n_reads, L] float32, or float64 with
+ * ADP_MVS_F64 (read r valid in [0, len[r])), one wave per read (adapted_amd/csrc/mvs_api.h).  len and the per-read positions:
+ * HOST int32 / int64 [n_reads], checked here (0 <= len <= L, positions >= 0).  flags: ADP_IN_DEVICE -- `sig` is a device
+ * pointer.  Windows must be >= 1 and search_increment_step >= 1 (the reference never returns otherwise).  Outputs: host memory.
+ *
+ * adp_mvs_check: mean_var_shift_polyA_check (mvs.py:45-158) with the mvs_polya fields and both flags.
+ * adp_mvs_detect_at_loc: mean_var_shift_polyA_detect_at_loc (mvs.py:181-338) with the mvs_polya fields and less_signal_ok.
+ *   info_out int32 [n_reads, 8]: 0 the result (check_vector.all() / the accept), 1 the check vector (bit j: entry j True; check
+ *   only), 2 status (0; 1 the reference raises IndexError; 2 bottleneck's ValueError), 3 and 4 the exception's numbers (ValueError:
+ *   the window and the slice size; IndexError: the index and the size, -1 and 0 for np.percentile of an empty slice), 5 (check
+ *   only) set when the read got past the early outs.  vals_out float64 [n_reads, 5]: mean, var, poly(A) median, local range, median shift as the reference returns them
+ *   (0.0 on the early outs).  idx_out int64 [n_reads]: detect_at_loc's index (0: none).
+ * adp_mvs_detect: mean_var_shift_polyA_detect (mvs.py:341-426) with the streaming fields (s_*) -> out int64 [n_reads] (0: none). */
+typedef struct adp_mvs_args {
+    /* [mvs_polya] */
+    double pA_mean_range[2], pA_var_range[2], median_shift_range[2], polyA_med_range[2], polyA_local_range[2];
+    int32_t search_window, pA_mean_window, pA_var_window, median_shift_window, polyA_window;
+    int32_t less_signal_ok, windowed_stats;
+    /* [streaming] */
+    int32_t min_obs_adapter, min_obs_post_loc, search_increment_step;
+    int32_t s_pA_mean_window, s_pA_var_window, s_median_shift_window, s_polyA_window;
+    int32_t pad;
+    double s_pA_mean_range[2], s_pA_var_range[2], s_median_shift_range[2], s_polyA_med_range[2], s_polyA_local_range[2];
+} adp_mvs_args;
+#define ADP_MVS_F64 2048
+int adp_sizeof_mvs_args(void);
+int adp_mvs_check(adp_handle *h, const void *sig, const int32_t *len, const int64_t *adapter_end, const int64_t *polya_end, int n_reads,
+                  int L, const adp_mvs_args *args, int flags, int32_t *info_out, double *vals_out);
+int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, const int64_t *loc, int n_reads, int L,
+                          const adp_mvs_args *args, int flags, int32_t *info_out, int64_t *idx_out, double *vals_out);
+int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *args, int flags,
+                   int64_t *out);
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);

@@ -1,0 +1,136 @@
+"""The reference's MVS poly(A) module (adapted/detect/mvs.py): the CPU restatement (tests/mvs_module_restated.py) against the
+vectors the REAL reference produced (tests/golden/mvs_module.npz, tools/gen_mvs_module_golden.py) bit for bit, its float32
+recurrences against oracle/bn_shim.py, and the drop-in's names, signatures and imports."""
+import inspect
+import os
+import sys
+import types
+import warnings
+
+import numpy as np
+import pytest
+
+import mvs_module_cases as M
+import mvs_module_restated as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "mvs_module.npz")
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+RESTATED = types.SimpleNamespace(mean_var_shift_polyA_check=R.check, mean_var_shift_polyA_detect_at_loc=R.detect_at_loc,
+                                 mean_var_shift_polyA_detect=R.detect)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def _params(case):
+    from adapted_amd.config.schema import MVSPolyAConfig, StreamingConfig
+
+    return M.mvs_params(MVSPolyAConfig, case), M.stream_params(StreamingConfig, case)
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in M.CASES])
+def test_restated_matches_reference(gold, name):
+    case = M.by_name(name)
+    x64, ae, pe, loc = M.inputs(case)
+    mp, sp = _params(case)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for dt in M.DTYPES:
+            x = M.as_dtype(x64, dt)
+            for key, fn, kw in M.CALLS:
+                want = str(gold["%s.%s.%s" % (name, dt, key)])
+                assert M.call(RESTATED, fn, x, ae, pe, loc, mp, sp, kw) == want, (dt, key)
+
+
+def test_fixture_covers_every_branch(gold):
+    """the cases reach each early out, both exceptions, accepts and rejects of all three functions"""
+    vals = [str(gold[k]) for k in gold.files if k.count(".") >= 2]
+    det = [str(gold[k]) for k in gold.files if k.endswith(".detect")]
+    assert any(v.startswith("raise IndexError: index 200") for v in vals)
+    assert any(v.startswith("raise IndexError: index -1") for v in vals)
+    assert any(v.startswith("raise ValueError: Moving window") for v in vals)
+    assert any(v == "int:0" for v in det) and any(v.startswith("np.int64:") for v in det)
+    assert str(gold["match_at_offset.f32.detect"]) == "np.int64:2600"  # min_obs_adapter + offset: the match at `offset` itself
+    assert str(gold["post_loc.f32.detect"]) == "int:0"
+    assert any(v.startswith("(bool:True, int:") for v in vals) and any(v.startswith("(bool:False, int:0,") for v in vals)
+    assert any(v.startswith("(np.bool:True, ndarray[bool]") for v in vals)
+    assert any(v.startswith("(bool:False, ndarray[bool][False, False, False, False, False], float:0x0.0p+0") for v in vals)
+
+
+@pytest.mark.parametrize("w", [1, 20, 100, 333])
+def test_float32_recurrences_match_bn_shim(w):
+    from oracle import bn_shim
+
+    x, _, _ = M.pa_read(3, 4000, nan_at=(50, 51, 700, 2999))
+    x = x.astype(np.float32)
+    for ours, shim in ((R.move_mean, bn_shim.move_mean), (R.move_var, bn_shim.move_var)):
+        got, want = ours(x, w), shim(x, w)
+        assert got.dtype == np.float32 and np.array_equal(got, want, equal_nan=True)
+
+
+def test_float64_recurrences_run_in_float64():
+    x, _, _ = M.pa_read(4, 3000)
+    m64, m32 = R.move_mean(x, 20), R.move_mean(x.astype(np.float32), 20)
+    assert m64.dtype == np.float64 and np.allclose(m64[19:], m32[19:], rtol=1e-5)
+    assert not np.array_equal(m64[19:], m32[19:].astype(np.float64))
+
+
+def test_module_names_and_signatures(gold):
+    from adapted_amd.detect import mvs
+
+    assert sorted(str(s) for s in gold["names"]) == sorted(M.NAMES)
+    for nm in M.NAMES:
+        assert callable(getattr(mvs, nm))
+    assert M.signature_rows(mvs) == [str(s) for s in gold["signatures"]]
+    for nm in ("mean_var_shift_polyA_check_batch", "mean_var_shift_polyA_detect_at_loc_batch", "mean_var_shift_polyA_detect_batch"):
+        assert callable(getattr(mvs, nm))
+
+
+def test_utils_match_reference_semantics():
+    from adapted_amd.detect import utils
+
+    assert utils.LOCAL_RANGE_PCTLS == (85, 15)
+    assert list(inspect.signature(utils.in_range).parameters) == ["val", "min", "max"]
+    assert list(inspect.signature(utils.range_is_empty).parameters) == ["range"]
+    assert utils.in_range(5.0, None, None) is True and utils.in_range(float("nan"), None, None) is False
+    assert utils.in_range(np.float32(0.1), None, 0.1) is False  # (float64 comparison: float32(0.1) > 0.1)
+    got = utils.in_range(np.array([1.0, np.nan, 3.0], dtype=np.float32), 2.0, None)
+    assert got.dtype == bool and got.tolist() == [False, False, True]
+    assert utils.range_is_empty(None) and utils.range_is_empty((None, None)) and utils.range_is_empty((-np.inf, np.inf))
+    assert not utils.range_is_empty((0.0, None))
+    from adapted_amd.detect import mvs
+
+    assert mvs.in_range is utils.in_range and mvs.LOCAL_RANGE_PCTLS is utils.LOCAL_RANGE_PCTLS
+
+
+def test_host_side_validation():
+    from adapted_amd.config.schema import MVSPolyAConfig, StreamingConfig
+    from adapted_amd.detect import mvs
+
+    with pytest.raises(TypeError):
+        mvs._as_rows(np.zeros((2, 10), dtype=np.complex64), [10, 10], None, None, np.float32)
+    with pytest.raises(ValueError):
+        mvs.mean_var_shift_polyA_check(np.zeros(100, np.float32), -1, 50, MVSPolyAConfig())
+    with pytest.raises(ValueError):
+        mvs.mean_var_shift_polyA_detect_at_loc(np.zeros(100, np.float32), -5)
+    bad = StreamingConfig()
+    bad.search_increment_step = 0
+    with pytest.raises(ValueError):
+        mvs.mean_var_shift_polyA_detect(np.zeros(100, np.float32), bad)
+    x, lens, f64 = mvs._as_rows(np.zeros((3, 7), dtype=np.int16), [7, 0, 3], None, None, np.float32)
+    assert x.dtype == np.float64 and f64
+
+
+def test_struct_size_matches_library():
+    """struct adp_mvs_args: the ctypes mirror in adapted_amd/lib.py against the library's own size"""
+    import ctypes
+
+    from adapted_amd import lib
+
+    L = lib.load()
+    assert L.adp_sizeof_mvs_args() == ctypes.sizeof(lib.AdpMvsArgs) == 224
