@@ -42,10 +42,17 @@ static thread_local std::string g_err;
             return ADP_ERR_HIP;                                                              \
         }                                                                                    \
     } while (0)
+// a helper's non-zero return code (g_err already set) ends the caller
+#define RCCHK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
+// grow-only device memory, released with its owner (not copyable: two owners would free it twice)
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return 0;
@@ -87,10 +94,7 @@ struct adp_handle {
     DevBuf rng0;      // per-read [0, T) ranges of the single-read layout
     // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
-    DevBuf tr_buf, tr_meta; // adp_c_llr_trace: staging of host arrays
-    DevBuf cd_buf, cd_meta; // adp_c_llr_detect / adp_c_llr_best_split: sums and staging; segments, chunk winners, per-read state
-    DevBuf lp_buf, lp_meta, lp_sum, lp_pk; // adp_llr_trace_*: trace staging; per-read arrays; block summaries; maxima + work lists
-    DevBuf mv_buf, mv_meta, mv_scr; // adp_mvs_*: signal staging; per-read inputs and outputs; per-slot series scratch
+    DevBuf ws;              // the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): one call's staging and scratch (ws_carve)
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
@@ -284,11 +288,6 @@ int adp_destroy(adp_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipEvent_t e : h->ev_sync) (void)hipEventDestroy(e);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
-    h->mbstat.release(); h->mbparams.release(); h->sphead.release();
-    DevBuf *all[] = {&h->cnn_actf[0], &h->cnn_actf[1], &h->series_plan, &h->cnn_wsp, &h->tr_buf, &h->tr_meta, &h->cd_buf, &h->cd_meta, &h->lp_buf, &h->lp_meta, &h->lp_sum, &h->lp_pk, &h->mv_buf, &h->mv_meta, &h->mv_scr, &h->op_arena, &h->op_used, &h->cstat, &h->cnn_w, &h->cnn_act[0], &h->cnn_act[1], &h->cnn_x, &h->cnn_sc, &h->ct_st, &h->ct_lnz, &h->ct_ap, &h->rng0, &h->mbs, &h->ghist, &h->gbelow, &h->gcnt, &h->cbuf, &h->fz, &h->fcnt, &h->n1heavy, &h->ct_pk, &h->ct_pv, &h->ct_out, &h->gstat, &h->down, &h->nvalid, &h->ck, &h->tail, &h->trace, &h->bmax, &h->bmin,
-                     &h->t1, &h->adapter_idx, &h->polya_idx, &h->bounds, &h->topk_none, &h->rows, &h->preq, &h->series, &h->have_series, &h->vscratch, &h->pk, &h->pkv, &h->npk,
-                     &h->mk, &h->st, &h->sp, &h->any_none, &h->sig_stage, &h->len_stage, &h->bounds_stage};
-    for (DevBuf *b : all) b->release();
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipStreamDestroy(h->stream3); }
@@ -297,7 +296,7 @@ int adp_destroy(adp_handle *h)
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h; // (the DevBufs free their memory)
     return ADP_OK;
 }
 
@@ -354,6 +353,11 @@ struct Scope {
     }
     ~Scope() { if (b) (void)hipEventRecord(b, st); }
 };
+
+// what a call reports through adp_kernel_times starts empty (the repeats of a call reset it too)
+static void reset_profile(adp_handle *h) { h->prof.clear(); h->ev_used = 0; h->last_grouped = false; }
+// a call that works on the device: the handle's device current, reset_profile
+static int begin_call(adp_handle *h) { HIPCHK(hipSetDevice(h->device)); reset_profile(h); return ADP_OK; }
 
 // ---- input staging -----------------------------------------------------------------
 static int stage_inputs(adp_handle *h, const float *signals, const int32_t *full_len, int n, int m, int flags,
@@ -914,7 +918,7 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
         if (rc < 0) return rc;
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+        reset_profile(h);
     }
     return ADP_OK;
 }
@@ -925,10 +929,7 @@ static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full
     if (!h || !signals || !full_len || n < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ && minibatch != 1) { g_err = "the single-read layout normalises every read on its own: minibatch must be 1"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear();
-    h->ev_used = 0;
-    h->last_grouped = false;
+    RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -962,10 +963,7 @@ int adp_detect_llr_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "the single-read layout takes float32 input"; return ADP_ERR_UNSUPPORTED; }
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear();
-    h->ev_used = 0;
-    h->last_grouped = false;
+    RCCHK(begin_call(h));
     // (samples at or beyond min(full_len, m) read as NaN: the padding is implied, so the passes always stop at a read's end)
     return llr_pipeline_t(h, SigI16{raw, scale, offset, full_len}, full_len, n_reads, m, minibatch, flags | ADP_TAILS_NAN, rows_out, mb_status, 8);
 }
@@ -979,6 +977,66 @@ __global__ void k_debug_log(const double *in, double *out, int n)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = log_cr_impl(in[i], lt, [](double u) { return log(u); });
 }
+
+} // extern "C"
+
+// ---- the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): workspace, staging and per-read checks
+
+// 256-byte aligned pieces of the handle's workspace `ws`; a Carve without a base only adds up their sizes
+struct Carve {
+    char *base = nullptr;
+    size_t off = 0;
+    // `count` elements of T -- none (nullptr) unless `want`
+    template <class T> T *take(size_t count, bool want = true)
+    {
+        if (!want) return nullptr;
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// a call's pieces of the workspace: `pieces(Carve &)` takes them all and runs twice -- first to add up the sizes, so that ws
+// grows once, before anything is enqueued (ensure() moves the buffer), then to hand out the pointers.  Every module call
+// completes before it returns, so the next one takes the same memory: a process holds the largest single call's need.
+template <class F> static int ws_carve(adp_handle *h, F &&pieces)
+{
+    Carve c;
+    pieces(c);
+    if (h->ws.ensure(c.off)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    c = Carve{h->ws.as<char>(), 0};
+    pieces(c);
+    return ADP_OK;
+}
+
+// copies on the handle's stream: a host array in, a result back
+static int h2d(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream)); return ADP_OK; }
+static int d2h(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream)); return ADP_OK; }
+
+// the device pointer of an input that is device memory with ADP_IN_DEVICE, else host memory: then copied to `piece` (a
+// workspace piece taken for it only in that case)
+template <class T> static int stage_in(adp_handle *h, int flags, const T *src, T *piece, size_t bytes, const T **dev)
+{
+    if (flags & ADP_IN_DEVICE) { *dev = src; return ADP_OK; }
+    *dev = piece;
+    return h2d(h, piece, src, bytes);
+}
+
+// the per-read checks (host arrays of n entries): lo <= a <= hi; 0 <= len <= L; 0 <= start <= end <= len; positions in [0, 2^40]
+template <class T> static bool all_in(const T *a, int n, T lo, T hi)
+{
+    for (int r = 0; r < n; r++) if (a[r] < lo || a[r] > hi) return false;
+    return true;
+}
+static bool lens_ok(const int32_t *len, int n, int L) { return all_in<int32_t>(len, n, 0, L); }
+static bool spans_ok(const int32_t *start, const int32_t *end, const int32_t *len, int n)
+{
+    for (int r = 0; r < n; r++) if (start[r] < 0 || start[r] > end[r] || end[r] > len[r]) return false;
+    return true;
+}
+static bool positions_ok(const int64_t *p, int n) { return all_in<int64_t>(p, n, 0, (int64_t)1 << 40); }
+
+extern "C" {
 
 // c_llr_trace / c_llr_trace_gains / _gains for a batch of float64 signals (trace_api.h)
 int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const int32_t *start, const int32_t *end, int n_reads,
@@ -997,51 +1055,41 @@ int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const 
         if (a.adapter_early_stop_stride < 1 || a.adapter_early_stop_window < 0) { g_err = "early-stop window / stride out of range"; return ADP_ERR_INVALID; }
         if (a.adapter_early_stop_stride % a.stride) { g_err = "early-stop stride is not a multiple of stride (the reference asserts, _c_llr.pyx:102)"; return ADP_ERR_INVALID; }
     }
-    for (int r = 0; r < n_reads; r++)
-        if (len[r] < 0 || len[r] > L || start[r] < 0 || start[r] > end[r] || end[r] > len[r]) { g_err = "need 0 <= start <= end <= len <= L for every read"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    const size_t row = (size_t)L * 8, mat = row * n_reads;
-    // device staging: [raw | c | c2 | gain] as far as the caller's arrays are host memory
-    const int need = (in_dev ? 0 : (from_sums ? 2 : 1)) + ((!from_sums && (!c_io || !out_dev)) ? 2 : 0) + (out_dev ? 0 : 1);
-    if (need && h->tr_buf.ensure(mat * need)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    if (h->tr_meta.ensure((size_t)n_reads * 12)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    double *pool = h->tr_buf.as<double>();
-    auto take = [&]() { double *p = pool; pool += (size_t)L * n_reads; return p; };
-    int32_t *dlen = h->tr_meta.as<int32_t>(), *dstart = dlen + n_reads, *dend = dstart + n_reads;
-    HIPCHK(hipMemcpyAsync(dlen, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dstart, start, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dend, end, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+    if (!lens_ok(len, n_reads, L) || !spans_ok(start, end, len, n_reads)) { g_err = "need 0 <= start <= end <= len <= L for every read"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t cells = (size_t)L * n_reads, mat = cells * 8, n4 = (size_t)n_reads * 4;
+    // the sums a raw call computes go to the caller's arrays when those are device outputs, else to the workspace
+    const bool own_c = !from_sums && !(c_io && out_dev);
+    int32_t *dlen, *dstart, *dend; double *s_raw, *s_c, *s_c2, *w_c, *w_c2, *w_g;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dlen = w.take<int32_t>(n_reads); dstart = w.take<int32_t>(n_reads); dend = w.take<int32_t>(n_reads);
+        s_raw = w.take<double>(cells, !from_sums && !in_dev);
+        s_c = w.take<double>(cells, from_sums && !in_dev); s_c2 = w.take<double>(cells, from_sums && !in_dev);
+        w_c = w.take<double>(cells, own_c); w_c2 = w.take<double>(cells, own_c);
+        w_g = w.take<double>(cells, !out_dev);
+    }));
+    RCCHK(h2d(h, dlen, len, n4)); RCCHK(h2d(h, dstart, start, n4)); RCCHK(h2d(h, dend, end, n4));
     const double *dc, *dc2;
-    double *dc_w = nullptr, *dc2_w = nullptr;
     if (from_sums) {
-        if (in_dev) { dc = c_io; dc2 = c2_io; }
-        else {
-            double *t0 = take(), *t1 = take();
-            HIPCHK(hipMemcpyAsync(t0, c_io, mat, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(t1, c2_io, mat, hipMemcpyHostToDevice, h->stream));
-            dc = t0; dc2 = t1;
-        }
+        RCCHK(stage_in(h, flags, c_io, s_c, mat, &dc));
+        RCCHK(stage_in(h, flags, c2_io, s_c2, mat, &dc2));
     } else {
-        const double *draw = raw;
-        if (!in_dev) { double *t = take(); HIPCHK(hipMemcpyAsync(t, raw, mat, hipMemcpyHostToDevice, h->stream)); draw = t; }
-        if (c_io && out_dev) { dc_w = c_io; dc2_w = c2_io; } else { dc_w = take(); dc2_w = take(); }
+        const double *draw;
+        RCCHK(stage_in(h, flags, raw, s_raw, mat, &draw));
+        double *wc = own_c ? w_c : c_io, *wc2 = own_c ? w_c2 : c2_io;
         { Scope s(h, "k_trace_cumsum");
-          hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, dc_w, dc2_w); }
-        dc = dc_w; dc2 = dc2_w;
+          hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, wc, wc2); }
+        dc = wc; dc2 = wc2;
     }
-    double *dg = out_dev ? gain_out : take();
+    double *dg = out_dev ? gain_out : w_g;
     TraceArgs ta = {a.min_obs, a.border_trim, a.stride, a.adapter_early_stopping, a.adapter_early_stop_window, a.adapter_early_stop_stride,
                     a.polya_early_stopping, a.polya_early_stop_window, a.polya_early_stop_stride};
     { Scope s(h, "k_trace_gains");
       hipLaunchKernelGGL(k_trace_gains, dim3(n_reads), dim3(64), 0, h->stream, dc, dc2, dlen, dstart, dend, L, ta, dg); }
     HIPCHK(hipGetLastError());
     if (!out_dev) {
-        HIPCHK(hipMemcpyAsync(gain_out, dg, mat, hipMemcpyDeviceToHost, h->stream));
-        if (!from_sums && c_io) {
-            HIPCHK(hipMemcpyAsync(c_io, dc_w, mat, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(c2_io, dc2_w, mat, hipMemcpyDeviceToHost, h->stream));
-        }
+        RCCHK(d2h(h, gain_out, dg, mat));
+        if (!from_sums && c_io) { RCCHK(d2h(h, c_io, dc, mat)); RCCHK(d2h(h, c2_io, dc2, mat)); }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
@@ -1058,46 +1106,28 @@ static void cd_splits(adp_handle *h, const double *dc, const double *dc2, int L,
       hipLaunchKernelGGL(k_split_reduce, dim3(n_seg), dim3(64), 0, h->stream, segs, nck, part_g, part_x, st_x, st_g); }
 }
 
-// the small per-call arrays of a detect / best-split call in cd_meta: segments (2 per read), chunk winners, state, rows
-struct CdMeta { CdSeg *segs, *psegs; double *part_g, *st_g, *med; int32_t *part_x, *st_x, *res, *len; };
-static int cd_meta(adp_handle *h, int n_reads, int L, CdMeta &m)
-{
-    const size_t nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK, n = (size_t)n_reads;
-    const size_t sz[] = {2 * n * sizeof(CdSeg), n * sizeof(CdSeg), 2 * n * nck * 8, 4 * n * 8, 4 * n * 8, 2 * n * nck * 4, 4 * n * 4, 4 * n * 4, n * 4};
-    size_t tot = 0;
-    for (size_t b : sz) tot += (b + 255) & ~(size_t)255;
-    if (h->cd_meta.ensure(tot)) return -1;
-    char *p = h->cd_meta.as<char>();
-    void *out[9];
-    for (int i = 0; i < 9; i++) { out[i] = p; p += (sz[i] + 255) & ~(size_t)255; }
-    m.segs = (CdSeg *)out[0]; m.psegs = (CdSeg *)out[1]; m.part_g = (double *)out[2]; m.st_g = (double *)out[3]; m.med = (double *)out[4];
-    m.part_x = (int32_t *)out[5]; m.st_x = (int32_t *)out[6]; m.res = (int32_t *)out[7]; m.len = (int32_t *)out[8];
-    return 0;
-}
-
 // _best_split (_c_llr.pyx:40-64) for a batch of rows of given sums: one segment per row
 int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const int32_t *len, const int32_t *start, const int32_t *end,
                          const int32_t *offset_head, const int32_t *offset_tail, int n_reads, int L, int flags, int64_t *x_out, double *gain_out)
 {
     if (!h || !c || !c2 || !len || !start || !end || !offset_head || !offset_tail || !x_out || !gain_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    for (int r = 0; r < n_reads; r++)
-        if (len[r] < 0 || len[r] > L || start[r] < 0 || start[r] > end[r] || end[r] > len[r] || offset_head[r] < 0 || offset_tail[r] < 0) {
-            g_err = "need 0 <= start <= end <= len <= L and offsets >= 0 for every row"; return ADP_ERR_INVALID;
-        }
-    const bool in_dev = (flags & ADP_IN_DEVICE) != 0;
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    CdMeta m;
-    if (cd_meta(h, n_reads, L, m)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    const size_t mat = (size_t)L * 8 * n_reads;
-    const double *dc = c, *dc2 = c2;
-    if (!in_dev) {
-        if (h->cd_buf.ensure(2 * mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-        double *t0 = h->cd_buf.as<double>(), *t1 = t0 + (size_t)L * n_reads;
-        HIPCHK(hipMemcpyAsync(t0, c, mat, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(t1, c2, mat, hipMemcpyHostToDevice, h->stream));
-        dc = t0; dc2 = t1;
+    if (!lens_ok(len, n_reads, L) || !spans_ok(start, end, len, n_reads) || !all_in(offset_head, n_reads, 0, INT32_MAX) ||
+        !all_in(offset_tail, n_reads, 0, INT32_MAX)) {
+        g_err = "need 0 <= start <= end <= len <= L and offsets >= 0 for every row"; return ADP_ERR_INVALID;
     }
+    const bool in_dev = (flags & ADP_IN_DEVICE) != 0;
+    RCCHK(begin_call(h));
+    const size_t cells = (size_t)L * n_reads, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
+    double *s_c, *s_c2, *part_g, *st_g; int32_t *part_x, *st_x; CdSeg *dsegs;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dsegs = w.take<CdSeg>(n_reads);
+        part_g = w.take<double>(n_reads * nck); part_x = w.take<int32_t>(n_reads * nck);
+        st_x = w.take<int32_t>(n_reads); st_g = w.take<double>(n_reads);
+        s_c = w.take<double>(cells, !in_dev); s_c2 = w.take<double>(cells, !in_dev);
+    }));
+    const double *dc, *dc2;
+    RCCHK(stage_in(h, flags, c, s_c, cells * 8, &dc));
+    RCCHK(stage_in(h, flags, c2, s_c2, cells * 8, &dc2));
     std::vector<CdSeg> segs(n_reads);
     for (int r = 0; r < n_reads; r++) {
         long lo = (long)start[r] + offset_head[r], hi = (long)end[r] - offset_tail[r];
@@ -1105,12 +1135,12 @@ int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const
         if (hi < lo) hi = lo; // (an empty range: the reference's loop does not run)
         segs[r] = CdSeg{r, start[r], end[r], (int32_t)lo, (int32_t)hi, r};
     }
-    HIPCHK(hipMemcpyAsync(m.segs, segs.data(), segs.size() * sizeof(CdSeg), hipMemcpyHostToDevice, h->stream));
-    cd_splits(h, dc, dc2, L, m.segs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+    RCCHK(h2d(h, dsegs, segs.data(), segs.size() * sizeof(CdSeg)));
+    cd_splits(h, dc, dc2, L, dsegs, n_reads, part_g, part_x, st_x, st_g);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> x(n_reads);
-    HIPCHK(hipMemcpyAsync(x.data(), m.st_x, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(gain_out, m.st_g, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    RCCHK(d2h(h, x.data(), st_x, (size_t)n_reads * 4));
+    RCCHK(d2h(h, gain_out, st_g, (size_t)n_reads * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int r = 0; r < n_reads; r++) x_out[r] = x[r];
     return ADP_OK;
@@ -1122,62 +1152,59 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
 {
     if (!h || !raw || !len || !rows_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (min_obs_adapter < 0 || border_trim < 0 || min_obs_polya < 0) { g_err = "offsets must be >= 0"; return ADP_ERR_INVALID; }
-    for (int r = 0; r < n_reads; r++)
-        if (len[r] < 1 || len[r] > L) { g_err = "need 1 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    if (!all_in(len, n_reads, 1, L)) { g_err = "need 1 <= len <= L for every read"; return ADP_ERR_INVALID; }
     const bool in_dev = (flags & ADP_IN_DEVICE) != 0, f32 = (flags & ADP_CLLR_F32) != 0, polya = (flags & ADP_CLLR_POLYA) != 0;
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    CdMeta m;
-    if (cd_meta(h, n_reads, L, m)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    const size_t cells = (size_t)L * n_reads, esz = f32 ? 4 : 8;
-    // [c | c2 | raw staging]
-    const size_t need = 2 * cells * 8 + (in_dev ? 0 : ((cells * esz + 255) & ~(size_t)255));
-    if (h->cd_buf.ensure(need)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    double *dc = h->cd_buf.as<double>(), *dc2 = dc + cells;
-    const void *draw = raw;
-    if (!in_dev) {
-        void *t = dc2 + cells;
-        HIPCHK(hipMemcpyAsync(t, raw, cells * esz, hipMemcpyHostToDevice, h->stream));
-        draw = t;
-    }
-    HIPCHK(hipMemcpyAsync(m.len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+    RCCHK(begin_call(h));
+    const size_t n = n_reads, cells = (size_t)L * n, esz = f32 ? 4 : 8, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
+    // the sums, the staged signal; segments (2 per read), chunk winners, the per-read state
+    double *dc, *dc2, *part_g, *st_g, *med; int32_t *part_x, *st_x, *res, *dlen; CdSeg *segs, *psegs; void *s_raw;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dc = w.take<double>(cells); dc2 = w.take<double>(cells); s_raw = w.take<char>(cells * esz, !in_dev);
+        segs = w.take<CdSeg>(2 * n); psegs = w.take<CdSeg>(n);
+        part_g = w.take<double>(2 * n * nck); part_x = w.take<int32_t>(2 * n * nck);
+        st_x = w.take<int32_t>(4 * n); st_g = w.take<double>(4 * n); med = w.take<double>(4 * n); res = w.take<int32_t>(4 * n);
+        dlen = w.take<int32_t>(n);
+    }));
+    const void *draw;
+    RCCHK(stage_in(h, flags, raw, s_raw, cells * esz, &draw));
+    RCCHK(h2d(h, dlen, len, n * 4));
     const CdArgs a = {min_obs_adapter, border_trim, min_obs_polya, polya ? 1 : 0};
     const int rb = (n_reads + 255) / 256;
     { Scope s(h, "k_trace_cumsum");
-      if (f32) hipLaunchKernelGGL(k_trace_cumsum<float>, dim3(n_reads), dim3(64), 0, h->stream, (const float *)draw, m.len, L, n_reads, dc, dc2);
-      else hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, (const double *)draw, m.len, L, n_reads, dc, dc2); }
+      if (f32) hipLaunchKernelGGL(k_trace_cumsum<float>, dim3(n_reads), dim3(64), 0, h->stream, (const float *)draw, dlen, L, n_reads, dc, dc2);
+      else hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, (const double *)draw, dlen, L, n_reads, dc, dc2); }
     { Scope s(h, "k_cd_plan");
-      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 0, m.len, n_reads, a, m.st_x, m.segs); }
-    cd_splits(h, dc, dc2, L, m.segs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 0, dlen, n_reads, a, st_x, segs); }
+    cd_splits(h, dc, dc2, L, segs, n_reads, part_g, part_x, st_x, st_g);
     { Scope s(h, "k_cd_plan");
-      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 1, m.len, n_reads, a, m.st_x, m.segs); }
-    cd_splits(h, dc, dc2, L, m.segs, 2 * n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 1, dlen, n_reads, a, st_x, segs); }
+    cd_splits(h, dc, dc2, L, segs, 2 * n_reads, part_g, part_x, st_x, st_g);
     { Scope s(h, "k_cd_medians");
-      if (f32) hipLaunchKernelGGL(k_cd_medians<float>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const float *)draw, m.len, L, a, m.st_x, m.st_g, m.res, m.med, m.psegs);
-      else hipLaunchKernelGGL(k_cd_medians<double>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const double *)draw, m.len, L, a, m.st_x, m.st_g, m.res, m.med, m.psegs); }
+      if (f32) hipLaunchKernelGGL(k_cd_medians<float>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const float *)draw, dlen, L, a, st_x, st_g, res, med, psegs);
+      else hipLaunchKernelGGL(k_cd_medians<double>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const double *)draw, dlen, L, a, st_x, st_g, res, med, psegs); }
     if (polya) {
-        cd_splits(h, dc, dc2, L, m.psegs, n_reads, m.part_g, m.part_x, m.st_x, m.st_g);
+        cd_splits(h, dc, dc2, L, psegs, n_reads, part_g, part_x, st_x, st_g);
         { Scope s(h, "k_cd_finish");
-          hipLaunchKernelGGL(k_cd_finish, dim3(rb), dim3(256), 0, h->stream, n_reads, m.st_x, m.res); }
+          hipLaunchKernelGGL(k_cd_finish, dim3(rb), dim3(256), 0, h->stream, n_reads, st_x, res); }
     }
     HIPCHK(hipGetLastError());
-    std::vector<int32_t> res((size_t)n_reads * 4), sx;
-    std::vector<double> sg, med;
-    HIPCHK(hipMemcpyAsync(res.data(), m.res, res.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    if (splits_out) { sx.resize((size_t)n_reads * 4); HIPCHK(hipMemcpyAsync(sx.data(), m.st_x, sx.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
+    std::vector<int32_t> hres(n * 4), sx;
+    std::vector<double> sg, hmed;
+    RCCHK(d2h(h, hres.data(), res, n * 16));
+    if (splits_out) { sx.resize(n * 4); RCCHK(d2h(h, sx.data(), st_x, n * 16)); }
     if (stats_out) {
-        sg.resize((size_t)n_reads * 4); med.resize((size_t)n_reads * 4);
-        HIPCHK(hipMemcpyAsync(sg.data(), m.st_g, sg.size() * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(med.data(), m.med, med.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        sg.resize(n * 4); hmed.resize(n * 4);
+        RCCHK(d2h(h, sg.data(), st_g, n * 32));
+        RCCHK(d2h(h, hmed.data(), med, n * 32));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < res.size(); i++) rows_out[i] = res[i];
+    for (size_t i = 0; i < hres.size(); i++) rows_out[i] = hres[i];
     for (int r = 0; r < n_reads; r++) {
-        const bool searched = res[r * 4 + 3] == 3 && res[r * 4 + 1] != 0;
+        const bool searched = hres[r * 4 + 3] == 3 && hres[r * 4 + 1] != 0;
         if (splits_out) for (int k = 0; k < 4; k++) splits_out[r * 4 + k] = (k == 3 && !searched) ? -1 : sx[r * 4 + k];
         if (stats_out) for (int k = 0; k < 4; k++) {
             stats_out[r * 8 + k] = (k == 3 && !searched) ? 0.0 : sg[r * 4 + k];
-            stats_out[r * 8 + 4 + k] = med[r * 4 + k];
+            stats_out[r * 8 + 4 + k] = hmed[r * 4 + k];
         }
     }
     return ADP_OK;
@@ -1185,42 +1212,11 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
 
 // ---- the reference's Python LLR module (adapted/detect/llr.py) on device traces (trace_peaks_api.h)
 
-// the trace rows on the device (staged when they are host memory) and the per-read int32 arrays copied to lp_meta
-static int lp_stage(adp_handle *h, const double *trace, int n_reads, int L, int flags, std::initializer_list<const int32_t *> ints,
-                    size_t out_bytes, const double **dtr, std::vector<int32_t *> &dints, void **dout)
+// block summaries of the trace rows: nsum blocks of SUMBLK points per row
+static void trace_blocksum(adp_handle *h, const double *dtr, const int32_t *dlen, int n_reads, int L, int nsum, int sanitize, double *bx, double *bn)
 {
-    const size_t mat = (size_t)L * 8 * n_reads;
-    if (!(flags & ADP_IN_DEVICE)) {
-        if (h->lp_buf.ensure(mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-        HIPCHK(hipMemcpyAsync(h->lp_buf.p, trace, mat, hipMemcpyHostToDevice, h->stream));
-        *dtr = h->lp_buf.as<double>();
-    } else *dtr = trace;
-    const size_t isz = ((size_t)n_reads * 4 + 255) & ~(size_t)255;
-    if (h->lp_meta.ensure(isz * ints.size() + out_bytes)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    char *p = h->lp_meta.as<char>();
-    for (const int32_t *a : ints) {
-        HIPCHK(hipMemcpyAsync(p, a, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-        dints.push_back((int32_t *)p);
-        p += isz;
-    }
-    *dout = p;
-    return ADP_OK;
-}
-
-static int lp_blocksum(adp_handle *h, const double *dtr, const int32_t *dlen, int n_reads, int L, int sanitize, double **bx, double **bn, int *nsum)
-{
-    *nsum = (L + SUMBLK - 1) / SUMBLK;
-    if (h->lp_sum.ensure((size_t)*nsum * n_reads * 16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    *bx = h->lp_sum.as<double>(); *bn = *bx + (size_t)*nsum * n_reads;
-    { Scope s(h, "k_trace_blocksum");
-      hipLaunchKernelGGL(k_trace_blocksum, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, *nsum, sanitize, *bx, *bn); }
-    return ADP_OK;
-}
-
-static bool lp_lens_ok(const int32_t *len, int n_reads, int L)
-{
-    for (int r = 0; r < n_reads; r++) if (len[r] < 0 || len[r] > L) return false;
-    return true;
+    Scope s(h, "k_trace_blocksum");
+    hipLaunchKernelGGL(k_trace_blocksum, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, nsum, sanitize, bx, bn);
 }
 
 int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const int32_t *min_obs, const int32_t *tail_trim, int stride,
@@ -1228,22 +1224,24 @@ int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const
 {
     if (!h || !trace || !len || !min_obs || !tail_trim || !start_out || !end_out || !early_stop_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (stride < 1) { g_err = "stride must be >= 1"; return ADP_ERR_INVALID; }
-    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    const double *dtr; std::vector<int32_t *> di; void *dout;
-    int rc = lp_stage(h, trace, n_reads, L, flags, {len, min_obs, tail_trim}, (size_t)n_reads * 12, &dtr, di, &dout);
-    if (rc) return rc;
-    int32_t *ds = (int32_t *)dout, *de = ds + n_reads, *des = de + n_reads;
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t n = n_reads, mat = (size_t)L * 8 * n;
+    double *s_tr; int32_t *dlen, *dmo, *dtt, *ds, *de, *des;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dmo = w.take<int32_t>(n); dtt = w.take<int32_t>(n);
+        ds = w.take<int32_t>(n); de = w.take<int32_t>(n); des = w.take<int32_t>(n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, mat, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dmo, min_obs, n * 4)); RCCHK(h2d(h, dtt, tail_trim, n * 4));
     const int interp = (flags & ADP_LLR_INTERP) && stride > 1;
     { Scope s(h, "k_trace_bounds");
-      hipLaunchKernelGGL(k_trace_bounds, dim3(n_reads), dim3(64), 0, h->stream, const_cast<double *>(dtr), di[0], L, di[1], di[2], stride, interp, ds, de, des); }
+      hipLaunchKernelGGL(k_trace_bounds, dim3(n_reads), dim3(64), 0, h->stream, const_cast<double *>(dtr), dlen, L, dmo, dtt, stride, interp, ds, de, des); }
     HIPCHK(hipGetLastError());
-    if (interp && !(flags & ADP_IN_DEVICE))
-        HIPCHK(hipMemcpyAsync(trace, dtr, (size_t)L * 8 * n_reads, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(start_out, ds, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(end_out, de, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(early_stop_out, des, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    if (interp && !(flags & ADP_IN_DEVICE)) RCCHK(d2h(h, trace, dtr, mat));
+    RCCHK(d2h(h, start_out, ds, n * 4)); RCCHK(d2h(h, end_out, de, n * 4)); RCCHK(d2h(h, early_stop_out, des, n * 4));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1252,27 +1250,32 @@ int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, 
                         int L, const adp_peak_args *args, int flags, int cap, int64_t *peaks_out, int64_t *count_out)
 {
     if (!h || !trace || !len || !clip_lo || !clip_hi || !args || !peaks_out || !count_out || n_reads < 1 || L < 1 || cap < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
     const int given = (flags & ADP_LLR_GIVEN_PEAK) != 0;
-    for (int r = 0; r < n_reads; r++)
-        if (given ? (clip_lo[r] < 0 || clip_lo[r] >= len[r]) : (clip_lo[r] < 0 || clip_lo[r] > clip_hi[r] || clip_hi[r] > len[r])) {
-            g_err = "need 0 <= clip_lo <= clip_hi <= len (with ADP_LLR_GIVEN_PEAK: 0 <= clip_lo < len) for every read"; return ADP_ERR_INVALID;
-        }
+    bool clips_ok = given || spans_ok(clip_lo, clip_hi, len, n_reads);
+    for (int r = 0; given && r < n_reads; r++) clips_ok = clips_ok && clip_lo[r] >= 0 && clip_lo[r] < len[r];
+    if (!clips_ok) { g_err = "need 0 <= clip_lo <= clip_hi <= len (with ADP_LLR_GIVEN_PEAK: 0 <= clip_lo < len) for every read"; return ADP_ERR_INVALID; }
     const adp_peak_args &a = *args;
     if ((a.plateau_on && a.plateau_s < 1) || (a.split_on && a.split_s < 0)) { g_err = "plateau s must be >= 1, split s >= 0"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    const double *dtr; std::vector<int32_t *> di; void *dout;
-    int rc = lp_stage(h, trace, n_reads, L, flags, {len, clip_lo, clip_hi}, (size_t)n_reads * 8 * (cap + 1), &dtr, di, &dout);
-    if (rc) return rc;
-    int64_t *dcnt = (int64_t *)dout, *dpk = dcnt + n_reads;
-    double *bx, *bn; int nsum;
-    if ((rc = lp_blocksum(h, dtr, di[0], n_reads, L, 0, &bx, &bn, &nsum))) return rc;
+    RCCHK(begin_call(h));
+    const size_t n = n_reads;
+    const int nsum = (L + SUMBLK - 1) / SUMBLK;
+    double *s_tr, *bx, *bn; int32_t *dlen, *dlo, *dhi; int64_t *dcnt, *dpk;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dlo = w.take<int32_t>(n); dhi = w.take<int32_t>(n);
+        dcnt = w.take<int64_t>(n); dpk = w.take<int64_t>(n * cap);
+        bx = w.take<double>(nsum * n); bn = w.take<double>(nsum * n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dlo, clip_lo, n * 4)); RCCHK(h2d(h, dhi, clip_hi, n * 4));
+    trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 0, bx, bn);
     { Scope s(h, "k_trace_peaks");
-      hipLaunchKernelGGL(k_trace_peaks, dim3(n_reads), dim3(64), 0, h->stream, dtr, di[0], L, di[1], di[2], bx, bn, nsum, a, given, cap, dpk, dcnt); }
+      hipLaunchKernelGGL(k_trace_peaks, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, dlo, dhi, bx, bn, nsum, a, given, cap, dpk, dcnt); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(count_out, dcnt, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(peaks_out, dpk, (size_t)n_reads * 8 * cap, hipMemcpyDeviceToHost, h->stream));
+    RCCHK(d2h(h, count_out, dcnt, n * 8));
+    RCCHK(d2h(h, peaks_out, dpk, n * 8 * cap));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1281,26 +1284,30 @@ int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, i
                        int64_t *out)
 {
     if (!h || !trace || !len || !args || !out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    if (!lp_lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
     const adp_spike_args &a = *args;
     if (!(a.min_peak_distance >= 1.0)) { g_err = "min_peak_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
     const double dd = ceil(a.min_peak_distance);
     const int dist = dd > (double)L ? L + 1 : (int)dd; // (beyond the row: every pair of maxima is within it)
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
-    const double *dtr; std::vector<int32_t *> di; void *dout;
-    int rc = lp_stage(h, trace, n_reads, L, flags, {len}, (size_t)n_reads * 8, &dtr, di, &dout);
-    if (rc) return rc;
-    int64_t *dres = (int64_t *)dout;
-    double *bx, *bn; int nsum;
-    if ((rc = lp_blocksum(h, dtr, di[0], n_reads, L, 1, &bx, &bn, &nsum))) return rc;
-    const int half = L / 2 + 1;
-    if (h->lp_pk.ensure((size_t)half * n_reads * 8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    uint32_t *pk = h->lp_pk.as<uint32_t>(), *wl = pk + (size_t)half * n_reads;
+    RCCHK(begin_call(h));
+    const size_t n = n_reads;
+    const int nsum = (L + SUMBLK - 1) / SUMBLK, half = L / 2 + 1;
+    double *s_tr, *bx, *bn; int32_t *dlen; int64_t *dres;
+    uint32_t *pk, *wl; // the maxima and the work lists of k_trace_spike, half entries per read each
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
+        bx = w.take<double>(nsum * n); bn = w.take<double>(nsum * n);
+        pk = w.take<uint32_t>(half * n); wl = w.take<uint32_t>(half * n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4));
+    trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 1, bx, bn);
     { Scope s(h, "k_trace_spike");
-      hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, di[0], L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
+      hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dres, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    RCCHK(d2h(h, out, dres, n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1313,38 +1320,13 @@ __attribute__((visibility("hidden"))) int mvs_launch_at_loc(bool f64, int grid, 
 __attribute__((visibility("hidden"))) int mvs_launch_stream(bool f64, int grid, hipStream_t st, const void *sig, const int32_t *len, int n, int L, const adp_mvs_args &a,
                       int64_t *out);
 
-// the signal rows on the device (staged when they are host memory), the per-read inputs and the outputs in mv_meta
-static int mv_stage(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags, std::initializer_list<const int64_t *> pos,
-                    size_t out_bytes, const void **dsig, const int32_t **dlen, std::vector<const int64_t *> &dpos, void **dout)
-{
-    const size_t esz = (flags & ADP_MVS_F64) ? 8 : 4, mat = (size_t)L * esz * n_reads;
-    if (!(flags & ADP_IN_DEVICE)) {
-        if (h->mv_buf.ensure(mat)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-        HIPCHK(hipMemcpyAsync(h->mv_buf.p, sig, mat, hipMemcpyHostToDevice, h->stream));
-        *dsig = h->mv_buf.p;
-    } else *dsig = sig;
-    const size_t isz = ((size_t)n_reads * 8 + 255) & ~(size_t)255;
-    if (h->mv_meta.ensure(isz * (1 + pos.size()) + out_bytes)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    char *p = h->mv_meta.as<char>();
-    HIPCHK(hipMemcpyAsync(p, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-    *dlen = (const int32_t *)p;
-    p += isz;
-    for (const int64_t *a : pos) {
-        HIPCHK(hipMemcpyAsync(p, a, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
-        dpos.push_back((const int64_t *)p);
-        p += isz;
-    }
-    *dout = p;
-    return ADP_OK;
-}
-
 static int mv_check_args(const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *a, std::initializer_list<const int64_t *> pos)
 {
     if (!sig || !len || !a || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    for (int r = 0; r < n_reads; r++) if (len[r] < 0 || len[r] > L) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
     for (const int64_t *p : pos) {
         if (!p) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-        for (int r = 0; r < n_reads; r++) if (p[r] < 0 || p[r] > ((int64_t)1 << 40)) { g_err = "positions must lie in [0, 2^40]"; return ADP_ERR_INVALID; }
+        if (!positions_ok(p, n_reads)) { g_err = "positions must lie in [0, 2^40]"; return ADP_ERR_INVALID; }
     }
     if (a->pA_mean_window < 1 || a->pA_var_window < 1 || a->s_pA_mean_window < 1 || a->s_pA_var_window < 1) {
         g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID;
@@ -1354,38 +1336,37 @@ static int mv_check_args(const void *sig, const int32_t *len, int n_reads, int L
 }
 
 // slots of the series kernels: one wave each, [2, L] elements of scratch per slot (at most ~512 MiB in all)
-static int mv_slots(adp_handle *h, int n_reads, int L, size_t esz, void **scr)
+static size_t mv_slots(int n_reads, int L, size_t esz)
 {
-    const size_t per = (size_t)2 * L * esz;
-    size_t slots = ((size_t)512 << 20) / per;
+    size_t slots = ((size_t)512 << 20) / ((size_t)2 * L * esz);
     if (slots < 64) slots = 64;
     if (slots > (size_t)n_reads) slots = n_reads;
     if (slots > 8192) slots = 8192;
-    if (h->mv_scr.ensure(per * slots)) { g_err = "device allocation failed"; return -1; }
-    *scr = h->mv_scr.p;
-    return (int)slots;
+    return slots;
 }
 
 int adp_mvs_check(adp_handle *h, const void *sig, const int32_t *len, const int64_t *adapter_end, const int64_t *polya_end, int n_reads,
                   int L, const adp_mvs_args *args, int flags, int32_t *info_out, double *vals_out)
 {
     if (!h || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    int rc = mv_check_args(sig, len, n_reads, L, args, {adapter_end, polya_end});
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {adapter_end, polya_end}));
+    RCCHK(begin_call(h));
     const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
-    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {adapter_end, polya_end}, (size_t)n_reads * (32 + 40), &ds, &dl, dp, &dout))) return rc;
-    int32_t *dinfo = (int32_t *)dout;
-    double *dvals = (double *)(dinfo + (size_t)n_reads * 8);
-    void *scr;
-    const int slots = mv_slots(h, n_reads, L, f64 ? 8 : 4, &scr);
-    if (slots < 1) return ADP_ERR_HIP;
+    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
+    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dae, *dpe; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dae = w.take<int64_t>(n); dpe = w.take<int64_t>(n);
+        dinfo = w.take<int32_t>(n * 8); dvals = w.take<double>(n * 5);
+        scr = w.take<char>(slots * 2 * L * esz);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dae, adapter_end, n * 8)); RCCHK(h2d(h, dpe, polya_end, n * 8));
     { Scope s(h, "k_mvs_check");
-      HIPCHK((hipError_t)mvs_launch_check(f64, slots, h->stream, ds, dl, n_reads, L, dp[0], dp[1], *args, scr, dinfo, dvals)); }
-    HIPCHK(hipMemcpyAsync(info_out, dinfo, (size_t)n_reads * 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(vals_out, dvals, (size_t)n_reads * 40, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK((hipError_t)mvs_launch_check(f64, (int)slots, h->stream, ds, dlen, n_reads, L, dae, dpe, *args, scr, dinfo, dvals)); }
+    RCCHK(d2h(h, info_out, dinfo, n * 32));
+    RCCHK(d2h(h, vals_out, dvals, n * 40));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1394,24 +1375,25 @@ int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, co
                           const adp_mvs_args *args, int flags, int32_t *info_out, int64_t *idx_out, double *vals_out)
 {
     if (!h || !info_out || !idx_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    int rc = mv_check_args(sig, len, n_reads, L, args, {loc});
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {loc}));
+    RCCHK(begin_call(h));
     const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
-    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {loc}, (size_t)n_reads * (32 + 8 + 40), &ds, &dl, dp, &dout))) return rc;
-    int32_t *dinfo = (int32_t *)dout;
-    int64_t *didx = (int64_t *)(dinfo + (size_t)n_reads * 8);
-    double *dvals = (double *)(didx + n_reads);
-    void *scr;
-    const int slots = mv_slots(h, n_reads, L, f64 ? 8 : 4, &scr);
-    if (slots < 1) return ADP_ERR_HIP;
+    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
+    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dloc, *didx; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dloc = w.take<int64_t>(n);
+        dinfo = w.take<int32_t>(n * 8); didx = w.take<int64_t>(n); dvals = w.take<double>(n * 5);
+        scr = w.take<char>(slots * 2 * L * esz);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dloc, loc, n * 8));
     { Scope s(h, "k_mvs_at_loc");
-      HIPCHK((hipError_t)mvs_launch_at_loc(f64, slots, h->stream, ds, dl, n_reads, L, dp[0], *args, scr, dinfo, didx, dvals)); }
-    HIPCHK(hipMemcpyAsync(info_out, dinfo, (size_t)n_reads * 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(idx_out, didx, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(vals_out, dvals, (size_t)n_reads * 40, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK((hipError_t)mvs_launch_at_loc(f64, (int)slots, h->stream, ds, dlen, n_reads, L, dloc, *args, scr, dinfo, didx, dvals)); }
+    RCCHK(d2h(h, info_out, dinfo, n * 32));
+    RCCHK(d2h(h, idx_out, didx, n * 8));
+    RCCHK(d2h(h, vals_out, dvals, n * 40));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1420,22 +1402,26 @@ int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_rea
                    int64_t *out)
 {
     if (!h || !out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    int rc = mv_check_args(sig, len, n_reads, L, args, {});
-    if (rc) return rc;
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {}));
     if (args->min_obs_adapter < 0 || args->min_obs_post_loc < 0 || args->s_median_shift_window < 0 || args->s_polyA_window < 0) {
         g_err = "min_obs_adapter, min_obs_post_loc and the windows must be >= 0"; return ADP_ERR_INVALID;
     }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const void *ds; const int32_t *dl; std::vector<const int64_t *> dp; void *dout;
-    if ((rc = mv_stage(h, sig, len, n_reads, L, flags, {}, (size_t)n_reads * 8, &ds, &dl, dp, &dout))) return rc;
-    int64_t *dres = (int64_t *)dout;
+    const size_t n = n_reads, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen; int64_t *dres;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4));
     // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
     const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
     { Scope s(h, "k_mvs_stream");
-      HIPCHK((hipError_t)mvs_launch_stream(f64, grid, h->stream, ds, dl, n_reads, L, *args, dres)); }
-    HIPCHK(hipMemcpyAsync(out, dres, (size_t)n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK((hipError_t)mvs_launch_stream(f64, grid, h->stream, ds, dlen, n_reads, L, *args, dres)); }
+    RCCHK(d2h(h, out, dres, n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1494,8 +1480,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -1531,7 +1516,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
         if (rc < 0) return rc;
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+        reset_profile(h);
     }
     return ADP_OK;
 }
@@ -1541,8 +1526,7 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
 {
     if (!h || !signals || !full_len || !bounds || n_reads < 1 || k < 1 || k > ADP_MAX_CAND) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -1565,7 +1549,7 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
         if (rc < 0) return rc;
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+        reset_profile(h);
     }
     return ADP_OK;
 }
@@ -1595,8 +1579,7 @@ int adp_cnn_topk(adp_handle *h, const float *scores_dev, const int64_t *adapter_
 {
     if (!h || !scores_dev || !adapter_pos_dev || !polya_pos_dev || !cand_out || !n_peaks_out || n_reads < 1 || Lo < 3 ||
         k < 1 || k > ADP_MAX_CAND) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     int rc = cnn_topk_dev(h, scores_dev, (const long long *)adapter_pos_dev, (const long long *)polya_pos_dev, n_reads, n_reads, Lo, k);
     if (rc) return rc;
     hipStream_t st = h->stream;
@@ -1637,8 +1620,7 @@ static int cnn_predict_dev(adp_handle *h, const float *scores, int n, int mbsize
 int adp_cnn_predict(adp_handle *h, const float *scores_dev, int n_reads, int minibatch, int Lo, int64_t *bounds_out)
 {
     if (!h || !scores_dev || !bounds_out || n_reads < 1 || minibatch < 1 || Lo < 3) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     int kk = 1;
     int rc = cnn_predict_dev(h, scores_dev, n_reads, minibatch, Lo, &kk);
     if (rc) return rc;
@@ -1665,8 +1647,7 @@ int adp_cnn_prepare(adp_handle *h, const float *signals, int n_reads, int m, int
 {
     if (!h || !signals || !prepared_out || n_reads < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (m != h->m) { g_err = "m differs from the handle's"; return ADP_ERR_CAPACITY; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     if (m <= off) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     const int Lc = (m - off + ds - 1) / ds;
@@ -1933,8 +1914,7 @@ static int cnn_forward_dev(adp_handle *h, const float *prepared, int n_reads, in
 int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, float *scores_out)
 {
     if (!h || !prepared || !scores_out || n_reads < 1 || Lc < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     h->cnn_redo_f32 = false;
     for (int attempt = 0; attempt < 2; attempt++) {
         if (h->op_used.ensure(8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
@@ -2036,8 +2016,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     if (m <= h->cfg.min_obs_adapter) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
     h->cnn_redo_f32 = false;
@@ -2078,7 +2057,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         if (rc < 0) return rc;
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+        reset_profile(h);
     }
     return ADP_OK;
 }
@@ -2101,8 +2080,7 @@ int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *ful
 {
     if (!h || !signals || !full_len || !ranges || !polya_out || !status_out || n < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    HIPCHK(hipSetDevice(h->device));
-    h->prof.clear(); h->ev_used = 0; h->last_grouped = false;
+    RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n, m, flags, &dsig, &dlen);
     if (rc) return rc;

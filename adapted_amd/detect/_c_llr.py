@@ -18,6 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import lib
+from ._rows import as_rows
 
 _ENGINE = None
 
@@ -145,14 +146,8 @@ def _gains_w_polya_early_stop(start, end, c, c2, offset_head, offset_tail, strid
 
 
 def _detect_batch(raw_signals, lens, min_obs_adapter, border_trim, min_obs_polya, polya, details, device):
-    x = np.asarray(raw_signals)
-    if x.ndim != 2:
-        raise ValueError("raw_signals must be [n, L]")
-    if x.dtype != np.float32:
-        x = np.ascontiguousarray(x, dtype=np.float64)
-    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
-    if lens.size != x.shape[0] or (lens.size and (lens.min() < 1 or lens.max() > x.shape[1])):
-        raise ValueError("need one length per read, 1 <= lens <= L (an empty read: the reference indexes outside its arrays)")
+    x, lens = as_rows(np.asarray(raw_signals), lens, None, None, lambda dt: dt if dt == np.float32 else np.dtype(np.float64), "raw_signals",
+                      1, "need one length per read, 1 <= lens <= L (an empty read: the reference indexes outside its arrays)")
     _check_offsets(min_obs_adapter=min_obs_adapter, border_trim=border_trim, min_obs_polya=min_obs_polya)
     if x.shape[0] == 0:
         z = np.zeros((0, 4), dtype=np.int64)

@@ -23,7 +23,8 @@ import numpy as np
 
 from .. import lib
 from . import _c_llr
-from ._c_llr import _gains, c_llr_trace, c_llr_trace_gains
+from ._c_llr import _engine, _gains, c_llr_trace, c_llr_trace_gains
+from ._rows import as_rows
 
 ##############################
 # LLR-based adapter detection
@@ -52,10 +53,6 @@ class LLRBoundariesLog:
 
     def to_string(self):
         return " ".join([f"{k}" for k, v in self.__dict__.items() if v])
-
-
-def _engine(device: int = 0):
-    return _c_llr._engine(device)
 
 
 _EMPTY_KNOTS = "array of sample points is empty"  # (numpy's np.interp message)
@@ -156,17 +153,7 @@ def _peak_args(prominence=1.0, width=0.0, rel_height=0.5, fix_plateau=False, pla
 
 def _as_rows(traces, lens, n, L):
     """host traces -> (float64 C-contiguous [n, L] array, lens int64 [n]); a device pointer passes through"""
-    if isinstance(traces, int):
-        if n is None or L is None:
-            raise ValueError("a device pointer needs n and L")
-        return traces, np.asarray(lens, dtype=np.int64).reshape(-1)
-    x = np.ascontiguousarray(traces, dtype=np.float64)
-    if x.ndim != 2:
-        raise ValueError("traces must be [n, L]")
-    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
-    if lens.size != x.shape[0] or (lens.size and (lens.min() < 0 or lens.max() > x.shape[1])):
-        raise ValueError("need one length per read, 0 <= lens <= L")
-    return x, lens
+    return as_rows(traces, lens, n, L, lambda dt: np.dtype(np.float64), "traces")
 
 
 def _peaks_batch(x, lens, lo, hi, args, cap, n, L, device, given=False):

@@ -27,14 +27,11 @@ import numpy as np
 
 from .. import lib
 from ..config.schema import MVSPolyAConfig, StreamingConfig
-from . import _c_llr
+from ._c_llr import _engine
+from ._rows import as_rows
 from .utils import LOCAL_RANGE_PCTLS, in_range  # noqa: F401  (the reference module imports both from here)
 
 ST_INDEX, ST_VALUE = 1, 2  # `status` of the batch forms (0: the reference returns)
-
-
-def _engine(device: int = 0):
-    return _c_llr._engine(device)
 
 
 def _rng(r):
@@ -81,24 +78,15 @@ def _work_dtype(dt) -> np.dtype:
 
 def _as_rows(signals, lens, n, L, dtype):
     """host signals -> (C-contiguous float32 / float64 [n, L] array, lens, f64); a device pointer passes through"""
-    if isinstance(signals, int):
-        if n is None or L is None:
-            raise ValueError("a device pointer needs n and L")
+    x, lens = as_rows(signals, lens, n, L, _work_dtype, "signals")
+    if isinstance(x, int):
         dt = np.dtype(dtype)
         if dt not in (np.float32, np.float64):
             raise TypeError("device signals must be float32 or float64")
-        return signals, np.asarray(lens, dtype=np.int64).reshape(-1), dt == np.float64
-    x = np.asarray(signals)
-    dt = _work_dtype(x.dtype)
-    x = np.ascontiguousarray(x, dtype=dt)
-    if x.ndim != 2:
-        raise ValueError("signals must be [n, L]")
-    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
-    if lens.size != x.shape[0] or (lens.size and (lens.min() < 0 or lens.max() > x.shape[1])):
-        raise ValueError("need one length per read, 0 <= lens <= L")
+        return x, lens, dt == np.float64
     if x.shape[1] == 0:  # (the library wants L >= 1: every read is empty)
-        x = np.zeros((x.shape[0], 1), dtype=dt)
-    return x, lens, dt == np.float64
+        x = np.zeros((x.shape[0], 1), dtype=x.dtype)
+    return x, lens, x.dtype == np.float64
 
 
 def _positions(v, nn, what):

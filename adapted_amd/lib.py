@@ -649,48 +649,64 @@ class Engine:
         del keep
         return self.attach_open_pores(rows)
 
+    # -- the reference's modules (adp_c_llr_*, adp_llr_*, adp_mvs_*): one input path ----------------------------------------
+    def _rows_in(self, x, n=None, L=None, dtypes=(np.float64,), convert=False, what="signals"):
+        """a module call's [n, L] input: a device pointer (int) with n and L given, or a host C-contiguous array of one of
+        ``dtypes`` (``convert``: made so, other dtypes widened to dtypes[0]) -> (pointer, flags, n, L, host array or None)"""
+        if isinstance(x, int):
+            if n is None or L is None:
+                raise ValueError("a device pointer needs n and L")
+            _check_runtime_once_torch_is_here()  # (device pointers come from torch: its runtime must be this library's)
+            return C.c_void_p(x), ADP_IN_DEVICE, int(n), int(L), None
+        a = np.asarray(x)
+        if convert:
+            a = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in dtypes else dtypes[0])
+        if a.dtype not in dtypes or not a.flags.c_contiguous or a.ndim != 2:
+            raise ValueError("%s: a C-contiguous %s [n, L] array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
+        return a.ctypes.data_as(C.c_void_p), 0, a.shape[0], a.shape[1], a
+
+    @staticmethod
+    def _per_read(a, n, what, dtype=np.int32):
+        """a per-read host array as the library takes it: C-contiguous ``dtype`` [n]"""
+        a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+        if a.size != n:
+            raise ValueError("%s needs one entry per read" % what)
+        return a
+
+    @staticmethod
+    def _ptrs(*arrs):
+        return [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs]
+
     def c_llr_trace(self, raw, lens, starts, ends, args: "AdpTraceArgs", sums=None, return_c_c2: bool = False):
         """adp_c_llr_trace: the reference's `c_llr_trace` (`c_llr_trace_gains` with ``sums=(c, c2)``) for a batch -- raw float64
         [n, L], per-read lens / starts / ends -> gains float64 [n, L] (and c, c2)"""
-        lens = np.ascontiguousarray(lens, dtype=np.int32)
-        starts = np.ascontiguousarray(starts, dtype=np.int32)
-        ends = np.ascontiguousarray(ends, dtype=np.int32)
         flags = 0
         if sums is not None:
-            c = np.ascontiguousarray(sums[0], dtype=np.float64)
-            c2 = np.ascontiguousarray(sums[1], dtype=np.float64)
+            c, c2 = (self._rows_in(s, convert=True, what="sums")[4] for s in sums)
             n, L = c.shape
             rawp = None
             flags |= ADP_TRACE_FROM_SUMS
         else:
-            raw = np.ascontiguousarray(raw, dtype=np.float64)
-            n, L = raw.shape
-            rawp = raw.ctypes.data_as(C.c_void_p)
-            c = np.zeros((n, L)) if return_c_c2 else None
-            c2 = np.zeros((n, L)) if return_c_c2 else None
-        if not (lens.size == starts.size == ends.size == n):
-            raise ValueError("lens / starts / ends need one entry per read")
+            rawp, _, n, L, raw = self._rows_in(raw, convert=True, what="raw signals")
+            c, c2 = (np.zeros((n, L)), np.zeros((n, L))) if return_c_c2 else (None, None)
+        lens, starts, ends = (self._per_read(a, n, w) for a, w in ((lens, "lens"), (starts, "starts"), (ends, "ends")))
         g = np.zeros((n, L))
-        self._check(self.lib.adp_c_llr_trace(self._h, rawp, lens.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
-                                             ends.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
-                                             g.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p) if c is not None else None,
-                                             c2.ctypes.data_as(C.c_void_p) if c2 is not None else None))
+        self._check(self.lib.adp_c_llr_trace(self._h, rawp, *self._ptrs(lens, starts, ends), int(n), int(L), C.byref(args), flags,
+                                             *self._ptrs(g, c, c2)))
         return (g, c, c2) if return_c_c2 else g
 
     def c_llr_best_split(self, c, c2, lens, starts, ends, offset_heads, offset_tails):
         """adp_c_llr_best_split: the reference's `_best_split` for a batch -- sums float64 [n, L], per-row lens / starts / ends /
         offsets -> (x int64 [n], gain float64 [n])"""
-        c = np.ascontiguousarray(c, dtype=np.float64)
-        c2 = np.ascontiguousarray(c2, dtype=np.float64)
+        c, c2 = (self._rows_in(s, convert=True, what="sums")[4] for s in (c, c2))
         n, L = c.shape
-        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (lens, starts, ends, offset_heads, offset_tails)]
-        if c2.shape != c.shape or any(a.size != n for a in arrs):
+        if c2.shape != c.shape:
             raise ValueError("c, c2 [n, L] and one entry per row of lens / starts / ends / offsets")
+        arrs = [self._per_read(a, n, w) for a, w in ((lens, "lens"), (starts, "starts"), (ends, "ends"), (offset_heads, "offset_heads"),
+                                                     (offset_tails, "offset_tails"))]
         x = np.zeros(n, dtype=np.int64)
         g = np.zeros(n)
-        self._check(self.lib.adp_c_llr_best_split(self._h, c.ctypes.data_as(C.c_void_p), c2.ctypes.data_as(C.c_void_p),
-                                                  *[a.ctypes.data_as(C.c_void_p) for a in arrs], int(n), int(L), 0,
-                                                  x.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p)))
+        self._check(self.lib.adp_c_llr_best_split(self._h, *self._ptrs(c, c2, *arrs), int(n), int(L), 0, *self._ptrs(x, g)))
         return x, g
 
     def c_llr_detect(self, raw, lens, min_obs_adapter: int, border_trim: int, min_obs_polya: int = 0, polya: bool = False,
@@ -698,138 +714,78 @@ class Engine:
         """adp_c_llr_detect: `c_llr_detect_adapter` / `c_llr_detect_adapter_polya` for a batch.  raw: float64 or float32 [n, L]
         host array, or a device pointer (int) with n, L and ``float32`` given.  -> rows int64 [n, 4] (adapter_start, adapter_end,
         polya_end, tuple length 2 or 3); with ``details`` also (splits int64 [n, 4], stats float64 [n, 8])"""
-        lens = np.ascontiguousarray(lens, dtype=np.int32)
-        flags = ADP_CLLR_POLYA if polya else 0
-        if isinstance(raw, int):
-            rawp = C.c_void_p(raw)
-            flags |= ADP_IN_DEVICE
-        else:
-            raw = np.ascontiguousarray(raw)
-            if raw.dtype not in (np.float32, np.float64):
-                raw = raw.astype(np.float64)
-            float32 = raw.dtype == np.float32
-            n, L = raw.shape
-            rawp = raw.ctypes.data_as(C.c_void_p)
-        if float32:
+        rawp, flags, n, L, a = self._rows_in(raw, n, L, (np.float64, np.float32), convert=True, what="raw signals")
+        if (a.dtype == np.float32) if a is not None else float32:
             flags |= ADP_CLLR_F32
-        if lens.size != n:
-            raise ValueError("lens needs one entry per read")
+        if polya:
+            flags |= ADP_CLLR_POLYA
+        lens = self._per_read(lens, n, "lens")
         rows = np.zeros((n, 4), dtype=np.int64)
         splits = np.zeros((n, 4), dtype=np.int64) if details else None
         stats = np.zeros((n, 8)) if details else None
-        self._check(self.lib.adp_c_llr_detect(self._h, rawp, lens.ctypes.data_as(C.c_void_p), int(n), int(L), int(min_obs_adapter),
-                                              int(border_trim), int(min_obs_polya), flags, rows.ctypes.data_as(C.c_void_p),
-                                              splits.ctypes.data_as(C.c_void_p) if details else None,
-                                              stats.ctypes.data_as(C.c_void_p) if details else None))
+        self._check(self.lib.adp_c_llr_detect(self._h, rawp, *self._ptrs(lens), int(n), int(L), int(min_obs_adapter), int(border_trim),
+                                              int(min_obs_polya), flags, *self._ptrs(rows, splits, stats)))
         return (rows, splits, stats) if details else rows
-
-    # -- the reference's Python LLR module (adp_llr_trace_*) ---------------------------------------------------------------
-    def _trace_in(self, trace, n, L):
-        """a host float64 [n, L] array or a device pointer (int) with n, L -> (pointer, flags, n, L, host array or None)"""
-        if isinstance(trace, int):
-            if n is None or L is None:
-                raise ValueError("a device pointer needs n and L")
-            return C.c_void_p(trace), ADP_IN_DEVICE, int(n), int(L), None
-        a = np.asarray(trace)
-        if a.dtype != np.float64 or not a.flags.c_contiguous or a.ndim != 2:
-            raise ValueError("traces: a C-contiguous float64 [n, L] array")
-        return a.ctypes.data_as(C.c_void_p), 0, a.shape[0], a.shape[1], a
-
-    @staticmethod
-    def _i32(a, n, what):
-        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
-        if a.size != n:
-            raise ValueError("%s needs one entry per read" % what)
-        return a
 
     def llr_trace_bounds(self, trace, lens, min_obs, tail_trim, stride: int, interp: bool, n: Optional[int] = None, L: Optional[int] = None):
         """adp_llr_trace_bounds: LLRTrace's start / end / early_stop, and with ``interp`` interp_stride IN PLACE (trace: a writable
         host float64 [n, L] array, or a device pointer with n, L) -> (start, end, early_stop) int32 [n] (early_stop bit 1: the
         knot set was empty)"""
-        p, flags, n, L, _ = self._trace_in(trace, n, L)
-        lens, mo, tt = (self._i32(a, n, w) for a, w in ((lens, "lens"), (min_obs, "min_obs"), (tail_trim, "tail_trim")))
-        st, en, es = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
+        ins = [self._per_read(a, n, w) for a, w in ((lens, "lens"), (min_obs, "min_obs"), (tail_trim, "tail_trim"))]
+        outs = [np.zeros(n, dtype=np.int32) for _ in range(3)]
         if interp:
             flags |= ADP_LLR_INTERP
-        self._check(self.lib.adp_llr_trace_bounds(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, mo, tt)), int(stride), int(n),
-                                                  int(L), flags, *(a.ctypes.data_as(C.c_void_p) for a in (st, en, es))))
-        return st, en, es
+        self._check(self.lib.adp_llr_trace_bounds(self._h, p, *self._ptrs(*ins), int(stride), int(n), int(L), flags, *self._ptrs(*outs)))
+        return tuple(outs)
 
     def llr_trace_peaks(self, trace, lens, clip_lo, clip_hi, args: "AdpPeakArgs", cap: int = 16, n: Optional[int] = None,
                         L: Optional[int] = None, given_peak: bool = False):
         """adp_llr_trace_peaks -> (peaks int64 [n, cap] padded with -1, counts int64 [n]: the true counts, also past cap).
         ``given_peak``: clip_lo holds one peak per read, only corrected (ADP_LLR_GIVEN_PEAK)"""
-        p, flags, n, L, _ = self._trace_in(trace, n, L)
+        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
         if given_peak:
             flags |= ADP_LLR_GIVEN_PEAK
-        lens, lo, hi = (self._i32(a, n, w) for a, w in ((lens, "lens"), (clip_lo, "clip_lo"), (clip_hi, "clip_hi")))
+        ins = [self._per_read(a, n, w) for a, w in ((lens, "lens"), (clip_lo, "clip_lo"), (clip_hi, "clip_hi"))]
         pk = np.zeros((n, int(cap)), dtype=np.int64)
         cnt = np.zeros(n, dtype=np.int64)
-        self._check(self.lib.adp_llr_trace_peaks(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, lo, hi)), int(n), int(L),
-                                                 C.byref(args), flags, int(cap), pk.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+        self._check(self.lib.adp_llr_trace_peaks(self._h, p, *self._ptrs(*ins), int(n), int(L), C.byref(args), flags, int(cap),
+                                                 *self._ptrs(pk, cnt)))
         return pk, cnt
 
     def llr_spike_peak(self, trace, lens, args: "AdpSpikeArgs", n: Optional[int] = None, L: Optional[int] = None):
         """adp_llr_spike_peak -> int64 [n]"""
-        p, flags, n, L, _ = self._trace_in(trace, n, L)
-        lens = self._i32(lens, n, "lens")
+        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
+        lens = self._per_read(lens, n, "lens")
         out = np.zeros(n, dtype=np.int64)
-        self._check(self.lib.adp_llr_spike_peak(self._h, p, lens.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
-                                                out.ctypes.data_as(C.c_void_p)))
+        self._check(self.lib.adp_llr_spike_peak(self._h, p, *self._ptrs(lens), int(n), int(L), C.byref(args), flags, *self._ptrs(out)))
         return out
 
-    # -- the reference's MVS poly(A) module (adp_mvs_*) --------------------------------------------------------------------
-    def _mvs_in(self, sig, n, L, f64):
-        """a host float32 / float64 [n, L] array or a device pointer (int) with n, L (and f64 for its dtype) -> (pointer, flags, n, L)"""
-        if isinstance(sig, int):
-            if n is None or L is None:
-                raise ValueError("a device pointer needs n and L")
-            return C.c_void_p(sig), ADP_IN_DEVICE | (ADP_MVS_F64 if f64 else 0), int(n), int(L)
-        a = np.asarray(sig)
-        if a.dtype not in (np.float32, np.float64) or not a.flags.c_contiguous or a.ndim != 2:
-            raise ValueError("signals: a C-contiguous float32 or float64 [n, L] array")
-        return a.ctypes.data_as(C.c_void_p), ADP_MVS_F64 if a.dtype == np.float64 else 0, a.shape[0], a.shape[1]
-
-    @staticmethod
-    def _i64(a, n, what):
-        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
-        if a.size != n:
-            raise ValueError("%s needs one entry per read" % what)
-        return a
+    def _mvs_call(self, fn, sig, lens, positions, args, n, L, f64, outs):
+        """adp_mvs_*: signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``), lens, the int64 positions, then
+        the outputs ``outs(n)`` -> those outputs"""
+        p, flags, n, L, a = self._rows_in(sig, n, L, (np.float32, np.float64))
+        if (a.dtype == np.float64) if a is not None else f64:
+            flags |= ADP_MVS_F64
+        ins = [self._per_read(lens, n, "lens")] + [self._per_read(v, n, w, np.int64) for v, w in positions]
+        res = outs(n)
+        self._check(fn(self._h, p, *self._ptrs(*ins), int(n), int(L), C.byref(args), flags, *self._ptrs(*res)))
+        return res
 
     def mvs_check(self, sig, lens, adapter_ends, polya_ends, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None,
                   f64: bool = False):
         """adp_mvs_check -> (info int32 [n, 8], vals float64 [n, 5])"""
-        p, flags, n, L = self._mvs_in(sig, n, L, f64)
-        lens = self._i32(lens, n, "lens")
-        ae, pe = self._i64(adapter_ends, n, "adapter_ends"), self._i64(polya_ends, n, "polya_ends")
-        info = np.zeros((n, 8), dtype=np.int32)
-        vals = np.zeros((n, 5), dtype=np.float64)
-        self._check(self.lib.adp_mvs_check(self._h, p, *(a.ctypes.data_as(C.c_void_p) for a in (lens, ae, pe)), int(n), int(L), C.byref(args),
-                                           flags, info.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p)))
-        return info, vals
+        return self._mvs_call(self.lib.adp_mvs_check, sig, lens, ((adapter_ends, "adapter_ends"), (polya_ends, "polya_ends")), args, n, L,
+                              f64, lambda n: (np.zeros((n, 8), dtype=np.int32), np.zeros((n, 5))))
 
     def mvs_detect_at_loc(self, sig, lens, locs, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
         """adp_mvs_detect_at_loc -> (info int32 [n, 8], idx int64 [n], vals float64 [n, 5])"""
-        p, flags, n, L = self._mvs_in(sig, n, L, f64)
-        lens = self._i32(lens, n, "lens")
-        lo = self._i64(locs, n, "locs")
-        info = np.zeros((n, 8), dtype=np.int32)
-        idx = np.zeros(n, dtype=np.int64)
-        vals = np.zeros((n, 5), dtype=np.float64)
-        self._check(self.lib.adp_mvs_detect_at_loc(self._h, p, lens.ctypes.data_as(C.c_void_p), lo.ctypes.data_as(C.c_void_p), int(n), int(L),
-                                                   C.byref(args), flags, info.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
-                                                   vals.ctypes.data_as(C.c_void_p)))
-        return info, idx, vals
+        return self._mvs_call(self.lib.adp_mvs_detect_at_loc, sig, lens, ((locs, "locs"),), args, n, L, f64,
+                              lambda n: (np.zeros((n, 8), dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros((n, 5))))
 
     def mvs_detect(self, sig, lens, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
         """adp_mvs_detect -> int64 [n] (0: no poly(A) found)"""
-        p, flags, n, L = self._mvs_in(sig, n, L, f64)
-        lens = self._i32(lens, n, "lens")
-        out = np.zeros(n, dtype=np.int64)
-        self._check(self.lib.adp_mvs_detect(self._h, p, lens.ctypes.data_as(C.c_void_p), int(n), int(L), C.byref(args), flags,
-                                            out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._mvs_call(self.lib.adp_mvs_detect, sig, lens, (), args, n, L, f64, lambda n: (np.zeros(n, dtype=np.int64),))[0]
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

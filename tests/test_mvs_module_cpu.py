@@ -111,9 +111,10 @@ def test_utils_match_reference_semantics():
 def test_host_side_validation():
     from adapted_amd.config.schema import MVSPolyAConfig, StreamingConfig
     from adapted_amd.detect import mvs
+    from adapted_amd.detect._rows import as_rows
 
     with pytest.raises(TypeError):
-        mvs._as_rows(np.zeros((2, 10), dtype=np.complex64), [10, 10], None, None, np.float32)
+        as_rows(np.zeros((2, 10), dtype=np.complex64), [10, 10], None, None, mvs._work_dtype, "signals")
     with pytest.raises(ValueError):
         mvs.mean_var_shift_polyA_check(np.zeros(100, np.float32), -1, 50, MVSPolyAConfig())
     with pytest.raises(ValueError):
@@ -122,8 +123,8 @@ def test_host_side_validation():
     bad.search_increment_step = 0
     with pytest.raises(ValueError):
         mvs.mean_var_shift_polyA_detect(np.zeros(100, np.float32), bad)
-    x, lens, f64 = mvs._as_rows(np.zeros((3, 7), dtype=np.int16), [7, 0, 3], None, None, np.float32)
-    assert x.dtype == np.float64 and f64
+    x, lens = as_rows(np.zeros((3, 7), dtype=np.int16), [7, 0, 3], None, None, mvs._work_dtype, "signals")
+    assert x.dtype == np.float64 and lens.tolist() == [7, 0, 3]
 
 
 def test_struct_size_matches_library():
