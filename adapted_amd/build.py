@@ -60,10 +60,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
         try:
             if force or stale():
                 tmp = "%s.%d.tmp" % (LIB, os.getpid())
-                # (mvs_kernels.hip: a translation unit of its own, so that its kernels leave the code the compiler makes for
-                # the detect path's kernels exactly as it was)
+                # (modules.hip: the reference-module drop-ins in a translation unit of their own, so that their kernels leave
+                # the code the compiler makes for the detect path's kernels exactly as it was)
                 cmd = [hipcc] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", tmp,
-                                         os.path.join(CSRC, "adapted_hip.hip"), os.path.join(CSRC, "mvs_kernels.hip")]
+                                         os.path.join(CSRC, "adapted_hip.hip"), os.path.join(CSRC, "modules.hip")]
                 if verbose:
                     print(" ".join(cmd))
                 subprocess.check_call(cmd)

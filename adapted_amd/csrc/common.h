@@ -214,6 +214,17 @@ static __device__ __forceinline__ float key2f(uint32_t k)
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
 }
+// order-preserving float64 <-> uint64 key
+static __device__ __forceinline__ uint64_t d2key(double d)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(d);
+    return u ^ ((uint64_t)((int64_t)u >> 63) | 0x8000000000000000ULL);
+}
+static __device__ __forceinline__ double key2d(uint64_t k)
+{
+    const uint64_t u = (k & 0x8000000000000000ULL) ? (k & 0x7fffffffffffffffULL) : ~k;
+    return __longlong_as_double((long long)u);
+}
 
 template <class T>
 static __device__ __forceinline__ T wave_sum(T v)

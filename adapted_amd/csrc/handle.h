@@ -1,0 +1,119 @@
+// handle.h -- what the library's translation units (adapted_hip.hip: the detect path; modules.hip: the reference-module
+// drop-ins) share on the host: the error string, the handle and the start / profiling scope of a call.  Nothing here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "adapted_hip.h"
+
+#define ADP_HIDDEN __attribute__((visibility("hidden")))
+
+// what adp_last_error returns: one object per thread (defined in adapted_hip.hip)
+extern ADP_HIDDEN thread_local std::string g_err;
+
+#define HIPCHK(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                       \
+            return ADP_ERR_HIP;                                                              \
+        }                                                                                    \
+    } while (0)
+// a helper's non-zero return code (g_err already set) ends the caller
+#define RCCHK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// grow-only device memory, released with its owner (not copyable: two owners would free it twice)
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int ensure(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        if (p) { if (hipFree(p) != hipSuccess) return -1; p = nullptr; cap = 0; }
+        if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return -1; }
+        cap = bytes;
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T *as() { return reinterpret_cast<T *>(p); }
+};
+
+struct ProfEntry { const char *name; hipEvent_t a, b; };
+#define ADP_MAX_LANES 4
+
+struct adp_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream3 = nullptr;          // copy stream (adp_memcpy_h2d_async)
+    hipEvent_t ev_copy[16] = {};            // adp_copy_mark / adp_copy_wait
+    hipStream_t stream2 = nullptr;          // side stream: the start-peak scan (HBM-bound) beside the float64 gains (ALU-bound)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_conv[3] = {};             // conv stack: layer 2 done (main -> side), layer 3 of an even / odd chunk done (side -> main)
+    adp_cfg cfg;
+    int max_reads = 0, m = 0;
+    // geometry of the LLR path
+    int T = 0, off = 0, ds = 1, L = 0, Lp = 0, nck = 0, nsum = 0;
+    DevBuf mbs, ghist, gbelow, gcnt, cbuf, fz, fcnt, n1heavy, ct_pk, ct_pv, ct_out, gstat, down, nvalid, ck, tail, trace, bmax, bmin, t1, adapter_idx, polya_idx;
+    DevBuf bounds, topk_none, rows, preq, series, have_series, vscratch, pk, pkv, npk, mk, st, sp, any_none, sig_stage, len_stage, bounds_stage;
+    int vslots = 0, vstride = 0, pslots = 0;
+    bool profiling = false;
+    std::vector<ProfEntry> prof;
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    int last_n = 0, last_nmb = 0;
+    int layout = 0;   // ADP_LAYOUT_*: 1 = the single-read API (pooled from sample 0)
+    int oh1 = 5;      // head offset of the first gains pass
+    int pos_off = 0;  // added to pooled indices * ds for sample positions
+    DevBuf rng0;      // per-read [0, T) ranges of the single-read layout
+    // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
+    DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
+    DevBuf ws;              // the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): one call's staging and scratch (ws_carve)
+    unsigned int op_last_used = 0;
+    bool cnn_have_w = false;
+    int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
+    // conv stack: 1 = split float16 MFMA (cnn_conv_split.h, the default), 0 = exact float32 MFMA (cnn_conv.h; ADP_CNN_CONV=f32).
+    // cnn_redo_f32: the split kernels met an activation outside the float16 range in this call -- it is being repeated in float32
+    int cnn_mode = 1;
+    DevBuf cnn_actf[2];                                  // the exact-float32 stack's activations [chunk][64][Lpad] (cnn_act: the split rows)
+    int cnn_f_Lpad = 0, cnn_f_L1 = 0, cnn_f_chunk = 0;
+    bool cnn_redo_f32 = false;
+    DevBuf cnn_wsp;          // split B fragments of layers 1 and 2
+    float cnn_sw[4] = {1.f, 1.f, 1.f, 1.f}; // scales of the split weights: layers 1, 2, 3 (folded into layer 2's kernel) and 0 (into layer 1's)
+    // grouped execution of the LLR path (llr_grouped): child handles ("lanes") with their own streams and a workspace for ONE
+    // group of minibatches; consecutive groups go to alternating lanes so that the phases of neighbouring groups overlap
+    adp_handle *lane[ADP_MAX_LANES] = {};
+    adp_handle *owner = nullptr;            // a lane's parent: owns the open-pore arena and collects the profile
+    DevBuf sphead;                          // K1 state between k_sp_head, the pooling pass and k_sp_tail
+    DevBuf mbstat, mbparams;                // parent: minibatch status / N1 parameters of a grouped call
+    std::vector<hipEvent_t> ev_sync;        // parent: phase-done events of the groups (no timing)
+    hipEvent_t ev_start = nullptr;          // parent: inputs staged, arena counter reset
+    bool last_grouped = false;
+    // launch attributes already requested through this handle (hipFuncSetAttribute per kernel instantiation and device; kept per
+    // handle -- a handle is used by one thread at a time -- instead of in process-wide statics)
+    unsigned attr_done = 0;
+    size_t lds_series_set = 0;
+};
+
+// ---- a call's start and its profiling scopes (adapted_hip.hip) --------------------------
+ADP_HIDDEN hipEvent_t next_event(adp_handle *h);
+// a call that works on the device: the handle's device current, the profile of the call before it dropped
+ADP_HIDDEN int begin_call(adp_handle *h);
+
+struct Scope {
+    adp_handle *h; hipEvent_t b = nullptr; hipStream_t st;
+    Scope(adp_handle *h_, const char *name, hipStream_t st_ = nullptr) : h(h_), st(st_ ? st_ : h_->stream)
+    {
+        if (!h->profiling || !name) return;
+        hipEvent_t a = next_event(h);
+        b = next_event(h);
+        (void)hipEventRecord(a, st);
+        h->prof.push_back({name, a, b});
+    }
+    ~Scope() { if (b) (void)hipEventRecord(b, st); }
+};

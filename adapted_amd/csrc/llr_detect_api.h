@@ -137,18 +137,6 @@ __global__ void k_cd_plan(int level, const int32_t *__restrict__ len, int n_read
     }
 }
 
-// order-preserving float64 <-> uint64 key (NaNs never reach the selection: a segment with a NaN has the median NaN)
-static __device__ __forceinline__ uint64_t d2key(double d)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(d);
-    return u ^ ((uint64_t)((int64_t)u >> 63) | 0x8000000000000000ULL);
-}
-static __device__ __forceinline__ double key2d(uint64_t k)
-{
-    const uint64_t u = (k & 0x8000000000000000ULL) ? (k & 0x7fffffffffffffffULL) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
 // The medians of raw[:x_head], raw[x_head:x_first], raw[x_first:x_tail], raw[x_tail:] (after the reference's fallbacks
 // x_head = 1 / x_tail = x_first + 1) with numpy's rules -- a NaN anywhere in the segment or an empty segment gives NaN, an even
 // count the mean (a + b) / 2.0 of the two middle values -- then the decision.  One workgroup per read.

@@ -22,8 +22,6 @@
 #include "log_cr.h"
 #include "wave_stats.h"
 
-__device__ const double g_logcr_table[3 * LOGCR_N] = LOGCR_TABLE;
-
 // ---------------------------------------------------------------- D1
 #define NP_TILE 512
 // grid = n_reads blocks of 256 threads; dynamic LDS = NP_TILE * ds floats

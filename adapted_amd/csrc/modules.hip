@@ -1,0 +1,461 @@
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*): their kernels and entry points, a
+// translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <initializer_list>
+#include <vector>
+
+#include "handle.h"
+#include "trace_api.h"
+#include "llr_detect_api.h"
+#include "trace_peaks_api.h"
+#include "mvs_api.h"
+
+// ---- workspace, staging and per-read checks of the entry points
+
+// 256-byte aligned pieces of the handle's workspace `ws`; a Carve without a base only adds up their sizes
+struct Carve {
+    char *base = nullptr;
+    size_t off = 0;
+    // `count` elements of T -- none (nullptr) unless `want`
+    template <class T> T *take(size_t count, bool want = true)
+    {
+        if (!want) return nullptr;
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// a call's pieces of the workspace: `pieces(Carve &)` takes them all and runs twice -- first to add up the sizes, so that ws
+// grows once, before anything is enqueued (ensure() moves the buffer), then to hand out the pointers.  Every module call
+// completes before it returns, so the next one takes the same memory: a process holds the largest single call's need.
+template <class F> static int ws_carve(adp_handle *h, F &&pieces)
+{
+    Carve c;
+    pieces(c);
+    if (h->ws.ensure(c.off)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    c = Carve{h->ws.as<char>(), 0};
+    pieces(c);
+    return ADP_OK;
+}
+
+// copies on the handle's stream: a host array in, a result back
+static int h2d(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream)); return ADP_OK; }
+static int d2h(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream)); return ADP_OK; }
+
+// the device pointer of an input that is device memory with ADP_IN_DEVICE, else host memory: then copied to `piece` (a
+// workspace piece taken for it only in that case)
+template <class T> static int stage_in(adp_handle *h, int flags, const T *src, T *piece, size_t bytes, const T **dev)
+{
+    if (flags & ADP_IN_DEVICE) { *dev = src; return ADP_OK; }
+    *dev = piece;
+    return h2d(h, piece, src, bytes);
+}
+
+// the per-read checks (host arrays of n entries): lo <= a <= hi; 0 <= len <= L; 0 <= start <= end <= len; positions in [0, 2^40]
+template <class T> static bool all_in(const T *a, int n, T lo, T hi)
+{
+    for (int r = 0; r < n; r++) if (a[r] < lo || a[r] > hi) return false;
+    return true;
+}
+static bool lens_ok(const int32_t *len, int n, int L) { return all_in<int32_t>(len, n, 0, L); }
+static bool spans_ok(const int32_t *start, const int32_t *end, const int32_t *len, int n)
+{
+    for (int r = 0; r < n; r++) if (start[r] < 0 || start[r] > end[r] || end[r] > len[r]) return false;
+    return true;
+}
+static bool positions_ok(const int64_t *p, int n) { return all_in<int64_t>(p, n, 0, (int64_t)1 << 40); }
+
+extern "C" {
+
+// c_llr_trace / c_llr_trace_gains / _gains for a batch of float64 signals (trace_api.h)
+int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const int32_t *start, const int32_t *end, int n_reads,
+                    int L, const adp_trace_args *args, int flags, double *gain_out, double *c_io, double *c2_io)
+{
+    if (!h || !len || !start || !end || !args || !gain_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    const bool from_sums = (flags & ADP_TRACE_FROM_SUMS) != 0, in_dev = (flags & ADP_IN_DEVICE) != 0, out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    if (from_sums ? (!c_io || !c2_io) : !raw) { g_err = "bad argument: no input signal / sums"; return ADP_ERR_INVALID; }
+    if (!from_sums && ((c_io == nullptr) != (c2_io == nullptr))) { g_err = "bad argument: c and c2 go together"; return ADP_ERR_INVALID; }
+    const adp_trace_args &a = *args;
+    if (a.stride < 1 || a.min_obs < 0 || a.border_trim < 0) { g_err = "stride must be >= 1, offsets >= 0"; return ADP_ERR_INVALID; }
+    if (a.polya_early_stopping > 0) {
+        if (a.adapter_early_stop_stride < 1 || a.polya_early_stop_stride < 1 || a.adapter_early_stop_window < 0 || a.polya_early_stop_window < 0) { g_err = "early-stop windows / strides out of range"; return ADP_ERR_INVALID; }
+        if (a.adapter_early_stop_stride % a.stride || a.polya_early_stop_stride % a.stride) { g_err = "early-stop stride is not a multiple of stride (the reference asserts, _c_llr.pyx:137-138)"; return ADP_ERR_INVALID; }
+    } else if (a.adapter_early_stopping > 0) {
+        if (a.adapter_early_stop_stride < 1 || a.adapter_early_stop_window < 0) { g_err = "early-stop window / stride out of range"; return ADP_ERR_INVALID; }
+        if (a.adapter_early_stop_stride % a.stride) { g_err = "early-stop stride is not a multiple of stride (the reference asserts, _c_llr.pyx:102)"; return ADP_ERR_INVALID; }
+    }
+    if (!lens_ok(len, n_reads, L) || !spans_ok(start, end, len, n_reads)) { g_err = "need 0 <= start <= end <= len <= L for every read"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t cells = (size_t)L * n_reads, mat = cells * 8, n4 = (size_t)n_reads * 4;
+    // the sums a raw call computes go to the caller's arrays when those are device outputs, else to the workspace
+    const bool own_c = !from_sums && !(c_io && out_dev);
+    int32_t *dlen, *dstart, *dend; double *s_raw, *s_c, *s_c2, *w_c, *w_c2, *w_g;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dlen = w.take<int32_t>(n_reads); dstart = w.take<int32_t>(n_reads); dend = w.take<int32_t>(n_reads);
+        s_raw = w.take<double>(cells, !from_sums && !in_dev);
+        s_c = w.take<double>(cells, from_sums && !in_dev); s_c2 = w.take<double>(cells, from_sums && !in_dev);
+        w_c = w.take<double>(cells, own_c); w_c2 = w.take<double>(cells, own_c);
+        w_g = w.take<double>(cells, !out_dev);
+    }));
+    RCCHK(h2d(h, dlen, len, n4)); RCCHK(h2d(h, dstart, start, n4)); RCCHK(h2d(h, dend, end, n4));
+    const double *dc, *dc2;
+    if (from_sums) {
+        RCCHK(stage_in(h, flags, c_io, s_c, mat, &dc));
+        RCCHK(stage_in(h, flags, c2_io, s_c2, mat, &dc2));
+    } else {
+        const double *draw;
+        RCCHK(stage_in(h, flags, raw, s_raw, mat, &draw));
+        double *wc = own_c ? w_c : c_io, *wc2 = own_c ? w_c2 : c2_io;
+        { Scope s(h, "k_trace_cumsum");
+          hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, wc, wc2); }
+        dc = wc; dc2 = wc2;
+    }
+    double *dg = out_dev ? gain_out : w_g;
+    TraceArgs ta = {a.min_obs, a.border_trim, a.stride, a.adapter_early_stopping, a.adapter_early_stop_window, a.adapter_early_stop_stride,
+                    a.polya_early_stopping, a.polya_early_stop_window, a.polya_early_stop_stride};
+    { Scope s(h, "k_trace_gains");
+      hipLaunchKernelGGL(k_trace_gains, dim3(n_reads), dim3(64), 0, h->stream, dc, dc2, dlen, dstart, dend, L, ta, dg); }
+    HIPCHK(hipGetLastError());
+    if (!out_dev) {
+        RCCHK(d2h(h, gain_out, dg, mat));
+        if (!from_sums && c_io) { RCCHK(d2h(h, c_io, dc, mat)); RCCHK(d2h(h, c2_io, dc2, mat)); }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// the split searches of one level: chunk winners, then per segment (llr_detect_api.h)
+static void cd_splits(adp_handle *h, const double *dc, const double *dc2, int L, const CdSeg *segs, int n_seg, double *part_g,
+                      int32_t *part_x, int32_t *st_x, double *st_g)
+{
+    const int nck = (L + CD_CHUNK - 1) / CD_CHUNK;
+    { Scope s(h, "k_split_part");
+      hipLaunchKernelGGL(k_split_part, dim3(n_seg, nck), dim3(CD_BLOCK), 0, h->stream, dc, dc2, L, segs, nck, part_g, part_x); }
+    { Scope s(h, "k_split_reduce");
+      hipLaunchKernelGGL(k_split_reduce, dim3(n_seg), dim3(64), 0, h->stream, segs, nck, part_g, part_x, st_x, st_g); }
+}
+
+// _best_split (_c_llr.pyx:40-64) for a batch of rows of given sums: one segment per row
+int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const int32_t *len, const int32_t *start, const int32_t *end,
+                         const int32_t *offset_head, const int32_t *offset_tail, int n_reads, int L, int flags, int64_t *x_out, double *gain_out)
+{
+    if (!h || !c || !c2 || !len || !start || !end || !offset_head || !offset_tail || !x_out || !gain_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L) || !spans_ok(start, end, len, n_reads) || !all_in(offset_head, n_reads, 0, INT32_MAX) ||
+        !all_in(offset_tail, n_reads, 0, INT32_MAX)) {
+        g_err = "need 0 <= start <= end <= len <= L and offsets >= 0 for every row"; return ADP_ERR_INVALID;
+    }
+    const bool in_dev = (flags & ADP_IN_DEVICE) != 0;
+    RCCHK(begin_call(h));
+    const size_t cells = (size_t)L * n_reads, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
+    double *s_c, *s_c2, *part_g, *st_g; int32_t *part_x, *st_x; CdSeg *dsegs;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dsegs = w.take<CdSeg>(n_reads);
+        part_g = w.take<double>(n_reads * nck); part_x = w.take<int32_t>(n_reads * nck);
+        st_x = w.take<int32_t>(n_reads); st_g = w.take<double>(n_reads);
+        s_c = w.take<double>(cells, !in_dev); s_c2 = w.take<double>(cells, !in_dev);
+    }));
+    const double *dc, *dc2;
+    RCCHK(stage_in(h, flags, c, s_c, cells * 8, &dc));
+    RCCHK(stage_in(h, flags, c2, s_c2, cells * 8, &dc2));
+    std::vector<CdSeg> segs(n_reads);
+    for (int r = 0; r < n_reads; r++) {
+        long lo = (long)start[r] + offset_head[r], hi = (long)end[r] - offset_tail[r];
+        if (lo > end[r]) lo = end[r];
+        if (hi < lo) hi = lo; // (an empty range: the reference's loop does not run)
+        segs[r] = CdSeg{r, start[r], end[r], (int32_t)lo, (int32_t)hi, r};
+    }
+    RCCHK(h2d(h, dsegs, segs.data(), segs.size() * sizeof(CdSeg)));
+    cd_splits(h, dc, dc2, L, dsegs, n_reads, part_g, part_x, st_x, st_g);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> x(n_reads);
+    RCCHK(d2h(h, x.data(), st_x, (size_t)n_reads * 4));
+    RCCHK(d2h(h, gain_out, st_g, (size_t)n_reads * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int r = 0; r < n_reads; r++) x_out[r] = x[r];
+    return ADP_OK;
+}
+
+// c_llr_detect_adapter (_c_llr.pyx:239-287) / c_llr_detect_adapter_polya (:290-365) for a batch (llr_detect_api.h)
+int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_reads, int L, int32_t min_obs_adapter, int32_t border_trim,
+                     int32_t min_obs_polya, int flags, int64_t *rows_out, int64_t *splits_out, double *stats_out)
+{
+    if (!h || !raw || !len || !rows_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (min_obs_adapter < 0 || border_trim < 0 || min_obs_polya < 0) { g_err = "offsets must be >= 0"; return ADP_ERR_INVALID; }
+    if (!all_in(len, n_reads, 1, L)) { g_err = "need 1 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const bool in_dev = (flags & ADP_IN_DEVICE) != 0, f32 = (flags & ADP_CLLR_F32) != 0, polya = (flags & ADP_CLLR_POLYA) != 0;
+    RCCHK(begin_call(h));
+    const size_t n = n_reads, cells = (size_t)L * n, esz = f32 ? 4 : 8, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
+    // the sums, the staged signal; segments (2 per read), chunk winners, the per-read state
+    double *dc, *dc2, *part_g, *st_g, *med; int32_t *part_x, *st_x, *res, *dlen; CdSeg *segs, *psegs; void *s_raw;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        dc = w.take<double>(cells); dc2 = w.take<double>(cells); s_raw = w.take<char>(cells * esz, !in_dev);
+        segs = w.take<CdSeg>(2 * n); psegs = w.take<CdSeg>(n);
+        part_g = w.take<double>(2 * n * nck); part_x = w.take<int32_t>(2 * n * nck);
+        st_x = w.take<int32_t>(4 * n); st_g = w.take<double>(4 * n); med = w.take<double>(4 * n); res = w.take<int32_t>(4 * n);
+        dlen = w.take<int32_t>(n);
+    }));
+    const void *draw;
+    RCCHK(stage_in(h, flags, raw, s_raw, cells * esz, &draw));
+    RCCHK(h2d(h, dlen, len, n * 4));
+    const CdArgs a = {min_obs_adapter, border_trim, min_obs_polya, polya ? 1 : 0};
+    const int rb = (n_reads + 255) / 256;
+    { Scope s(h, "k_trace_cumsum");
+      if (f32) hipLaunchKernelGGL(k_trace_cumsum<float>, dim3(n_reads), dim3(64), 0, h->stream, (const float *)draw, dlen, L, n_reads, dc, dc2);
+      else hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, (const double *)draw, dlen, L, n_reads, dc, dc2); }
+    { Scope s(h, "k_cd_plan");
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 0, dlen, n_reads, a, st_x, segs); }
+    cd_splits(h, dc, dc2, L, segs, n_reads, part_g, part_x, st_x, st_g);
+    { Scope s(h, "k_cd_plan");
+      hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 1, dlen, n_reads, a, st_x, segs); }
+    cd_splits(h, dc, dc2, L, segs, 2 * n_reads, part_g, part_x, st_x, st_g);
+    { Scope s(h, "k_cd_medians");
+      if (f32) hipLaunchKernelGGL(k_cd_medians<float>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const float *)draw, dlen, L, a, st_x, st_g, res, med, psegs);
+      else hipLaunchKernelGGL(k_cd_medians<double>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const double *)draw, dlen, L, a, st_x, st_g, res, med, psegs); }
+    if (polya) {
+        cd_splits(h, dc, dc2, L, psegs, n_reads, part_g, part_x, st_x, st_g);
+        { Scope s(h, "k_cd_finish");
+          hipLaunchKernelGGL(k_cd_finish, dim3(rb), dim3(256), 0, h->stream, n_reads, st_x, res); }
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> hres(n * 4), sx;
+    std::vector<double> sg, hmed;
+    RCCHK(d2h(h, hres.data(), res, n * 16));
+    if (splits_out) { sx.resize(n * 4); RCCHK(d2h(h, sx.data(), st_x, n * 16)); }
+    if (stats_out) {
+        sg.resize(n * 4); hmed.resize(n * 4);
+        RCCHK(d2h(h, sg.data(), st_g, n * 32));
+        RCCHK(d2h(h, hmed.data(), med, n * 32));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < hres.size(); i++) rows_out[i] = hres[i];
+    for (int r = 0; r < n_reads; r++) {
+        const bool searched = hres[r * 4 + 3] == 3 && hres[r * 4 + 1] != 0;
+        if (splits_out) for (int k = 0; k < 4; k++) splits_out[r * 4 + k] = (k == 3 && !searched) ? -1 : sx[r * 4 + k];
+        if (stats_out) for (int k = 0; k < 4; k++) {
+            stats_out[r * 8 + k] = (k == 3 && !searched) ? 0.0 : sg[r * 4 + k];
+            stats_out[r * 8 + 4 + k] = hmed[r * 4 + k];
+        }
+    }
+    return ADP_OK;
+}
+
+// ---- the reference's Python LLR module (adapted/detect/llr.py) on device traces (trace_peaks_api.h)
+
+// block summaries of the trace rows: nsum blocks of SUMBLK points per row
+static void trace_blocksum(adp_handle *h, const double *dtr, const int32_t *dlen, int n_reads, int L, int nsum, int sanitize, double *bx, double *bn)
+{
+    Scope s(h, "k_trace_blocksum");
+    hipLaunchKernelGGL(k_trace_blocksum, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, nsum, sanitize, bx, bn);
+}
+
+int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const int32_t *min_obs, const int32_t *tail_trim, int stride,
+                         int n_reads, int L, int flags, int32_t *start_out, int32_t *end_out, int32_t *early_stop_out)
+{
+    if (!h || !trace || !len || !min_obs || !tail_trim || !start_out || !end_out || !early_stop_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (stride < 1) { g_err = "stride must be >= 1"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t n = n_reads, mat = (size_t)L * 8 * n;
+    double *s_tr; int32_t *dlen, *dmo, *dtt, *ds, *de, *des;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dmo = w.take<int32_t>(n); dtt = w.take<int32_t>(n);
+        ds = w.take<int32_t>(n); de = w.take<int32_t>(n); des = w.take<int32_t>(n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, mat, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dmo, min_obs, n * 4)); RCCHK(h2d(h, dtt, tail_trim, n * 4));
+    const int interp = (flags & ADP_LLR_INTERP) && stride > 1;
+    { Scope s(h, "k_trace_bounds");
+      hipLaunchKernelGGL(k_trace_bounds, dim3(n_reads), dim3(64), 0, h->stream, const_cast<double *>(dtr), dlen, L, dmo, dtt, stride, interp, ds, de, des); }
+    HIPCHK(hipGetLastError());
+    if (interp && !(flags & ADP_IN_DEVICE)) RCCHK(d2h(h, trace, dtr, mat));
+    RCCHK(d2h(h, start_out, ds, n * 4)); RCCHK(d2h(h, end_out, de, n * 4)); RCCHK(d2h(h, early_stop_out, des, n * 4));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, const int32_t *clip_lo, const int32_t *clip_hi, int n_reads,
+                        int L, const adp_peak_args *args, int flags, int cap, int64_t *peaks_out, int64_t *count_out)
+{
+    if (!h || !trace || !len || !clip_lo || !clip_hi || !args || !peaks_out || !count_out || n_reads < 1 || L < 1 || cap < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const int given = (flags & ADP_LLR_GIVEN_PEAK) != 0;
+    bool clips_ok = given || spans_ok(clip_lo, clip_hi, len, n_reads);
+    for (int r = 0; given && r < n_reads; r++) clips_ok = clips_ok && clip_lo[r] >= 0 && clip_lo[r] < len[r];
+    if (!clips_ok) { g_err = "need 0 <= clip_lo <= clip_hi <= len (with ADP_LLR_GIVEN_PEAK: 0 <= clip_lo < len) for every read"; return ADP_ERR_INVALID; }
+    const adp_peak_args &a = *args;
+    if ((a.plateau_on && a.plateau_s < 1) || (a.split_on && a.split_s < 0)) { g_err = "plateau s must be >= 1, split s >= 0"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t n = n_reads;
+    const int nsum = (L + SUMBLK - 1) / SUMBLK;
+    double *s_tr, *bx, *bn; int32_t *dlen, *dlo, *dhi; int64_t *dcnt, *dpk;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dlo = w.take<int32_t>(n); dhi = w.take<int32_t>(n);
+        dcnt = w.take<int64_t>(n); dpk = w.take<int64_t>(n * cap);
+        bx = w.take<double>(nsum * n); bn = w.take<double>(nsum * n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dlo, clip_lo, n * 4)); RCCHK(h2d(h, dhi, clip_hi, n * 4));
+    trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 0, bx, bn);
+    { Scope s(h, "k_trace_peaks");
+      hipLaunchKernelGGL(k_trace_peaks, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, dlo, dhi, bx, bn, nsum, a, given, cap, dpk, dcnt); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, count_out, dcnt, n * 8));
+    RCCHK(d2h(h, peaks_out, dpk, n * 8 * cap));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, int n_reads, int L, const adp_spike_args *args, int flags,
+                       int64_t *out)
+{
+    if (!h || !trace || !len || !args || !out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const adp_spike_args &a = *args;
+    if (!(a.min_peak_distance >= 1.0)) { g_err = "min_peak_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
+    const double dd = ceil(a.min_peak_distance);
+    const int dist = dd > (double)L ? L + 1 : (int)dd; // (beyond the row: every pair of maxima is within it)
+    RCCHK(begin_call(h));
+    const size_t n = n_reads;
+    const int nsum = (L + SUMBLK - 1) / SUMBLK, half = L / 2 + 1;
+    double *s_tr, *bx, *bn; int32_t *dlen; int64_t *dres;
+    uint32_t *pk, *wl; // the maxima and the work lists of k_trace_spike, half entries per read each
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
+        bx = w.take<double>(nsum * n); bn = w.take<double>(nsum * n);
+        pk = w.take<uint32_t>(half * n); wl = w.take<uint32_t>(half * n);
+    }));
+    const double *dtr;
+    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
+    RCCHK(h2d(h, dlen, len, n * 4));
+    trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 1, bx, bn);
+    { Scope s(h, "k_trace_spike");
+      hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, out, dres, n * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// ---- the reference's MVS poly(A) module (adapted/detect/mvs.py) on batched signals (mvs_api.h)
+
+static int mv_check_args(const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *a, std::initializer_list<const int64_t *> pos)
+{
+    if (!sig || !len || !a || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    for (const int64_t *p : pos) {
+        if (!p) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+        if (!positions_ok(p, n_reads)) { g_err = "positions must lie in [0, 2^40]"; return ADP_ERR_INVALID; }
+    }
+    if (a->pA_mean_window < 1 || a->pA_var_window < 1 || a->s_pA_mean_window < 1 || a->s_pA_var_window < 1) {
+        g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID;
+    }
+    if (a->search_increment_step < 1) { g_err = "search_increment_step must be >= 1"; return ADP_ERR_INVALID; }
+    return ADP_OK;
+}
+
+// slots of the series kernels: one wave each, [2, L] elements of scratch per slot (at most ~512 MiB in all)
+static size_t mv_slots(int n_reads, int L, size_t esz)
+{
+    size_t slots = ((size_t)512 << 20) / ((size_t)2 * L * esz);
+    if (slots < 64) slots = 64;
+    if (slots > (size_t)n_reads) slots = n_reads;
+    if (slots > 8192) slots = 8192;
+    return slots;
+}
+
+int adp_mvs_check(adp_handle *h, const void *sig, const int32_t *len, const int64_t *adapter_end, const int64_t *polya_end, int n_reads,
+                  int L, const adp_mvs_args *args, int flags, int32_t *info_out, double *vals_out)
+{
+    if (!h || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {adapter_end, polya_end}));
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
+    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dae, *dpe; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dae = w.take<int64_t>(n); dpe = w.take<int64_t>(n);
+        dinfo = w.take<int32_t>(n * 8); dvals = w.take<double>(n * 5);
+        scr = w.take<char>(slots * 2 * L * esz);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dae, adapter_end, n * 8)); RCCHK(h2d(h, dpe, polya_end, n * 8));
+    { Scope s(h, "k_mvs_check");
+      if (f64) hipLaunchKernelGGL(k_mvs_check<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dae, dpe, *args, (double *)scr, dinfo, dvals);
+      else hipLaunchKernelGGL(k_mvs_check<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dae, dpe, *args, (float *)scr, dinfo, dvals); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, info_out, dinfo, n * 32));
+    RCCHK(d2h(h, vals_out, dvals, n * 40));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, const int64_t *loc, int n_reads, int L,
+                          const adp_mvs_args *args, int flags, int32_t *info_out, int64_t *idx_out, double *vals_out)
+{
+    if (!h || !info_out || !idx_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {loc}));
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
+    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dloc, *didx; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dloc = w.take<int64_t>(n);
+        dinfo = w.take<int32_t>(n * 8); didx = w.take<int64_t>(n); dvals = w.take<double>(n * 5);
+        scr = w.take<char>(slots * 2 * L * esz);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dloc, loc, n * 8));
+    { Scope s(h, "k_mvs_at_loc");
+      if (f64) hipLaunchKernelGGL(k_mvs_at_loc<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dloc, *args, (double *)scr, dinfo, didx, dvals);
+      else hipLaunchKernelGGL(k_mvs_at_loc<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dloc, *args, (float *)scr, dinfo, didx, dvals); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, info_out, dinfo, n * 32));
+    RCCHK(d2h(h, idx_out, didx, n * 8));
+    RCCHK(d2h(h, vals_out, dvals, n * 40));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *args, int flags,
+                   int64_t *out)
+{
+    if (!h || !out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(mv_check_args(sig, len, n_reads, L, args, {}));
+    if (args->min_obs_adapter < 0 || args->min_obs_post_loc < 0 || args->s_median_shift_window < 0 || args->s_polyA_window < 0) {
+        g_err = "min_obs_adapter, min_obs_post_loc and the windows must be >= 0"; return ADP_ERR_INVALID;
+    }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen; int64_t *dres;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4));
+    // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
+    const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
+    { Scope s(h, "k_mvs_stream");
+      if (f64) hipLaunchKernelGGL(k_mvs_stream<double>, dim3(grid), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, *args, dres);
+      else hipLaunchKernelGGL(k_mvs_stream<float>, dim3(grid), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, *args, dres); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, out, dres, n * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+} // extern "C"

@@ -6,8 +6,8 @@
 //
 // Each kernel is instantiated for float (the pipeline's calibrated signals) and double (float64 and widened integer input):
 // bottleneck runs its recurrences in the input dtype, numpy's medians and sums too.  The float instantiations use the float32
-// selections and sums of wave_stats.h; the double ones the 64-bit radix select below (llr_detect_api.h's keys) and numpy's
-// pairwise sum restated in one lane.  k_validate's mvs_check / mvs_detect_at_loc (validate.h) are not touched.
+// selections and sums of wave_stats.h; the double ones the 64-bit radix select below (common.h's d2key) and np_sum.h's
+// pairwise float64 sum.  k_validate's mvs_check / mvs_detect_at_loc (validate.h) are not touched.
 //
 // The bottleneck chains are the NaN-aware recurrences of bottleneck/src/move_template.c (a NaN sample is counted out of the
 // window; a window with fewer than `window` valid samples yields NaN): on NaN-free input they perform exactly the operations of
@@ -16,13 +16,13 @@
 // global memory).  k_mvs_stream keeps only the current chunk of both series, in LDS: the values at position i depend on samples
 // <= i alone, so the walk never needs the whole series, and its scratch is bounded per wave, not per read.
 //
-// Compiled in a translation unit of its own (mvs_kernels.hip, with the launchers adp_mvs_* call), apart from adapted_hip.hip: calls from here
-// into the shared helpers would otherwise change how the compiler optimises them across the detect path's kernels
-// (k_validate's code changed when this header was part of that unit).  It therefore carries its own copies of the few small
-// helpers of validate.h and llr_detect_api.h it needs.
+// Compiled in modules.hip with the other module drop-ins, apart from adapted_hip.hip: calls from here into the shared helpers
+// of wave_stats.h would otherwise change how the compiler optimises them across the detect path's kernels (k_validate's code
+// changed when this header was part of that unit).  In a unit of its own it calls them freely.
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "np_sum.h"
 #include "wave_stats.h"
 
 #define MVC_CHUNK 512
@@ -35,18 +35,6 @@
 #define MVS_ST_VALUE 2 // bottleneck's ValueError "Moving window (=w) must between 1 and n, inclusive" (info[3] = w, info[4] = n)
 
 static __device__ __forceinline__ bool in_range_d(double v, double lo, double hi) { return lo <= v && v <= hi; }
-
-// order-preserving float64 <-> uint64 key (as llr_detect_api.h's d2key / key2d)
-static __device__ __forceinline__ uint64_t mv_d2key(double d)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(d);
-    return u ^ ((uint64_t)((int64_t)u >> 63) | 0x8000000000000000ULL);
-}
-static __device__ __forceinline__ double mv_key2d(uint64_t k)
-{
-    const uint64_t u = (k & 0x8000000000000000ULL) ? (k & 0x7fffffffffffffffULL) : ~k;
-    return __longlong_as_double((long long)u);
-}
 
 template <class T> struct MvsLds {
     T in[MVC_HIST + MVC_CHUNK]; // buf[k] = x[lo + k]
@@ -200,7 +188,7 @@ static __device__ __noinline__ double mv_select_d(const double *x, int n, int k,
         for (int i = ln; i < n; i += 64) {
             const double v = x[i];
             if (skipnan && v != v) continue;
-            const uint64_t key = mv_d2key(v);
+            const uint64_t key = d2key(v);
             if ((key & mask) == prefix) __hip_atomic_fetch_add(&ws->hist[(key >> shift) & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         ws_sync();
@@ -217,7 +205,7 @@ static __device__ __noinline__ double mv_select_d(const double *x, int n, int k,
         mask |= (uint64_t)255 << shift;
         kk -= below;
     }
-    return mv_key2d(prefix);
+    return key2d(prefix);
 }
 
 // np.median(x[0, n)): NaN for an empty slice or one with a NaN
@@ -260,16 +248,7 @@ static __device__ double mv_nanmedian(const double *s, int n, LDS WaveScratch *w
 static __device__ void mv_med_lrange(const float *x, int n, LDS WaveScratch *ws, float &med, double &lr)
 {
     if (mv_any_nan(x, n)) { med = __builtin_nanf(""); lr = __builtin_nan(""); return; }
-    // (wave_median_local_range's three ranks, restated here rather than called: another call site could change how the compiler
-    // inlines it into k_validate, whose code this module must leave as it is)
-    int lo85, hi85, lo15, hi15; double g85, g15;
-    ws_pct_ranks(n, 85.0, lo85, hi85, g85);
-    ws_pct_ranks(n, 15.0, lo15, hi15, g15);
-    const int k[3] = {n / 2, hi85, hi15};
-    float vk[3], vkm1[3];
-    wave_select_ranks<RowF32, 3>(as_row(x), n, k, 0, 0.0f, ws, vk, vkm1);
-    med = (n & 1) ? vk[0] : (vkm1[0] + vk[0]) / 2.0f;
-    lr = ws_pct_value(vk[1], vkm1[1], lo85, hi85, g85) - ws_pct_value(vk[2], vkm1[2], lo15, hi15, g15);
+    wave_median_local_range(x, n, ws, med, lr);
 }
 static __device__ __forceinline__ double mv_pct_d(const double *x, int n, double q100, LDS WaveScratch *ws)
 {
@@ -288,61 +267,20 @@ static __device__ void mv_med_lrange(const double *x, int n, LDS WaveScratch *ws
     lr = mv_pct_d(x, n, 85.0, ws) - mv_pct_d(x, n, 15.0, ws);
 }
 
-// numpy's pairwise float64 sum (pairwise_sum of loops_utils.h.src) of xform(a[0, n)), n <= 8192, in one lane
-static __device__ __forceinline__ double mv_xf(double v, int mode, double c) { if (mode == 0) return v; const double d = v - c; return d * d; }
-static __device__ __noinline__ double mv_pw_leaf(const double *a, int n, int mode, double c)
-{
-    if (n < 8) {
-        double res = 0.;
-        for (int i = 0; i < n; i++) res += mv_xf(a[i], mode, c);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = mv_xf(a[j], mode, c);
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] += mv_xf(a[i + j], mode, c);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += mv_xf(a[i], mode, c);
-    return res;
-}
-template <int D>
-static __device__ __noinline__ double mv_pw(const double *a, int n, int mode, double c)
-{
-    if (n <= 128) return mv_pw_leaf(a, n, mode, c);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return mv_pw<D - 1>(a, n2, mode, c) + mv_pw<D - 1>(a + n2, n - n2, mode, c);
-}
-template <>
-__device__ __noinline__ double mv_pw<0>(const double *a, int n, int mode, double c) { return mv_pw_leaf(a, n, mode, c); }
-
-// np.add.reduce: 8192-element blocks added in sequence to 0 (the identity), each block pairwise -- the same order
-// wave_np_sum_t restates for float32.  Lane 0 sums, every lane returns the value.
-static __device__ double mv_np_sum_d(const double *x, int n, int mode, double c)
-{
-    double total = 0.0;
-    if (lane_id() == 0)
-        for (int s = 0; s < n; s += 8192) total += mv_pw<7>(x + s, min(8192, n - s), mode, c);
-    return __shfl(total, 0);
-}
-
 // np.mean / np.var (ddof 0) of x[0, n): NaN for an empty slice (numpy's 0 / 0)
-// (wave_np_mean / wave_np_var's arithmetic over the shared wave_np_sum, for the reason given at mv_med_lrange)
-static __device__ float mv_np_mean(const float *x, int n, LDS WaveScratch *ws) { return wave_np_sum(as_row(x), n, 0, 0.0f, ws) / (float)n; }
-static __device__ float mv_np_var(const float *x, int n, LDS WaveScratch *ws)
+// (float32: wave_stats.h's)
+static __device__ float mv_np_mean(const float *x, int n, LDS WaveScratch *ws) { return wave_np_mean(x, n, ws); }
+static __device__ float mv_np_var(const float *x, int n, LDS WaveScratch *ws) { return wave_np_var(x, n, ws, nullptr); }
+// (float64: np_sum.h's sum; its LDS state takes the place of the selections' scratch, idle meanwhile)
+static_assert(sizeof(NpSumLds) <= sizeof(WaveScratch) && alignof(NpSumLds) <= 16, "np_sum_wave's state must fit the wave scratch it reuses");
+static __device__ double mv_np_mean(const double *x, int n, LDS WaveScratch *ws)
 {
-    const float mu = wave_np_sum(as_row(x), n, 0, 0.0f, ws) / (float)n;
-    return wave_np_sum(as_row(x), n, 2, mu, ws) / (float)n;
+    return np_sum_wave(n, [&](long k) { return x[k]; }, (LDS NpSumLds *)ws) / (double)n;
 }
-static __device__ double mv_np_mean(const double *x, int n, LDS WaveScratch *) { return mv_np_sum_d(x, n, 0, 0.0) / (double)n; }
-static __device__ double mv_np_var(const double *x, int n, LDS WaveScratch *)
+static __device__ double mv_np_var(const double *x, int n, LDS WaveScratch *ws)
 {
-    const double mu = mv_np_sum_d(x, n, 0, 0.0) / (double)n;
-    return mv_np_sum_d(x, n, 2, mu) / (double)n;
+    const double mu = mv_np_mean(x, n, ws);
+    return np_sum_wave(n, [&](long k) { const double d = x[k] - mu; return d * d; }, (LDS NpSumLds *)ws) / (double)n;
 }
 
 // the array form of in_range (utils.py:26) on a series value: float32 against the bounds cast to float32 (numpy 1.x value-based

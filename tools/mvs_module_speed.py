@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Reads/s of the MVS poly(A) module's batch forms (adp_mvs_check, adp_mvs_detect_at_loc, adp_mvs_detect:
-adapted_amd/csrc/mvs_api.h) with float32 reads resident in HBM, at 16 000 and 200 000 samples; per-kernel times from
-adp_kernel_times (HIP events on the handle's stream).  The reads: an adapter, a poly(A) at a depth of its own, RNA; every fifth
+adapted_amd/csrc/mvs_api.h) with float32 (or, --dtype float64, float64) reads resident in HBM, at 16 000 and 200 000 samples;
+per-kernel times from adp_kernel_times (HIP events on the handle's stream).  check_whole: the check without windowed_stats, whose
+mean and variance are numpy-ordered sums over the poly(A).  The reads: an adapter, a poly(A) at a depth of its own, RNA; every fifth
 without a poly(A), so that the streaming walk runs to the read's end.
 
-  python tools/mvs_module_speed.py [--reads N] [--reps R] [--out FILE]
+  python tools/mvs_module_speed.py [--reads N] [--reps R] [--dtype float32|float64] [--out FILE]
   python3.9 tools/mvs_module_speed.py --reference [--out FILE]   (build container only: the reference's mvs.py with the real
                                                                   bottleneck on one CPU core, on the same reads)"""
 import argparse
@@ -39,20 +40,22 @@ def reads(n, L, seed=3):
     return x, ae, pe
 
 
-def device(n, L, reps):
+def device(n, L, reps, dtype=np.float32):
     from adapted_amd.config.schema import MVSPolyAConfig, StreamingConfig
     from adapted_amd.detect import mvs
 
     eng = mvs._engine()
     x, ae, pe = reads(n, L)
+    x = x.astype(dtype, copy=False)
     lens = np.full(n, L, dtype=np.int32)
-    out = dict(samples=L, reads=n, reps=reps, dtype="float32", resident=True)
+    out = dict(samples=L, reads=n, reps=reps, dtype=np.dtype(dtype).name, resident=True)
     d = eng.dev_alloc(x.nbytes)
     try:
         eng.h2d(d, x)
-        kw = dict(n=n, L=L, dtype=np.float32)
+        kw = dict(n=n, L=L, dtype=dtype)
         forms = {
             "check": lambda: mvs.mean_var_shift_polyA_check_batch(d, lens, ae, pe, MVSPolyAConfig(), **kw),
+            "check_whole": lambda: mvs.mean_var_shift_polyA_check_batch(d, lens, ae, pe, MVSPolyAConfig(), windowed_stats=False, **kw),
             "detect_at_loc": lambda: mvs.mean_var_shift_polyA_detect_at_loc_batch(d, lens, ae, MVSPolyAConfig(), **kw),
             "detect": lambda: mvs.mean_var_shift_polyA_detect_batch(d, lens, StreamingConfig(), **kw),
         }
@@ -104,13 +107,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=2000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.reference:
         res = [reference(min(a.reads, 400), 16_000), reference(min(a.reads, 100), 200_000)]
     else:
-        res = [device(a.reads, 16_000, a.reps), device(a.reads, 200_000, a.reps)]
+        res = [device(a.reads, 16_000, a.reps, np.dtype(a.dtype)), device(a.reads, 200_000, a.reps, np.dtype(a.dtype))]
     for r in res:
         print(json.dumps(r))
     if a.out:
