@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include "llr_detect_api.h"
 #include "trace_peaks_api.h"
 #include "mvs_api.h"
+#include "sigstats_api.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -67,6 +68,54 @@ static bool spans_ok(const int32_t *start, const int32_t *end, const int32_t *le
     return true;
 }
 static bool positions_ok(const int64_t *p, int n) { return all_in<int64_t>(p, n, 0, (int64_t)1 << 40); }
+
+// ---- the signal statistics modules (sigstats_api.h)
+
+// the segments of a call, checked: rows in [0, n_reads), positions <= 2^40
+static int seg_check(const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg)
+{
+    if (!sig || !len || !segs || n_reads < 1 || L < 1 || n_seg < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    const int64_t pmax = (int64_t)1 << 40;
+    for (int g = 0; g < n_seg; g++) {
+        if (segs[g].row < 0 || segs[g].row >= n_reads) { g_err = "need 0 <= row < n_reads for every segment"; return ADP_ERR_INVALID; }
+        if (segs[g].start > pmax || segs[g].end > pmax) { g_err = "positions must lie in [0, 2^40]"; return ADP_ERR_INVALID; }
+    }
+    return ADP_OK;
+}
+
+// median and MAD on the device -> dmm [rows, 2] ([1, 2] with ADP_SS_WHOLE; then dlen[0] holds n_reads * L)
+template <class T>
+static int ss_med_mad_dev(adp_handle *h, const T *ds, const int32_t *dlen, int n_reads, int L, int flags, double *dmm, SsPop *dst,
+                           uint32_t *dhist)
+{
+    const int skip = (flags & ADP_SS_NANSKIP) != 0;
+    if (!(flags & ADP_SS_WHOLE)) {
+        Scope s(h, "k_row_med_mad");
+        hipLaunchKernelGGL(k_row_med_mad<T>, dim3(n_reads), dim3(SS_BLOCK), 0, h->stream, ds, dlen, n_reads, (long long)L, skip, dmm);
+        return ADP_OK;
+    }
+    const long long N = (long long)n_reads * L;
+    const bool grid = (flags & ADP_SS_FORCE_GRID) || (!(flags & ADP_SS_FORCE_WAVE) && N > ADP_SS_GRID_MIN);
+    if (!grid) {
+        Scope s(h, "k_row_med_mad");
+        hipLaunchKernelGGL(k_row_med_mad<T>, dim3(1), dim3(SS_BLOCK), 0, h->stream, ds, dlen, 1, N, skip, dmm);
+        return ADP_OK;
+    }
+    long long nb = (N + 4095) / 4096;
+    if (nb > (long long)h->n_cu * 8) nb = (long long)h->n_cu * 8;
+    HIPCHK(hipMemsetAsync(dhist, 0, 512 * sizeof(uint32_t), h->stream));
+    for (int sel = 0; sel < 2; sel++) {
+        HIPCHK(hipMemsetAsync(dst, 0, sizeof(SsPop), h->stream));
+        for (int pass = 0; pass < (int)sizeof(typename SsKey<T>::type); pass++) {
+            { Scope s(h, "k_pop_hist");
+              hipLaunchKernelGGL(k_pop_hist<T>, dim3((unsigned)nb), dim3(SS_POP_BLOCK), 0, h->stream, ds, N, sel ? dmm : (const double *)nullptr, pass, skip, dst, dhist); }
+            { Scope s(h, "k_pop_pick");
+              hipLaunchKernelGGL(k_pop_pick<T>, dim3(1), dim3(64), 0, h->stream, pass, skip, dst, dhist, dmm + sel); }
+        }
+    }
+    return ADP_OK;
+}
 
 extern "C" {
 
@@ -454,6 +503,194 @@ int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_rea
       else hipLaunchKernelGGL(k_mvs_stream<float>, dim3(grid), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, *args, dres); }
     HIPCHK(hipGetLastError());
     RCCHK(d2h(h, out, dres, n * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// ---- the reference's partition statistics (adapted/partition/signal_partitions.py) on batched segments (sigstats_api.h)
+
+int adp_sizeof_seg(void) { return (int)sizeof(adp_seg); }
+
+int adp_seg_stats(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, int flags,
+                  double *stats_out, int64_t *count_out)
+{
+    if (!h || !stats_out || !count_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen; SsSeg *dsegs; double *dstats; int64_t *dcnt;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns);
+        dstats = w.take<double>(ns * 4); dcnt = w.take<int64_t>(ns);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    { Scope s(h, "k_seg_stats");
+      if (f64) hipLaunchKernelGGL(k_seg_stats<double>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, dstats, dcnt);
+      else hipLaunchKernelGGL(k_seg_stats<float>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, dstats, dcnt); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, stats_out, dstats, ns * 32));
+    RCCHK(d2h(h, count_out, dcnt, ns * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_sizeof_real_range_args(void) { return (int)sizeof(adp_real_range_args); }
+
+static int ss_rows_check(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags)
+{
+    if (!h || !sig || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (flags & ADP_SS_WHOLE) {
+        if ((long long)n_reads * L > 0x7fffffffLL) { g_err = "a population of at most 2^31 - 1 samples"; return ADP_ERR_INVALID; }
+    } else if (!len || !lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    return ADP_OK;
+}
+
+int adp_med_mad(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags, double *out)
+{
+    RCCHK(ss_rows_check(h, sig, len, n_reads, L, flags));
+    if (!out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0, whole = (flags & ADP_SS_WHOLE) != 0;
+    const size_t n = n_reads, esz = f64 ? 8 : 4, rows = whole ? 1 : n;
+    void *s_sig; int32_t *dlen; double *dmm; SsPop *dst; uint32_t *dhist;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dmm = w.take<double>(rows * 2); dst = w.take<SsPop>(1); dhist = w.take<uint32_t>(512);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    const int32_t total = (int32_t)((long long)n_reads * L * (whole ? 1 : 0));
+    if (whole) RCCHK(h2d(h, dlen, &total, 4)); else RCCHK(h2d(h, dlen, len, n * 4));
+    if (f64) RCCHK(ss_med_mad_dev(h, (const double *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
+    else RCCHK(ss_med_mad_dev(h, (const float *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, out, dmm, rows * 16));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_normalize(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, double outlier_thresh, int flags,
+                  double *medmad_io, void *out, int32_t *status_out)
+{
+    RCCHK(ss_rows_check(h, sig, len, n_reads, L, flags));
+    if (!medmad_io || !out || !status_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    const bool f64 = (flags & ADP_MVS_F64) != 0, whole = (flags & ADP_SS_WHOLE) != 0, clip = (flags & ADP_SS_CLIP) != 0, out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    int nbx = (L + 1023) / 1024;
+    if (nbx > 64) nbx = 64;
+    if ((long long)n_reads * nbx > 0x7fffffffLL) { g_err = "too many rows"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t n = n_reads, esz = f64 ? 8 : 4, rows = whole ? 1 : n, mat = (size_t)L * esz * n;
+    void *s_sig, *w_out; int32_t *dlen, *dstat; double *dmm; SsPop *dst; uint32_t *dhist;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>(mat, !(flags & ADP_IN_DEVICE)); w_out = w.take<char>(mat, !out_dev);
+        dlen = w.take<int32_t>(n); dstat = w.take<int32_t>(rows); dmm = w.take<double>(rows * 2); dst = w.take<SsPop>(1); dhist = w.take<uint32_t>(512);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, mat, &ds));
+    const int32_t total = (int32_t)((long long)n_reads * L * (whole ? 1 : 0));
+    if (whole) RCCHK(h2d(h, dlen, &total, 4)); else RCCHK(h2d(h, dlen, len, n * 4));
+    if (clip) RCCHK(h2d(h, dmm, medmad_io, rows * 16));
+    else if (f64) RCCHK(ss_med_mad_dev(h, (const double *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
+    else RCCHK(ss_med_mad_dev(h, (const float *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
+    void *dout = out_dev ? out : w_out;
+    if (!out_dev) HIPCHK(hipMemsetAsync(dout, 0, mat, h->stream)); // (cells behind a read's end, rows of MAD 0: zeros on the host)
+    const int32_t *klen = whole ? nullptr : dlen;
+    { Scope s(h, "k_clip_scale");
+      if (f64) hipLaunchKernelGGL(k_clip_scale<double>, dim3((unsigned)(n * nbx)), dim3(256), 0, h->stream, (const double *)ds, klen, (long long)L, dmm, outlier_thresh, whole ? 1 : 0, clip ? 1 : 0, nbx, (double *)dout, dstat);
+      else hipLaunchKernelGGL(k_clip_scale<float>, dim3((unsigned)(n * nbx)), dim3(256), 0, h->stream, (const float *)ds, klen, (long long)L, dmm, outlier_thresh, whole ? 1 : 0, clip ? 1 : 0, nbx, (float *)dout, dstat); }
+    HIPCHK(hipGetLastError());
+    if (!out_dev) RCCHK(d2h(h, out, dout, mat));
+    if (!clip) RCCHK(d2h(h, medmad_io, dmm, rows * 16));
+    RCCHK(d2h(h, status_out, dstat, rows * 4));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_pool_mean(adp_handle *h, const void *data, int n_rows, int n_cols, int pool_size, int flags, void *out)
+{
+    if (!h || !data || !out || n_rows < 1 || n_cols < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (pool_size < 1) { g_err = "pool_size must be >= 1"; return ADP_ERR_INVALID; }
+    const bool f64 = (flags & ADP_MVS_F64) != 0, out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    const long long n_out = ((long long)n_cols + pool_size - 1) / pool_size;
+    const int nbx = (int)((n_out + 255) / 256);
+    const long long grid = pool_size <= 128 ? (long long)n_rows * nbx : (long long)n_rows * n_out;
+    if (grid > 0x7fffffffLL) { g_err = "too many outputs for one call"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const size_t esz = f64 ? 8 : 4, in_b = (size_t)n_rows * n_cols * esz, out_b = (size_t)n_rows * n_out * esz;
+    void *s_in, *w_out;
+    RCCHK(ws_carve(h, [&](Carve &w) { s_in = w.take<char>(in_b, !(flags & ADP_IN_DEVICE)); w_out = w.take<char>(out_b, !out_dev); }));
+    const void *dd;
+    RCCHK(stage_in(h, flags, data, s_in, in_b, &dd));
+    void *dout = out_dev ? out : w_out;
+    if (pool_size <= 128) {
+        Scope s(h, "k_pool_mean");
+        if (f64) hipLaunchKernelGGL(k_pool_mean<double>, dim3((unsigned)grid), dim3(256), 0, h->stream, (const double *)dd, n_rows, (long long)n_cols, pool_size, n_out, nbx, (double *)dout);
+        else hipLaunchKernelGGL(k_pool_mean<float>, dim3((unsigned)grid), dim3(256), 0, h->stream, (const float *)dd, n_rows, (long long)n_cols, pool_size, n_out, nbx, (float *)dout);
+    } else {
+        Scope s(h, "k_pool_mean_wave");
+        if (f64) hipLaunchKernelGGL(k_pool_mean_wave<double>, dim3((unsigned)grid), dim3(64), 0, h->stream, (const double *)dd, n_rows, (long long)n_cols, pool_size, n_out, (double *)dout);
+        else hipLaunchKernelGGL(k_pool_mean_wave<float>, dim3((unsigned)grid), dim3(64), 0, h->stream, (const float *)dd, n_rows, (long long)n_cols, pool_size, n_out, (float *)dout);
+    }
+    HIPCHK(hipGetLastError());
+    if (!out_dev) RCCHK(d2h(h, out, dout, out_b));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_real_range(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                   const adp_real_range_args *args, int flags, int32_t *info_out, double *vals_out)
+{
+    if (!h || !args || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
+    if (args->mean_window < 1 || args->max_obs_local_range < 1) { g_err = "mean_window and max_obs_local_range must be >= 1"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen, *dinfo; SsSeg *dsegs; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns); dinfo = w.take<int32_t>(ns * 2); dvals = w.take<double>(ns * 3);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    { Scope s(h, "k_real_range");
+      if (f64) hipLaunchKernelGGL(k_real_range<double>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, *args, dinfo, dvals);
+      else hipLaunchKernelGGL(k_real_range<float>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, *args, dinfo, dvals); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, info_out, dinfo, ns * 8));
+    RCCHK(d2h(h, vals_out, dvals, ns * 24));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, double lo,
+                   double hi, double min_obs_diff, int flags, int cap, int64_t *pos_out, int64_t *count_out)
+{
+    if (!h || !pos_out || !count_out || cap < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
+    if (lo != lo || hi != hi || min_obs_diff != min_obs_diff) { g_err = "the range and min_obs_diff must be numbers"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen; SsSeg *dsegs; int64_t *dpos, *dcnt;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns); dpos = w.take<int64_t>(ns * cap); dcnt = w.take<int64_t>(ns * 3);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    { Scope s(h, "k_open_pores");
+      if (f64) hipLaunchKernelGGL(k_open_pores<double>, dim3(n_seg), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, lo, hi, min_obs_diff, cap, dpos, dcnt);
+      else hipLaunchKernelGGL(k_open_pores<float>, dim3(n_seg), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, lo, hi, min_obs_diff, cap, dpos, dcnt); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
+    RCCHK(d2h(h, count_out, dcnt, ns * 24));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }

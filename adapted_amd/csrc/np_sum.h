@@ -1,22 +1,23 @@
-// np_sum.h -- np.add.reduce of a float64 array in numpy's order, by one wave (trace_peaks_api.h: np.nanstd; mvs_api.h: np.mean /
-// np.var of float64 input).
+// np_sum.h -- np.add.reduce of a float64 (or, with float accumulators, float32) array in numpy's order, by one workgroup (a wave, or several)
+// (trace_peaks_api.h: np.nanstd; mvs_api.h: np.mean / np.var of float64 input; sigstats_api.h: both types).
 #pragma once
 #include "common.h"
 
 #define LP_MAXLEAF 136 // leaves of numpy's pairwise tree over one 8192-element buffer (each leaf > 56 elements: at most 147; 128 for 8192)
 
 // ---------------------------------------------------------------- numpy's add.reduce order, one wave
-// np.add.reduce over a contiguous float64 array: buffers of <= 8192 elements added in sequence to 0.0, each summed by the
+// np.add.reduce over a contiguous array of A (double, float): buffers of <= 8192 elements added in sequence to 0.0, each summed by the
 // pairwise recursion (numpy/_core/src/umath/loops_utils.h.src pairwise_sum: a node longer than 128 splits at
-// n2 = n / 2 - (n / 2) % 8; a leaf of >= 8 elements uses 8 interleaved accumulators).  The leaves are summed by the lanes in
-// parallel, the tree is combined by lane 0 with a stack in LDS (no private arrays: no scratch).
-struct NpSumLds {
+// n2 = n / 2 - (n / 2) % 8; a leaf of >= 8 elements uses 8 interleaved accumulators).  The leaves are summed by the threads of
+// the workgroup in parallel, the tree is combined by thread 0 with a stack in LDS (no private arrays: no scratch).
+template <class A> struct NpSumLdsT {
     int loff[LP_MAXLEAF];
-    double lsum[LP_MAXLEAF];
+    A lsum[LP_MAXLEAF];
     int so[16], sn[16], sph[16];
-    double val[16];
-    double out;
+    A val[16];
+    A out;
 };
+typedef NpSumLdsT<double> NpSumLds;
 
 // the leaf of numpy's tree over [0, nb) that holds position p: (offset, length)
 static __device__ __forceinline__ int2 np_leaf_of(int nb, int p)
@@ -31,35 +32,35 @@ static __device__ __forceinline__ int2 np_leaf_of(int nb, int p)
     return make_int2(o, n);
 }
 
-template <class F>
-static __device__ __forceinline__ double np_pw_leaf(int o, int n, F get)
+template <class A = double, class F>
+static __device__ __forceinline__ A np_pw_leaf(int o, int n, F get)
 {
     if (n < 8) {
-        double res = 0.0;
+        A res = (A)0;
         for (int i = 0; i < n; i++) res += get(o + i);
         return res;
     }
-    double r0 = get(o), r1 = get(o + 1), r2 = get(o + 2), r3 = get(o + 3), r4 = get(o + 4), r5 = get(o + 5), r6 = get(o + 6), r7 = get(o + 7);
+    A r0 = get(o), r1 = get(o + 1), r2 = get(o + 2), r3 = get(o + 3), r4 = get(o + 4), r5 = get(o + 5), r6 = get(o + 6), r7 = get(o + 7);
     int i;
     for (i = 8; i < n - (n % 8); i += 8) {
         r0 += get(o + i); r1 += get(o + i + 1); r2 += get(o + i + 2); r3 += get(o + i + 3);
         r4 += get(o + i + 4); r5 += get(o + i + 5); r6 += get(o + i + 6); r7 += get(o + i + 7);
     }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    A res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
     for (; i < n; i++) res += get(o + i);
     return res;
 }
 
-// sum of get(k), k in [0, n), in numpy's order.  Uniform call; every lane gets the result.
-template <class F>
-static __device__ double np_sum_wave(long n, F get, LDS NpSumLds *s)
+// sum of get(k), k in [0, n), in numpy's order, accumulated in A (what get returns).  Uniform call of the whole workgroup; every thread gets the result.
+template <class F, class A>
+static __device__ A np_sum_wave(long n, F get, LDS NpSumLdsT<A> *s)
 {
-    const int ln = lane_id();
-    double t = 0.0;
+    const int ln = threadIdx.x, nt = blockDim.x;
+    A t = (A)0;
     for (long b0 = 0; b0 < n; b0 += 8192) {
         const int nb = (int)(n - b0 < 8192 ? n - b0 : 8192);
         auto gb = [&](int k) { return get(b0 + k); };
-        // the leaves, in order (every lane walks them alike: <= 7 levels per leaf)
+        // the leaves, in order (every thread walks them alike: <= 7 levels per leaf)
         int nl = 0;
         for (int p = 0; p < nb; nl++) {
             const int2 lf = np_leaf_of(nb, p);
@@ -67,9 +68,9 @@ static __device__ double np_sum_wave(long n, F get, LDS NpSumLds *s)
             p = lf.x + lf.y;
         }
         __syncthreads();
-        for (int k = ln; k < nl; k += 64) {
+        for (int k = ln; k < nl; k += nt) {
             const int o = s->loff[k], e = (k + 1 < nl) ? s->loff[k + 1] : nb;
-            s->lsum[k] = np_pw_leaf(o, e - o, gb);
+            s->lsum[k] = np_pw_leaf<A>(o, e - o, gb);
         }
         __syncthreads();
         if (ln == 0) {
@@ -79,7 +80,7 @@ static __device__ double np_sum_wave(long n, F get, LDS NpSumLds *s)
             while (sp > 0) {
                 sp--;
                 const int o = s->so[sp], nn = s->sn[sp];
-                if (s->sph[sp]) { const double rr = s->val[--rs], ll = s->val[--rs]; s->val[rs++] = ll + rr; continue; }
+                if (s->sph[sp]) { const A rr = s->val[--rs], ll = s->val[--rs]; s->val[rs++] = ll + rr; continue; }
                 if (nn <= 128) { s->val[rs++] = s->lsum[leaf++]; continue; }
                 int n2 = nn / 2;
                 n2 -= n2 % 8;

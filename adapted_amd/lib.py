@@ -257,7 +257,8 @@ def load():
     assert_one_runtime()
     if (lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize
             or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)
-            or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs)):
+            or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs) or lib.adp_sizeof_seg() != SEG_DTYPE.itemsize
+            or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     lib.adp_last_error.restype = C.c_char_p
     lib.adp_stream.restype = C.c_void_p
@@ -274,7 +275,8 @@ EXPORTS = ["adp_abi_version", "adp_sizeof_cfg", "adp_sizeof_row", "adp_last_erro
            "adp_cnn_set_weights", "adp_cnn_forward", "adp_cnn_predict", "adp_detect_cnn", "adp_open_pores_arena", "adp_detect_llr_i16", "adp_expand_ragged_i16",
            "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect", "adp_sizeof_peak_args", "adp_sizeof_spike_args",
            "adp_llr_trace_bounds", "adp_llr_trace_peaks", "adp_llr_spike_peak", "adp_sizeof_mvs_args", "adp_mvs_check",
-           "adp_mvs_detect_at_loc", "adp_mvs_detect"]
+           "adp_mvs_detect_at_loc", "adp_mvs_detect", "adp_sizeof_seg", "adp_seg_stats",
+           "adp_sizeof_real_range_args", "adp_med_mad", "adp_normalize", "adp_pool_mean", "adp_real_range", "adp_open_pores"]
 
 
 class AdpTraceArgs(C.Structure):
@@ -306,12 +308,27 @@ class AdpMvsArgs(C.Structure):
                                               "s_polyA_local_range")]
 
 
+class AdpRealRangeArgs(C.Structure):
+    """struct adp_real_range_args (include/adapted_hip.h): the [real_range] parameters real_range_check reads"""
+    _fields_ = [(k, C.c_double * 2) for k in ("mean_start_range", "mean_end_range", "local_range")] + \
+               [(k, C.c_int32) for k in ("mean_window", "max_obs_local_range")]
+
+
+# struct adp_seg (include/adapted_hip.h): a segment signal[row, start:end] of a batch
+SEG_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("row", "<i4"), ("pad", "<i4")])
+
 ADP_TRACE_FROM_SUMS = 64
 ADP_LLR_INTERP = 512
 ADP_LLR_GIVEN_PEAK = 1024
 ADP_CLLR_POLYA = 128
 ADP_CLLR_F32 = 256
 ADP_MVS_F64 = 2048
+ADP_SS_NANSKIP = 4096
+ADP_SS_WHOLE = 8192
+ADP_SS_CLIP = 16384
+ADP_SS_FORCE_GRID = 32768
+ADP_SS_FORCE_WAVE = 65536
+ADP_SS_GRID_MIN = 16384
 
 
 class MinibatchDropped(RuntimeError):
@@ -786,6 +803,119 @@ class Engine:
     def mvs_detect(self, sig, lens, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
         """adp_mvs_detect -> int64 [n] (0: no poly(A) found)"""
         return self._mvs_call(self.lib.adp_mvs_detect, sig, lens, (), args, n, L, f64, lambda n: (np.zeros(n, dtype=np.int64),))[0]
+
+    def _sig_in(self, sig, n, L, f64):
+        """a signal statistics call's signals -> (pointer, flags with the dtype's, n, L, dtype)"""
+        p, flags, n, L, a = self._rows_in(sig, n, L, (np.float32, np.float64))
+        if (a.dtype == np.float64) if a is not None else f64:
+            flags |= ADP_MVS_F64
+        return p, flags, n, L, np.dtype(np.float64 if flags & ADP_MVS_F64 else np.float32)
+
+    def _segs(self, rows, starts, ends):
+        """struct adp_seg [n_seg] of per-segment rows, starts and ends"""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        segs = np.zeros(rows.size, dtype=SEG_DTYPE)
+        segs["row"] = rows
+        segs["start"] = self._per_read(starts, rows.size, "starts", np.int64)
+        segs["end"] = self._per_read(ends, rows.size, "ends", np.int64)
+        return segs
+
+    def seg_stats(self, sig, lens, rows, starts, ends, n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
+        """adp_seg_stats: signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``), lens, and per segment its
+        row, start and end -> (stats float64 [n_seg, 4]: mean, std, median, MAD; counts int64 [n_seg]: the clipped sizes)"""
+        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
+        stats = np.zeros((segs.size, 4))
+        cnt = np.zeros(segs.size, dtype=np.int64)
+        self._check(self.lib.adp_seg_stats(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size), flags,
+                                           *self._ptrs(stats, cnt)))
+        return stats, cnt
+
+    @staticmethod
+    def _ss_flags(with_nan, whole, regime):
+        return ((ADP_SS_NANSKIP if with_nan else 0) | (ADP_SS_WHOLE if whole else 0)
+                | {None: 0, "grid": ADP_SS_FORCE_GRID, "wave": ADP_SS_FORCE_WAVE}[regime])
+
+    def med_mad(self, sig, lens=None, with_nan: bool = False, whole: bool = False, n: Optional[int] = None, L: Optional[int] = None,
+                f64: bool = False, regime: Optional[str] = None):
+        """adp_med_mad -> float64 [n, 2] (median, MAD of every row's [0, lens[r])), or with ``whole`` [1, 2] of the whole array as
+        one population.  ``regime``: "grid" / "wave" force the many-workgroup / the one-workgroup selection of a whole population"""
+        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        flags |= self._ss_flags(with_nan, whole, regime)
+        lens = None if whole else self._per_read(lens, n, "lens")
+        out = np.zeros((1 if whole else n, 2))
+        self._check(self.lib.adp_med_mad(self._h, p, *self._ptrs(lens), int(n), int(L), flags, *self._ptrs(out)))
+        return out
+
+    def normalize(self, sig, lens=None, outlier_thresh: float = 5.0, with_nan: bool = False, whole: bool = False, clip_medmad=None,
+                  n: Optional[int] = None, L: Optional[int] = None, f64: bool = False, out_ptr: Optional[int] = None,
+                  regime: Optional[str] = None):
+        """adp_normalize -> (out [n, L] of the input's type (None with ``out_ptr``, a device pointer the rows are written to),
+        medmad float64 [n, 2] or [1, 2], status int32 [n] or [1]: 1 where the MAD is 0).  ``clip_medmad``: the clip alone, about
+        the given (median, MAD) rows"""
+        p, flags, n, L, dt = self._sig_in(sig, n, L, f64)
+        flags |= self._ss_flags(with_nan, whole, regime)
+        rows = 1 if whole else n
+        lens = None if whole else self._per_read(lens, n, "lens")
+        if clip_medmad is not None:
+            flags |= ADP_SS_CLIP
+            mm = np.ascontiguousarray(clip_medmad, dtype=np.float64).reshape(-1, 2)
+            if mm.shape[0] != rows:
+                raise ValueError("clip_medmad needs one (median, MAD) per row, or one with whole")
+        else:
+            mm = np.zeros((rows, 2))
+        status = np.zeros(rows, dtype=np.int32)
+        if out_ptr is not None:
+            flags |= ADP_OUT_DEVICE
+            out, outp = None, C.c_void_p(int(out_ptr))
+        else:
+            out = np.zeros((n, L), dtype=dt)
+            outp = out.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.adp_normalize(self._h, p, *self._ptrs(lens), int(n), int(L), C.c_double(outlier_thresh), flags,
+                                           *self._ptrs(mm), outp, *self._ptrs(status)))
+        return out, mm, status
+
+    def pool_mean(self, data, pool_size: int, n: Optional[int] = None, L: Optional[int] = None, f64: bool = False,
+                  out_ptr: Optional[int] = None):
+        """adp_pool_mean: data [n, L] -> [n, ceil(L / pool_size)] of the input's type (None with ``out_ptr``)"""
+        p, flags, n, L, dt = self._sig_in(data, n, L, f64)
+        n_out = -(-L // int(pool_size))
+        if out_ptr is not None:
+            flags |= ADP_OUT_DEVICE
+            out, outp = None, C.c_void_p(int(out_ptr))
+        else:
+            out = np.zeros((n, n_out), dtype=dt)
+            outp = out.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.adp_pool_mean(self._h, p, int(n), int(L), int(pool_size), flags, outp))
+        return out
+
+    def real_range(self, sig, lens, rows, starts, ends, args: "AdpRealRangeArgs", n: Optional[int] = None, L: Optional[int] = None,
+                   f64: bool = False):
+        """adp_real_range -> (info int32 [n_seg, 2]: result, stage; vals float64 [n_seg, 3]: mean_start, mean_end, local range)"""
+        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
+        info = np.zeros((segs.size, 2), dtype=np.int32)
+        vals = np.zeros((segs.size, 3))
+        self._check(self.lib.adp_real_range(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size),
+                                            C.byref(args), flags, *self._ptrs(info, vals)))
+        return info, vals
+
+    def open_pores(self, sig, lens, rows, starts, ends, lo: float, hi: float, min_obs_diff: float, cap: int = 16,
+                   n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
+        """adp_open_pores -> (pos int64 [n_seg, cap'] padded with -1, counts int64 [n_seg, 3]: kept, in range, the last in range).
+        cap' >= cap: the call is repeated with the largest count when a list did not fit, so no list is cut short"""
+        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
+        cnt = np.zeros((segs.size, 3), dtype=np.int64)
+        cap = max(int(cap), 1)
+        while True:
+            pos = np.zeros((segs.size, cap), dtype=np.int64)
+            self._check(self.lib.adp_open_pores(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size),
+                                                C.c_double(lo), C.c_double(hi), C.c_double(min_obs_diff), flags, cap,
+                                                *self._ptrs(pos, cnt)))
+            if cnt[:, 0].max() <= cap:
+                return pos, cnt
+            cap = int(cnt[:, 0].max())
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

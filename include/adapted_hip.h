@@ -421,6 +421,64 @@ int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, co
 int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_mvs_args *args, int flags,
                    int64_t *out);
 
+/* The reference's partition statistics (adapted/partition/signal_partitions.py: calc_partition_stats), batched: n_seg segments
+ * signal[row, start:end] of signals [n_reads, L] float32, or float64 with ADP_MVS_F64 (read r valid in [0, len[r])), one wave per
+ * segment (adapted_amd/csrc/sigstats_api.h).  A segment is clipped to its read as a Python slice is (end or start beyond len[row]);
+ * start < 0 or end <= start gives an empty one.  len and segs: HOST arrays, checked here (0 <= len <= L, 0 <= row < n_reads,
+ * positions <= 2^40).  flags: ADP_IN_DEVICE -- `sig` is a device pointer.  Outputs, host memory: stats_out float64 [n_seg, 4] --
+ * np.mean, np.std, np.median and np.median(np.abs(x - median)) of the clipped slice, computed in the signals' type in numpy's
+ * order of operations and widened exactly (NaN x 4 for an empty slice; a NaN sample makes all four NaN); count_out int64 [n_seg]
+ * -- the clipped slice's size. */
+typedef struct adp_seg {
+    int64_t start, end;
+    int32_t row, pad;
+} adp_seg;
+int adp_sizeof_seg(void);
+int adp_seg_stats(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, int flags,
+                  double *stats_out, int64_t *count_out);
+
+/* The reference's signal statistics modules next to it, on the same batches (float32, or float64 with ADP_MVS_F64;
+ * ADP_IN_DEVICE: `sig` / `data` is a device pointer; every call completes before it returns; outputs: host memory unless said
+ * otherwise).  Kernels: adapted_amd/csrc/sigstats_api.h.
+ *
+ * adp_med_mad: med_mad (adapted/detect/normalize.py) of every row's [0, len[r]) -> out float64 [n_reads, 2]; with ADP_SS_WHOLE
+ *   of the whole [n_reads, L] array as one population (len is not read and may be NULL) -> out [1, 2].  ADP_SS_NANSKIP:
+ *   np.nanmedian's (with_nan=True).  Nothing counted: NaN.  A population of more than ADP_SS_GRID_MIN samples is selected by
+ *   many workgroups, a smaller one by one workgroup; ADP_SS_FORCE_GRID / ADP_SS_FORCE_WAVE choose (tests).
+ * adp_normalize: normalize_signal -- (clip(x, med - mad * thresh, med + mad * thresh) - med) / mad with each row's own median
+ *   and MAD, or the whole array's with ADP_SS_WHOLE -> out [n_reads, L] of the input's type (host, or device with
+ *   ADP_OUT_DEVICE; cells behind len[r] are not written), medmad_io float64 [n_reads, 2] / [1, 2], status_out int32 [n_reads] /
+ *   [1]: 1 where the MAD is 0 (the reference raises ValueError; the row is not written).  ADP_SS_CLIP: clip_signal -- medmad_io
+ *   is an INPUT and only the clip is applied.
+ * adp_pool_mean: efficient_average_pooling (adapted/detect/downscale.py) of data [n_rows, n_cols] -> out [n_rows,
+ *   ceil(n_cols / pool_size)] of the input's type (host, or device with ADP_OUT_DEVICE); a ragged last block is filled with zeros.
+ * adp_real_range: real_range_check (adapted/detect/real_range.py) of the segments -> info_out int32 [n_seg, 2]: the result; the
+ *   stage reached (0 fewer than 2 * mean_window samples, 1 a mean out of range, 2 the local range taken); vals_out float64
+ *   [n_seg, 3]: mean_start, mean_end (the input type's values), local range (float64).
+ * adp_open_pores: find_open_pores (adapted/detect/anomalies.py) of the segments: positions from the segment's start, in
+ *   [lo, hi], whose distance to the preceding position in range is >= min_obs_diff -> pos_out int64 [n_seg, cap] (the first cap
+ *   of them, then -1), count_out int64 [n_seg, 3]: their number (also past cap: call again with a larger cap), the number of
+ *   positions in range, the last of those (-1: none). */
+#define ADP_SS_NANSKIP 4096
+#define ADP_SS_WHOLE 8192
+#define ADP_SS_CLIP 16384
+#define ADP_SS_FORCE_GRID 32768
+#define ADP_SS_FORCE_WAVE 65536
+#define ADP_SS_GRID_MIN 16384
+typedef struct adp_real_range_args {
+    double mean_start_range[2], mean_end_range[2], local_range[2];
+    int32_t mean_window, max_obs_local_range;
+} adp_real_range_args;
+int adp_sizeof_real_range_args(void);
+int adp_med_mad(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags, double *out);
+int adp_normalize(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, double outlier_thresh, int flags,
+                  double *medmad_io, void *out, int32_t *status_out);
+int adp_pool_mean(adp_handle *h, const void *data, int n_rows, int n_cols, int pool_size, int flags, void *out);
+int adp_real_range(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                   const adp_real_range_args *args, int flags, int32_t *info_out, double *vals_out);
+int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, double lo,
+                   double hi, double min_obs_diff, int flags, int cap, int64_t *pos_out, int64_t *count_out);
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
