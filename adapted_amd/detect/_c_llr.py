@@ -18,19 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import lib
-from ._rows import as_rows
-
-_ENGINE = None
-
-
-def _engine(device: int = 0):
-    global _ENGINE
-    if _ENGINE is None or _ENGINE.device != device:
-        from ..config import get_chemistry_specific_config
-
-        spc = get_chemistry_specific_config("RNA004")  # (the trace API reads nothing from the configuration)
-        _ENGINE = lib.Engine(spc, 1, spc.sig_preload_size, device=device)
-    return _ENGINE
+from ._rows import _engine, as_rows  # noqa: F401  (_engine: the modules' engine, reached through this module too)
 
 
 def _args(min_obs, border_trim, stride, adapter_early_stopping, adapter_early_stop_window, adapter_early_stop_stride,

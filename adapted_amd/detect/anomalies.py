@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._sigstats import _engine, as_work, bounds, positions, rows_in
+from ._rows import _engine, as_work, bounds, positions, rows_in
 from .utils import in_range  # noqa: F401  (the reference module imports it from here)
 
 

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._sigstats import _engine, as_work
+from ._rows import _engine, as_work
 
 
 def _pool(pool_size) -> int:

@@ -3,7 +3,7 @@ the same arguments and return types, so that ``from adapted.detect.llr import ..
 ``from adapted_amd.detect.llr import ...``.  Next to the drop-ins sit their batch forms (``*_batch``): padded float64 [n, L] traces
 with per-read lengths, or a device pointer (int) with ``n`` and ``L``, so that resident traces never cross PCIe.
 
-Every per-read function is one batch call with n = 1 on the engine `_c_llr._engine` caches; the traces come from `_c_llr`, the
+Every per-read function is one batch call with n = 1 on the engine `_rows._engine` caches; the traces come from `_c_llr`, the
 derived state of `LLRTrace` from ``adp_llr_trace_bounds``, the peaks from ``adp_llr_trace_peaks`` and the poly(A) end from
 ``adp_llr_spike_peak`` (adapted_amd/csrc/trace_peaks_api.h).  There is no CPU path: without the HIP library every function raises
 ``HipLibraryError``.  Only numpy is needed (no scipy, no attrs).
@@ -23,8 +23,8 @@ import numpy as np
 
 from .. import lib
 from . import _c_llr
-from ._c_llr import _engine, _gains, c_llr_trace, c_llr_trace_gains
-from ._rows import as_rows
+from ._c_llr import _gains, c_llr_trace, c_llr_trace_gains
+from ._rows import _engine, as_rows
 
 ##############################
 # LLR-based adapter detection

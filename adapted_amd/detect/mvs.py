@@ -27,30 +27,25 @@ import numpy as np
 
 from .. import lib
 from ..config.schema import MVSPolyAConfig, StreamingConfig
-from ._c_llr import _engine
-from ._rows import as_rows
+from ._rows import _engine, bounds, position, positions, rows_in
+from ._rows import work_dtype as _work_dtype  # noqa: F401  (the module's dtype rule under its name here)
 from .utils import LOCAL_RANGE_PCTLS, in_range  # noqa: F401  (the reference module imports both from here)
 
 ST_INDEX, ST_VALUE = 1, 2  # `status` of the batch forms (0: the reference returns)
-
-
-def _rng(r):
-    lo, hi = (None, None) if r is None else r
-    return (-np.inf if lo is None else float(lo), np.inf if hi is None else float(hi))
 
 
 def _args(params=None, stream=None, less_signal_ok=False, windowed_stats=True) -> "lib.AdpMvsArgs":
     a = lib.AdpMvsArgs()
     if params is not None:
         for k in ("pA_mean_range", "pA_var_range", "median_shift_range", "polyA_med_range", "polyA_local_range"):
-            getattr(a, k)[:] = _rng(getattr(params, k))
+            getattr(a, k)[:] = bounds(getattr(params, k), nan_ok=True)
         for k in ("search_window", "pA_mean_window", "pA_var_window", "median_shift_window", "polyA_window"):
             setattr(a, k, int(getattr(params, k)))
     else:
         a.pA_mean_window = a.pA_var_window = 1
     if stream is not None:
         for k in ("pA_mean_range", "pA_var_range", "median_shift_range", "polyA_med_range", "polyA_local_range"):
-            getattr(a, "s_" + k)[:] = _rng(getattr(stream, k))
+            getattr(a, "s_" + k)[:] = bounds(getattr(stream, k), nan_ok=True)
         for k in ("pA_mean_window", "pA_var_window", "median_shift_window", "polyA_window"):
             setattr(a, "s_" + k, int(getattr(stream, k)))
         a.min_obs_adapter, a.min_obs_post_loc = int(stream.min_obs_adapter), int(stream.min_obs_post_loc)
@@ -67,47 +62,11 @@ def _args(params=None, stream=None, less_signal_ok=False, windowed_stats=True) -
     return a
 
 
-def _work_dtype(dt) -> np.dtype:
-    dt = np.dtype(dt)
-    if dt == np.float32 or dt == np.float64:
-        return dt
-    if np.issubdtype(dt, np.integer):
-        return np.dtype(np.float64)
-    raise TypeError("calibrated signals must be float32, float64 or integer, not %s" % dt)
-
-
-def _as_rows(signals, lens, n, L, dtype):
-    """host signals -> (C-contiguous float32 / float64 [n, L] array, lens, f64); a device pointer passes through"""
-    x, lens = as_rows(signals, lens, n, L, _work_dtype, "signals")
-    if isinstance(x, int):
-        dt = np.dtype(dtype)
-        if dt not in (np.float32, np.float64):
-            raise TypeError("device signals must be float32 or float64")
-        return x, lens, dt == np.float64
-    if x.shape[1] == 0:  # (the library wants L >= 1: every read is empty)
-        x = np.zeros((x.shape[0], 1), dtype=x.dtype)
-    return x, lens, x.dtype == np.float64
-
-
-def _positions(v, nn, what):
-    v = np.asarray(v, dtype=np.int64).reshape(-1)
-    if v.size != nn:
-        raise ValueError("%s needs one entry per read" % what)
-    if v.size and v.min() < 0:
-        raise ValueError("%s must be >= 0 (negative positions are not supported)" % what)
-    return v
-
-
-def _nrows(x, n):
-    return int(n) if isinstance(x, int) else x.shape[0]
-
-
 def _check_raw(signals, lens, adapter_ends, polya_ends, params, less_signal_ok=False, windowed_stats=True, n=None, L=None,
                     dtype=np.float32, device=0):
     """adp_mvs_check as it comes: (info int32 [n, 8], vals float64 [n, 5]) -- include/adapted_hip.h"""
-    x, lens, f64 = _as_rows(signals, lens, n, L, dtype)
-    nn = _nrows(x, n)
-    ae, pe = _positions(adapter_ends, nn, "adapter_ends"), _positions(polya_ends, nn, "polya_ends")
+    x, lens, f64, nn = rows_in(signals, lens, n, L, dtype, count_lens=False)
+    ae, pe = positions(adapter_ends, nn, "adapter_ends"), positions(polya_ends, nn, "polya_ends")
     a = _args(params, None, less_signal_ok, windowed_stats)
     if nn == 0:
         return np.zeros((0, 8), dtype=np.int32), np.zeros((0, 5))
@@ -134,9 +93,8 @@ def mean_var_shift_polyA_detect_at_loc_batch(signals, lens, locs, params, less_s
 
 
 def _at_loc_raw(signals, lens, locs, params, less_signal_ok, n, L, dtype, device):
-    x, lens, f64 = _as_rows(signals, lens, n, L, dtype)
-    nn = _nrows(x, n)
-    lo = _positions(locs, nn, "locs")
+    x, lens, f64, nn = rows_in(signals, lens, n, L, dtype, count_lens=False)
+    lo = positions(locs, nn, "locs")
     a = _args(params, None, less_signal_ok, True)
     if nn == 0:
         return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64), np.zeros((0, 5)), np.zeros((0, 8), dtype=np.int32)
@@ -147,9 +105,8 @@ def _at_loc_raw(signals, lens, locs, params, less_signal_ok, n, L, dtype, device
 def mean_var_shift_polyA_detect_batch(signals, lens, params=None, device=0, n: Optional[int] = None, L: Optional[int] = None,
                                       dtype=np.float32):
     """`mean_var_shift_polyA_detect` for many reads -> int64 [n] (0: none found)"""
-    x, lens, f64 = _as_rows(signals, lens, n, L, dtype)
+    x, lens, f64, nn = rows_in(signals, lens, n, L, dtype, count_lens=False)
     a = _args(None, StreamingConfig() if params is None else params)
-    nn = _nrows(x, n)
     if nn == 0:
         return np.zeros(0, dtype=np.int64)
     return _engine(device).mvs_detect(x, lens, a, n=n, L=L, f64=f64)
@@ -170,19 +127,12 @@ def _one(calibrated_signal):
     return x, [x.shape[1]], np.issubdtype(x.dtype, np.integer)
 
 
-def _pos(v, what):
-    v = int(v)
-    if v < 0:
-        raise ValueError("%s must be >= 0 (negative positions are not supported)" % what)
-    return v
-
-
 def mean_var_shift_polyA_check(calibrated_signal, adapter_end, polya_end, params, return_values=False, less_signal_ok=False,
                                windowed_stats=True):
     """mvs.py:45-158 -> check_vector.all() (np.bool_; False on the early outs), or with ``return_values`` the tuple
     (ok, check_vector bool [5], mean, var, polya_med, polya_local_range, med_shift)"""
     x, lens, integer = _one(calibrated_signal)
-    info, vals = _check_raw(x, lens, [_pos(adapter_end, "adapter_end")], [_pos(polya_end, "polya_end")], params,
+    info, vals = _check_raw(x, lens, [position(adapter_end, "adapter_end")], [position(polya_end, "polya_end")], params,
                                  less_signal_ok, windowed_stats)
     _raise(info[0], integer)
     if not info[0, 5]:
@@ -197,7 +147,7 @@ def mean_var_shift_polyA_check(calibrated_signal, adapter_end, polya_end, params
 def mean_var_shift_polyA_detect_at_loc(calibrated_signal, loc=0, params=MVSPolyAConfig(), return_values=False, less_signal_ok=True):
     """mvs.py:181-338 -> bool, or with ``return_values`` (found, idx, mean, var, polya_med, polya_local_range, med_shift)"""
     x, lens, integer = _one(calibrated_signal)
-    ok, idx, vals, info = _at_loc_raw(x, lens, [_pos(loc, "loc")], params, less_signal_ok, None, None, np.float32, 0)
+    ok, idx, vals, info = _at_loc_raw(x, lens, [position(loc, "loc")], params, less_signal_ok, None, None, np.float32, 0)
     _raise(info[0], integer)
     res = bool(ok[0])
     if not return_values:

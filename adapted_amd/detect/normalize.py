@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._sigstats import _engine, as_work, rows_in
+from ._rows import _engine, as_work, rows_in
 
 ST_MAD_ZERO = 1  # `status` of normalize_signal_batch: the reference raises ValueError
 

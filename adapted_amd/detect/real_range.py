@@ -15,7 +15,7 @@ import numpy as np
 
 from .. import lib
 from ..config.schema import RealRangeConfig
-from ._sigstats import _engine, as_work, bounds, positions, rows_in
+from ._rows import _engine, as_work, bounds, positions, rows_in
 from .utils import LOCAL_RANGE_PCTLS, in_range  # noqa: F401  (the reference module imports both from here)
 
 STAGE_SHORT, STAGE_MEANS, STAGE_LOCAL_RANGE = 0, 1, 2  # `stage` of the batch form

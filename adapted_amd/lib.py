@@ -7,6 +7,7 @@ There is no CPU fallback: if the HIP library cannot be loaded the import of this
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import sys
 from typing import List, Optional, Sequence
@@ -255,28 +256,20 @@ def load():
     except Exception as e:  # no CPU fallback by design
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
+    try:
+        for name, proto in PROTOTYPES.items():
+            ret, params = proto.split(":")
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
+    except AttributeError as e:
+        raise HipLibraryError("libadapted_hip.so does not export what include/adapted_hip.h declares: %s" % e) from e
     if (lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize
             or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)
             or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs) or lib.adp_sizeof_seg() != SEG_DTYPE.itemsize
             or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
-    lib.adp_last_error.restype = C.c_char_p
-    lib.adp_stream.restype = C.c_void_p
     _LIB = lib
     return lib
-
-
-EXPORTS = ["adp_abi_version", "adp_sizeof_cfg", "adp_sizeof_row", "adp_last_error", "adp_device_count", "adp_create",
-           "adp_destroy", "adp_set_config", "adp_stream", "adp_synchronize", "adp_detect_llr", "adp_detect_start_peak",
-           "adp_cnn_prepare", "adp_validate_candidates", "adp_llr_refine_polya", "adp_synth_fill", "adp_dev_alloc", "adp_dev_free",
-           "adp_memcpy_h2d", "adp_memcpy_d2h", "adp_set_profiling", "adp_kernel_times", "adp_debug_fetch",
-           "adp_debug_llr_upto", "adp_debug_log", "adp_cnn_topk", "adp_host_alloc", "adp_host_free", "adp_memcpy_h2d_async",
-           "adp_copy_mark", "adp_copy_wait", "adp_debug_divcheck", "adp_calibrate_i16", "adp_expand_ragged", "adp_set_layout",
-           "adp_cnn_set_weights", "adp_cnn_forward", "adp_cnn_predict", "adp_detect_cnn", "adp_open_pores_arena", "adp_detect_llr_i16", "adp_expand_ragged_i16",
-           "adp_c_llr_trace", "adp_c_llr_best_split", "adp_c_llr_detect", "adp_sizeof_peak_args", "adp_sizeof_spike_args",
-           "adp_llr_trace_bounds", "adp_llr_trace_peaks", "adp_llr_spike_peak", "adp_sizeof_mvs_args", "adp_mvs_check",
-           "adp_mvs_detect_at_loc", "adp_mvs_detect", "adp_sizeof_seg", "adp_seg_stats",
-           "adp_sizeof_real_range_args", "adp_med_mad", "adp_normalize", "adp_pool_mean", "adp_real_range", "adp_open_pores"]
 
 
 class AdpTraceArgs(C.Structure):
@@ -331,6 +324,117 @@ ADP_SS_FORCE_WAVE = 65536
 ADP_SS_GRID_MIN = 16384
 
 
+# -- the C ABI, declared once -------------------------------------------------------------------------------------------------
+# include/adapted_hip.h as "return: parameters", in header order.  Scalars: int, int32, uint32, uint64, float, double.  T* points
+# to elements T: a number type, adp_row (ROW_DTYPE), adp_seg (SEG_DTYPE), void (anything), one of the structs above, or a handle.
+# load() turns every line into restype / argtypes; tests/test_host_cpu.py holds the table against the header.
+PROTOTYPES = {
+    "adp_abi_version": "int:",
+    "adp_sizeof_cfg": "int:",
+    "adp_sizeof_row": "int:",
+    "adp_last_error": "char*:",
+    "adp_device_count": "int:",
+    "adp_create": "int: int adp_cfg* int int adp_handle**",
+    "adp_destroy": "int: adp_handle*",
+    "adp_set_config": "int: adp_handle* adp_cfg*",
+    "adp_set_layout": "int: adp_handle* int",
+    "adp_stream": "void*: adp_handle*",
+    "adp_synchronize": "int: adp_handle*",
+    "adp_detect_llr": "int: adp_handle* float* int32* int int int int adp_row* int32*",
+    "adp_detect_llr_i16": "int: adp_handle* int16* int32* float* float* int int int int adp_row* int32*",
+    "adp_detect_start_peak": "int: adp_handle* float* int32* int int int int adp_row*",
+    "adp_cnn_prepare": "int: adp_handle* float* int int int float*",
+    "adp_cnn_set_weights": "int: adp_handle* float* float* float* float* float* float* float* float*",
+    "adp_cnn_forward": "int: adp_handle* float* int int float*",
+    "adp_cnn_predict": "int: adp_handle* float* int int int int64*",
+    "adp_cnn_topk": "int: adp_handle* float* int64* int64* int int int int32* int32*",
+    "adp_detect_cnn": "int: adp_handle* float* int32* int int int int adp_row* int64*",
+    "adp_validate_candidates": "int: adp_handle* float* int32* int int int64* int int adp_row*",
+    "adp_llr_refine_polya": "int: adp_handle* float* int32* int int int64* int int64* int32*",
+    "adp_open_pores_arena": "int: adp_handle* int32* uint64 uint64*",
+    "adp_synth_fill": "int: adp_handle* float* int32* int int uint32 uint32 int",
+    "adp_dev_alloc": "int: adp_handle* uint64 void**",
+    "adp_dev_free": "int: adp_handle* void*",
+    "adp_memcpy_h2d": "int: adp_handle* void* void* uint64",
+    "adp_memcpy_d2h": "int: adp_handle* void* void* uint64",
+    "adp_calibrate_i16": "int: adp_handle* int16* int32* float* float* int int float*",
+    "adp_expand_ragged": "int: adp_handle* void* int int64* int32* float* float* int int float*",
+    "adp_expand_ragged_i16": "int: adp_handle* int16* int64* int32* int int int16*",
+    "adp_host_alloc": "int: adp_handle* uint64 void**",
+    "adp_host_free": "int: adp_handle* void*",
+    "adp_memcpy_h2d_async": "int: adp_handle* void* void* uint64",
+    "adp_copy_mark": "int: adp_handle* int",
+    "adp_copy_wait": "int: adp_handle* int",
+    "adp_c_llr_trace": "int: adp_handle* double* int32* int32* int32* int int adp_trace_args* int double* double* double*",
+    "adp_c_llr_best_split": "int: adp_handle* double* double* int32* int32* int32* int32* int32* int int int int64* double*",
+    "adp_c_llr_detect": "int: adp_handle* void* int32* int int int32 int32 int32 int int64* int64* double*",
+    "adp_sizeof_peak_args": "int:",
+    "adp_sizeof_spike_args": "int:",
+    "adp_llr_trace_bounds": "int: adp_handle* double* int32* int32* int32* int int int int int32* int32* int32*",
+    "adp_llr_trace_peaks": "int: adp_handle* double* int32* int32* int32* int int adp_peak_args* int int int64* int64*",
+    "adp_llr_spike_peak": "int: adp_handle* double* int32* int int adp_spike_args* int int64*",
+    "adp_sizeof_mvs_args": "int:",
+    "adp_mvs_check": "int: adp_handle* void* int32* int64* int64* int int adp_mvs_args* int int32* double*",
+    "adp_mvs_detect_at_loc": "int: adp_handle* void* int32* int64* int int adp_mvs_args* int int32* int64* double*",
+    "adp_mvs_detect": "int: adp_handle* void* int32* int int adp_mvs_args* int int64*",
+    "adp_sizeof_seg": "int:",
+    "adp_seg_stats": "int: adp_handle* void* int32* int int adp_seg* int int double* int64*",
+    "adp_sizeof_real_range_args": "int:",
+    "adp_med_mad": "int: adp_handle* void* int32* int int int double*",
+    "adp_normalize": "int: adp_handle* void* int32* int int double int double* void* int32*",
+    "adp_pool_mean": "int: adp_handle* void* int int int int void*",
+    "adp_real_range": "int: adp_handle* void* int32* int int adp_seg* int adp_real_range_args* int int32* double*",
+    "adp_open_pores": "int: adp_handle* void* int32* int int adp_seg* int double double double int int int64* int64*",
+    "adp_set_profiling": "int: adp_handle* int",
+    "adp_kernel_times": "int: adp_handle* char** float* int",
+    "adp_debug_fetch": "int: adp_handle* int void* uint64",
+    "adp_debug_llr_upto": "int: adp_handle* float* int32* int int int int int",
+    "adp_debug_divcheck": "int: adp_handle* float uint32 uint32 uint64*",
+    "adp_debug_log": "int: adp_handle* double* double* int",
+}
+EXPORTS = list(PROTOTYPES)
+
+_VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
+_RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
+_SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_POINTEES = {"adp_cfg": AdpCfg, "adp_trace_args": AdpTraceArgs, "adp_peak_args": AdpPeakArgs, "adp_spike_args": AdpSpikeArgs,
+            "adp_mvs_args": AdpMvsArgs, "adp_real_range_args": AdpRealRangeArgs, "adp_handle*": _VoidP, "void*": _VoidP,
+            "char*": C.c_char_p}
+_ELEMENTS = {"float": np.float32, "double": np.float64, "int16": np.int16, "int32": np.int32, "int64": np.int64, "uint32": np.uint32,
+             "uint64": np.uint64, "void": None, "adp_row": ROW_DTYPE, "adp_seg": SEG_DTYPE}
+_CTYPES_ARGUMENT = (C._SimpleCData, C.Array, C._Pointer, type(C.byref(C.c_int())))
+
+
+class _Pointer:
+    """argtypes entry of a pointer to numbers, rows or segments -- the one place where an argument becomes an address.  Takes a
+    device pointer (int) or None; a ctypes object (c_void_p, byref(...), a ctypes array) as it is; a numpy array only when it is
+    C-contiguous and of the element type the header names (``void``: of any).  The array is an argument of the call and lives as
+    long as it does."""
+
+    def __init__(self, element):
+        self.element, self.dtype = element, _ELEMENTS[element]
+
+    def from_param(self, v):
+        if isinstance(v, np.ndarray):
+            if not v.flags.c_contiguous or (self.dtype is not None and v.dtype != self.dtype):
+                raise TypeError("%s *: a C-contiguous %s array, not %s%s" % (self.element, np.dtype(self.dtype or np.void).name, v.dtype,
+                                                                            "" if v.flags.c_contiguous else " with strides"))
+            return C.c_void_p(v.ctypes.data)
+        if isinstance(v, _CTYPES_ARGUMENT):
+            return v
+        return C.c_void_p(v if v is None else operator.index(v))
+
+
+def _argtype(kind):
+    """the ctypes side of one parameter kind of PROTOTYPES"""
+    if kind in _SCALARS:
+        return _SCALARS[kind]
+    if kind == "adp_handle*":
+        return _VoidP
+    element = kind[:-1]
+    return C.POINTER(_POINTEES[element]) if element in _POINTEES else _Pointer(element)
+
+
 class MinibatchDropped(RuntimeError):
     """batch-level failure of one minibatch (the reference drops it and logs): status = ADP_MB_*"""
 
@@ -339,10 +443,13 @@ class MinibatchDropped(RuntimeError):
         self.status = status
 
 
-def _rng(r):
-    lo = -np.inf if r is None or r[0] is None else float(r[0])
-    hi = np.inf if r is None or r[1] is None else float(r[1])
-    return (C.c_double * 2)(lo, hi)
+def bounds(r, nan_ok=False):
+    """a (min, max) range with None for an open end -> (float, float)"""
+    lo, hi = (None, None) if r is None else r
+    lo, hi = (-np.inf if lo is None else float(lo), np.inf if hi is None else float(hi))
+    if not nan_ok and (lo != lo or hi != hi):
+        raise ValueError("a range bound must be a number or None")
+    return lo, hi
 
 
 def make_cfg(spc) -> AdpCfg:
@@ -361,14 +468,14 @@ def make_cfg(spc) -> AdpCfg:
         setattr(c, k, int(getattr(M, k)))
     for k in ("pA_mean_range", "pA_var_range", "median_shift_range", "polyA_med_range", "polyA_local_range",
               "pA_mean_adapter_med_scale_range"):
-        setattr(c, k, _rng(getattr(M, k)))
+        setattr(c, k, bounds(getattr(M, k), nan_ok=True))
     R = spc.real_range
     for k in ("detect_open_pores", "real_signal_check", "mean_window", "max_obs_local_range"):
         setattr(c, k, int(getattr(R, k)))
     for k in ("mean_start_range", "mean_end_range", "local_range", "adapter_mad_range"):
-        setattr(c, k, _rng(getattr(R, k)))
+        setattr(c, k, bounds(getattr(R, k), nan_ok=True))
     c.detect_med_shift, c.med_shift_window = int(spc.med_shift.detect_med_shift), int(spc.med_shift.med_shift_window)
-    c.med_shift_range = _rng(spc.med_shift.med_shift_range)
+    c.med_shift_range = bounds(spc.med_shift.med_shift_range, nan_ok=True)
     S = spc.rna_start_peak
     c.sp_downscale_factor, c.start_peak_max_idx = int(S.downscale_factor), int(S.start_peak_max_idx)
     c.sp_offset1, c.sp_offset2, c.open_pore_pa = int(S.offset1), int(S.offset2), float(S.open_pore_pa)
@@ -452,7 +559,8 @@ def open_pore_float_column(results: List[DetectResults]) -> List[DetectResults]:
 
 
 class Engine:
-    """One GPU's detect engine: a handle of libadapted_hip.so sized for (max_reads, m)."""
+    """One GPU's detect engine: a handle of libadapted_hip.so sized for (max_reads, m).  The library's functions carry their
+    prototypes (PROTOTYPES): ints, floats, device pointers and numpy arrays are passed as they are, and checked there."""
 
     def __init__(self, spc, max_reads: int, m: int, device: int = 0, single_read_layout: bool = False):
         """single_read_layout: the engine of combined_detect_llr (adapted/detect/combined.py:39-119): pooled from sample 0, every
@@ -461,7 +569,7 @@ class Engine:
         self.spc = spc
         self.cfg = make_cfg(spc)
         self.max_reads, self.m, self.device = int(max_reads), int(m), int(device)
-        self._h = C.c_void_p()
+        self._h = _VoidP()
         self._pinned = {}
         self._check(self.lib.adp_create(self.device, C.byref(self.cfg), self.max_reads, self.m, C.byref(self._h)))
         if single_read_layout:
@@ -476,7 +584,7 @@ class Engine:
     def close(self):
         if self._h:
             self.lib.adp_destroy(self._h)
-            self._h = C.c_void_p()
+            self._h = _VoidP()
 
     def __del__(self):
         try:
@@ -505,51 +613,46 @@ class Engine:
 
     # -- device memory ------------------------------------------------------------------
     def dev_alloc(self, nbytes: int) -> int:
-        p = C.c_void_p()
-        self._check(self.lib.adp_dev_alloc(self._h, C.c_uint64(nbytes), C.byref(p)))
+        p = _VoidP()
+        self._check(self.lib.adp_dev_alloc(self._h, nbytes, C.byref(p)))
         return int(p.value)
 
     def dev_free(self, ptr: int):
-        self._check(self.lib.adp_dev_free(self._h, C.c_void_p(ptr)))
+        self._check(self.lib.adp_dev_free(self._h, ptr))
 
     def calibrate_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, out_dev: int):
         """int16 ADC samples [n, m] + per-read (scale, offset) -> float32 [n, m] NaN-padded, on the device (asynchronous
         on the handle's stream: the detect call that follows is ordered behind it)"""
-        self._check(self.lib.adp_calibrate_i16(self._h, C.c_void_p(raw_dev), C.c_void_p(len_dev), C.c_void_p(scale_dev),
-                                               C.c_void_p(offset_dev), int(n), self.m, C.c_void_p(out_dev)))
+        self._check(self.lib.adp_calibrate_i16(self._h, raw_dev, len_dev, scale_dev, offset_dev, int(n), self.m, out_dev))
 
     def expand_ragged(self, packed_dev: int, is_int16: bool, offs_dev: int, len_dev: int, n: int, out_dev: int,
                       scale_dev: int = 0, offset_dev: int = 0):
         """reads packed back to back (float32 pA, or int16 ADC + per-read calibration) -> float32 [n, m] NaN-padded, on the
         device (asynchronous on the handle's stream)"""
-        self._check(self.lib.adp_expand_ragged(self._h, C.c_void_p(packed_dev), int(bool(is_int16)), C.c_void_p(offs_dev),
-                                               C.c_void_p(len_dev), C.c_void_p(scale_dev or None), C.c_void_p(offset_dev or None),
-                                               int(n), self.m, C.c_void_p(out_dev)))
+        self._check(self.lib.adp_expand_ragged(self._h, packed_dev, bool(is_int16), offs_dev, len_dev, scale_dev or None,
+                                               offset_dev or None, int(n), self.m, out_dev))
 
     def expand_ragged_i16(self, packed_dev: int, offs_dev: int, len_dev: int, n: int, out_dev: int):
         """packed raw int16 reads -> raw int16 [n, m] on the device (what detect_llr_rows_i16 reads); asynchronous"""
-        self._check(self.lib.adp_expand_ragged_i16(self._h, C.c_void_p(packed_dev), C.c_void_p(offs_dev), C.c_void_p(len_dev), int(n), self.m,
-                                                   C.c_void_p(out_dev)))
+        self._check(self.lib.adp_expand_ragged_i16(self._h, packed_dev, offs_dev, len_dev, int(n), self.m, out_dev))
 
     def host_alloc(self, shape, dtype) -> np.ndarray:
         """page-locked host array (staging for h2d_async); release with host_free(arr)"""
         dt = np.dtype(dtype)
         n = int(np.prod(shape))
-        p = C.c_void_p()
-        self._check(self.lib.adp_host_alloc(self._h, C.c_uint64(max(1, n * dt.itemsize)), C.byref(p)))
+        p = _VoidP()
+        self._check(self.lib.adp_host_alloc(self._h, max(1, n * dt.itemsize), C.byref(p)))
         buf = (C.c_char * (n * dt.itemsize)).from_address(p.value)
         arr = np.frombuffer(buf, dtype=dt).reshape(shape)
         self._pinned[arr.ctypes.data] = p.value
         return arr
 
     def host_free(self, arr: np.ndarray):
-        p = self._pinned.pop(arr.ctypes.data)
-        self._check(self.lib.adp_host_free(self._h, C.c_void_p(p)))
+        self._check(self.lib.adp_host_free(self._h, self._pinned.pop(arr.ctypes.data)))
 
     def h2d_async(self, dst: int, arr: np.ndarray, nbytes: Optional[int] = None):
         """copy from a PINNED host array on the handle's copy stream; copy_mark(slot) then copy_wait(slot) before use"""
-        self._check(self.lib.adp_memcpy_h2d_async(self._h, C.c_void_p(dst), arr.ctypes.data_as(C.c_void_p),
-                                                  C.c_uint64(arr.nbytes if nbytes is None else nbytes)))
+        self._check(self.lib.adp_memcpy_h2d_async(self._h, dst, arr, arr.nbytes if nbytes is None else nbytes))
 
     def copy_mark(self, slot: int):
         self._check(self.lib.adp_copy_mark(self._h, int(slot)))
@@ -559,16 +662,15 @@ class Engine:
 
     def h2d(self, dst: int, arr: np.ndarray):
         a = np.ascontiguousarray(arr)
-        self._check(self.lib.adp_memcpy_h2d(self._h, C.c_void_p(dst), a.ctypes.data_as(C.c_void_p), C.c_uint64(a.nbytes)))
+        self._check(self.lib.adp_memcpy_h2d(self._h, dst, a, a.nbytes))
 
     def d2h(self, arr: np.ndarray, src: int):
         assert arr.flags.c_contiguous
-        self._check(self.lib.adp_memcpy_d2h(self._h, arr.ctypes.data_as(C.c_void_p), C.c_void_p(src), C.c_uint64(arr.nbytes)))
+        self._check(self.lib.adp_memcpy_d2h(self._h, arr, src, arr.nbytes))
 
     def synth_fill(self, dev_signals: int, dev_full_len: Optional[int], n: int, seed: int, first_read: int,
                    decorate: bool = True):
-        self._check(self.lib.adp_synth_fill(self._h, C.c_void_p(dev_signals), C.c_void_p(dev_full_len or 0), int(n), self.m,
-                                            C.c_uint32(seed), C.c_uint32(first_read), int(decorate)))
+        self._check(self.lib.adp_synth_fill(self._h, dev_signals, dev_full_len or None, int(n), self.m, seed, first_read, int(decorate)))
 
     # -- operators ------------------------------------------------------------------------
     def attach_open_pores(self, rows: Optional[np.ndarray]):
@@ -578,10 +680,10 @@ class Engine:
             return rows
         big = np.flatnonzero(rows["n_open_pores"] > MAX_OPEN_PORES)
         if big.size:
-            used = C.c_uint64(0)
-            self._check(self.lib.adp_open_pores_arena(self._h, None, C.c_uint64(0), C.byref(used)))
-            arena = np.zeros(int(used.value), dtype=np.int32)
-            self._check(self.lib.adp_open_pores_arena(self._h, arena.ctypes.data_as(C.c_void_p), C.c_uint64(arena.size), C.byref(used)))
+            used = np.zeros(1, dtype=np.uint64)
+            self._check(self.lib.adp_open_pores_arena(self._h, None, 0, used))
+            arena = np.zeros(int(used[0]), dtype=np.int32)
+            self._check(self.lib.adp_open_pores_arena(self._h, arena, arena.size, used))
             for i in big:
                 off, no = int(rows[i]["open_pores_more"]), int(rows[i]["n_open_pores"])
                 if off < 0 or off + no > arena.size:
@@ -589,98 +691,92 @@ class Engine:
                 rows[i]["open_pores_more"] = register_open_pores(arena[off:off + no])
         return rows
 
-    def _in_ptrs(self, signals, full_lens, n, device_ptrs):
+    def _in(self, signals, full_lens, n, device_ptrs):
+        """a detect call's minibatch -> (signals, full_lens, flags): device pointers, or float32 [n, m] and int32 [n] host arrays"""
         if device_ptrs:
             _check_runtime_once_torch_is_here()  # (device pointers come from torch: its runtime must be this library's)
-            return C.c_void_p(int(signals)), C.c_void_p(int(full_lens)), ADP_IN_DEVICE, None
+            return int(signals), int(full_lens), ADP_IN_DEVICE
         sig = np.ascontiguousarray(signals, dtype=np.float32)
         lens = np.ascontiguousarray(full_lens, dtype=np.int32)
         if sig.ndim != 2 or sig.shape != (n, self.m) or lens.shape != (n,):
             raise ValueError("signals must be float32 [n, %d] and full_lens int32 [n]" % self.m)
-        return sig.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), 0, (sig, lens)
+        return sig, lens, 0
+
+    @staticmethod
+    def _out(dev, shape, dtype=ROW_DTYPE):
+        """a call's main output -> (host array or None, what the call is given, flags): a zeroed host array, or the caller's
+        device buffer ``dev`` with ADP_OUT_DEVICE"""
+        if dev is not None:
+            return None, dev, ADP_OUT_DEVICE
+        out = np.zeros(shape, dtype=dtype)
+        return out, out, 0
 
     def detect_llr_rows(self, signals, full_lens, n: int, minibatch: int, with_start_peak: bool = False,
                         device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False):
         """-> (rows ndarray[ROW_DTYPE] or None when rows_dev is given, mb_status int32[n_mb]).
         tails_nan: the caller guarantees that every row is NaN from min(full_len, m) on (the reference's own padding,
         adapted/file_proc.py:170-174); the streaming passes then skip the padding (ADP_TAILS_NAN)."""
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, device_ptrs)
-        if with_start_peak:
-            flags |= ADP_WITH_START_PEAK
-        if tails_nan:
-            flags |= ADP_TAILS_NAN
-        n_mb = (n + minibatch - 1) // minibatch
-        mbs = np.zeros(n_mb, dtype=np.int32)
-        if rows_dev is not None:
-            flags |= ADP_OUT_DEVICE
-            rows, rp = None, C.c_void_p(rows_dev)
-        else:
-            rows = np.zeros(n, dtype=ROW_DTYPE)
-            rp = rows.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.adp_detect_llr(self._h, sp, lp, int(n), self.m, int(minibatch), flags, rp,
-                                            mbs.ctypes.data_as(C.c_void_p)))
-        del keep
+        sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        flags |= out_flag | (ADP_WITH_START_PEAK if with_start_peak else 0) | (ADP_TAILS_NAN if tails_nan else 0)
+        mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
+        self._check(self.lib.adp_detect_llr(self._h, sig, lens, n, self.m, minibatch, flags, rows_arg, mbs))
         return self.attach_open_pores(rows), mbs
 
     def detect_llr_rows_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, minibatch: int,
                             with_start_peak: bool = False, rows_dev: Optional[int] = None):
         """adp_detect_llr over RAW int16 samples resident on the device (per-read calibration applied in registers):
         -> (rows or None when rows_dev is given, mb_status)"""
-        flags = ADP_IN_DEVICE | (ADP_WITH_START_PEAK if with_start_peak else 0)
-        n_mb = (n + minibatch - 1) // minibatch
-        mbs = np.zeros(n_mb, dtype=np.int32)
-        if rows_dev is not None:
-            flags |= ADP_OUT_DEVICE
-            rows, rp = None, C.c_void_p(rows_dev)
-        else:
-            rows = np.zeros(n, dtype=ROW_DTYPE)
-            rp = rows.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.adp_detect_llr_i16(self._h, C.c_void_p(int(raw_dev)), C.c_void_p(int(len_dev)), C.c_void_p(int(scale_dev)),
-                                                C.c_void_p(int(offset_dev)), int(n), self.m, int(minibatch), flags, rp,
-                                                mbs.ctypes.data_as(C.c_void_p)))
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        flags = ADP_IN_DEVICE | out_flag | (ADP_WITH_START_PEAK if with_start_peak else 0)
+        mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
+        self._check(self.lib.adp_detect_llr_i16(self._h, int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev), n, self.m,
+                                                minibatch, flags, rows_arg, mbs))
         return self.attach_open_pores(rows), mbs
 
     def detect_start_peak_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False):
         """adp_detect_start_peak over n reads in ONE library call: the pandas float-column quirk couples the reads of a minibatch
         (the library walks the minibatches), the open-pore arena belongs to the call (offsets of every minibatch index it)"""
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, device_ptrs)
+        sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         rows = np.zeros(n, dtype=ROW_DTYPE)
-        self._check(self.lib.adp_detect_start_peak(self._h, sp, lp, int(n), self.m, int(minibatch), flags,
-                                                   rows.ctypes.data_as(C.c_void_p)))
-        del keep
+        self._check(self.lib.adp_detect_start_peak(self._h, sig, lens, n, self.m, int(minibatch), flags, rows))
         return self.attach_open_pores(rows)
 
     def validate_rows(self, signals, full_lens, n: int, bounds: np.ndarray, device_ptrs: bool = False,
                       topk_none: bool = False):
         """bounds int64 [n, 1+k] (host) -> rows"""
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, device_ptrs)
+        sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         if topk_none:
             flags |= ADP_TOPK_NONE
         b = np.ascontiguousarray(bounds, dtype=np.int64)
-        k = b.shape[1] - 1
         rows = np.zeros(n, dtype=ROW_DTYPE)
         if device_ptrs:
             flags |= ADP_BOUNDS_HOST  # the signals are resident, the candidate table comes from the host
-        self._check(self.lib.adp_validate_candidates(self._h, sp, lp, int(n), self.m, b.ctypes.data_as(C.c_void_p), int(k),
-                                                     flags, rows.ctypes.data_as(C.c_void_p)))
-        del keep
+        self._check(self.lib.adp_validate_candidates(self._h, sig, lens, n, self.m, b, b.shape[1] - 1, flags, rows))
         return self.attach_open_pores(rows)
 
     # -- the reference's modules (adp_c_llr_*, adp_llr_*, adp_mvs_*): one input path ----------------------------------------
     def _rows_in(self, x, n=None, L=None, dtypes=(np.float64,), convert=False, what="signals"):
         """a module call's [n, L] input: a device pointer (int) with n and L given, or a host C-contiguous array of one of
-        ``dtypes`` (``convert``: made so, other dtypes widened to dtypes[0]) -> (pointer, flags, n, L, host array or None)"""
+        ``dtypes`` (``convert``: made so, other dtypes widened to dtypes[0]) -> (the pointer or the array, flags, n, L)"""
         if isinstance(x, int):
             if n is None or L is None:
                 raise ValueError("a device pointer needs n and L")
             _check_runtime_once_torch_is_here()  # (device pointers come from torch: its runtime must be this library's)
-            return C.c_void_p(x), ADP_IN_DEVICE, int(n), int(L), None
+            return x, ADP_IN_DEVICE, int(n), int(L)
         a = np.asarray(x)
         if convert:
             a = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in dtypes else dtypes[0])
         if a.dtype not in dtypes or not a.flags.c_contiguous or a.ndim != 2:
             raise ValueError("%s: a C-contiguous %s [n, L] array" % (what, " or ".join(np.dtype(d).name for d in dtypes)))
-        return a.ctypes.data_as(C.c_void_p), 0, a.shape[0], a.shape[1], a
+        return a, 0, a.shape[0], a.shape[1]
+
+    def _sig_in(self, sig, n, L, f64):
+        """signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``) -> (the pointer or the array, flags with
+        ADP_MVS_F64 for float64, n, L, dtype)"""
+        sig, flags, n, L = self._rows_in(sig, n, L, (np.float32, np.float64))
+        dt = np.dtype(np.float64 if f64 else np.float32) if isinstance(sig, int) else sig.dtype
+        return sig, flags | (ADP_MVS_F64 if dt == np.float64 else 0), n, L, dt
 
     @staticmethod
     def _per_read(a, n, what, dtype=np.int32):
@@ -690,32 +786,27 @@ class Engine:
             raise ValueError("%s needs one entry per read" % what)
         return a
 
-    @staticmethod
-    def _ptrs(*arrs):
-        return [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrs]
-
     def c_llr_trace(self, raw, lens, starts, ends, args: "AdpTraceArgs", sums=None, return_c_c2: bool = False):
         """adp_c_llr_trace: the reference's `c_llr_trace` (`c_llr_trace_gains` with ``sums=(c, c2)``) for a batch -- raw float64
         [n, L], per-read lens / starts / ends -> gains float64 [n, L] (and c, c2)"""
         flags = 0
         if sums is not None:
-            c, c2 = (self._rows_in(s, convert=True, what="sums")[4] for s in sums)
+            c, c2 = (self._rows_in(s, convert=True, what="sums")[0] for s in sums)
             n, L = c.shape
-            rawp = None
+            raw = None
             flags |= ADP_TRACE_FROM_SUMS
         else:
-            rawp, _, n, L, raw = self._rows_in(raw, convert=True, what="raw signals")
+            raw, _, n, L = self._rows_in(raw, convert=True, what="raw signals")
             c, c2 = (np.zeros((n, L)), np.zeros((n, L))) if return_c_c2 else (None, None)
         lens, starts, ends = (self._per_read(a, n, w) for a, w in ((lens, "lens"), (starts, "starts"), (ends, "ends")))
         g = np.zeros((n, L))
-        self._check(self.lib.adp_c_llr_trace(self._h, rawp, *self._ptrs(lens, starts, ends), int(n), int(L), C.byref(args), flags,
-                                             *self._ptrs(g, c, c2)))
+        self._check(self.lib.adp_c_llr_trace(self._h, raw, lens, starts, ends, n, L, C.byref(args), flags, g, c, c2))
         return (g, c, c2) if return_c_c2 else g
 
     def c_llr_best_split(self, c, c2, lens, starts, ends, offset_heads, offset_tails):
         """adp_c_llr_best_split: the reference's `_best_split` for a batch -- sums float64 [n, L], per-row lens / starts / ends /
         offsets -> (x int64 [n], gain float64 [n])"""
-        c, c2 = (self._rows_in(s, convert=True, what="sums")[4] for s in (c, c2))
+        c, c2 = (self._rows_in(s, convert=True, what="sums")[0] for s in (c, c2))
         n, L = c.shape
         if c2.shape != c.shape:
             raise ValueError("c, c2 [n, L] and one entry per row of lens / starts / ends / offsets")
@@ -723,7 +814,7 @@ class Engine:
                                                      (offset_tails, "offset_tails"))]
         x = np.zeros(n, dtype=np.int64)
         g = np.zeros(n)
-        self._check(self.lib.adp_c_llr_best_split(self._h, *self._ptrs(c, c2, *arrs), int(n), int(L), 0, *self._ptrs(x, g)))
+        self._check(self.lib.adp_c_llr_best_split(self._h, c, c2, *arrs, n, L, 0, x, g))
         return x, g
 
     def c_llr_detect(self, raw, lens, min_obs_adapter: int, border_trim: int, min_obs_polya: int = 0, polya: bool = False,
@@ -731,8 +822,8 @@ class Engine:
         """adp_c_llr_detect: `c_llr_detect_adapter` / `c_llr_detect_adapter_polya` for a batch.  raw: float64 or float32 [n, L]
         host array, or a device pointer (int) with n, L and ``float32`` given.  -> rows int64 [n, 4] (adapter_start, adapter_end,
         polya_end, tuple length 2 or 3); with ``details`` also (splits int64 [n, 4], stats float64 [n, 8])"""
-        rawp, flags, n, L, a = self._rows_in(raw, n, L, (np.float64, np.float32), convert=True, what="raw signals")
-        if (a.dtype == np.float32) if a is not None else float32:
+        raw, flags, n, L = self._rows_in(raw, n, L, (np.float64, np.float32), convert=True, what="raw signals")
+        if float32 if isinstance(raw, int) else raw.dtype == np.float32:
             flags |= ADP_CLLR_F32
         if polya:
             flags |= ADP_CLLR_POLYA
@@ -740,53 +831,50 @@ class Engine:
         rows = np.zeros((n, 4), dtype=np.int64)
         splits = np.zeros((n, 4), dtype=np.int64) if details else None
         stats = np.zeros((n, 8)) if details else None
-        self._check(self.lib.adp_c_llr_detect(self._h, rawp, *self._ptrs(lens), int(n), int(L), int(min_obs_adapter), int(border_trim),
-                                              int(min_obs_polya), flags, *self._ptrs(rows, splits, stats)))
+        self._check(self.lib.adp_c_llr_detect(self._h, raw, lens, n, L, int(min_obs_adapter), int(border_trim), int(min_obs_polya),
+                                              flags, rows, splits, stats))
         return (rows, splits, stats) if details else rows
 
     def llr_trace_bounds(self, trace, lens, min_obs, tail_trim, stride: int, interp: bool, n: Optional[int] = None, L: Optional[int] = None):
         """adp_llr_trace_bounds: LLRTrace's start / end / early_stop, and with ``interp`` interp_stride IN PLACE (trace: a writable
         host float64 [n, L] array, or a device pointer with n, L) -> (start, end, early_stop) int32 [n] (early_stop bit 1: the
         knot set was empty)"""
-        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
+        trace, flags, n, L = self._rows_in(trace, n, L, what="traces")
         ins = [self._per_read(a, n, w) for a, w in ((lens, "lens"), (min_obs, "min_obs"), (tail_trim, "tail_trim"))]
         outs = [np.zeros(n, dtype=np.int32) for _ in range(3)]
         if interp:
             flags |= ADP_LLR_INTERP
-        self._check(self.lib.adp_llr_trace_bounds(self._h, p, *self._ptrs(*ins), int(stride), int(n), int(L), flags, *self._ptrs(*outs)))
+        self._check(self.lib.adp_llr_trace_bounds(self._h, trace, *ins, int(stride), n, L, flags, *outs))
         return tuple(outs)
 
     def llr_trace_peaks(self, trace, lens, clip_lo, clip_hi, args: "AdpPeakArgs", cap: int = 16, n: Optional[int] = None,
                         L: Optional[int] = None, given_peak: bool = False):
         """adp_llr_trace_peaks -> (peaks int64 [n, cap] padded with -1, counts int64 [n]: the true counts, also past cap).
         ``given_peak``: clip_lo holds one peak per read, only corrected (ADP_LLR_GIVEN_PEAK)"""
-        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
+        trace, flags, n, L = self._rows_in(trace, n, L, what="traces")
         if given_peak:
             flags |= ADP_LLR_GIVEN_PEAK
         ins = [self._per_read(a, n, w) for a, w in ((lens, "lens"), (clip_lo, "clip_lo"), (clip_hi, "clip_hi"))]
         pk = np.zeros((n, int(cap)), dtype=np.int64)
         cnt = np.zeros(n, dtype=np.int64)
-        self._check(self.lib.adp_llr_trace_peaks(self._h, p, *self._ptrs(*ins), int(n), int(L), C.byref(args), flags, int(cap),
-                                                 *self._ptrs(pk, cnt)))
+        self._check(self.lib.adp_llr_trace_peaks(self._h, trace, *ins, n, L, C.byref(args), flags, int(cap), pk, cnt))
         return pk, cnt
 
     def llr_spike_peak(self, trace, lens, args: "AdpSpikeArgs", n: Optional[int] = None, L: Optional[int] = None):
         """adp_llr_spike_peak -> int64 [n]"""
-        p, flags, n, L, _ = self._rows_in(trace, n, L, what="traces")
+        trace, flags, n, L = self._rows_in(trace, n, L, what="traces")
         lens = self._per_read(lens, n, "lens")
         out = np.zeros(n, dtype=np.int64)
-        self._check(self.lib.adp_llr_spike_peak(self._h, p, *self._ptrs(lens), int(n), int(L), C.byref(args), flags, *self._ptrs(out)))
+        self._check(self.lib.adp_llr_spike_peak(self._h, trace, lens, n, L, C.byref(args), flags, out))
         return out
 
     def _mvs_call(self, fn, sig, lens, positions, args, n, L, f64, outs):
         """adp_mvs_*: signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``), lens, the int64 positions, then
         the outputs ``outs(n)`` -> those outputs"""
-        p, flags, n, L, a = self._rows_in(sig, n, L, (np.float32, np.float64))
-        if (a.dtype == np.float64) if a is not None else f64:
-            flags |= ADP_MVS_F64
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
         ins = [self._per_read(lens, n, "lens")] + [self._per_read(v, n, w, np.int64) for v, w in positions]
         res = outs(n)
-        self._check(fn(self._h, p, *self._ptrs(*ins), int(n), int(L), C.byref(args), flags, *self._ptrs(*res)))
+        self._check(fn(self._h, sig, *ins, n, L, C.byref(args), flags, *res))
         return res
 
     def mvs_check(self, sig, lens, adapter_ends, polya_ends, args: "AdpMvsArgs", n: Optional[int] = None, L: Optional[int] = None,
@@ -804,13 +892,6 @@ class Engine:
         """adp_mvs_detect -> int64 [n] (0: no poly(A) found)"""
         return self._mvs_call(self.lib.adp_mvs_detect, sig, lens, (), args, n, L, f64, lambda n: (np.zeros(n, dtype=np.int64),))[0]
 
-    def _sig_in(self, sig, n, L, f64):
-        """a signal statistics call's signals -> (pointer, flags with the dtype's, n, L, dtype)"""
-        p, flags, n, L, a = self._rows_in(sig, n, L, (np.float32, np.float64))
-        if (a.dtype == np.float64) if a is not None else f64:
-            flags |= ADP_MVS_F64
-        return p, flags, n, L, np.dtype(np.float64 if flags & ADP_MVS_F64 else np.float32)
-
     def _segs(self, rows, starts, ends):
         """struct adp_seg [n_seg] of per-segment rows, starts and ends"""
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
@@ -823,12 +904,11 @@ class Engine:
     def seg_stats(self, sig, lens, rows, starts, ends, n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
         """adp_seg_stats: signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``), lens, and per segment its
         row, start and end -> (stats float64 [n_seg, 4]: mean, std, median, MAD; counts int64 [n_seg]: the clipped sizes)"""
-        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
         lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
         stats = np.zeros((segs.size, 4))
         cnt = np.zeros(segs.size, dtype=np.int64)
-        self._check(self.lib.adp_seg_stats(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size), flags,
-                                           *self._ptrs(stats, cnt)))
+        self._check(self.lib.adp_seg_stats(self._h, sig, lens, n, L, segs, segs.size, flags, stats, cnt))
         return stats, cnt
 
     @staticmethod
@@ -840,11 +920,11 @@ class Engine:
                 f64: bool = False, regime: Optional[str] = None):
         """adp_med_mad -> float64 [n, 2] (median, MAD of every row's [0, lens[r])), or with ``whole`` [1, 2] of the whole array as
         one population.  ``regime``: "grid" / "wave" force the many-workgroup / the one-workgroup selection of a whole population"""
-        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
         flags |= self._ss_flags(with_nan, whole, regime)
         lens = None if whole else self._per_read(lens, n, "lens")
         out = np.zeros((1 if whole else n, 2))
-        self._check(self.lib.adp_med_mad(self._h, p, *self._ptrs(lens), int(n), int(L), flags, *self._ptrs(out)))
+        self._check(self.lib.adp_med_mad(self._h, sig, lens, n, L, flags, out))
         return out
 
     def normalize(self, sig, lens=None, outlier_thresh: float = 5.0, with_nan: bool = False, whole: bool = False, clip_medmad=None,
@@ -853,7 +933,7 @@ class Engine:
         """adp_normalize -> (out [n, L] of the input's type (None with ``out_ptr``, a device pointer the rows are written to),
         medmad float64 [n, 2] or [1, 2], status int32 [n] or [1]: 1 where the MAD is 0).  ``clip_medmad``: the clip alone, about
         the given (median, MAD) rows"""
-        p, flags, n, L, dt = self._sig_in(sig, n, L, f64)
+        sig, flags, n, L, dt = self._sig_in(sig, n, L, f64)
         flags |= self._ss_flags(with_nan, whole, regime)
         rows = 1 if whole else n
         lens = None if whole else self._per_read(lens, n, "lens")
@@ -865,54 +945,39 @@ class Engine:
         else:
             mm = np.zeros((rows, 2))
         status = np.zeros(rows, dtype=np.int32)
-        if out_ptr is not None:
-            flags |= ADP_OUT_DEVICE
-            out, outp = None, C.c_void_p(int(out_ptr))
-        else:
-            out = np.zeros((n, L), dtype=dt)
-            outp = out.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.adp_normalize(self._h, p, *self._ptrs(lens), int(n), int(L), C.c_double(outlier_thresh), flags,
-                                           *self._ptrs(mm), outp, *self._ptrs(status)))
+        out, out_arg, out_flag = self._out(out_ptr, (n, L), dt)
+        self._check(self.lib.adp_normalize(self._h, sig, lens, n, L, outlier_thresh, flags | out_flag, mm, out_arg, status))
         return out, mm, status
 
     def pool_mean(self, data, pool_size: int, n: Optional[int] = None, L: Optional[int] = None, f64: bool = False,
                   out_ptr: Optional[int] = None):
         """adp_pool_mean: data [n, L] -> [n, ceil(L / pool_size)] of the input's type (None with ``out_ptr``)"""
-        p, flags, n, L, dt = self._sig_in(data, n, L, f64)
-        n_out = -(-L // int(pool_size))
-        if out_ptr is not None:
-            flags |= ADP_OUT_DEVICE
-            out, outp = None, C.c_void_p(int(out_ptr))
-        else:
-            out = np.zeros((n, n_out), dtype=dt)
-            outp = out.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.adp_pool_mean(self._h, p, int(n), int(L), int(pool_size), flags, outp))
+        data, flags, n, L, dt = self._sig_in(data, n, L, f64)
+        out, out_arg, out_flag = self._out(out_ptr, (n, -(-L // int(pool_size))), dt)
+        self._check(self.lib.adp_pool_mean(self._h, data, n, L, int(pool_size), flags | out_flag, out_arg))
         return out
 
     def real_range(self, sig, lens, rows, starts, ends, args: "AdpRealRangeArgs", n: Optional[int] = None, L: Optional[int] = None,
                    f64: bool = False):
         """adp_real_range -> (info int32 [n_seg, 2]: result, stage; vals float64 [n_seg, 3]: mean_start, mean_end, local range)"""
-        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
         lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
         info = np.zeros((segs.size, 2), dtype=np.int32)
         vals = np.zeros((segs.size, 3))
-        self._check(self.lib.adp_real_range(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size),
-                                            C.byref(args), flags, *self._ptrs(info, vals)))
+        self._check(self.lib.adp_real_range(self._h, sig, lens, n, L, segs, segs.size, C.byref(args), flags, info, vals))
         return info, vals
 
     def open_pores(self, sig, lens, rows, starts, ends, lo: float, hi: float, min_obs_diff: float, cap: int = 16,
                    n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
         """adp_open_pores -> (pos int64 [n_seg, cap'] padded with -1, counts int64 [n_seg, 3]: kept, in range, the last in range).
         cap' >= cap: the call is repeated with the largest count when a list did not fit, so no list is cut short"""
-        p, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
         lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
         cnt = np.zeros((segs.size, 3), dtype=np.int64)
         cap = max(int(cap), 1)
         while True:
             pos = np.zeros((segs.size, cap), dtype=np.int64)
-            self._check(self.lib.adp_open_pores(self._h, p, *self._ptrs(lens), int(n), int(L), *self._ptrs(segs), int(segs.size),
-                                                C.c_double(lo), C.c_double(hi), C.c_double(min_obs_diff), flags, cap,
-                                                *self._ptrs(pos, cnt)))
+            self._check(self.lib.adp_open_pores(self._h, sig, lens, n, L, segs, segs.size, lo, hi, min_obs_diff, flags, cap, pos, cnt))
             if cnt[:, 0].max() <= cap:
                 return pos, cnt
             cap = int(cnt[:, 0].max())
@@ -921,34 +986,24 @@ class Engine:
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""
         cand = np.zeros((n, k), dtype=np.int32)
         cnt = np.zeros(n, dtype=np.int32)
-        self._check(self.lib.adp_cnn_topk(self._h, C.c_void_p(int(scores_ptr)), C.c_void_p(int(adapter_pos_ptr)),
-                                          C.c_void_p(int(polya_pos_ptr)), int(n), int(Lo), int(k), cand.ctypes.data_as(C.c_void_p),
-                                          cnt.ctypes.data_as(C.c_void_p)))
+        self._check(self.lib.adp_cnn_topk(self._h, int(scores_ptr), int(adapter_pos_ptr), int(polya_pos_ptr), n, int(Lo), k, cand, cnt))
         return cand, cnt
 
     def cnn_predict(self, scores_ptr: int, n: int, minibatch: int, Lo: int) -> np.ndarray:
         """C3 + the scaling of cnn_detect on the device: int64 [n, 1 + max(k, 1)] (adapter end, poly(A) candidates; samples)"""
         k = max(1, int(self.cfg.polya_cand_k))
         out = np.zeros((n, 1 + k), dtype=np.int64)
-        self._check(self.lib.adp_cnn_predict(self._h, C.c_void_p(int(scores_ptr)), int(n), int(minibatch), int(Lo),
-                                             out.ctypes.data_as(C.c_void_p)))
+        self._check(self.lib.adp_cnn_predict(self._h, int(scores_ptr), n, int(minibatch), int(Lo), out))
         return out
 
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
                         want_bounds: bool = True):
         """combined_detect_cnn without the short-read fallback -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k])"""
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, device_ptrs)
+        sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         k = max(1, int(self.cfg.polya_cand_k))
         bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
-        if rows_dev is not None:
-            flags |= ADP_OUT_DEVICE
-            rows, rp = None, C.c_void_p(rows_dev)
-        else:
-            rows = np.zeros(n, dtype=ROW_DTYPE)
-            rp = rows.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.adp_detect_cnn(self._h, sp, lp, int(n), self.m, int(minibatch), flags, rp,
-                                            bounds.ctypes.data_as(C.c_void_p) if want_bounds else None))
-        del keep
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        self._check(self.lib.adp_detect_cnn(self._h, sig, lens, n, self.m, int(minibatch), flags | out_flag, rows_arg, bounds))
         return self.attach_open_pores(rows), bounds
 
     def cnn_set_weights(self, state):
@@ -964,53 +1019,45 @@ class Engine:
             if a.shape != shape:
                 raise ValueError("CNN weight %s has shape %s, expected %s" % (key, a.shape, shape))
             arrs.append(a)
-        self._check(self.lib.adp_cnn_set_weights(self._h, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+        self._check(self.lib.adp_cnn_set_weights(self._h, *arrs))
         self._cnn_weights_id = id(state)
 
     def cnn_forward(self, prepared_dev: int, n: int, Lc: int, scores_dev: int):
         """C2 on the device (hand-written conv stack): prepared float32 [n, Lc] -> scores float32 [n, 2, Lo]"""
-        self._check(self.lib.adp_cnn_forward(self._h, C.c_void_p(int(prepared_dev)), int(n), int(Lc), C.c_void_p(int(scores_dev))))
+        self._check(self.lib.adp_cnn_forward(self._h, int(prepared_dev), int(n), int(Lc), int(scores_dev)))
 
     def cnn_prepare(self, signals, n: int, out_dev_ptr: int, device_ptrs: bool = False):
         """C1 into a device buffer float32 [n, Lc] (e.g. a torch tensor's data_ptr)."""
-        if device_ptrs:
-            self._check(self.lib.adp_cnn_prepare(self._h, C.c_void_p(int(signals)), int(n), self.m, ADP_OUT_DEVICE | ADP_IN_DEVICE,
-                                                 C.c_void_p(int(out_dev_ptr))))
-            return
-        sig = np.ascontiguousarray(signals, dtype=np.float32)
-        self._check(self.lib.adp_cnn_prepare(self._h, sig.ctypes.data_as(C.c_void_p), int(n), self.m, ADP_OUT_DEVICE,
-                                             C.c_void_p(int(out_dev_ptr))))
+        sig, flags = (int(signals), ADP_IN_DEVICE) if device_ptrs else (np.ascontiguousarray(signals, dtype=np.float32), 0)
+        self._check(self.lib.adp_cnn_prepare(self._h, sig, int(n), self.m, flags | ADP_OUT_DEVICE, int(out_dev_ptr)))
 
     def llr_refine_polya(self, signals, full_lens, n: int, ranges: np.ndarray):
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, False)
+        sig, lens, flags = self._in(signals, full_lens, n, False)
         rg = np.ascontiguousarray(ranges, dtype=np.int64)
         out = np.zeros(n, dtype=np.int64)
         st = np.zeros(n, dtype=np.int32)
-        self._check(self.lib.adp_llr_refine_polya(self._h, sp, lp, int(n), self.m, rg.ctypes.data_as(C.c_void_p), flags,
-                                                  out.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p)))
-        del keep
+        self._check(self.lib.adp_llr_refine_polya(self._h, sig, lens, n, self.m, rg, flags, out, st))
         return out, st
 
     # -- debug (tests) ------------------------------------------------------------------------
     def debug_divcheck(self, d: float, first_bits: int, count: int) -> int:
-        out = C.c_uint64(0)
-        self._check(self.lib.adp_debug_divcheck(self._h, C.c_float(d), C.c_uint32(first_bits), C.c_uint32(count), C.byref(out)))
-        return int(out.value)
+        out = np.zeros(1, dtype=np.uint64)
+        self._check(self.lib.adp_debug_divcheck(self._h, d, first_bits, count, out))
+        return int(out[0])
 
     def debug_log(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.empty_like(x)
-        self._check(self.lib.adp_debug_log(self._h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), int(x.size)))
+        self._check(self.lib.adp_debug_log(self._h, x, y, x.size))
         return y
 
     def debug_llr_upto(self, signals, full_lens, n, minibatch, stage):
-        sp, lp, flags, keep = self._in_ptrs(signals, full_lens, n, False)
-        self._check(self.lib.adp_debug_llr_upto(self._h, sp, lp, int(n), self.m, int(minibatch), flags, int(stage)))
-        del keep
+        sig, lens, flags = self._in(signals, full_lens, n, False)
+        self._check(self.lib.adp_debug_llr_upto(self._h, sig, lens, n, self.m, int(minibatch), flags, int(stage)))
 
     def debug_fetch(self, what: int, n: int):
         lp = np.zeros(1, dtype=np.int32)
-        self._check(self.lib.adp_debug_fetch(self._h, 6, lp.ctypes.data_as(C.c_void_p), C.c_uint64(4)))
+        self._check(self.lib.adp_debug_fetch(self._h, 6, lp, 4))
         Lp = int(lp[0])
         if what == 6:
             return Lp
@@ -1020,15 +1067,15 @@ class Engine:
             raise ValueError("use debug_norm_params")
         shp, dt = shapes[what]
         a = np.zeros(shp, dtype=dt)
-        self._check(self.lib.adp_debug_fetch(self._h, what, a.ctypes.data_as(C.c_void_p), C.c_uint64(a.nbytes)))
+        self._check(self.lib.adp_debug_fetch(self._h, what, a, a.nbytes))
         return a
 
     def debug_counters(self, n: int = 8):
         a = np.zeros(n, dtype=np.uint64)
-        self._check(self.lib.adp_debug_fetch(self._h, 8, a.ctypes.data_as(C.c_void_p), C.c_uint64(8 * n)))
+        self._check(self.lib.adp_debug_fetch(self._h, 8, a, 8 * n))
         return a
 
     def debug_norm_params(self, n_mb: int):
         a = np.zeros((n_mb, 4), dtype=np.float64)
-        self._check(self.lib.adp_debug_fetch(self._h, 0, a.ctypes.data_as(C.c_void_p), C.c_uint64(a.nbytes)))
+        self._check(self.lib.adp_debug_fetch(self._h, 0, a, a.nbytes))
         return a

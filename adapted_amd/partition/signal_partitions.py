@@ -24,7 +24,7 @@ from typing import Optional
 import numpy as np
 
 from ..container_types import Boundaries
-from ..detect._sigstats import _engine, position, positions, rows_in
+from ..detect._rows import _engine, position, positions, rows_in
 
 
 @dataclass

@@ -137,6 +137,68 @@ def test_abi_library_loads_and_exports_header_symbols():
         assert hasattr(L, sym), sym
 
 
+def _header_prototypes():
+    """include/adapted_hip.h, comments stripped -> {name: (return kind, [parameter kinds])} in lib.PROTOTYPES' vocabulary:
+    `const` and the parameter names dropped, int32_t -> int32, one * per level of indirection"""
+    with open(os.path.join(ROOT, "include", "adapted_hip.h")) as fh:
+        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
+
+    def kind(decl, named):
+        m = re.fullmatch(r"(?:const\s+)?(\w+?)(?:_t)?\s*((?:\*\s*)*)" + (r"\w+" if named else ""), decl.strip())
+        assert m, decl
+        return m.group(1) + "*" * m.group(2).count("*")
+
+    protos = {}
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+\s*\**)\s*(adp_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
+        params = [] if params.strip() == "void" else [kind(p, True) for p in params.split(",")]
+        protos[name] = (kind(ret, False), params)
+    return protos
+
+
+def test_abi_prototype_table_matches_the_header():
+    """lib.PROTOTYPES restates every prototype of include/adapted_hip.h -- name, return kind, parameter count, and per position
+    the scalar kind or the pointer's element -- and load() binds every function to it; a call that breaks its prototype is
+    refused before the library is entered (no GPU needed: ctypes converts the arguments first)"""
+    from adapted_amd import lib
+
+    declared = _header_prototypes()
+    assert len(declared) == 62 and set(declared) == set(lib.PROTOTYPES) == set(lib.EXPORTS)
+    scalars = {"int", "int32", "uint32", "uint64", "float", "double"}
+    L = lib.load()
+    for name, (ret, params) in declared.items():
+        got_ret, got_params = lib.PROTOTYPES[name].split(":")
+        assert got_ret == ret, name
+        assert got_params.split() == params, name
+        assert all(p in scalars or p.endswith("*") for p in params), name
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        assert fn.restype is {"int": ctypes.c_int, "char*": ctypes.c_char_p, "void*": ctypes.c_void_p}[ret], name
+        for p, t in zip(params, fn.argtypes):  # scalars are bound at their width, number pointers to the header's element
+            if p in scalars:
+                assert t is getattr(ctypes, "c_" + p), (name, p)
+            elif p[:-1] in lib._ELEMENTS:
+                assert isinstance(t, lib._Pointer) and t.element == p[:-1], (name, p)
+            else:                                      # a handle, or a struct / out-parameter of exactly that type
+                assert t is (ctypes.c_void_p if p == "adp_handle*" else ctypes.POINTER(lib._POINTEES[p[:-1]])), (name, p)
+    assert sum(len(p) for _, p in declared.values()) == 220 + 130
+    with pytest.raises(TypeError):
+        L.adp_synchronize()                                       # an argument missing
+    lens64 = np.zeros(4, dtype=np.int64)
+    with pytest.raises(ctypes.ArgumentError, match="argument 3.*int32"):
+        L.adp_med_mad(None, None, lens64, 4, 8, 0, None)          # an int64 array for `const int32_t *len`
+    with pytest.raises(ctypes.ArgumentError, match="strides"):
+        L.adp_debug_log(None, np.zeros((4, 2))[:, 0], np.zeros(4), 4)
+    with pytest.raises(ctypes.ArgumentError):
+        L.adp_copy_mark(None, 1.5)                                # a float for an int
+    p = lib._Pointer("int32")
+    assert p.from_param(None).value is None and p.from_param(1 << 40).value == 1 << 40  # (a device pointer keeps its 64 bits)
+    a = np.zeros(3, dtype=np.int32)
+    assert p.from_param(a).value == a.ctypes.data and lib._Pointer("void").from_param(lens64).value == lens64.ctypes.data
+    ref = ctypes.byref(ctypes.c_int32())
+    assert p.from_param(ref) is ref
+    assert lib._Pointer("adp_row").dtype == lib.ROW_DTYPE and lib._Pointer("adp_seg").dtype == lib.SEG_DTYPE
+
+
 def test_no_cpu_fallback_without_gpu():
     """Without a GPU the operators must fail loudly, not fall back to anything."""
     from adapted_amd import lib

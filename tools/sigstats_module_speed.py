@@ -56,7 +56,7 @@ def _timed(eng, fn, reps):
 def device(n, L, reps, dtype=np.float32):
     from adapted_amd.config.schema import RealRangeConfig
     from adapted_amd.detect import anomalies, downscale, normalize, real_range
-    from adapted_amd.detect._sigstats import _engine
+    from adapted_amd.detect._rows import _engine
     from adapted_amd.partition import signal_partitions as sp
 
     eng = _engine()
@@ -97,7 +97,7 @@ def device(n, L, reps, dtype=np.float32):
 
 def sweep(reps, dtype=np.float32):
     """median / MAD of one resident population: one wave against many workgroups"""
-    from adapted_amd.detect._sigstats import _engine
+    from adapted_amd.detect._rows import _engine
 
     eng = _engine()
     rng = np.random.default_rng(5)
