@@ -13,7 +13,6 @@
 #include "adapted_hip.h"
 #include "handle.h"
 #include "common.h"
-__device__ int g_ablate = 0;
 __device__ unsigned long long g_dbg[ADP_NDBG] = {0};
 // k_partition_stats' tallies (slots 0-4 of what = 8), spread over ADP_NTALLY cache lines by workgroup: every workgroup adding to ONE
 // address serialises device-wide -- 2 x 96 000 same-address atomics were 7.7 ms of the kernel's 13 at the default window
@@ -309,19 +308,20 @@ __global__ void k_mb_params_out(const MbState *mbs, int n_mb, double *out)
     }
 }
 
-// developer switch ADP_ABLATE (bit mask that skips parts of kernels in timing experiments; results are wrong when set):
-// the device copy is refreshed only when the environment value changes
-static void sync_ablate(hipStream_t st)
+#ifdef ADP_ABLATE
+// (common.h: ABLATED) the device's copy is refreshed when the environment's value is not the one this handle copied last
+__device__ int g_ablate = 0;
+static void sync_ablate(adp_handle *h)
 {
-    static int current = 0;
     const char *ab = getenv("ADP_ABLATE");
     const int want = ab ? atoi(ab) : 0;
-    if (want != current) {
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ablate), &want, sizeof(int), 0, hipMemcpyHostToDevice, st);
-        (void)hipStreamSynchronize(st);
-        current = want;
+    if (want != h->ablate) {
+        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ablate), &want, sizeof(int), 0, hipMemcpyHostToDevice, h->stream);
+        (void)hipStreamSynchronize(h->stream);
+        h->ablate = want;
     }
 }
+#endif
 
 static int env_int(const char *name, int dflt)
 {
@@ -436,7 +436,9 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
         (void)hipMemsetAsync(h->have_series.p, 0, (size_t)n, h->stream);
     }
     int grid = n < h->vslots ? n : h->vslots;
-    sync_ablate(h->stream);
+#ifdef ADP_ABLATE
+    sync_ablate(h);
+#endif
     // open-pore lists longer than a row holds go to the arena of the CALL (arena_begin / arena_end: cumulative over every
     // launch of the call, shared by the lanes of a grouped call; a call that overflowed it is repeated on a larger one)
     adp_handle *a = h->owner ? h->owner : h;
@@ -550,6 +552,26 @@ struct PhaseSync {
 static __device__ __host__ inline SigF32 sig_from(const SigF32 &s, size_t r0, int m) { return SigF32{s.base + r0 * (size_t)m}; }
 static __device__ __host__ inline SigI16 sig_from(const SigI16 &s, size_t r0, int m) { return SigI16{s.base + r0 * (size_t)m, s.scale + r0, s.offset + r0, s.full_len + r0}; }
 
+// k_cumsum and k_cumsum_gather share the launch's waves (llr_stream.h; ADP_CUMSUM_GATHER=0: k_cumsum takes them all, same results)
+static void launch_cumsum(adp_handle *h, int n)
+{
+    const int split = env_int("ADP_CUMSUM_GATHER", 1) != 0;
+    hipLaunchKernelGGL(k_cumsum, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n,
+                       h->nck, h->ck.as<double2>(), h->tail.as<double2>(), split);
+    if (split)
+        hipLaunchKernelGGL(k_cumsum_gather, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n,
+                           h->nck, h->ck.as<double2>(), h->tail.as<double2>());
+}
+
+// pkv: the maxima's heights as k_gains<2> listed them, or null.  ADP_PK_PREFIX=0: the whole list of maxima at once (peaks.h; same results)
+static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv)
+{
+    const int grid = n < h->pslots ? n : h->pslots;
+    hipLaunchKernelGGL(k_polya_peak, dim3(grid), dim3(64), (size_t)(((h->Lp / 2 + 1) + 8) / 16 + 2) * 4, h->stream, h->trace.as<double>(), h->nvalid.as<int32_t>(), h->Lp,
+                       h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, mbsize, h->mbs.as<MbState>(),
+                       h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>(), pkv, env_int("ADP_PK_PREFIX", PK_PREFIX));
+}
+
 template <class SIG>
 static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags,
                        adp_row *rows_dev, int rows_kind /* hipMemcpyKind of the row delivery */, int32_t *mb_status_dev, double *mb_params_dev,
@@ -564,7 +586,9 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     rc = alloc_all(h, n, true);
     if (rc) return rc;
     hipStream_t st = h->stream;
-    sync_ablate(st);
+#ifdef ADP_ABLATE
+    sync_ablate(h);
+#endif
     if (ps && ps->wait[0]) HIPCHK(hipStreamWaitEvent(st, ps->wait[0], 0));
     MbState *mbs = h->mbs.as<MbState>();
     HIPCHK(hipMemsetAsync(mbs, 0, (size_t)n_mb * sizeof(MbState), st));
@@ -637,12 +661,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         if (ps && ps->wait[1]) HIPCHK(hipStreamWaitEvent(st, ps->wait[1], 0));
         if (upto >= 3) {
             Scope s(h, "k_cumsum");
-            const int split = env_int("ADP_CUMSUM_GATHER", 1) != 0;
-            hipLaunchKernelGGL(k_cumsum, dim3((n + 63) / 64), dim3(64), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n,
-                               h->nck, h->ck.as<double2>(), h->tail.as<double2>(), split);
-            if (split)
-                hipLaunchKernelGGL(k_cumsum_gather, dim3((n + 63) / 64), dim3(64), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n,
-                                   h->nck, h->ck.as<double2>(), h->tail.as<double2>());
+            launch_cumsum(h, n);
         }
         if (upto >= 4) {
             Scope s(h, "k_gains<1>");
@@ -667,10 +686,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         }
         if (upto >= 7) {
             Scope s(h, "k_polya_peak");
-            int grid = n < h->pslots ? n : h->pslots;
-            hipLaunchKernelGGL(k_polya_peak, dim3(grid), dim3(64), (size_t)(((h->Lp / 2 + 1) + 8) / 16 + 2) * 4, st, h->trace.as<double>(), h->nvalid.as<int32_t>(), h->Lp,
-                               h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, minibatch, mbs,
-                               h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>(), pkvp);
+            launch_polya_peak(h, n, minibatch, pkvp);
         }
         if (ps && ps->done[1]) HIPCHK(hipEventRecord(ps->done[1], st));
     }
@@ -1555,17 +1571,11 @@ int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *ful
     if (rc) return rc;
     hipLaunchKernelGGL(k_norm_pool<SigF32>, dim3(n), dim3(256), (size_t)NP_TILE * h->ds * 4, st, SigF32{dsig}, m, h->T, h->off, h->ds, h->L, h->Lp, 1, mbs,
                        h->down.as<float>(), h->nvalid.as<int32_t>(), (const int64_t *)drng, dlen);
-    hipLaunchKernelGGL(k_cumsum, dim3((n + 63) / 64), dim3(64), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n, h->nck,
-                       h->ck.as<double2>(), h->tail.as<double2>(), 1);
-    hipLaunchKernelGGL(k_cumsum_gather, dim3((n + 63) / 64), dim3(64), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, n, h->nck,
-                       h->ck.as<double2>(), h->tail.as<double2>());
+    launch_cumsum(h, n);
     hipLaunchKernelGGL(k_gains<1>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
                        h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), 1, mbs, h->trace.as<double>(),
                        h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 1, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, (double *)nullptr, n, 5);
-    int grid = n < h->pslots ? n : h->pslots;
-    hipLaunchKernelGGL(k_polya_peak, dim3(grid), dim3(64), (size_t)(((h->Lp / 2 + 1) + 8) / 16 + 2) * 4, st, h->trace.as<double>(), h->nvalid.as<int32_t>(), h->Lp,
-                       h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, 1, mbs,
-                       h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>());
+    launch_polya_peak(h, n, 1, nullptr); // (k_gains<1> lists no heights)
     hipLaunchKernelGGL(k_refine_out, dim3((n + 255) / 256), dim3(256), 0, st, mbs, h->nvalid.as<int32_t>(), h->polya_idx.as<int32_t>(),
                        (const int64_t *)drng, n, h->ds, dout, dstat);
     HIPCHK(hipMemcpyAsync(polya_out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, st));

@@ -35,8 +35,7 @@
 #define BS_MAXCHUNK 128   // whole 8192-sample chunks per segment (1 Mi samples); longer segments take the generic path
 #define BS_BINS18 1536    // fallback passes C/D: 18-bit buckets, collect capacity 1536
 
-// (defined in adapted_hip.hip) timing experiments only (ADP_ABLATE); results are wrong when non-zero
-extern __device__ int g_ablate;
+// (both defined in adapted_hip.hip; ABLATED(bits), common.h: timing experiments of a -DADP_ABLATE build, the constant false in the product)
 extern __device__ unsigned long long g_bs_tally[ADP_NTALLY][8];
 extern __device__ unsigned long long g_dbg[ADP_NDBG]; // debug tallies (adp_debug_fetch what=8): 0-4 here, 5-7 N1, 8-15 phase cycles here
 
@@ -421,7 +420,7 @@ static __device__ __noinline__ SumAux block_np_sum(X x, int n, int mode, float c
     __syncthreads();
     phase(25);
     const int tail = n - s;
-    if (tail > 0 && !(g_ablate & 4)) {
+    if (tail > 0 && !ABLATED(4)) {
         phase(26);
         const float rt = bs_ragged_sum<SIDE>(x + s, tail, mode, c, bs, param, aux, aux2);
         if (tid < 64) total += rt;
@@ -936,7 +935,7 @@ static __device__ SegStats block_segment_stats(X x, int n, LDS BS *bs, bool have
     for (int i = tid; i < BS_BINS + 4; i += BS::NT) bs->hist[i] = 0; // (the bins and the dump cells behind them)
     __syncthreads();
     sp.key = wlo;
-    SumAux p1 = (have_medmad || (g_ablate & 2048)) ? block_np_sum<SIDE_NONE>(x, n, 0, 0.f, bs, sp) : block_np_sum<SIDE_HIST>(x, n, 0, 0.f, bs, sp);
+    SumAux p1 = (have_medmad || ABLATED(2048)) ? block_np_sum<SIDE_NONE>(x, n, 0, 0.f, bs, sp) : block_np_sum<SIDE_HIST>(x, n, 0, 0.f, bs, sp);
     o.mean = p1.sum / (float)n;
     if (o.mean != o.mean) {
         // a NaN mean: a NaN sample (np.std, np.median and the MAD are NaN as well then) or infinities of both signs (they are
@@ -973,21 +972,21 @@ static __device__ SegStats block_segment_stats(X x, int n, LDS BS *bs, bool have
                 hw = __uint_as_float(__float_as_uint(hm) + 2u);
             }
         }
-        if (!fallback_med && !(g_ablate & 2)) predicted = bs_predict_mad(bs, wlo, k1, c, w0, P, Q);
+        if (!fallback_med && !ABLATED(2)) predicted = bs_predict_mad(bs, wlo, k1, c, w0, P, Q);
         __syncthreads();
         if (tid == 0) { bs->ncollect = 0; bs->nmad = 0; bs->kmin = 0xffffffffu; bs->kmax = 0u; }
         __syncthreads();
     }
     phase(1);
     // ---- pass B: variance + median bucket + MAD bracket --------------------------------------
-    sp.key = wlo + (uint32_t)bin; sp.c = c; sp.hw = hw; sp.do_mad = (predicted && !(g_ablate & 16384)) ? 1 : 0;
+    sp.key = wlo + (uint32_t)bin; sp.c = c; sp.hw = hw; sp.do_mad = (predicted && !ABLATED(16384)) ? 1 : 0;
     if (sp.do_mad) { sp.P = P; sp.Q = Q; } else { sp.P = __builtin_inff(); sp.Q = -1.0f; } // (no bracket: nothing flagged for it)
-    if (g_ablate & 4096) { o.sd = 0; o.med = 0; o.mad = 0; return o; }
-    SumAux p2 = (have_medmad || fallback_med || (g_ablate & (2048 | 8192))) ? block_np_sum<SIDE_NONE>(x, n, 2, o.mean, bs, sp)
+    if (ABLATED(4096)) { o.sd = 0; o.med = 0; o.mad = 0; return o; }
+    SumAux p2 = (have_medmad || fallback_med || ABLATED(2048 | 8192)) ? block_np_sum<SIDE_NONE>(x, n, 2, o.mean, bs, sp)
                                               : block_np_sum<SIDE_COLLECT>(x, n, 2, o.mean, bs, sp);
     o.sd = sqrtf(p2.sum / (float)n);
     phase(2);
-    if (have_medmad || (g_ablate & (2048 | 8192 | 131072))) { o.med = med_in; o.mad = mad_in; return o; }
+    if (have_medmad || ABLATED(2048 | 8192 | 131072)) { o.med = med_in; o.mad = mad_in; return o; }
     if (fallback_med) {
         __syncthreads();
         if (tid < 64) { float m_ = wave_median(x, n, 0, 0.f, &bs->u.ws); if (tid == 0) bs->bcast[1] = m_; }
@@ -1017,7 +1016,7 @@ static __device__ SegStats block_segment_stats(X x, int n, LDS BS *bs, bool have
         o.med = bs_median_from_bucket(bs, bs_collect(bs), bs->ncollect, n, rk, below_key);
     }
     phase(3);
-    if (g_ablate & 32768) { o.mad = 0.f; return o; }
+    if (ABLATED(32768)) { o.mad = 0.f; return o; }
     // ---- MAD inside the bracket, if it can be proven ---------------------------------------------
     bool done = false;
     if (predicted && !fallback_med) {
@@ -1047,7 +1046,7 @@ static __device__ SegStats block_segment_stats(X x, int n, LDS BS *bs, bool have
                                  atomicAdd(&g_dbg[16], (unsigned long long)bs->nmad); atomicAdd(&g_dbg[17], (unsigned long long)bs->ncollect);
                                  if (bs->nmad > 2048) atomicAdd(&g_dbg[18], 1ull); if (bs->nmad > 3072) atomicAdd(&g_dbg[19], 1ull); }
 #endif
-    if (tid == 0 && n >= 8192 && !(g_ablate & 262144)) { // tallies for the large segments only
+    if (tid == 0 && n >= 8192 && !ABLATED(262144)) { // tallies for the large segments only
         unsigned long long *tl = g_bs_tally[blockIdx.x & (ADP_NTALLY - 1)]; // (a line of its own per 1 / ADP_NTALLY of the workgroups)
         atomicAdd(&tl[0], 1ull);
         if (done) atomicAdd(&tl[1], 1ull);
@@ -1090,7 +1089,7 @@ static __device__ __forceinline__ void bs_partitions_of_read(const ROW sig, cons
         long long a = st < S ? st : S, b = en < S ? en : S;
         int n = (int)(b - a);
         SegStats s;
-        if (n <= 0 || ((g_ablate & 8) && p < 2)) s.mean = s.sd = s.med = s.mad = __builtin_nanf("");
+        if (n <= 0 || (ABLATED(8) && p < 2)) s.mean = s.sd = s.med = s.mad = __builtin_nanf("");
         else s = block_segment_stats(sig + a, n, bs, p == 0 && q.have_adapter_medmad, q.adapter_med, q.adapter_mad);
         if (threadIdx.x == 0) {
             row->col[c_len[p]] = (double)(en - st);

@@ -26,7 +26,7 @@
 #include "cand_stats.h"
 #include "common.h"
 
-extern __device__ int g_ablate; // (timing experiments, ADP_ABLATE: 2^20 no finish, 2^21 no sweep B, 2^23 no sweep A; tools/experiments/cs2_ablate.sh)
+// (ABLATED, common.h -- timing experiments of a -DADP_ABLATE build: 2^20 no finish, 2^21 no sweep B, 2^23 no sweep A; tools/experiments/cs2_ablate.sh)
 #define CS2_MAXC 16  // candidates per round (polya_cand_k beyond it: more rounds)
 #define CS2_QPC 10   // queries per candidate: 6 on the slice (median pair, two percentile pairs), 2 + 2 on the series
 #define CS2_SEGSH 27 // list entry = segment << 27 | key bits below the bin
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
                     LDS uint32_t *h = (LDS uint32_t *)sh->hist + j * NB;
                     const uint32_t kl = klo[j]; const int sf = shf[j];
                     int nm = nanmin[j];
-                    if (!(g_ablate & (1 << 23)))
+                    if (!ABLATED(1 << 23))
                     cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, [&](float v, int i) {
                         if (v != v) { nm = i < nm ? i : nm; return; }
                         const uint32_t key = f2key(v);
@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
                     const LDS uint8_t *lut = (const LDS uint8_t *)sh->lut + j * NB;
                     const uint32_t kl = klo[j]; const int sf = shf[j];
                     const uint32_t lowmask = sf ? ((1u << sf) - 1u) : 0u;
-                    if (!(g_ablate & (1 << 21)))
+                    if (!ABLATED(1 << 21))
                     cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, [&](float v, int i) {
                         (void)i;
                         if (v != v) return;
@@ -346,7 +346,7 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
         // ---- finish, short lists: a THREAD per query (round 4: at the default window a bin holds a few dozen elements, and the wave-per-query
         // loop below -- a ballot per bit and 64 entries, 25 queries in turn per wave -- was a third of the kernel); the query is done when its
         // rank comes back as -1
-        if (THREADS <= 256 && !(g_ablate & (1 << 20))) { // (the small shape: at the 200 k window the lists are long and this phase only adds to the wave loop: 15.0 -> 15.7 ms)
+        if (THREADS <= 256 && !ABLATED(1 << 20)) { // (the small shape: at the 200 k window the lists are long and this phase only adds to the wave loop: 15.0 -> 15.7 ms)
             const LDS uint32_t *pool = (const LDS uint32_t *)sh->hist;
             for (int qi = tid; qi < nc * CS2_QPC; qi += THREADS) {
                 const int k = sh->q_k[qi];
@@ -388,7 +388,7 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
             const LDS uint32_t *pool = (const LDS uint32_t *)sh->hist;
             for (int qi = wv; qi < nc * CS2_QPC; qi += NW) {
                 const int k = sh->q_k[qi];
-                if (k < 0 || (g_ablate & (1 << 20))) continue;
+                if (k < 0 || ABLATED(1 << 20)) continue;
                 const int c = qi / CS2_QPC, t = qi % CS2_QPC, j = cs2_arr(t);
                 const int b = sh->q_bin[qi];
                 if (b < 1 || b > NB - 2 || sh->q_cnt[qi] >= (1 << 20)) continue; // (c_bad is set)

@@ -18,6 +18,15 @@
 #define TRACE_TILE 1024 // pooled samples handled per wave iteration in the gains kernel (64 lanes x CK)
 #define SUMBLK 64      // trace summary block (max/min per 64 trace points)
 
+// ABLATED(bits): timing experiments that skip a part of a hot kernel (results are wrong then).  Only a -DADP_ABLATE build
+// (tools/experiments/cs2_ablate.sh) reads the mask from the environment's ADP_ABLATE; the product ignores the variable.
+#ifdef ADP_ABLATE
+extern __device__ int g_ablate;
+#define ABLATED(bits) ((g_ablate & (bits)) != 0)
+#else
+#define ABLATED(bits) false
+#endif
+
 // per-minibatch state of the batch-global normalisation (N1)
 struct MbState {
     unsigned long long n_valid;   // non-NaN samples in batch[:, :T]

@@ -98,6 +98,9 @@ struct adp_handle {
     // handle -- a handle is used by one thread at a time -- instead of in process-wide statics)
     unsigned attr_done = 0;
     size_t lds_series_set = 0;
+#ifdef ADP_ABLATE
+    int ablate = 0;   // the mask this handle last copied to its device (sync_ablate)
+#endif
 };
 
 // ---- a call's start and its profiling scopes (adapted_hip.hip) --------------------------

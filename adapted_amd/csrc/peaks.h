@@ -19,7 +19,6 @@
 #include "common.h"
 #include "find_peaks.h"
 
-extern __device__ int g_ablate;
 extern __device__ unsigned long long g_dbg[ADP_NDBG]; // (debug tallies; 16-23: k_polya_peak in a -DADP_PHASE_TIMING build)
 
 // ---------------------------------------------------------------- adapter end (P1 + P2 + P3 + A1)
@@ -118,7 +117,7 @@ __global__ void __launch_bounds__(64) k_adapter_peak(const double *__restrict__ 
 #define PK_STEP 16 // kept maxima examined per step of step 4
 #endif
 #ifndef PK_PREFIX
-#define PK_PREFIX 224 // maxima of the first attempt (one round of step 2; 96 000 reads at the 200 k window: 5.2 ms without the prefix, 2.88 with 896, 2.50 with 448, 2.30 with 224, 2.38 with 112); ADP_ABLATE bit 2^24: the whole list at once, as before
+#define PK_PREFIX 224 // maxima of the first attempt (one round of step 2; 96 000 reads at the 200 k window: 5.2 ms without the prefix, 2.88 with 896, 2.50 with 448, 2.30 with 224, 2.38 with 112); the default of the kernel's `prefix` argument, which the host takes from ADP_PK_PREFIX (0: the whole list at once, as before; same results)
 #endif
 #define PST_NONE 0u
 #define PST_REMOVED 1u
@@ -127,7 +126,7 @@ __global__ void __launch_bounds__(64) k_adapter_peak(const double *__restrict__ 
 
 // persistent grid of waves.  pk[Lp/2+1] int32 per READ (list of maxima, pre-filled by k_gains; ends up holding
 // the kept ones), mk[Lp/2+1] uint32 per SLOT (work list of undecided maxima: ordinal << 8 | neighbour mask);
-// the states live in dynamic LDS: ((Lp/2+1) + 8) / 16 + 2 words per wave.
+// the states live in dynamic LDS: ((Lp/2+1) + 8) / 16 + 2 words per wave.  prefix: the first attempt's maxima (0: all).
 //
 // Strict local maxima are at least two samples apart, so at most four of them lie within the minimum distance
 // (|dp| <= 9) on either side of a maximum: the neighbourhood is the ordinals k-4 .. k+4, whatever the positions.
@@ -136,7 +135,7 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                                                    const int32_t *__restrict__ adapter_idx, int n_reads, int mbsize,
                                                    const MbState *__restrict__ mbs, int32_t *__restrict__ pk_all,
                                                    uint32_t *__restrict__ mk_all, int32_t *__restrict__ polya_idx,
-                                                   const int32_t *__restrict__ npk_all, const double *__restrict__ pkv_all = nullptr)
+                                                   const int32_t *__restrict__ npk_all, const double *__restrict__ pkv_all, int prefix)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t stw_raw[];
     LDS uint32_t *stw = (LDS uint32_t *)stw_raw; // ordinal k is slot k + 4 (slots 0..3 stay PST_NONE)
@@ -193,14 +192,14 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                     npk += __popcll(m);
                 }
             }
-            if (g_ablate & 256) npk = 0;
+            if (ABLATED(256)) npk = 0;
             // Only the first two survivors in index order are wanted, and they lie near the front of almost every trace: steps 2-4 run
             // on a PREFIX of the list first (the first wn maxima; the maxima behind it read as undecided, so a state that depends on
             // them stays undecided -- whatever is decided is final: the fixed point is unique).  The answer stands when the second
             // survivor was found among maxima in front of the first undecided one; otherwise the steps run again on the whole list.
             int p0 = -1, p1 = -1;
             for (int attempt = 0; attempt < 2; attempt++) {
-            const int wn = (attempt == 0 && npk > PK_PREFIX && !(g_ablate & 16777216)) ? PK_PREFIX : npk;
+            const int wn = (attempt == 0 && prefix > 0 && npk > prefix) ? prefix : npk;
             __syncthreads();
             for (int w = ln; w < (wn + 8 + 15) / 16 + 1; w += 64) stw[w] = 0;
             __syncthreads();
@@ -276,7 +275,7 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
             }
             __syncthreads();
             // 3. fixed point of "kept iff no kept higher-priority neighbour"
-            if (g_ablate & 512) nund = 0;
+            if (ABLATED(512)) nund = 0;
             while (nund > 0) {
                 int w = 0;
                 for (int base4 = 0; base4 < nund; base4 += 256) { // (four list loads in flight; the rewritten list stays
@@ -351,7 +350,7 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
             p0 = -1; p1 = -1;
             // (16 candidates per step: the second survivor is among the first 32 kept maxima of almost every read, and
             // every candidate with a long walk costs the whole wave a cooperative scan)
-            for (int base = 0; base < nkept && p1 < 0 && !(g_ablate & 1024); base += PK_STEP) {
+            for (int base = 0; base < nkept && p1 < 0 && !ABLATED(1024); base += PK_STEP) {
                 int k = base + ln;
                 int i = (ln < PK_STEP && k < nkept) ? kl[k] : -1;
                 const bool ok = wave_peak_ok(tv, i, 1.0, 10.0, 0.5);

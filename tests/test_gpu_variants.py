@@ -4,7 +4,10 @@ waves (series_pipe.h), layer 3 of the conv stack as a kernel of its own (`ADP_CN
 `ADP_CNN_OVERLAP=0`, against a chunk's last layer beside the next chunk's first) against layer 3 in layer 2's epilogue, every sampled row in the first level of N1's sample (`ADP_N1_S0=1`), the lane-per-read series kernel on the LLR
 path (`ADP_SERIES_PIPE_LLR=0`).  (The variants that lost their A/B in rounds 2-4 left the product in round 5:
 tools/experiments/r05_pruned_variants.patch.)  Reference rows: V1-V4 adapted/detect/combined.py:358-631, mvs.py:45-158; C2
-adapted/detect/cnn.py:16-52."""
+adapted/detect/cnn.py:16-52.
+`ADP_ABLATE` is no such switch: it belongs to a `-DADP_ABLATE` build of the library (timing experiments, wrong rows) and the product
+ignores it."""
+import functools
 import os
 
 import numpy as np
@@ -12,7 +15,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("ADP_SERIES_PIPE", "ADP_CNN_OVERLAP", "ADP_N1_S0", "ADP_SERIES_PIPE_LLR", "ADP_CNN_FOLD", "ADP_CNN_FUSE_IN", "ADP_CUMSUM_GATHER")
+SWITCHES = ("ADP_SERIES_PIPE", "ADP_CNN_OVERLAP", "ADP_N1_S0", "ADP_SERIES_PIPE_LLR", "ADP_CNN_FOLD", "ADP_CNN_FUSE_IN", "ADP_CUMSUM_GATHER", "ADP_PK_PREFIX",
+            "ADP_ABLATE")
 
 
 def _with_env(env, fn):
@@ -52,11 +56,10 @@ def _spc(primary, max_obs_trace=None, **over):
     return spc
 
 
-@pytest.mark.parametrize("window, k, quantise, windows", [(None, 10, 0.0, None), (60000, 10, 0.18, None), (200000, 10, 0.0, None), (200000, 15, 0.18, None),
-                                                           (34000, 3, 0.0, (48, 12)), (34000, 10, 0.0, (101, 23))])
-def test_cnn_path_variants_give_the_same_rows(window, k, quantise, windows):
-    from adapted_amd import lib, synth
-    from adapted_amd.detect import cnn
+@functools.lru_cache(maxsize=None)
+def _cnn_batch(window, k, quantise, windows):
+    """(spc, signals, lengths, [(read, position of its NaN hole)]): shared by the tests, which leave it unchanged"""
+    from adapted_amd import synth
 
     over = {"cnn_boundaries__polya_cand_k": k}
     if windows:
@@ -80,6 +83,17 @@ def test_cnn_path_variants_give_the_same_rows(window, k, quantise, windows):
         if at > 6000:
             sig[r, at: at + 3] = np.nan
             nan_reads.append((r, at))
+    return spc, sig, lens, tuple(nan_reads)
+
+
+@pytest.mark.parametrize("window, k, quantise, windows", [(None, 10, 0.0, None), (60000, 10, 0.18, None), (200000, 10, 0.0, None), (200000, 15, 0.18, None),
+                                                           (34000, 3, 0.0, (48, 12)), (34000, 10, 0.0, (101, 23))])
+def test_cnn_path_variants_give_the_same_rows(window, k, quantise, windows):
+    from adapted_amd import lib
+    from adapted_amd.detect import cnn
+
+    spc, sig, lens, nan_reads = _cnn_batch(window, k, quantise, windows)
+    n, m = sig.shape
     ref = None
     # (ADP_CNN_FOLD=0: layer 3 as a kernel of its own sums the same products in another order -- scores differ in their last bits, which
     # flips a near-tied candidate on about one read in 10^4: not on these)
@@ -107,9 +121,10 @@ def test_cnn_path_variants_give_the_same_rows(window, k, quantise, windows):
         assert got == ref, env
 
 
-@pytest.mark.parametrize("window", [None, 200000])
-def test_llr_path_switches_give_the_same_rows(window):
-    from adapted_amd import lib, synth
+@functools.lru_cache(maxsize=None)
+def _llr_batch(window):
+    """(spc, signals, lengths) with a NaN hole and a long open_pores list: shared by the tests, which leave it unchanged"""
+    from adapted_amd import synth
 
     spc = _spc("llr", window)
     m = spc.sig_preload_size
@@ -119,6 +134,15 @@ def test_llr_path_switches_give_the_same_rows(window):
     sig[5, 3000:3004] = np.nan                          # a NaN hole inside a read
     for j in range(21):
         sig[9, 120 + 40 * j: 123 + 40 * j] = 260.0      # an open_pores list beyond 16 entries
+    return spc, sig, lens
+
+
+@pytest.mark.parametrize("window", [None, 200000])
+def test_llr_path_switches_give_the_same_rows(window):
+    from adapted_amd import lib
+
+    spc, sig, lens = _llr_batch(window)
+    n, m = sig.shape
     eng = lib.Engine(spc, n, m, device=0)
     a, _ = _with_env({}, lambda: eng.detect_llr_rows(sig, lens, n, 48, with_start_peak=True))
     d, _ = _with_env({"ADP_N1_S0": "1", "ADP_SERIES_PIPE_LLR": "0"}, lambda: eng.detect_llr_rows(sig, lens, n, 48, with_start_peak=True))  # (every sampled row in N1's first level; the lane-per-read series kernel)
@@ -128,8 +152,8 @@ def test_llr_path_switches_give_the_same_rows(window):
 
 def test_polya_peak_on_a_prefix_of_the_maxima_equals_the_whole_list():
     """P4 (reference adapted/detect/llr.py:406-479): k_polya_peak settles the distance rule and the survivors on the first 224 maxima and
-    takes the whole list only when that does not show the second survivor; ADP_ABLATE bit 2^24 (read when the engine is made) runs the
-    whole list at once, as before round 4.  Reads with few, one or no survivor (flat tails, short reads) take the second attempt."""
+    takes the whole list only when that does not show the second survivor; ADP_PK_PREFIX=0 runs the whole list at once, as before
+    round 4.  Reads with few, one or no survivor (flat tails, short reads) take the second attempt."""
     from adapted_amd import lib, synth
 
     spc = _spc("llr", 200000)
@@ -142,7 +166,7 @@ def test_polya_peak_on_a_prefix_of_the_maxima_equals_the_whole_list():
         a = int(rng.integers(8000, 20000))
         sig[r, a:lens[r]] = (80.0 + rng.normal(0.0, 4.0, max(0, int(lens[r]) - a))).astype(np.float32)[: max(0, min(m, int(lens[r])) - a)]
     got = []
-    for env in ({}, {"ADP_ABLATE": "16777216"}):
+    for env in ({}, {"ADP_PK_PREFIX": "0"}):
         def run():
             eng = lib.Engine(spc, n, m, device=0)
             try:
@@ -150,25 +174,16 @@ def test_polya_peak_on_a_prefix_of_the_maxima_equals_the_whole_list():
                 return _canon(rows, lib), rows["col"][:, lib.COLS.index("{primary}_polya_end")].copy()
             finally:
                 eng.close()
-        old = os.environ.get("ADP_ABLATE")
-        try:
-            os.environ.pop("ADP_ABLATE", None)
-            os.environ.update(env)
-            got.append(run())
-        finally:
-            os.environ.pop("ADP_ABLATE", None)
-            if old is not None:
-                os.environ["ADP_ABLATE"] = old
+        got.append(_with_env(env, run))
     assert got[0][0] == got[1][0]
     pe = got[0][1]
     assert (pe > 0).sum() >= n // 3 and (pe == 0).sum() >= 5   # both kinds of read are there
 
 
-def test_cumsum_kernels_share_a_launch_by_the_lengths_of_a_waves_reads():
-    """k_cumsum_gather takes the waves whose 64 reads have one length, k_cumsum the others (round 5): a batch with a wave of full-length reads,
-    a wave of mixed lengths, a wave of equal SHORT reads (fewer pooled samples than one gathered line holds) and a ragged last wave gives the
-    rows of the launch in which k_cumsum takes every wave (ADP_CUMSUM_GATHER=0)."""
-    from adapted_amd import lib, synth
+@functools.lru_cache(maxsize=None)
+def _wave_mix_batch():
+    """(spc, signals, lengths): a wave of full-length reads, a wave of mixed lengths, a wave of equal short reads, a ragged last wave"""
+    from adapted_amd import synth
 
     spc = _spc("llr", None)
     m = spc.sig_preload_size
@@ -178,6 +193,17 @@ def test_cumsum_kernels_share_a_launch_by_the_lengths_of_a_waves_reads():
     lens[128:192] = 2600
     lens[192:] = [m, 5000, m, 1800, m, m, 9000, 1012]
     sig, lens = synth.synth_batch(31, 0, n, m, lens)
+    return spc, sig, lens
+
+
+def test_cumsum_kernels_share_a_launch_by_the_lengths_of_a_waves_reads():
+    """k_cumsum_gather takes the waves whose 64 reads have one length, k_cumsum the others (round 5): a batch with a wave of full-length reads,
+    a wave of mixed lengths, a wave of equal SHORT reads (fewer pooled samples than one gathered line holds) and a ragged last wave gives the
+    rows of the launch in which k_cumsum takes every wave (ADP_CUMSUM_GATHER=0)."""
+    from adapted_amd import lib
+
+    spc, sig, lens = _wave_mix_batch()
+    n, m = sig.shape
 
     def run():
         eng = lib.Engine(spc, n, m, device=0)
@@ -187,3 +213,54 @@ def test_cumsum_kernels_share_a_launch_by_the_lengths_of_a_waves_reads():
         finally:
             eng.close()
     assert _with_env({}, run) == _with_env({"ADP_CUMSUM_GATHER": "0"}, run)
+
+
+def test_the_refine_path_honours_the_cumsum_and_prefix_switches():
+    """Engine.llr_refine_polya (the short-read fallback of the CNN path, reference adapted/detect/combined.py:251-301) launches the same
+    cumulative-sum pair and k_polya_peak as the detect path: k_cumsum alone (ADP_CUMSUM_GATHER=0) and the whole list of maxima at once
+    (ADP_PK_PREFIX=0) give the positions and the status of the default launch."""
+    from adapted_amd import lib
+
+    spc, sig, lens = _wave_mix_batch()
+    n, m = sig.shape
+    ranges = np.stack([np.full(n, 2000), np.minimum(lens, m)], axis=1).astype(np.int64)
+
+    def run():
+        eng = lib.Engine(spc, n, m, device=0)
+        try:
+            pos, status = eng.llr_refine_polya(sig, lens, n, ranges)
+            return pos.tobytes(), status.tobytes()
+        finally:
+            eng.close()
+    ref = _with_env({}, run)
+    assert (np.frombuffer(ref[0], dtype=np.int64) > 0).sum() >= (n + 2) // 3   # (not equal because all are empty)
+    for env in ({"ADP_CUMSUM_GATHER": "0"}, {"ADP_PK_PREFIX": "0"}):
+        assert _with_env(env, run) == ref, env
+
+
+def test_the_product_ignores_adp_ablate():
+    """The ablation mask is compiled into a -DADP_ABLATE build only (common.h: ABLATED): with the variable set to bits that skip work in
+    k_partition_stats (8, 4096), k_validate (16), k_polya_peak (256) and k_cand_stats2 (2^20, 2^23) the product gives the rows it gives
+    without it, on the LLR path and on the CNN path.  (A library that reads the variable turns the adapter and poly(A) statistics of every
+    successful read into NaN at bit 8.)"""
+    from adapted_amd import lib
+    from adapted_amd.detect import cnn
+
+    def run():
+        spc, sig, lens = _llr_batch(None)
+        n, m = sig.shape
+        eng = lib.Engine(spc, n, m, device=0)
+        try:
+            llr = _canon(eng.detect_llr_rows(sig, lens, n, 48, with_start_peak=True)[0], lib)
+        finally:
+            eng.close()
+        spc, sig, lens, _ = _cnn_batch(None, 10, 0.0, None)
+        n, m = sig.shape
+        eng = lib.Engine(spc, n, m, device=0)
+        try:
+            cnn.ensure_weights(eng, None, spc)
+            rows, bounds = eng.detect_cnn_rows(sig, lens, n, n // 2)
+            return llr, _canon(rows, lib), bounds.tobytes()
+        finally:
+            eng.close()
+    assert _with_env({}, run) == _with_env({"ADP_ABLATE": str(8 | 16 | 256 | 4096 | 1 << 20 | 1 << 23)}, run)

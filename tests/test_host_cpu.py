@@ -736,3 +736,34 @@ def test_every_lds_array_of_the_library_is_declared_16_byte_aligned():
                 if "[" in code or re.search(r"__shared__\s+(WaveScratch|N1Sel)\b", code):
                     bad.append("%s:%d: %s" % (os.path.basename(path), no, code.strip()))
     assert not bad, "\n".join(bad)
+
+
+def test_the_ablation_mask_exists_only_in_a_build_that_defines_adp_ablate():
+    """`ADP_ABLATE` skips parts of hot kernels for timing experiments and the rows are wrong when it is set: the product neither has the
+    device mask nor reads the variable.  In adapted_amd/csrc every line that names `g_ablate` or reads `ADP_ABLATE` from the environment
+    lies between an `#ifdef ADP_ABLATE` and its `#else` / `#endif`, and the product's flags do not define the macro."""
+    import glob
+
+    from adapted_amd import build
+
+    root = os.path.join(ROOT, "adapted_amd", "csrc")
+    bad, inside = [], 0
+    for path in sorted(glob.glob(os.path.join(root, "*"))):
+        stack = []  # one entry per open conditional: does its current branch belong to the ADP_ABLATE build?
+        with open(path) as fh:
+            for no, line in enumerate(fh, 1):
+                word = re.match(r"\s*#\s*(ifdef|ifndef|if|else|elif|endif)\b\s*(\w*)", line)
+                if word and word.group(1) in ("ifdef", "ifndef", "if"):
+                    stack.append(word.group(1) == "ifdef" and word.group(2) == "ADP_ABLATE")
+                elif word and word.group(1) in ("else", "elif"):
+                    stack[-1] = False
+                elif word:
+                    stack.pop()
+                if re.search(r'\bg_ablate\b|"ADP_ABLATE"', line):
+                    inside += any(stack)
+                    if not any(stack):
+                        bad.append("%s:%d: %s" % (os.path.basename(path), no, line.strip()))
+        assert not stack, path
+    assert not bad, "\n".join(bad)
+    assert inside >= 3  # (the mask's declaration, its definition and the read of the variable: the search does find them)
+    assert not any("ADP_ABLATE" in f for f in build.FLAGS)

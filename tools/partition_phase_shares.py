@@ -1,7 +1,8 @@
 """Shares of k_partition_stats' phases (pass A, bucket search / MAD prediction, pass B, median, MAD selection) from the cycle
 tallies of a -DADP_PHASE_TIMING build of the library:
 
-    hipcc <flags of adapted_amd/build.py> -DADP_PHASE_TIMING -o /tmp/phase.so adapted_amd/csrc/adapted_hip.hip
+    hipcc <flags of adapted_amd/build.py> -DADP_PHASE_TIMING -Iinclude -Iadapted_amd/csrc -o /tmp/phase.so \
+        adapted_amd/csrc/adapted_hip.hip adapted_amd/csrc/modules.hip
     ADAPTED_HIP_LIB=/tmp/phase.so python tools/partition_phase_shares.py [pareto | default]
 """
 import sys, numpy as np
