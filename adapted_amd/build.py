@@ -19,7 +19,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))
-                  + [os.path.join(ROOT, "include", "adapted_hip.h")])
+                  + glob.glob(os.path.join(ROOT, "include", "*.h")))
 
 
 STAMP = LIB + ".sources.sha256"  # digest of the sources the library was built from (travels with it; not in git)

@@ -165,6 +165,12 @@ StreamingConfig = _make("streaming", SECTIONS["streaming"])
 CNNBoundariesConfig = _make("cnn_boundaries", SECTIONS["cnn_boundaries"])
 MedShiftConfig = _make("med_shift", SECTIONS["med_shift"])
 RNAStartPeakConfig = _make("rna_start_peak", SECTIONS["rna_start_peak"])
+# moving_mean_adapter_start_detect's parameters (adapted_amd/detect/adapter_start.py).  As in the reference the class stands alone:
+# no section of SigProcConfig, not read from or written to TOML
+MMAdapterStartConfig = _make("mm_adapter_start", [
+    ("detect_adapter_start", bool, False), ("window", int, 100), ("min_obs_adapter", int, 2500), ("min_shift", float, 20.0),
+    ("min_pA_current", float, 90.0),
+])
 
 SECTION_CLASSES = {
     "core": CoreConfig, "llr_boundaries": LLRBoundariesConfig, "mvs_polya": MVSPolyAConfig,

@@ -17,7 +17,7 @@ from typing import Any, Dict, Optional
 
 from . import toml_io
 from .schema import (PRESETS, SECTION_CLASSES, SPEEDS, CNNBoundariesConfig, CoreConfig,
-                     LLRBoundariesConfig, MedShiftConfig, MVSPolyAConfig, RealRangeConfig,
+                     LLRBoundariesConfig, MedShiftConfig, MMAdapterStartConfig, MVSPolyAConfig, RealRangeConfig,  # noqa: F401
                      RNAStartPeakConfig, StreamingConfig, _Section)
 from .._version import __version__
 

@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak and the adapter start): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "trace_peaks_api.h"
 #include "mvs_api.h"
 #include "sigstats_api.h"
+#include "startmods_api.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -691,6 +692,73 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
     HIPCHK(hipGetLastError());
     RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
     RCCHK(d2h(h, count_out, dcnt, ns * 24));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// ---- the reference's start-peak and adapter-start modules (adapted/detect/start_peak.py, adapter_start.py; startmods_api.h)
+
+int adp_sizeof_start_peak_args(void) { return (int)sizeof(adp_start_peak_args); }
+int adp_sizeof_adapter_start_args(void) { return (int)sizeof(adp_adapter_start_args); }
+
+int adp_start_peak(adp_handle *h, const void *sig, const int32_t *full_len, int n_reads, int m, const adp_start_peak_args *args,
+                   int flags, int32_t *info_out, double *vals_out)
+{
+    if (!h || !sig || !full_len || !args || !info_out || !vals_out || n_reads < 1 || m < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!all_in<int32_t>(full_len, n_reads, 0, INT32_MAX)) { g_err = "need full_len >= 0 for every read"; return ADP_ERR_INVALID; }
+    if (args->downscale_factor < 1) { g_err = "downscale_factor must be >= 1"; return ADP_ERR_INVALID; }
+    if (args->offset1 < 0 || args->offset2 < 0 || args->start_peak_max_idx < 0) { g_err = "offset1, offset2 and start_peak_max_idx must be >= 0"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, esz = f64 ? 8 : 4;
+    void *s_sig; int32_t *dlen, *dinfo; double *dvals;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)m * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dinfo = w.take<int32_t>(n * 5); dvals = w.take<double>(n * 2);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)m * esz * n, &ds));
+    RCCHK(h2d(h, dlen, full_len, n * 4));
+    // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
+    const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
+    { Scope s(h, "k_startpeak_mod");
+      if (f64) hipLaunchKernelGGL(k_startpeak_mod<double>, dim3(grid), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, m, *args, dinfo, dvals);
+      else hipLaunchKernelGGL(k_startpeak_mod<float>, dim3(grid), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, m, *args, dinfo, dvals); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, info_out, dinfo, n * 20));
+    RCCHK(d2h(h, vals_out, dvals, n * 16));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_adapter_start(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_adapter_start_args *args,
+                      int flags, int32_t *info_out, int64_t *out, int64_t *cand_out, double *diff_out)
+{
+    if (!h || !sig || !len || !args || !info_out || !out || !cand_out || !diff_out || n_reads < 1 || L < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
+    if (args->window < 1) { g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID; }
+    if (args->min_obs_adapter < 0) { g_err = "min_obs_adapter must be >= 0"; return ADP_ERR_INVALID; }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    // (a slot holds both series of one read, as the MVS series kernels' do: the same byte budget)
+    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
+    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dout, *dcand; double *ddiff;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dlen = w.take<int32_t>(n); dinfo = w.take<int32_t>(n * 4); dout = w.take<int64_t>(n); dcand = w.take<int64_t>(n); ddiff = w.take<double>(n);
+        scr = w.take<char>(slots * 2 * L * esz);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dlen, len, n * 4));
+    { Scope s(h, "k_adapter_start");
+      if (f64) hipLaunchKernelGGL(k_adapter_start<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, *args, (double *)scr, dinfo, dout, dcand, ddiff);
+      else hipLaunchKernelGGL(k_adapter_start<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, *args, (float *)scr, dinfo, dout, dcand, ddiff); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, info_out, dinfo, n * 16));
+    RCCHK(d2h(h, out, dout, n * 8));
+    RCCHK(d2h(h, cand_out, dcand, n * 8));
+    RCCHK(d2h(h, diff_out, ddiff, n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }

@@ -257,7 +257,7 @@ def load():
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
     try:
-        for name, proto in PROTOTYPES.items():
+        for name, proto in list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -266,7 +266,9 @@ def load():
     if (lib.adp_sizeof_cfg() != C.sizeof(AdpCfg) or lib.adp_sizeof_row() != ROW_DTYPE.itemsize
             or lib.adp_sizeof_peak_args() != C.sizeof(AdpPeakArgs) or lib.adp_sizeof_spike_args() != C.sizeof(AdpSpikeArgs)
             or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs) or lib.adp_sizeof_seg() != SEG_DTYPE.itemsize
-            or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)):
+            or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)
+            or lib.adp_sizeof_start_peak_args() != C.sizeof(AdpStartPeakArgs)
+            or lib.adp_sizeof_adapter_start_args() != C.sizeof(AdpAdapterStartArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     _LIB = lib
     return lib
@@ -306,6 +308,19 @@ class AdpRealRangeArgs(C.Structure):
     _fields_ = [(k, C.c_double * 2) for k in ("mean_start_range", "mean_end_range", "local_range")] + \
                [(k, C.c_int32) for k in ("mean_window", "max_obs_local_range")]
 
+
+class AdpStartPeakArgs(C.Structure):
+    """struct adp_start_peak_args (include/adapted_hip.h): the [rna_start_peak] parameters detect_rna_start_peak reads"""
+    _fields_ = [("open_pore_pa", C.c_double)] + [(k, C.c_int32) for k in ("downscale_factor", "start_peak_max_idx", "offset1", "offset2")]
+
+
+class AdpAdapterStartArgs(C.Structure):
+    """struct adp_adapter_start_args (include/adapted_hip.h): MMAdapterStartConfig's parameters"""
+    _fields_ = [(k, C.c_double) for k in ("min_shift", "min_pA_current")] + [(k, C.c_int32) for k in ("window", "min_obs_adapter")]
+
+
+# the chunk length of k_adapter_start's LDS staging (ASC_CHUNK, adapted_amd/csrc/startmods_api.h): its chains change path there
+ADAPTER_START_CHUNK = 512
 
 # struct adp_seg (include/adapted_hip.h): a segment signal[row, start:end] of a batch
 SEG_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("row", "<i4"), ("pad", "<i4")])
@@ -393,12 +408,21 @@ PROTOTYPES = {
     "adp_debug_log": "int: adp_handle* double* double* int",
 }
 EXPORTS = list(PROTOTYPES)
+# include/adapted_hip_startmods.h (the header adapted_hip.h includes for the start-peak and adapter-start modules), in the same
+# vocabulary; load() binds both tables, tests/test_startmods_module_cpu.py holds this one against its header
+MODULE_PROTOTYPES = {
+    "adp_sizeof_start_peak_args": "int:",
+    "adp_sizeof_adapter_start_args": "int:",
+    "adp_start_peak": "int: adp_handle* void* int32* int int adp_start_peak_args* int int32* double*",
+    "adp_adapter_start": "int: adp_handle* void* int32* int int adp_adapter_start_args* int int32* int64* int64* double*",
+}
 
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
 _RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
 _SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
 _POINTEES = {"adp_cfg": AdpCfg, "adp_trace_args": AdpTraceArgs, "adp_peak_args": AdpPeakArgs, "adp_spike_args": AdpSpikeArgs,
-            "adp_mvs_args": AdpMvsArgs, "adp_real_range_args": AdpRealRangeArgs, "adp_handle*": _VoidP, "void*": _VoidP,
+            "adp_mvs_args": AdpMvsArgs, "adp_real_range_args": AdpRealRangeArgs, "adp_start_peak_args": AdpStartPeakArgs,
+            "adp_adapter_start_args": AdpAdapterStartArgs, "adp_handle*": _VoidP, "void*": _VoidP,
             "char*": C.c_char_p}
 _ELEMENTS = {"float": np.float32, "double": np.float64, "int16": np.int16, "int32": np.int32, "int64": np.int64, "uint32": np.uint32,
              "uint64": np.uint64, "void": None, "adp_row": ROW_DTYPE, "adp_seg": SEG_DTYPE}
@@ -981,6 +1005,26 @@ class Engine:
             if cnt[:, 0].max() <= cap:
                 return pos, cnt
             cap = int(cnt[:, 0].max())
+
+    def start_peak(self, sig, full_lens, args: "AdpStartPeakArgs", n: Optional[int] = None, m: Optional[int] = None, f64: bool = False):
+        """adp_start_peak: signals float32 / float64 [n, m] (a device pointer: float64 with ``f64``), the full lengths (they may
+        exceed m) -> (info int32 [n, 5]: valid, start_peak_idx, next_greater_idx, open_pore_idx or -1, flagged type -- pooled
+        indices; vals float64 [n, 2]: start_peak_pa, next_greater_pa)"""
+        sig, flags, n, m, _ = self._sig_in(sig, n, m, f64)
+        info, vals = np.zeros((n, 5), dtype=np.int32), np.zeros((n, 2))
+        self._check(self.lib.adp_start_peak(self._h, sig, self._per_read(full_lens, n, "full_signal_lens"), n, m, C.byref(args), flags,
+                                            info, vals))
+        return info, vals
+
+    def adapter_start(self, sig, lens, args: "AdpAdapterStartArgs", n: Optional[int] = None, L: Optional[int] = None, f64: bool = False):
+        """adp_adapter_start -> (info int32 [n, 4]: status, the exception's window and slice size, accepted; adapter_start int64
+        [n]; cand int64 [n]; difference[cand] float64 [n])"""
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        info = np.zeros((n, 4), dtype=np.int32)
+        out, cand, diff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
+        self._check(self.lib.adp_adapter_start(self._h, sig, self._per_read(lens, n, "lens"), n, L, C.byref(args), flags, info, out,
+                                               cand, diff))
+        return info, out, cand, diff
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

@@ -479,6 +479,10 @@ int adp_real_range(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, double lo,
                    double hi, double min_obs_diff, int flags, int cap, int64_t *pos_out, int64_t *count_out);
 
+/* The reference's start-peak and adapter-start modules (adp_start_peak, adp_adapter_start): the part of this ABI that is declared
+ * in a header of its own, with its own prototype table in adapted_amd/lib.py (MODULE_PROTOTYPES). */
+#include "adapted_hip_startmods.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
