@@ -28,6 +28,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_topk.h"
 #include "cnn_conv.h"
 #include "cnn_conv_split.h"
+#include "cnn_fallback.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -334,20 +335,24 @@ static int env_int(const char *name, int dflt)
 // stream(s) drained): how much the call wanted; > capacity = lists were dropped: grow and tell the caller to run again.
 static int arena_begin(adp_handle *h)
 {
-    if (h->op_used.ensure(8) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    HIPCHK(hipMemsetAsync(h->op_used.p, 0, 8, h->stream)); // [0] arena words wanted, [1] the split conv stack's out-of-range flag
+    if (h->op_used.ensure(16) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    // [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read fallback
+    HIPCHK(hipMemsetAsync(h->op_used.p, 0, 16, h->stream));
     return 0;
 }
 // -> 0 done, 1 run the call again (arena grown), < 0 error
 // (cnn: the call ran the conv stack -- its out-of-range flag is read with the counter; set = repeat the call on the float32 kernels)
-static int arena_end(adp_handle *h, bool cnn = false)
+// (n_sel: the call ran k_cnn_fb_select -- its count comes with the same copy; left 0 when the call is to be repeated)
+static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr)
 {
     const bool conv_flag = cnn && h->cnn_mode == 1 && !h->cnn_redo_f32;
-    if (!h->cfg.detect_open_pores && !conv_flag) { h->op_last_used = 0; return 0; }
-    unsigned int w[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(w, h->op_used.p, 8, hipMemcpyDeviceToHost, h->stream));
+    if (n_sel) *n_sel = 0;
+    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel) { h->op_last_used = 0; return 0; }
+    unsigned int w[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(w, h->op_used.p, 12, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (conv_flag && w[1]) { h->cnn_redo_f32 = true; return 1; }
+    if (n_sel && (!h->cfg.detect_open_pores || (size_t)w[0] * 4 <= h->op_arena.cap)) *n_sel = w[2];
     if (!h->cfg.detect_open_pores) { h->op_last_used = 0; return 0; }
     const unsigned int used = w[0];
     h->op_last_used = used;
@@ -367,12 +372,19 @@ static int launch_cand_stats2(adp_handle *h, const float *sig, const int32_t *dl
     return 0;
 }
 
+// where a validation finds its candidates and leaves its rows: the handle's own buffers, unless the call still needs those
+// (the second phase of adp_detect_cnn, cnn_fallback_run)
+struct ValBufs { const int64_t *bounds; const int8_t *topk_none; adp_row *rows; };
+
 template <class SIG>
 static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int kmax, int mbsize,
-                           bool gate_mb)
+                           bool gate_mb, const ValBufs *vb = nullptr)
 {
+    const int64_t *bounds = vb ? vb->bounds : h->bounds.as<int64_t>();
+    adp_row *rows = vb ? vb->rows : h->rows.as<adp_row>();
+    if (vb && std::is_same<SIG, SigF32>::value) { g_err = "launch_validate: the float32 series kernels work on the handle's own bounds"; return ADP_ERR_INVALID; }
     ValidateInT<SIG> in;
-    in.sig = dsig; in.full_len = dlen; in.bounds = h->bounds.as<int64_t>(); in.topk_none = h->topk_none.as<int8_t>();
+    in.sig = dsig; in.full_len = dlen; in.bounds = bounds; in.topk_none = vb ? vb->topk_none : h->topk_none.as<int8_t>();
     in.kmax = kmax; in.n_reads = n; in.m = m; in.mbsize = mbsize;
     in.mbs = gate_mb ? h->mbs.as<MbState>() : nullptr;
     in.scratch = h->vscratch.as<float>(); in.scratch_stride = h->vstride;
@@ -417,7 +429,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
         }
         if (!piped) {
             Scope s(h, "k_mvs_series");
-            hipLaunchKernelGGL(k_mvs_series<SIG>, dim3((n + 63) / 64), dim3(64), 0, h->stream, dsig, dlen, n, m, h->bounds.as<int64_t>(), kmax, h->cfg,
+            hipLaunchKernelGGL(k_mvs_series<SIG>, dim3((n + 63) / 64), dim3(64), 0, h->stream, dsig, dlen, n, m, bounds, kmax, h->cfg,
                                h->series.as<float>(), cap, h->have_series.as<int8_t>());
         }
         if constexpr (std::is_same<SIG, SigF32>::value) {
@@ -444,12 +456,12 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     adp_handle *a = h->owner ? h->owner : h;
     in.op_arena = a->op_arena.as<int32_t>(); in.op_used = a->op_used.as<unsigned int>(); in.op_cap = (unsigned int)(a->op_arena.cap / 4);
     { Scope s(h, "k_validate");
-      hipLaunchKernelGGL(k_validate<SIG>, dim3(grid), dim3(64), 0, h->stream, in, h->cfg, h->rows.as<adp_row>(), h->preq.as<PartReq>()); }
+      hipLaunchKernelGGL(k_validate<SIG>, dim3(grid), dim3(64), 0, h->stream, in, h->cfg, rows, h->preq.as<PartReq>()); }
     { Scope s(h, "k_partition_stats");
       // (the kernel is a template on the workgroup size: 512 threads x 2 and 1024 x 1 per CU, and the second pass walking a segment from its
       // end, were measured and dropped in round 5 -- 28.2 / 38.5 against 24.5 ms; +-1 %: profiles/r05_tried_and_dropped.txt)
       hipLaunchKernelGGL((k_partition_stats<SIG, BS_THREADS, 5>), dim3(n), dim3(BS_THREADS), sizeof(BlockScratch), h->stream, dsig, m, h->preq.as<PartReq>(),
-                         h->rows.as<adp_row>()); }
+                         rows); }
     return 0;
 }
 
@@ -1258,7 +1270,7 @@ static int cnn_forward_split(adp_handle *h, adp_handle *wh, const float *prepare
         h->cnn_Lpad = Lrows; h->cnn_L1 = L1; h->cnn_chunk = (int)((h->cnn_act[0].cap - CNS_SLACK) / per_read); if (h->cnn_chunk > 65535) h->cnn_chunk = 65535;
     }
     C = h->cnn_chunk < n_reads ? h->cnn_chunk : n_reads;
-    if (wh->op_used.ensure(8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    if (wh->op_used.ensure(16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     int32_t *flag = wh->op_used.as<int32_t>() + 1;
     const float *W = wh->cnn_w.as<float>();
     const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
@@ -1385,7 +1397,7 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
     RCCHK(begin_call(h));
     h->cnn_redo_f32 = false;
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (h->op_used.ensure(8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        if (h->op_used.ensure(16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
         HIPCHK(hipMemsetAsync(h->op_used.as<int32_t>() + 1, 0, 4, h->stream));
         int rc = cnn_forward_dev(h, prepared, n_reads, Lc, scores_out);
         if (rc) return rc;
@@ -1402,9 +1414,12 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
 
 // combined_detect_cnn up to (not including) the short-read fallback: C1 prepare -> C2 conv stack -> C3 predict -> V1 with the
 // k candidates, enqueued on the handle's stream without waiting for anything on the host.  bounds_dst (may be NULL): int64
-// [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.
+// [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.  fb_select: the fallback's selection over these reads rides
+// directly behind the validation kernels, in front of the row copy (kernel after kernel: behind the copy it would wait for the
+// copy engine's signal and the host for the kernel's).
+static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride);
 static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
-                       int rows_kind, int64_t *bounds_dst, int bounds_kind)
+                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false)
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     const int Lc = (m - off + ds - 1) / ds, L1 = (Lc - 1) / 3 + 1, Lo = 3 * L1 - 2;
@@ -1423,9 +1438,113 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     HIPCHK(hipMemsetAsync(h->topk_none.p, 0, (size_t)n_reads, st));
     rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, kk, n_reads, false);
     if (rc) return rc;
+    if (fb_select) RCCHK(cnn_fallback_select(h, dlen, n_reads, h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk));
     if (rows_dst) HIPCHK(hipMemcpyAsync(rows_dst, h->rows.p, (size_t)n_reads * sizeof(adp_row), (hipMemcpyKind)rows_kind, st));
     HIPCHK(hipGetLastError());
     return ADP_OK;
+}
+
+extern "C++" {
+__global__ void k_refine_out(const MbState *mbs, const int32_t *nvalid, const int32_t *polya_idx, const int64_t *ranges, int n,
+                             int ds, int64_t *out, int32_t *status)
+{
+    int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    int st = 0;
+    if (mbs[r].status == ADP_MB_MAD_ZERO) st = ADP_F_EXC_MAD_ZERO;
+    else if (nvalid[r] <= 0) st = ADP_F_EXC_EMPTY_TRACE;
+    int p = polya_idx[r];
+    out[r] = (st == 0 && p > 0) ? (int64_t)p * ds + ranges[2 * r] : 0;
+    status[r] = st;
+}
+
+// The fallback's chain (combined.py:258-301) over n reads, enqueued on the handle's stream (alloc_all(h, n, true) done): per-read
+// normalisation, the LLR trace (offsets 5/5) over [drng[2r], drng[2r+1]) and P4 on it -> dout[r] the new poly(A) end in samples or 0,
+// dstat[r] 0 or the ADP_F_EXC_* code of the exception the reference raises.  dlen, drng, dout, dstat: device arrays over the n reads.
+template <class SIG>
+static int refine_chain(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, const int64_t *drng, int64_t *dout, int32_t *dstat)
+{
+    hipStream_t st = h->stream;
+    if (h->mbs.ensure((size_t)n * sizeof(MbState)) || h->ghist.ensure((size_t)n * N1_BINS * 4) || h->gbelow.ensure((size_t)n * 8) || h->gcnt.ensure((size_t)n * 8 * N1_NCNT)) {
+        g_err = "device allocation failed"; return ADP_ERR_HIP;
+    }
+    MbState *mbs = h->mbs.as<MbState>();
+    HIPCHK(hipMemsetAsync(mbs, 0, (size_t)n * sizeof(MbState), st));
+    HIPCHK(hipMemsetAsync(h->ghist.p, 0, (size_t)n * N1_BINS * 4, st));
+    HIPCHK(hipMemsetAsync(h->gbelow.p, 0, (size_t)n * 8, st));
+    HIPCHK(hipMemsetAsync(h->adapter_idx.p, 0, (size_t)n * 4, st));
+    HIPCHK(hipMemsetAsync(h->gcnt.p, 0, (size_t)n * 8 * N1_NCNT, st));
+    { Scope s(h, "k_n1 (refine)");
+      int rc = launch_n1(h, dsig, n, m, h->T, 1, n, false); // per-read normalisation: every read is its own minibatch
+      if (rc) return rc; }
+    { Scope s(h, "k_norm_pool (refine)");
+      hipLaunchKernelGGL(k_norm_pool<SIG>, dim3(n), dim3(256), (size_t)NP_TILE * h->ds * 4, st, dsig, m, h->T, h->off, h->ds, h->L, h->Lp, 1, mbs,
+                         h->down.as<float>(), h->nvalid.as<int32_t>(), drng, dlen); }
+    { Scope s(h, "k_gains (refine)");
+      launch_cumsum(h, n);
+      hipLaunchKernelGGL(k_gains<1>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
+                         h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), 1, mbs, h->trace.as<double>(),
+                         h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 1, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, (double *)nullptr, n, 5); }
+    { Scope s(h, "k_polya_peak (refine)");
+      launch_polya_peak(h, n, 1, nullptr); // (k_gains<1> lists no heights)
+      hipLaunchKernelGGL(k_refine_out, dim3((n + 255) / 256), dim3(256), 0, st, mbs, h->nvalid.as<int32_t>(), h->polya_idx.as<int32_t>(),
+                         drng, n, h->ds, dout, dstat); }
+    return 0;
+}
+} // extern "C++"
+
+// ---- the short-read fallback of combined_detect_cnn (combined.py:251-301) behind the first pass (cnn_fallback.h) -----------------
+static bool cnn_fallback_wanted(const adp_handle *h, int flags, const adp_row *rows_out)
+{
+    return (flags & ADP_CNN_FALLBACK) && h->cfg.fallback_to_llr_short_reads && rows_out;
+}
+// rows / bounds: the CALL's device row buffer and predictions (int64 [n, bstride]) once every read's first pass is in them.
+// Enqueues the selection on the handle's stream; the count reaches the host in arena_end's copy.
+static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride)
+{
+    if (h->fb_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    Scope s(h, "k_cnn_fb_select");
+    hipLaunchKernelGGL(k_cnn_fb_select, dim3(1), dim3(FB_SEL_THREADS), 0, h->stream, rows, bounds, bstride, dlen, n, 2ll * h->cfg.max_obs_adapter,
+                       h->fb_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 2);
+    return 0;
+}
+
+// The second phase over the n_sel selected reads, enqueued on the handle's stream: the chain, the re-validation (k = 1,
+// polya_end_topk given) and the merge into `rows`.  The selected signal rows are read where they lie (SigIdx); the re-validated
+// rows and their candidates have buffers of their own -- the handle's hold the first pass (launch_validate's ValBufs).  Open-pore
+// lists of re-validated rows go to the same arena of the call: the caller looks at its counter once more.
+static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dlen, int m, adp_row *rows, const int64_t *bounds, int bstride, int n_sel)
+{
+    hipStream_t st = h->stream;
+    int rc = alloc_all(h, n_sel, true);
+    if (rc) return rc;
+    const size_t N = (size_t)n_sel;
+    // ranges 16 N | new poly(A) ends 8 N | bounds of the re-validation 16 N | status 4 N | full_len 4 N | counts 8 | topk_none N
+    if (h->fb_ws.ensure(N * 49 + 8) || h->fb_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    int64_t *drng = h->fb_ws.as<int64_t>(), *dout = drng + 2 * N, *db2 = dout + N;
+    int32_t *dstat = reinterpret_cast<int32_t *>(db2 + 2 * N), *dlen_sub = dstat + N;
+    unsigned int *counts = reinterpret_cast<unsigned int *>(dlen_sub + N);
+    int8_t *topk = reinterpret_cast<int8_t *>(counts + 2);
+    const int32_t *sel = h->fb_sel.as<int32_t>();
+    const SigIdx sig{dsig, sel};
+    HIPCHK(hipMemsetAsync(counts, 0, 8 + N, st)); // (both counts and topk_none: polya_end_topk is given)
+    { Scope s(h, "k_cnn_fb_gather");
+      hipLaunchKernelGGL(k_cnn_fb_gather, dim3((n_sel + 255) / 256), dim3(256), 0, st, sel, n_sel, 0, bounds, bstride, dlen, dlen_sub, drng,
+                         (const int64_t *)nullptr, (const int32_t *)nullptr, (int64_t *)nullptr); }
+    rc = refine_chain(h, sig, dlen_sub, n_sel, m, drng, dout, dstat);
+    if (rc) return rc;
+    { Scope s(h, "k_cnn_fb_gather");
+      hipLaunchKernelGGL(k_cnn_fb_gather, dim3((n_sel + 255) / 256), dim3(256), 0, st, sel, n_sel, 1, bounds, bstride, dlen, dlen_sub, drng,
+                         (const int64_t *)dout, (const int32_t *)dstat, db2); }
+    const ValBufs vb{db2, topk, h->fb_rows.as<adp_row>()};
+    rc = launch_validate(h, sig, dlen_sub, n_sel, m, 1, n_sel, false, &vb);
+    if (rc) return rc;
+    { Scope s(h, "k_cnn_fb_merge");
+      hipLaunchKernelGGL(k_cnn_fb_merge, dim3(n_sel), dim3(64), 0, st, sel, n_sel, (const int64_t *)dout, (const int32_t *)dstat,
+                         (const adp_row *)h->fb_rows.as<adp_row>(), rows, counts); }
+    h->fb_counts = counts;
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // Chunks of whole minibatches over two lanes, free-running: while one lane's chunk is in the conv stack (matrix cores, one
@@ -1439,8 +1558,11 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     const int G = (n_mb + mb_per_group - 1) / mb_per_group;
     const int k = h->cfg.polya_cand_k, kk = k < 1 ? 1 : k;
     const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    // the fallback runs once on this handle, over the call's device row buffer, when all lanes have drained: it needs the
+    // predictions of all reads here whether the caller wants them or not
+    const bool fb = cnn_fallback_wanted(h, flags, rows_out);
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
-    if ((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || (bounds_out && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8))) {
+    if ((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || ((bounds_out || fb) && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8))) {
         g_err = "device allocation failed"; return ADP_ERR_HIP;
     }
     adp_handle *lanes[ADP_MAX_LANES];
@@ -1450,7 +1572,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
         lanes[i]->prof.clear(); lanes[i]->ev_used = 0;
     }
     adp_row *rows_dev = rows_out ? (out_dev ? rows_out : h->rows.as<adp_row>()) : nullptr;
-    int64_t *bounds_dev = bounds_out ? h->bounds.as<int64_t>() : nullptr;
+    int64_t *bounds_dev = (bounds_out || fb) ? h->bounds.as<int64_t>() : nullptr;
     for (int attempt = 0; attempt < 3; attempt++) {
         int rc = arena_begin(h);
         if (rc) return rc;
@@ -1465,11 +1587,21 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
-        rc = arena_end(h, true);
+        if (fb) RCCHK(cnn_fallback_select(h, dlen, n, rows_dev, bounds_dev, 1 + kk));
+        unsigned int n_sel = 0;
+        rc = arena_end(h, true, fb ? &n_sel : nullptr);
         if (rc < 0) return rc;
+        h->fb_n_sel = n_sel; h->fb_counts = nullptr;
+        if (rc == 0 && n_sel) {
+            RCCHK(cnn_fallback_run(h, dsig, dlen, m, rows_dev, bounds_dev, 1 + kk, (int)n_sel));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = arena_end(h);
+            if (rc < 0) return rc;
+        }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
         for (int i = 0; i < n_lanes; i++) { lanes[i]->prof.clear(); lanes[i]->ev_used = 0; }
+        h->prof.clear(); h->ev_used = 0;
     }
     if (rows_out && !out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
     if (bounds_out) HIPCHK(hipMemcpyAsync(bounds_out, h->bounds.p, (size_t)n * (1 + kk) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1477,8 +1609,8 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     return ADP_OK;
 }
 
-// combined_detect_cnn up to its short-read fallback in one call.  bounds_out (host, may be NULL): int64 [n, 1 + max(k, 1)], what
-// cnn_detect returns.
+// combined_detect_cnn in one call: up to its short-read fallback, or with ADP_CNN_FALLBACK (and cfg.fallback_to_llr_short_reads)
+// the whole of it.  bounds_out (host, may be NULL): int64 [n, 1 + max(k, 1)], what cnn_detect returns.
 int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
                    adp_row *rows_out, int64_t *bounds_out)
 {
@@ -1488,6 +1620,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     if (m <= h->cfg.min_obs_adapter) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
     h->cnn_redo_f32 = false;
+    h->fb_n_sel = 0; h->fb_counts = nullptr;
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -1514,33 +1647,37 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         if (G < n_lanes) n_lanes = G;
         if (G >= 2) return cnn_grouped(h, dsig, dlen, n_reads, m, minibatch, flags, rows_out, bounds_out, per, n_lanes);
     }
+    // The fallback: the selection rides behind the first pass and its count comes back with the arena counter at the call's one
+    // synchronisation point -- a call without selected reads (every call over full-length reads) ends there, its rows delivered
+    // as before.  Otherwise the second phase follows and the merged rows are delivered over the first ones.  Its re-validated rows
+    // append to the call's arena; a read's open-pore list depends on its adapter end alone, so the second phase wants at most what
+    // the first one did and an arena grown for the first (to twice its demand) holds both: three attempts are still enough.
+    const bool fb = cnn_fallback_wanted(h, flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    const int kk = h->cfg.polya_cand_k < 1 ? 1 : h->cfg.polya_cand_k; // (the stride of the predictions, as cnn_predict_dev lays them out)
     for (int attempt = 0; attempt < 3; attempt++) {
         rc = arena_begin(h);
         if (rc) return rc;
-        rc = cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, (flags & ADP_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         bounds_out, hipMemcpyDeviceToHost);
+        rc = cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                         bounds_out, hipMemcpyDeviceToHost, fb);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
-        rc = arena_end(h, true);
+        unsigned int n_sel = 0;
+        rc = arena_end(h, true, fb ? &n_sel : nullptr);
         if (rc < 0) return rc;
+        h->fb_n_sel = n_sel; h->fb_counts = nullptr;
+        if (rc == 0 && n_sel) {
+            // (device rows: merged where the caller has them; host rows: merged in the handle's buffer and delivered again)
+            RCCHK(cnn_fallback_run(h, dsig, dlen, m, out_dev ? rows_out : h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk, (int)n_sel));
+            if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = arena_end(h);
+            if (rc < 0) return rc;
+        }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
         reset_profile(h);
     }
     return ADP_OK;
-}
-
-__global__ void k_refine_out(const MbState *mbs, const int32_t *nvalid, const int32_t *polya_idx, const int64_t *ranges, int n,
-                             int ds, int64_t *out, int32_t *status)
-{
-    int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    int st = 0;
-    if (mbs[r].status == ADP_MB_MAD_ZERO) st = ADP_F_EXC_MAD_ZERO;
-    else if (nvalid[r] <= 0) st = ADP_F_EXC_EMPTY_TRACE;
-    int p = polya_idx[r];
-    out[r] = (st == 0 && p > 0) ? (int64_t)p * ds + ranges[2 * r] : 0;
-    status[r] = st;
 }
 
 int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *full_len, int n, int m, const int64_t *ranges,
@@ -1555,29 +1692,13 @@ int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *ful
     hipStream_t st = h->stream;
     rc = alloc_all(h, n, true);
     if (rc) return rc;
-    if (h->mbs.ensure((size_t)n * sizeof(MbState)) || h->ghist.ensure((size_t)n * N1_BINS * 4) || h->gbelow.ensure((size_t)n * 8) || h->gcnt.ensure((size_t)n * 8 * N1_NCNT) ||
-        h->bounds_stage.ensure((size_t)n * 16 + (size_t)n * 12)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    if (h->bounds_stage.ensure((size_t)n * 16 + (size_t)n * 12)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     int64_t *drng = h->bounds_stage.as<int64_t>();
     int64_t *dout = drng + 2 * (size_t)n;
     int32_t *dstat = reinterpret_cast<int32_t *>(dout + n);
     HIPCHK(hipMemcpyAsync(drng, ranges, (size_t)n * 16, (flags & ADP_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    MbState *mbs = h->mbs.as<MbState>();
-    HIPCHK(hipMemsetAsync(mbs, 0, (size_t)n * sizeof(MbState), st));
-    HIPCHK(hipMemsetAsync(h->ghist.p, 0, (size_t)n * N1_BINS * 4, st));
-    HIPCHK(hipMemsetAsync(h->gbelow.p, 0, (size_t)n * 8, st));
-    HIPCHK(hipMemsetAsync(h->adapter_idx.p, 0, (size_t)n * 4, st));
-    HIPCHK(hipMemsetAsync(h->gcnt.p, 0, (size_t)n * 8 * N1_NCNT, st));
-    rc = launch_n1(h, SigF32{dsig}, n, m, h->T, 1, n, false); // per-read normalisation: every read is its own minibatch
+    rc = refine_chain(h, SigF32{dsig}, dlen, n, m, drng, dout, dstat);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_norm_pool<SigF32>, dim3(n), dim3(256), (size_t)NP_TILE * h->ds * 4, st, SigF32{dsig}, m, h->T, h->off, h->ds, h->L, h->Lp, 1, mbs,
-                       h->down.as<float>(), h->nvalid.as<int32_t>(), (const int64_t *)drng, dlen);
-    launch_cumsum(h, n);
-    hipLaunchKernelGGL(k_gains<1>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
-                       h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), 1, mbs, h->trace.as<double>(),
-                       h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 1, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, (double *)nullptr, n, 5);
-    launch_polya_peak(h, n, 1, nullptr); // (k_gains<1> lists no heights)
-    hipLaunchKernelGGL(k_refine_out, dim3((n + 255) / 256), dim3(256), 0, st, mbs, h->nvalid.as<int32_t>(), h->polya_idx.as<int32_t>(),
-                       (const int64_t *)drng, n, h->ds, dout, dstat);
     HIPCHK(hipMemcpyAsync(polya_out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(status_out, dstat, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipGetLastError());
@@ -1781,6 +1902,11 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
     case 5: src = h->polya_idx.p; break;
     case 6: { int32_t lp = h->Lp; if (bytes < 4) return ADP_ERR_INVALID; memcpy(host_out, &lp, 4); return ADP_OK; }
     case 7: src = h->t1.p; break;
+    case 10: { // the last adp_detect_cnn call's fallback: reads selected, exception rows made, rows re-validated
+        if (bytes < 12) return ADP_ERR_INVALID;
+        int32_t c[3] = {(int32_t)h->fb_n_sel, 0, 0};
+        if (h->fb_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->fb_counts, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;
               HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg), bytes, 0, hipMemcpyDeviceToHost));

@@ -194,6 +194,15 @@ struct SigI16 {
     }
     __device__ __forceinline__ bool vec_ok(int m) const { return (m & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 7) == 0; }
 };
+// a SUBSET of resident float32 rows, read in place: row j of the subset is row idx[j] of the matrix (the CNN path's short-read
+// fallback, cnn_fallback.h: per-read arrays of such a launch -- full_len, ranges, bounds -- are indexed by j)
+struct SigIdx {
+    typedef RowF32 Row;
+    const float *base;
+    const int32_t *idx;
+    __device__ __forceinline__ Row row(long long j, int m) const { return Row{(const GLB float *)base + (size_t)idx[j] * m}; }
+    __device__ __forceinline__ bool vec_ok(int m) const { return (m & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0; }
+};
 // plain float arrays (series, pooled values, copies) go through the same helpers as rows
 // x[i] if ok, else some valid element's value or 0 (the caller does not use it): the load pattern each row type is fastest with
 static __device__ __forceinline__ float ld_if(const RowF32 &x, long long i, bool ok) { return ok ? x.p[i] : 0.f; }

@@ -74,6 +74,11 @@ struct adp_handle {
     // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
     DevBuf ws;              // the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): one call's staging and scratch (ws_carve)
+    // the CNN path's short-read fallback (cnn_fallback.h): the selected reads' indices [reads of the call]; the per-subset arrays
+    // of its chain and re-validation (carved by cnn_fallback_run) and the re-validated rows [selected reads]
+    DevBuf fb_sel, fb_ws, fb_rows;
+    unsigned int fb_n_sel = 0;              // reads the last adp_detect_cnn call selected
+    unsigned int *fb_counts = nullptr;      // device: [0] exception rows made, [1] rows re-validated by that call (null: it ran no second phase)
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;

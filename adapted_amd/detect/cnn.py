@@ -3,8 +3,11 @@
 Everything numeric is the HIP library: ``prepare_data`` (pool + per-read median / MAD normalisation, C1), the conv net
 itself (C2: hand-written, the two 64 -> 64 layers on the float32 matrix cores -- adapted_amd/csrc/cnn_conv.h), ``cnn_predict``
 (C3: both arg-maxes, scipy's find_peaks(distance=5) on the flattened scores, the per-read top-k and the reference's
-row-compaction quirk -- adapted_amd/csrc/cnn_topk.h) and the candidate validation loop (V1 with k candidates).  The product
-path (``detect_rows`` / ``detect_rows_device``) is ONE library call, ``adp_detect_cnn``, plus the rare short-read fallback.
+row-compaction quirk -- adapted_amd/csrc/cnn_topk.h), the candidate validation loop (V1 with k candidates) and the short-read
+fallback (C4: selection, the LLR chain and the re-validation on the rows where they lie -- adapted_amd/csrc/cnn_fallback.h).  The
+product path (``detect_rows`` / ``detect_rows_device``) is ONE library call, ``adp_detect_cnn`` with ``ADP_CNN_FALLBACK``: no
+host work behind it.  ``fallback="host"`` is the same fallback applied by the caller (three more library calls and the affected
+reads over PCIe): what ``conv="torch"`` uses, and the yardstick of tests/test_gpu_cnn_fallback.py -- the rows are the same.
 PyTorch is optional: ``load_cnn_model`` returns the reference's ``nn.Sequential`` (state-dict compatible), and
 ``conv="torch"`` runs the conv stack through PyTorch-ROCm / MIOpen instead (kept as the float32 cross-check of C2; the
 hand-written stack is 3.4x faster at the 200 k window).
@@ -190,12 +193,22 @@ def _need_fallback(rows, bounds, lens, spc):
                           & (pe - ae > 1000) & (np.asarray(lens).astype(np.int64) < 2 * spc.core.max_obs_adapter))
 
 
-def detect_rows_device(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None) -> np.ndarray:
-    """combined_detect_cnn over a DEVICE-resident batch (pointers) -> adp_row[]; ONE library call (adp_detect_cnn); the
-    short-read fallback needs the host copy of the few affected reads only.  minibatch: reads per call of the reference
-    (its find_peaks and row compaction work on one minibatch); default: the whole batch."""
+def _fallback_mode(fallback: str) -> str:
+    if fallback not in ("device", "host"):
+        raise ValueError('fallback must be "device" or "host"')
+    return fallback
+
+
+def detect_rows_device(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
+                       fallback: str = "device") -> np.ndarray:
+    """combined_detect_cnn over a DEVICE-resident batch (pointers) -> adp_row[]; ONE library call (adp_detect_cnn), the
+    short-read fallback included.  minibatch: reads per call of the reference (its find_peaks and row compaction work on one
+    minibatch); default: the whole batch.  fallback = "host": the fallback applied here instead, on host copies of the
+    affected reads (same rows)."""
     ensure_weights(eng, model, spc)
     m = eng.m
+    if _fallback_mode(fallback) == "device":
+        return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True)[0]
     rows, bounds = eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True)
     if spc.cnn_boundaries.fallback_to_llr_short_reads:
         idx = _need_fallback(rows, bounds, lens_host, spc)
@@ -220,12 +233,16 @@ def _apply_fallback(eng, rows, idx, sig_sub, lens_sub, bounds, spc):
         rows[ii] = eng.validate_rows(sig_sub[redo], lens_sub[redo], len(ii), b2)
 
 
-def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip") -> np.ndarray:
+def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
     """combined_detect_cnn over one batch -> adp_row[] (reference adapted/detect/combined.py:230-309).
-    conv = "torch": the conv stack through PyTorch-ROCm instead of the library's own (cross-check)."""
+    conv = "torch": the conv stack through PyTorch-ROCm instead of the library's own (cross-check; its fallback is the host's).
+    fallback = "host": the short-read fallback applied here, behind the library call, instead of inside it (same rows)."""
     n = sig.shape[0]
     if int(spc.cnn_boundaries.polya_cand_k) < 1:
         raise ValueError("polya_cand_k must be >= 1")
+    if conv == "hip" and _fallback_mode(fallback) == "device":
+        ensure_weights(eng, model, spc)
+        return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True)[0]
     if conv == "hip":
         ensure_weights(eng, model, spc)
         rows, bounds = eng.detect_cnn_rows(sig, lens, n, n)

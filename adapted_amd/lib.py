@@ -24,6 +24,7 @@ MAX_CAND = 16
 MAX_OPEN_PORES = 16
 
 ADP_IN_DEVICE, ADP_OUT_DEVICE, ADP_WITH_START_PEAK, ADP_TOPK_NONE, ADP_BOUNDS_HOST, ADP_TAILS_NAN = 1, 2, 4, 8, 16, 32
+ADP_CNN_FALLBACK = 1 << 17  # adp_detect_cnn: the short-read LLR fallback inside the call
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
 COLS = ["signal_len", "preloaded", "adapter_start", "adapter_end", "adapter_len", "adapter_mean",
@@ -1041,9 +1042,13 @@ class Engine:
         return out
 
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
-                        want_bounds: bool = True):
-        """combined_detect_cnn without the short-read fallback -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k])"""
+                        want_bounds: bool = True, fallback: bool = False):
+        """combined_detect_cnn -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k]).  fallback: with the short-read
+        fallback applied on the device (ADP_CNN_FALLBACK; where the configuration has it on); without it the rows are those in
+        front of the fallback.  bounds: what cnn_detect returned, either way."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
+        if fallback:
+            flags |= ADP_CNN_FALLBACK
         k = max(1, int(self.cfg.polya_cand_k))
         bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
         rows, rows_arg, out_flag = self._out(rows_dev, n)
@@ -1113,6 +1118,12 @@ class Engine:
         a = np.zeros(shp, dtype=dt)
         self._check(self.lib.adp_debug_fetch(self._h, what, a, a.nbytes))
         return a
+
+    def debug_cnn_fallback(self):
+        """the fallback of the last detect_cnn_rows call: (reads selected, exception rows made, rows re-validated)"""
+        a = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.adp_debug_fetch(self._h, 10, a, a.nbytes))
+        return tuple(int(v) for v in a)
 
     def debug_counters(self, n: int = 8):
         a = np.zeros(n, dtype=np.uint64)

@@ -13,8 +13,9 @@
  *                              c_llr_trace :202-236, c_llr_trace_gains :176-199, _gains :67-88
  *   adp_detect_start_peak   <- combined_detect_start_peak(...)   adapted/detect/combined.py:312-355
  *                              (detect_rna_start_peak, adapted/detect/start_peak.py:7-119)
- *   adp_detect_cnn          <- combined_detect_cnn(...)          adapted/detect/combined.py:230-250 (up to its short-read
- *                              fallback :251-301 = adp_llr_refine_polya + adp_validate_candidates)
+ *   adp_detect_cnn          <- combined_detect_cnn(...)          adapted/detect/combined.py:230-309 (with ADP_CNN_FALLBACK; without
+ *                              the flag up to its short-read fallback :251-301, which callers then apply themselves with
+ *                              adp_llr_refine_polya + adp_validate_candidates)
  *   adp_cnn_prepare         <- prepare_data(...)                 adapted/detect/cnn.py:70-82
  *   adp_cnn_forward         <- BoundariesCNN.forward / cnn_score adapted/detect/cnn.py:16-52, 85-98 (hand-written conv
  *                              stack; default: float16 matrix cores on split float32 operands at float32 accuracy,
@@ -70,6 +71,8 @@ extern "C" {
 #define ADP_TAILS_NAN 32           /* adp_detect_llr: the caller guarantees that row r is NaN from min(full_len[r], m) on (the
                                       padding of adapted/file_proc.py:170-174): the streaming passes then stop at the read's
                                       end instead of reading the padding.  Without the flag the rows are taken as they are. */
+#define ADP_CNN_FALLBACK (1 << 17)  /* adp_detect_cnn: apply the short-read LLR fallback (adapted/detect/combined.py:251-301) inside the
+                                      call, where cfg.fallback_to_llr_short_reads is set: the rows are combined_detect_cnn's */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -235,9 +238,17 @@ int adp_cnn_predict(adp_handle *h, const float *scores_dev, int n_reads, int min
  * All n reads are one minibatch. */
 int adp_cnn_topk(adp_handle *h, const float *scores_dev, const int64_t *adapter_pos_dev, const int64_t *polya_pos_dev,
                  int n_reads, int Lo, int k, int32_t *cand_out, int32_t *n_peaks_out);
-/* combined_detect_cnn (adapted/detect/combined.py:230-309) in one call, up to its short-read fallback (the caller applies
- * that with adp_llr_refine_polya + adp_validate_candidates, :251-301): prepare_data -> conv net -> cnn_predict -> the
- * validate_boundaries loop.  Needs adp_cnn_set_weights.  bounds_out (HOST, may be NULL) as adp_cnn_predict. */
+/* combined_detect_cnn (adapted/detect/combined.py:230-309) in one call: prepare_data -> conv net -> cnn_predict -> the
+ * validate_boundaries loop, and with ADP_CNN_FALLBACK in `flags` (and cfg.fallback_to_llr_short_reads != 0; rows_out given) its
+ * short-read fallback (:251-301) on the device.  A read takes the fallback when its first row failed without an exception code
+ * (ADP_F_IS_EXCEPTION), both of its predictions are > 0 and more than 1000 samples apart, and full_len < 2 * max_obs_adapter.
+ * For such a read the chain of adp_llr_refine_polya runs over [adapter_end, polya_end) of the resident row; an exception status
+ * (ADP_F_EXC_EMPTY_TRACE / ADP_F_EXC_MAD_ZERO) makes the row the all-None row with that fail_code; a new poly(A) end > 0 has
+ * the read validated again with (adapter_end, new polya_end), k = 1, and that row REPLACES the first one (also when it fails
+ * again); otherwise the first row stays.  Rows of both passes share the call's one open-pore arena.  Without the flag the call
+ * stops in front of the fallback (callers that apply it themselves with adp_llr_refine_polya + adp_validate_candidates).
+ * Needs adp_cnn_set_weights.  bounds_out (HOST, may be NULL) as adp_cnn_predict: what cnn_detect returned -- the fallback does
+ * not rewrite it. */
 int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
                    adp_row *rows_out, int64_t *bounds_out);
 /* Validate with explicit primary boundaries: bounds int64 [n_reads, 1 + k] = adapter_end, k poly(A)
@@ -495,7 +506,8 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *       8 process-wide tallies uint64[8..48] (cumulative): 0 large S1 segments, 1 MAD brackets that held, 2 generic median
  *         selections, 3 MADs not predicted, 4 MAD bracket overflows (0-4 are kept on 256 cache lines by workgroup and summed
  *         here: per-workgroup device atomics on one address serialise chip-wide), 5 single-pass N1 attempts, 6 / 7 their
- *         median / MAD misses, 22 / 23 N1 heavy keys / samples; the rest: phase cycles of -DADP_PHASE_TIMING builds */
+ *         median / MAD misses, 22 / 23 N1 heavy keys / samples; the rest: phase cycles of -DADP_PHASE_TIMING builds
+ *       10 int32[3], the fallback of the last adp_detect_cnn call: reads selected, exception rows made, rows re-validated */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
