@@ -144,7 +144,8 @@ def test_full_size_permutation_and_composition_properties():
 def test_quantised_signals_vs_oracle(oracle_mod, kind):
     """Calibrated int16 ADC data lie on a grid (~0.18 pA): thousands of samples share a value, the buckets and brackets of
     the exact selections overflow their lists and the tie paths take over (k_partition_stats: one-value bucket, key
-    counters; N1: the multi-pass selection).  Every field identical to the oracle at the full window size."""
+    counters; N1: the multi-pass selection).  Every field identical to the oracle at the full window size, and the kernel's
+    tallies of the one-value bucket (g_dbg[20]) and of the key counters (g_dbg[21]) say that those paths ran."""
     from adapted_amd import lib, synth
 
     spc = _spc200k()
@@ -162,8 +163,11 @@ def test_quantised_signals_vs_oracle(oracle_mod, kind):
         sig = (np.round(sig / q) * q).astype(np.float32)
         sig[:, :6000] += f32(0.0)  # (adapter / poly(A) compressed alike: most reads fail validation, the statistics are still exact)
     eng = lib.Engine(spc, n, m, device=0)
+    c0 = eng.debug_counters(22).copy()
     rows, mbs = eng.detect_llr_rows(sig, lens, n, n, with_start_peak=True)
+    c1 = eng.debug_counters(22)
     assert mbs[0] == 0
+    assert int(c1[20] + c1[21]) > int(c0[20] + c0[21]), (c0, c1)
     got = lib.rows_to_results(rows, "llr")
     want = oracle_mod.detect_llr(sig, lens, spc, with_start_peak=True)
     assert not _rows_equal(got, want), _rows_equal(got, want)[:10]
