@@ -29,6 +29,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_conv.h"
 #include "cnn_conv_split.h"
 #include "cnn_fallback.h"
+#include "cnn_second_opinion.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -336,23 +337,28 @@ static int env_int(const char *name, int dflt)
 static int arena_begin(adp_handle *h)
 {
     if (h->op_used.ensure(16) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    // [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read fallback
+    // [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read fallback,
+    // [3] reads selected for its LLR second opinion
     HIPCHK(hipMemsetAsync(h->op_used.p, 0, 16, h->stream));
     return 0;
 }
 // -> 0 done, 1 run the call again (arena grown), < 0 error
 // (cnn: the call ran the conv stack -- its out-of-range flag is read with the counter; set = repeat the call on the float32 kernels)
 // (n_sel: the call ran k_cnn_fb_select -- its count comes with the same copy; left 0 when the call is to be repeated)
-static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr)
+// (n_so: the same for k_cnn_so_select)
+static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr)
 {
     const bool conv_flag = cnn && h->cnn_mode == 1 && !h->cnn_redo_f32;
     if (n_sel) *n_sel = 0;
-    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel) { h->op_last_used = 0; return 0; }
-    unsigned int w[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(w, h->op_used.p, 12, hipMemcpyDeviceToHost, h->stream));
+    if (n_so) *n_so = 0;
+    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel && !n_so) { h->op_last_used = 0; return 0; }
+    unsigned int w[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(w, h->op_used.p, 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (conv_flag && w[1]) { h->cnn_redo_f32 = true; return 1; }
-    if (n_sel && (!h->cfg.detect_open_pores || (size_t)w[0] * 4 <= h->op_arena.cap)) *n_sel = w[2];
+    const bool arena_ok = !h->cfg.detect_open_pores || (size_t)w[0] * 4 <= h->op_arena.cap;
+    if (n_sel && arena_ok) *n_sel = w[2];
+    if (n_so && arena_ok) *n_so = w[3];
     if (!h->cfg.detect_open_pores) { h->op_last_used = 0; return 0; }
     const unsigned int used = w[0];
     h->op_last_used = used;
@@ -1416,10 +1422,11 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
 // k candidates, enqueued on the handle's stream without waiting for anything on the host.  bounds_dst (may be NULL): int64
 // [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.  fb_select: the fallback's selection over these reads rides
 // directly behind the validation kernels, in front of the row copy (kernel after kernel: behind the copy it would wait for the
-// copy engine's signal and the host for the kernel's).
+// copy engine's signal and the host for the kernel's).  so_select: the second opinion's selection, in the same place.
 static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride);
+static int cnn_second_select(adp_handle *h, int n, const adp_row *rows);
 static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
-                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false)
+                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false, bool so_select = false)
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     const int Lc = (m - off + ds - 1) / ds, L1 = (Lc - 1) / 3 + 1, Lo = 3 * L1 - 2;
@@ -1439,6 +1446,7 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, kk, n_reads, false);
     if (rc) return rc;
     if (fb_select) RCCHK(cnn_fallback_select(h, dlen, n_reads, h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk));
+    if (so_select) RCCHK(cnn_second_select(h, n_reads, h->rows.as<adp_row>()));
     if (rows_dst) HIPCHK(hipMemcpyAsync(rows_dst, h->rows.p, (size_t)n_reads * sizeof(adp_row), (hipMemcpyKind)rows_kind, st));
     HIPCHK(hipGetLastError());
     return ADP_OK;
@@ -1547,6 +1555,54 @@ static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dle
     return 0;
 }
 
+// ---- the LLR second opinion for reads the CNN path fails (ADP_CNN_SECOND_LLR, cnn_second_opinion.h) ------------------------------
+static bool cnn_second_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_CNN_SECOND_LLR) && rows_out; }
+// rows: the CALL's device row buffer once every read's row of the CNN path is in it (behind the first pass, and again behind the
+// fallback's merge when that ran).  The count reaches the host in arena_end's copy.
+static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
+{
+    if (h->so_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    Scope s(h, "k_cnn_so_select");
+    hipLaunchKernelGGL(k_cnn_so_select, dim3(1), dim3(SO_SEL_THREADS), 0, h->stream, rows, n, h->so_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 3);
+    return 0;
+}
+
+// The second opinion for the n_so selected reads, enqueued on the handle's stream.  The LLR primary is the LLR path's own up to
+// k_polya_peak (llr_enqueue, stage 7) over ALL n reads in their minibatches -- N1 and the minibatch status are those
+// adp_detect_llr computes -- with its boundaries in a buffer of this phase (the handle's bounds / topk_none / rows hold the CNN
+// path's).  The validation (k = 1) reads the selected rows in place and leaves its rows in so_rows; the merge copies those that
+// passed into `rows`.  Open-pore lists of the second rows append to the call's arena: the caller looks at its counter once more.
+static int cnn_second_run(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so)
+{
+    hipStream_t st = h->stream;
+    int rc = llr_enqueue(h, SigF32{dsig}, dlen, n, m, minibatch, flags & ADP_TAILS_NAN, nullptr, 0, nullptr, nullptr, 7, nullptr);
+    if (rc) return rc;
+    const size_t R = (size_t)n, N = (size_t)n_so;
+    // LLR bounds of all reads 16 R | bounds of the validation 16 N | full_len 4 N | counts 16 | topk_none of all reads R | of the subset N
+    if (h->so_ws.ensure(R * 17 + N * 21 + 16) || h->so_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    int64_t *ball = h->so_ws.as<int64_t>(), *b2 = ball + 2 * R;
+    int32_t *dlen_sub = reinterpret_cast<int32_t *>(b2 + 2 * N);
+    unsigned int *counts = reinterpret_cast<unsigned int *>(dlen_sub + N);
+    int8_t *tall = reinterpret_cast<int8_t *>(counts + 4), *tsub = tall + R;
+    const int32_t *sel = h->so_sel.as<int32_t>();
+    const MbState *mbs = h->mbs.as<MbState>();
+    HIPCHK(hipMemsetAsync(counts, 0, 16, st));
+    if (h->L > 0) // (else every minibatch is ADP_MB_EMPTY_TRACE: k_cnn_so_gather reads no bounds)
+        hipLaunchKernelGGL(k_llr_bounds, dim3((n + 255) / 256), dim3(256), 0, st, h->adapter_idx.as<int32_t>(), h->polya_idx.as<int32_t>(), n, h->ds,
+                           h->pos_off, ball, tall, 0);
+    { Scope s(h, "k_cnn_so_gather");
+      hipLaunchKernelGGL(k_cnn_so_gather, dim3((n_so + 255) / 256), dim3(256), 0, st, sel, n_so, minibatch, mbs, dlen, (const int64_t *)ball,
+                         (const int8_t *)tall, dlen_sub, b2, tsub); }
+    const ValBufs vb{b2, tsub, h->so_rows.as<adp_row>()};
+    rc = launch_validate(h, SigIdx{dsig, sel}, dlen_sub, n_so, m, 1, n_so, false, &vb);
+    if (rc) return rc;
+    { Scope s(h, "k_cnn_so_merge");
+      hipLaunchKernelGGL(k_cnn_so_merge, dim3(n_so), dim3(64), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)h->so_rows.as<adp_row>(), rows, counts); }
+    h->so_counts = counts;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // Chunks of whole minibatches over two lanes, free-running: while one lane's chunk is in the conv stack (matrix cores, one
 // wave per SIMD, little HBM traffic), the other's is in the candidate validation -- the moving-window recurrences (latency of one
 // wave's instruction stream, ~11 ms per launch whatever the number of reads), the order-statistics sweeps (HBM), the partition
@@ -1560,7 +1616,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
     // the fallback runs once on this handle, over the call's device row buffer, when all lanes have drained: it needs the
     // predictions of all reads here whether the caller wants them or not
-    const bool fb = cnn_fallback_wanted(h, flags, rows_out);
+    const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out);
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
     if ((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || ((bounds_out || fb) && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8))) {
         g_err = "device allocation failed"; return ADP_ERR_HIP;
@@ -1588,12 +1644,22 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
         if (fb) RCCHK(cnn_fallback_select(h, dlen, n, rows_dev, bounds_dev, 1 + kk));
-        unsigned int n_sel = 0;
-        rc = arena_end(h, true, fb ? &n_sel : nullptr);
+        if (so) RCCHK(cnn_second_select(h, n, rows_dev));
+        unsigned int n_sel = 0, n_so = 0;
+        rc = arena_end(h, true, fb ? &n_sel : nullptr, so ? &n_so : nullptr);
         if (rc < 0) return rc;
         h->fb_n_sel = n_sel; h->fb_counts = nullptr;
+        h->so_n_sel = 0; h->so_counts = nullptr;
         if (rc == 0 && n_sel) {
             RCCHK(cnn_fallback_run(h, dsig, dlen, m, rows_dev, bounds_dev, 1 + kk, (int)n_sel));
+            if (so) RCCHK(cnn_second_select(h, n, rows_dev)); // (the merge changed rows: select again)
+            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
+            if (rc < 0) return rc;
+        }
+        if (rc == 0 && n_so) {
+            h->so_n_sel = n_so;
+            RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows_dev, (int)n_so));
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h);
             if (rc < 0) return rc;
@@ -1621,6 +1687,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
     h->cnn_redo_f32 = false;
     h->fb_n_sel = 0; h->fb_counts = nullptr;
+    h->so_n_sel = 0; h->so_counts = nullptr;
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -1652,22 +1719,37 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     // as before.  Otherwise the second phase follows and the merged rows are delivered over the first ones.  Its re-validated rows
     // append to the call's arena; a read's open-pore list depends on its adapter end alone, so the second phase wants at most what
     // the first one did and an arena grown for the first (to twice its demand) holds both: three attempts are still enough.
-    const bool fb = cnn_fallback_wanted(h, flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    // The second opinion (ADP_CNN_SECOND_LLR) works the same way on the rows behind the fallback: its selection rides behind the
+    // first pass (and once more behind a fallback merge), its count comes back in the same copy, and a call whose reads all passed
+    // ends there.  Its rows' open-pore lists depend on the LLR adapter end: they may want more than the first pass did, and the
+    // counter is cumulative over the call -- attempt 1 can fall short in the first pass, attempt 2 in this phase, attempt 3 holds both.
+    const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
     const int kk = h->cfg.polya_cand_k < 1 ? 1 : h->cfg.polya_cand_k; // (the stride of the predictions, as cnn_predict_dev lays them out)
     for (int attempt = 0; attempt < 3; attempt++) {
         rc = arena_begin(h);
         if (rc) return rc;
         rc = cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         bounds_out, hipMemcpyDeviceToHost, fb);
+                         bounds_out, hipMemcpyDeviceToHost, fb, so);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
-        unsigned int n_sel = 0;
-        rc = arena_end(h, true, fb ? &n_sel : nullptr);
+        unsigned int n_sel = 0, n_so = 0;
+        rc = arena_end(h, true, fb ? &n_sel : nullptr, so ? &n_so : nullptr);
         if (rc < 0) return rc;
         h->fb_n_sel = n_sel; h->fb_counts = nullptr;
+        h->so_n_sel = 0; h->so_counts = nullptr;
+        // (device rows: merged where the caller has them; host rows: merged in the handle's buffer and delivered again)
+        adp_row *merged = out_dev ? rows_out : h->rows.as<adp_row>();
         if (rc == 0 && n_sel) {
-            // (device rows: merged where the caller has them; host rows: merged in the handle's buffer and delivered again)
-            RCCHK(cnn_fallback_run(h, dsig, dlen, m, out_dev ? rows_out : h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk, (int)n_sel));
+            RCCHK(cnn_fallback_run(h, dsig, dlen, m, merged, h->bounds.as<int64_t>(), 1 + kk, (int)n_sel));
+            if (so) RCCHK(cnn_second_select(h, n_reads, merged)); // (the merge changed rows: select again)
+            if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
+            if (rc < 0) return rc;
+        }
+        if (rc == 0 && n_so) {
+            h->so_n_sel = n_so;
+            RCCHK(cnn_second_run(h, dsig, dlen, n_reads, m, minibatch, flags, merged, (int)n_so));
             if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h);
@@ -1907,6 +1989,11 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         int32_t c[3] = {(int32_t)h->fb_n_sel, 0, 0};
         if (h->fb_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->fb_counts, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
+    case 11: { // the last adp_detect_cnn call's LLR second opinion: reads selected, rows replaced, re-validated and still failing, minibatches without one
+        if (bytes < 16) return ADP_ERR_INVALID;
+        int32_t c[4] = {(int32_t)h->so_n_sel, 0, 0, 0};
+        if (h->so_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->so_counts, 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        memcpy(host_out, c, 16); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;
               HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg), bytes, 0, hipMemcpyDeviceToHost));

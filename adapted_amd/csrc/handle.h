@@ -79,6 +79,11 @@ struct adp_handle {
     DevBuf fb_sel, fb_ws, fb_rows;
     unsigned int fb_n_sel = 0;              // reads the last adp_detect_cnn call selected
     unsigned int *fb_counts = nullptr;      // device: [0] exception rows made, [1] rows re-validated by that call (null: it ran no second phase)
+    // the CNN path's LLR second opinion (cnn_second_opinion.h): the failed reads' indices [reads of the call]; the LLR bounds of all
+    // reads and the per-subset arrays of the validation (carved by cnn_second_run); the second rows [selected reads]
+    DevBuf so_sel, so_ws, so_rows;
+    unsigned int so_n_sel = 0;              // reads the last adp_detect_cnn call selected for it
+    unsigned int *so_counts = nullptr;      // device: [0] rows replaced, [1] re-validated and still failing, [2] minibatches without one (null: none ran)
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;

@@ -257,6 +257,52 @@ def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = 
     return rows
 
 
+def _second_opinion_form(conv: str, fallback: str):
+    """the LLR second opinion runs inside adp_detect_cnn, behind the library's own conv stack and fallback: the host-side
+    variants of either have no such form"""
+    if conv != "hip":
+        raise ValueError('the LLR second opinion runs inside the library call: conv must be "hip"')
+    if _fallback_mode(fallback) != "device":
+        raise ValueError('the LLR second opinion runs inside the library call: fallback must be "device"')
+
+
+def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+    """detect_rows with the LLR second opinion (ADP_CNN_SECOND_LLR): a read whose row fails gets the row combined_detect_llr2
+    returns for it on this batch, where that row passes (``reserved_`` bit 0 marks it; lib.rows_to_results names its primary
+    columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call."""
+    _second_opinion_form(conv, fallback)
+    n = sig.shape[0]
+    if int(spc.cnn_boundaries.polya_cand_k) < 1:
+        raise ValueError("polya_cand_k must be >= 1")
+    ensure_weights(eng, model, spc)
+    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=True)[0]
+
+
+def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
+                                      fallback: str = "device") -> np.ndarray:
+    """detect_rows_device with the LLR second opinion, per minibatch as combined_detect_llr2 would see it (its normalisation is
+    the minibatch's).  ONE library call over the resident batch."""
+    _second_opinion_form("hip", fallback)
+    ensure_weights(eng, model, spc)
+    return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True, second_opinion=True)[0]
+
+
+def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0) -> List[DetectResults]:
+    """combined_detect_cnn, and for the reads it fails combined_detect_llr2 on the same batch where that passes (an extension;
+    such results carry ``llr_adapter_end`` / ``llr_polya_end`` instead of the ``cnn_*`` pair).  Always a list."""
+    from .combined import _as_batch, get_engine
+
+    sig, lens = _as_batch(batch_of_signals, full_signal_lens)
+    n, m = sig.shape
+    if n == 0:
+        return []
+    eng = get_engine(spc, n, m, device)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        rows = detect_rows_second_opinion(eng, sig, lens, model, spc)
+    return lib.rows_to_results(rows, "cnn", consume=True)
+
+
 def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
                         device: int = 0, conv: str = "hip") -> Union[List[DetectResults], DetectResults]:
     """model: the nn.Sequential of load_cnn_model, a dict of weight arrays (load_cnn_weights), or None (the config's model)"""

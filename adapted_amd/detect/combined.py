@@ -153,3 +153,11 @@ def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarr
     from . import cnn as _cnn
 
     return _cnn.combined_detect_cnn(batch_of_signals, full_signal_lens, model, spc, device=device, conv=conv)
+
+
+def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
+                            device: int = 0) -> List[DetectResults]:
+    """The CNN operator with an LLR second opinion for the reads it fails (an extension: adapted_amd/detect/cnn.py)."""
+    from . import cnn as _cnn
+
+    return _cnn.combined_detect_cnn_llr(batch_of_signals, full_signal_lens, model, spc, device=device)

@@ -25,6 +25,8 @@ MAX_OPEN_PORES = 16
 
 ADP_IN_DEVICE, ADP_OUT_DEVICE, ADP_WITH_START_PEAK, ADP_TOPK_NONE, ADP_BOUNDS_HOST, ADP_TAILS_NAN = 1, 2, 4, 8, 16, 32
 ADP_CNN_FALLBACK = 1 << 17  # adp_detect_cnn: the short-read LLR fallback inside the call
+ADP_CNN_SECOND_LLR = 1 << 18  # adp_detect_cnn: reads that fail get the LLR path's row where that one passes (row["reserved_"] bit 0)
+ROW_FROM_SECOND_LLR = 1  # bit of row["reserved_"]
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
 COLS = ["signal_len", "preloaded", "adapter_start", "adapter_end", "adapter_len", "adapter_mean",
@@ -521,10 +523,16 @@ def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> Li
     """adp_row[] -> DetectResults, value for value what the reference's validate_boundaries
     returns (types: python int / float, np.float32 where the reference keeps numpy scalars).
     consume: the rows are not needed again -- their overflow open_pores lists leave the registry (a long run converts
-    every row exactly once: adapted_amd/main.py)."""
+    every row exactly once: adapted_amd/main.py).
+    A row made by the CNN path's LLR second opinion (``reserved_`` bit 0) is named as the LLR path names it, whatever ``primary``."""
     out = []
-    names = [c.format(primary=primary) for c in COLS]
+    names_of = {primary: [c.format(primary=primary) for c in COLS]}
+    if rows.size and (rows["reserved_"] & ROW_FROM_SECOND_LLR).any():
+        names_of["llr"] = [c.format(primary="llr") for c in COLS]
+    row_primary = primary
     for r in rows:
+        primary = "llr" if int(r["reserved_"]) & ROW_FROM_SECOND_LLR else row_primary
+        names = names_of[primary]
         fc = int(r["fail_code"])
         if 9 <= fc <= 14:  # the reference raised inside its per-read try block
             out.append(DetectResults(success=False, fail_reason=fail_reason_of(r)))
@@ -1042,13 +1050,16 @@ class Engine:
         return out
 
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
-                        want_bounds: bool = True, fallback: bool = False):
+                        want_bounds: bool = True, fallback: bool = False, second_opinion: bool = False):
         """combined_detect_cnn -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k]).  fallback: with the short-read
         fallback applied on the device (ADP_CNN_FALLBACK; where the configuration has it on); without it the rows are those in
-        front of the fallback.  bounds: what cnn_detect returned, either way."""
+        front of the fallback.  bounds: what cnn_detect returned, either way.  second_opinion: reads whose row fails get the
+        row of the LLR path on their minibatch where that one passes (ADP_CNN_SECOND_LLR; such rows carry reserved_ bit 0)."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         if fallback:
             flags |= ADP_CNN_FALLBACK
+        if second_opinion:
+            flags |= ADP_CNN_SECOND_LLR
         k = max(1, int(self.cfg.polya_cand_k))
         bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
         rows, rows_arg, out_flag = self._out(rows_dev, n)
@@ -1123,6 +1134,13 @@ class Engine:
         """the fallback of the last detect_cnn_rows call: (reads selected, exception rows made, rows re-validated)"""
         a = np.zeros(3, dtype=np.int32)
         self._check(self.lib.adp_debug_fetch(self._h, 10, a, a.nbytes))
+        return tuple(int(v) for v in a)
+
+    def debug_cnn_second_opinion(self):
+        """the LLR second opinion of the last detect_cnn_rows call: (reads selected, rows replaced, rows re-validated and still
+        failing, minibatches with a selected read that gave none)"""
+        a = np.zeros(4, dtype=np.int32)
+        self._check(self.lib.adp_debug_fetch(self._h, 11, a, a.nbytes))
         return tuple(int(v) for v in a)
 
     def debug_counters(self, n: int = 8):

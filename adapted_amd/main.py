@@ -47,6 +47,8 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-b", "--batch_size", type=int, default=4000, help="Number of reads per output file.")
     d.add_argument("-s", "--minibatch_size", type=int, default=1000, help="Number of reads per minibatch (normalisation unit).")
     d.add_argument("--start_peak", action="store_true", help="(extension) also fill the start_peak_* columns on the LLR path")
+    d.add_argument("--second_opinion", type=str, choices=["llr"], default=None,
+                   help="(extension) CNN primary: reads it fails get the LLR detector's boundaries where those pass validation")
     d.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     d.add_argument("--int16_ingest", action="store_true",
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
@@ -126,8 +128,25 @@ def _init_dist(device=None):
     return dist
 
 
+def _load_spc(args):
+    spc = load_nested_config_from_file(args.config) if args.config else get_chemistry_specific_config(args.chemistry)
+    if args.max_obs_trace:
+        spc.core.max_obs_trace = args.max_obs_trace
+    spc.update_primary_method()
+    spc.update_sig_preload_size()
+    return spc
+
+
+def _check_second_opinion(args):
+    """--second_opinion goes with the CNN primary only: said before a GPU is touched"""
+    if getattr(args, "second_opinion", None) and (args.config or args.chemistry):
+        primary = _load_spc(args).primary_method
+        if primary != "cnn":
+            raise SystemExit("--second_opinion llr needs the CNN primary (cnn_boundaries.cnn_detect); this configuration's primary is %s." % primary)
+
+
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False):
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None):
     rank, ws, local = parallel.world()
     if device is None:
         device = local
@@ -151,7 +170,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     # decodes only the groups of whole minibatches a GroupSharder assigns to it (balanced by preloaded samples).
     GROUP = 4  # minibatches per staging slot and detect call (normalisation stays per minibatch)
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
-                        model=model, int16_input=int16_ingest, group=GROUP, ragged=True)
+                        model=model, int16_input=int16_ingest, group=GROUP, ragged=True, second_opinion=second_opinion)
+    n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     sharder = GroupSharder(ws, rank, m) if multi else None
     ordinals: List[int] = []  # stream index of the first read of every group this rank yields
 
@@ -172,6 +192,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             my_ids.extend(tagged[:, 0].tolist())
             my_ord.extend(int(x) for x in tagged[:, 1])
         else:
+            n_second[0] += int(((rows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             res = lib.rows_to_results(rows, primary, consume=True)
             writer.add([ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for rid, r in zip(tagged[:, 0], res)])
@@ -191,6 +212,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
         if rank == 0:
             ids = [x for part in lists for x in part[0]]
             order = np.argsort(np.array([x for part in lists for x in part[1]], dtype=np.int64), kind="stable")
+            n_second[0] += int(((allrows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
             writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for i, r in zip(order, res)])
@@ -201,6 +223,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
                      tot / max(time.time() - t0, 1e-9), ws)
         if tot:
             logging.info("Pass: %d (%.2f%%), fail: %d", writer.n[True], 100.0 * writer.n[True] / tot, writer.n[False])
+        if second_opinion:
+            logging.info("Second opinion (%s): %d of the passing reads", second_opinion, n_second[0])
     if multi:
         dist.barrier()
         logging.info("process group: backend %s, %d rank(s); HIP runtimes mapped: %s", dist.get_backend(), ws, ", ".join(lib.hip_runtimes()))
@@ -219,9 +243,11 @@ def main(argv=None):
         for k, v in cmd.items():
             if not hasattr(args, k):
                 setattr(args, k, v)
+        _check_second_opinion(args)
     else:
         args.output = args.output or os.getcwd()
         run_dir = os.path.join(args.output, "adapted_" + __version__.replace(".", "_") + "_" + str(uuid.uuid4())[:8])
+        _check_second_opinion(args)
         dist = _init_dist(getattr(args, "device", None))
         if dist is not None:  # one run directory for all ranks: rank 0's name
             box = [run_dir]
@@ -238,11 +264,7 @@ def main(argv=None):
     if not files:
         print("No valid input files found.\nProvided path: {}".format(args.input))
         raise SystemExit(1)
-    spc = load_nested_config_from_file(args.config) if args.config else get_chemistry_specific_config(args.chemistry)
-    if args.max_obs_trace:
-        spc.core.max_obs_trace = args.max_obs_trace
-    spc.update_primary_method()
-    spc.update_sig_preload_size()
+    spc = _load_spc(args)
     rank = parallel.world()[0]
     if rank == 0:
         os.makedirs(run_dir, exist_ok=True)
@@ -262,7 +284,7 @@ def main(argv=None):
         logging.info("Found %d previously processed reads.", len(excl))
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
-               int16_ingest=getattr(args, "int16_ingest", False))
+               int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None))
     logging.info("Done.")
 
 

@@ -29,7 +29,10 @@ from . import lib
 
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
-                 with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False):
+                 with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
+                 second_opinion: Optional[str] = None):
+        """second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
+        minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py)."""
         """int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
         to float32 pA on the device (adp_calibrate_i16), so only 2 bytes per sample cross PCIe.  get_buffers() then hands
         out (raw, lengths, scale, offset) instead of (signals, lengths)."""
@@ -43,6 +46,11 @@ class HostPipeline:
         self.N = self.mb * max(1, int(group))  # reads per slot
         self.primary, self.with_start_peak, self.model, self.i16 = primary, with_start_peak, model, bool(int16_input)
         self.ragged = bool(ragged)
+        if second_opinion not in (None, "llr"):
+            raise ValueError('second_opinion must be None or "llr"')
+        if second_opinion and primary != "cnn":
+            raise ValueError("second_opinion needs the CNN primary")
+        self.second_opinion = second_opinion
         self.eng = lib.Engine(spc, self.N, self.m, device=self.device)
         self.slots = []
         # int16 input + LLR primary: the kernels read the raw samples themselves (adp_detect_llr_i16) -- no float32 matrix is made
@@ -138,7 +146,8 @@ class HostPipeline:
         from .detect import cnn as _cnn
 
         # (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
-        return _cnn.detect_rows_device(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
+        detect = _cnn.detect_rows_device_second_opinion if self.second_opinion else _cnn.detect_rows_device
+        return detect(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
 
     # -- driver -------------------------------------------------------------------------------
     def run(self, fill: Callable[[Callable[[], Tuple[np.ndarray, np.ndarray]]], Iterable[Tuple[int, object]]],

@@ -73,6 +73,8 @@ extern "C" {
                                       end instead of reading the padding.  Without the flag the rows are taken as they are. */
 #define ADP_CNN_FALLBACK (1 << 17)  /* adp_detect_cnn: apply the short-read LLR fallback (adapted/detect/combined.py:251-301) inside the
                                       call, where cfg.fallback_to_llr_short_reads is set: the rows are combined_detect_cnn's */
+#define ADP_CNN_SECOND_LLR (1 << 18) /* adp_detect_cnn: a read whose row fails gets the row of combined_detect_llr2 on its minibatch, if
+                                      that row passes (an extension; adp_row.reserved_ bit 0 marks such a row) */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -152,7 +154,8 @@ typedef struct adp_row {
     int32_t open_pores[ADP_MAX_OPEN_PORES]; /* the first ADP_MAX_OPEN_PORES positions */
     int32_t open_pores_more;   /* n_open_pores > ADP_MAX_OPEN_PORES: the WHOLE list lies at this offset of the call's
                                   open-pore arena (adp_open_pores_arena); -1 otherwise */
-    int32_t reserved_;
+    int32_t reserved_;         /* bit 0: the row was made by the LLR second opinion of adp_detect_cnn (ADP_CNN_SECOND_LLR): its
+                                  primary columns are the LLR's.  0 in every other row of every call */
 } adp_row;
 
 typedef struct adp_handle adp_handle;
@@ -248,7 +251,14 @@ int adp_cnn_topk(adp_handle *h, const float *scores_dev, const int64_t *adapter_
  * again); otherwise the first row stays.  Rows of both passes share the call's one open-pore arena.  Without the flag the call
  * stops in front of the fallback (callers that apply it themselves with adp_llr_refine_polya + adp_validate_candidates).
  * Needs adp_cnn_set_weights.  bounds_out (HOST, may be NULL) as adp_cnn_predict: what cnn_detect returned -- the fallback does
- * not rewrite it. */
+ * not rewrite it.
+ * With ADP_CNN_SECOND_LLR in `flags` (rows_out given; an extension, the reference keeps its two detectors apart) every read whose
+ * row has success == 0 behind all of the above -- exception rows included -- gets an LLR second opinion in the same call: the
+ * LLR primary exactly as adp_detect_llr computes it for the read's minibatch in ADP_LAYOUT_MINIBATCH (N1 over all reads of the
+ * minibatch), then the validation with those boundaries (k = 1).  Where that row passes it REPLACES the read's row, with bit 0 of
+ * adp_row.reserved_ set; otherwise the CNN path's row stays, byte for byte.  A minibatch whose LLR status is not ADP_MB_OK (where
+ * combined_detect_llr2 raises) gives none of its reads a second opinion.  Rows of reads that pass the CNN path are never touched;
+ * bounds_out stays what cnn_detect returned; the second rows' open-pore lists share the call's arena. */
 int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
                    adp_row *rows_out, int64_t *bounds_out);
 /* Validate with explicit primary boundaries: bounds int64 [n_reads, 1 + k] = adapter_end, k poly(A)
@@ -507,7 +517,9 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *         selections, 3 MADs not predicted, 4 MAD bracket overflows (0-4 are kept on 256 cache lines by workgroup and summed
  *         here: per-workgroup device atomics on one address serialise chip-wide), 5 single-pass N1 attempts, 6 / 7 their
  *         median / MAD misses, 22 / 23 N1 heavy keys / samples; the rest: phase cycles of -DADP_PHASE_TIMING builds
- *       10 int32[3], the fallback of the last adp_detect_cnn call: reads selected, exception rows made, rows re-validated */
+ *       10 int32[3], the fallback of the last adp_detect_cnn call: reads selected, exception rows made, rows re-validated
+ *       11 int32[4], the LLR second opinion of the last adp_detect_cnn call: reads selected, rows replaced, rows re-validated and
+ *          still failing, minibatches (with a selected read) that gave none */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
