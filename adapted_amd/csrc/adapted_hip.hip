@@ -30,6 +30,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_conv_split.h"
 #include "cnn_fallback.h"
 #include "cnn_second_opinion.h"
+#include "polya_truncated.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -336,29 +337,31 @@ static int env_int(const char *name, int dflt)
 // stream(s) drained): how much the call wanted; > capacity = lists were dropped: grow and tell the caller to run again.
 static int arena_begin(adp_handle *h)
 {
-    if (h->op_used.ensure(16) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    if (h->op_used.ensure(32) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     // [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read fallback,
-    // [3] reads selected for its LLR second opinion
-    HIPCHK(hipMemsetAsync(h->op_used.p, 0, 16, h->stream));
+    // [3] reads selected for its LLR second opinion, [4] reads whose tail window passed the truncation look's T1 (ADP_FLAG_TRUNCATED)
+    HIPCHK(hipMemsetAsync(h->op_used.p, 0, 20, h->stream));
     return 0;
 }
 // -> 0 done, 1 run the call again (arena grown), < 0 error
 // (cnn: the call ran the conv stack -- its out-of-range flag is read with the counter; set = repeat the call on the float32 kernels)
 // (n_sel: the call ran k_cnn_fb_select -- its count comes with the same copy; left 0 when the call is to be repeated)
-// (n_so: the same for k_cnn_so_select)
-static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr)
+// (n_so: the same for k_cnn_so_select; n_pt: for k_pt_select)
+static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr, unsigned int *n_pt = nullptr)
 {
     const bool conv_flag = cnn && h->cnn_mode == 1 && !h->cnn_redo_f32;
     if (n_sel) *n_sel = 0;
     if (n_so) *n_so = 0;
-    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel && !n_so) { h->op_last_used = 0; return 0; }
-    unsigned int w[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(w, h->op_used.p, 16, hipMemcpyDeviceToHost, h->stream));
+    if (n_pt) *n_pt = 0;
+    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel && !n_so && !n_pt) { h->op_last_used = 0; return 0; }
+    unsigned int w[5] = {0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(w, h->op_used.p, n_pt ? 20 : 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (conv_flag && w[1]) { h->cnn_redo_f32 = true; return 1; }
     const bool arena_ok = !h->cfg.detect_open_pores || (size_t)w[0] * 4 <= h->op_arena.cap;
     if (n_sel && arena_ok) *n_sel = w[2];
     if (n_so && arena_ok) *n_so = w[3];
+    if (n_pt && arena_ok) *n_pt = w[4];
     if (!h->cfg.detect_open_pores) { h->op_last_used = 0; return 0; }
     const unsigned int used = w[0];
     h->op_last_used = used;
@@ -384,7 +387,7 @@ struct ValBufs { const int64_t *bounds; const int8_t *topk_none; adp_row *rows; 
 
 template <class SIG>
 static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int kmax, int mbsize,
-                           bool gate_mb, const ValBufs *vb = nullptr)
+                           bool gate_mb, const ValBufs *vb = nullptr, bool polya_truncated = false)
 {
     const int64_t *bounds = vb ? vb->bounds : h->bounds.as<int64_t>();
     adp_row *rows = vb ? vb->rows : h->rows.as<adp_row>();
@@ -463,6 +466,10 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     in.op_arena = a->op_arena.as<int32_t>(); in.op_used = a->op_used.as<unsigned int>(); in.op_cap = (unsigned int)(a->op_arena.cap / 4);
     { Scope s(h, "k_validate");
       hipLaunchKernelGGL(k_validate<SIG>, dim3(grid), dim3(64), 0, h->stream, in, h->cfg, rows, h->preq.as<PartReq>()); }
+    if (polya_truncated) { // (Boundaries.polya_truncated: no RNA partition, signal_partitions.py:74-77)
+        Scope s(h, "k_pt_preq");
+        hipLaunchKernelGGL(k_pt_preq, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->preq.as<PartReq>(), n);
+    }
     { Scope s(h, "k_partition_stats");
       // (the kernel is a template on the workgroup size: 512 threads x 2 and 1024 x 1 per CU, and the second pass walking a segment from its
       // end, were measured and dropped in round 5 -- 28.2 / 38.5 against 24.5 ms; +-1 %: profiles/r05_tried_and_dropped.txt)
@@ -737,6 +744,80 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     return ADP_OK;
 }
 
+// ---- the truncation look (ADP_FLAG_TRUNCATED, polya_truncated.h) --------------------------------------------------------------
+static bool trunc_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_FLAG_TRUNCATED) && rows_out; }
+// what the flag cannot go with, said before anything is launched
+static int trunc_supported(const adp_handle *h)
+{
+    const adp_cfg &c = h->cfg;
+    const int W = c.median_shift_window;
+    if (!c.mvs_detect_check) { g_err = "ADP_FLAG_TRUNCATED needs mvs_detect_check (its tests are the MVS check's)"; return ADP_ERR_UNSUPPORTED; }
+    if (c.mvs_detect_overwrite) { g_err = "ADP_FLAG_TRUNCATED does not go with mvs_detect_overwrite"; return ADP_ERR_UNSUPPORTED; }
+    if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "ADP_FLAG_TRUNCATED does not go with the single-read layout"; return ADP_ERR_UNSUPPORTED; }
+    if (W > PT_WMAX) { g_err = "ADP_FLAG_TRUNCATED: median_shift_window is longer than the tail test holds in LDS (4096)"; return ADP_ERR_UNSUPPORTED; }
+    if (c.pA_var_window < 1 || c.pA_mean_window < 1 || c.pA_var_window + 2 >= W || c.pA_mean_window + 2 >= W) {
+        g_err = "ADP_FLAG_TRUNCATED: pA_mean_window and pA_var_window must lie in [1, median_shift_window - 3]"; return ADP_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+// T1 over the n rows of the CALL's device row buffer once every read's final row is in it, and the selection; the count reaches the
+// host in arena_end's copy (n_pt).
+static int trunc_enqueue_t1(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows)
+{
+    // verdicts n | counts 16 (8-byte aligned behind the verdicts)
+    const size_t voff = ((size_t)n + 15) & ~(size_t)15;
+    if (h->pt_sel.ensure((size_t)n * 4) || h->pt_ws.ensure(voff + 16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    int8_t *verdict = h->pt_ws.as<int8_t>();
+    unsigned int *counts = reinterpret_cast<unsigned int *>(verdict + voff);
+    h->pt_counts = counts; h->pt_n_t1 = 0;
+    HIPCHK(hipMemsetAsync(counts, 0, 16, h->stream));
+    { Scope s(h, "k_pt_t1");
+      hipLaunchKernelGGL(k_pt_t1, dim3(n), dim3(64), (size_t)3 * h->cfg.median_shift_window * 4, h->stream, dsig, dlen, n, m, h->cfg, rows, verdict); }
+    { Scope s(h, "k_pt_select");
+      hipLaunchKernelGGL(k_pt_select, dim3(1), dim3(PT_SEL_THREADS), 0, h->stream, (const int8_t *)verdict, n, h->pt_sel.as<int32_t>(),
+                         h->op_used.as<unsigned int>() + 4, counts); }
+    return 0;
+}
+// T2 and the merge for the n_t1 reads that passed T1, enqueued on the handle's stream.  T2's rows have a buffer of their own (the
+// handle's may be the call's); their open-pore lists append to the call's arena: the caller looks at its counter once more.
+static int trunc_run_t2(adp_handle *h, const float *dsig, const int32_t *dlen, int m, adp_row *rows, int n_t1)
+{
+    int rc = alloc_all(h, n_t1, false);
+    if (rc) return rc;
+    const size_t N = (size_t)n_t1;
+    // bounds of the validation 16 N | full_len 4 N | topk_none N
+    if (h->pt_b2.ensure(N * 21) || h->pt_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    int64_t *b2 = h->pt_b2.as<int64_t>();
+    int32_t *dlen_sub = reinterpret_cast<int32_t *>(b2 + 2 * N);
+    int8_t *tsub = reinterpret_cast<int8_t *>(dlen_sub + N);
+    const int32_t *sel = h->pt_sel.as<int32_t>();
+    { Scope s(h, "k_pt_gather");
+      hipLaunchKernelGGL(k_pt_gather, dim3((n_t1 + 255) / 256), dim3(256), 0, h->stream, sel, n_t1, m, dlen, (const adp_row *)rows, dlen_sub, b2, tsub); }
+    const ValBufs vb{b2, tsub, h->pt_rows.as<adp_row>()};
+    rc = launch_validate(h, SigIdx{dsig, sel}, dlen_sub, n_t1, m, 1, n_t1, false, &vb, true);
+    if (rc) return rc;
+    { Scope s(h, "k_pt_merge");
+      hipLaunchKernelGGL(k_pt_merge, dim3(n_t1), dim3(64), 0, h->stream, sel, n_t1, (const adp_row *)h->pt_rows.as<adp_row>(), rows, h->pt_counts); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// The look behind a call whose rows are final in `rows` (device) and whose stream(s) have drained: -> 0 done, 1 run the call
+// again (arena grown), < 0 error.  t1_enqueued: the caller put trunc_enqueue_t1 in front of its own arena_end and hands the count in.
+static int trunc_finish(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows, bool t1_enqueued, unsigned int n_pt)
+{
+    int rc;
+    if (!t1_enqueued) {
+        RCCHK(trunc_enqueue_t1(h, dsig, dlen, n, m, rows));
+        rc = arena_end(h, false, nullptr, nullptr, &n_pt); // (with n_pt it copies the counter and waits for the stream)
+        if (rc) return rc;
+    }
+    h->pt_n_t1 = n_pt;
+    if (!n_pt) return 0;
+    RCCHK(trunc_run_t2(h, dsig, dlen, m, rows, (int)n_pt));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return arena_end(h);
+}
+
 // how a call's minibatches are cut into groups: ADP_GROUPS (unset / 1: one group = the plain serial pipeline, 0: automatic = three
 // groups per lane, k: aim at k groups); ADP_LANES (streams the groups rotate over, default 2); ADP_STAGGER (bit p set: phase p of
 // group g + 1 starts after phase p of group g; default 1 = the streaming S phases take turns, which keeps neighbouring groups one
@@ -801,8 +882,16 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
-        rc = arena_end(h);
+        const bool pt = trunc_wanted(flags, rows_out);
+        unsigned int n_pt = 0;
+        if constexpr (std::is_same<SIG, SigF32>::value) {
+            if (pt) RCCHK(trunc_enqueue_t1(h, dsig.base, dlen, n, m, rows_dev)); // (arena_end waits for this stream)
+        }
+        rc = arena_end(h, false, nullptr, nullptr, pt ? &n_pt : nullptr);
         if (rc < 0) return rc;
+        if constexpr (std::is_same<SIG, SigF32>::value) {
+            if (rc == 0 && pt) { rc = trunc_finish(h, dsig.base, dlen, n, m, rows_dev, true, n_pt); if (rc < 0) return rc; }
+        }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
         for (int i = 0; i < n_lanes; i++) { lanes[i]->prof.clear(); lanes[i]->ev_used = 0; }
@@ -834,12 +923,19 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
         return llr_grouped(h, dsig, dlen, n, m, minibatch, flags, rows_out, mb_status, per, n_lanes);
     }
     h->last_grouped = false;
+    // ADP_FLAG_TRUNCATED: the look rides behind the validation on the device rows (the caller's, or the handle's -- host rows are
+    // then delivered once, behind it); its T1 count comes back with the arena counter
+    const bool pt = upto >= 8 && trunc_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
     for (int attempt = 0; attempt < 3; attempt++) {
         int rc = arena_begin(h);
         if (rc) return rc;
-        rc = llr_enqueue(h, dsig, dlen, n, m, minibatch, flags, upto >= 8 ? rows_out : nullptr,
-                         (flags & ADP_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, nullptr, nullptr, upto, nullptr);
+        rc = llr_enqueue(h, dsig, dlen, n, m, minibatch, flags, upto >= 8 && !(pt && !out_dev) ? rows_out : nullptr,
+                         out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, nullptr, nullptr, upto, nullptr);
         if (rc) return rc;
+        adp_row *pt_rows = out_dev ? rows_out : h->rows.as<adp_row>();
+        if constexpr (std::is_same<SIG, SigF32>::value) {
+            if (pt) RCCHK(trunc_enqueue_t1(h, dsig.base, dlen, n, m, pt_rows));
+        }
         if (mb_status) {
             // through a small device buffer -> host
             hipLaunchKernelGGL(k_mb_status_out, dim3((n_mb + 255) / 256), dim3(256), 0, h->stream, h->mbs.as<MbState>(), n_mb, h->gbelow.as<int32_t>());
@@ -848,8 +944,19 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
         if (upto < 8) break;
-        rc = arena_end(h);
+        unsigned int n_pt = 0;
+        rc = arena_end(h, false, nullptr, nullptr, pt ? &n_pt : nullptr);
         if (rc < 0) return rc;
+        if constexpr (std::is_same<SIG, SigF32>::value) {
+            if (rc == 0 && pt) {
+                rc = trunc_finish(h, dsig.base, dlen, n, m, pt_rows, true, n_pt);
+                if (rc < 0) return rc;
+                if (rc == 0 && !out_dev) {
+                    HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+                    HIPCHK(hipStreamSynchronize(h->stream));
+                }
+            }
+        }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
         reset_profile(h);
@@ -863,6 +970,8 @@ static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full
     if (!h || !signals || !full_len || n < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ && minibatch != 1) { g_err = "the single-read layout normalises every read on its own: minibatch must be 1"; return ADP_ERR_INVALID; }
+    h->pt_n_t1 = 0; h->pt_counts = nullptr;
+    if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n, m, flags, &dsig, &dlen);
@@ -897,6 +1006,7 @@ int adp_detect_llr_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "the single-read layout takes float32 input"; return ADP_ERR_UNSUPPORTED; }
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_llr)"; return ADP_ERR_UNSUPPORTED; }
     RCCHK(begin_call(h));
     // (samples at or beyond min(full_len, m) read as NaN: the padding is implied, so the passes always stop at a read's end)
     return llr_pipeline_t(h, SigI16{raw, scale, offset, full_len}, full_len, n_reads, m, minibatch, flags | ADP_TAILS_NAN, rows_out, mb_status, 8);
@@ -966,6 +1076,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED goes with adp_detect_llr and adp_detect_cnn"; return ADP_ERR_UNSUPPORTED; }
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
@@ -1012,6 +1123,8 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
 {
     if (!h || !signals || !full_len || !bounds || n_reads < 1 || k < 1 || k > ADP_MAX_CAND) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    const bool truncated = (flags & ADP_POLYA_TRUNCATED) != 0;
+    if (truncated && h->cfg.mvs_detect_check && h->cfg.mvs_detect_overwrite) { g_err = "ADP_POLYA_TRUNCATED does not go with mvs_detect_overwrite"; return ADP_ERR_UNSUPPORTED; }
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
@@ -1025,7 +1138,7 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
         HIPCHK(hipMemcpyAsync(h->bounds.p, bounds, (size_t)n_reads * (1 + k) * 8,
                               ((flags & ADP_IN_DEVICE) && !(flags & ADP_BOUNDS_HOST)) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(h->topk_none.p, (flags & ADP_TOPK_NONE) ? 1 : 0, (size_t)n_reads, st));
-        rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false);
+        rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated);
         if (rc) return rc;
         rc = deliver_rows(h, n_reads, flags, rows_out);
         if (rc) return rc;
@@ -1664,6 +1777,10 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
             rc = arena_end(h);
             if (rc < 0) return rc;
         }
+        if (rc == 0 && trunc_wanted(flags, rows_out)) { // (behind everything else: every read's final row)
+            rc = trunc_finish(h, dsig, dlen, n, m, rows_dev, false, 0);
+            if (rc < 0) return rc;
+        }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
         for (int i = 0; i < n_lanes; i++) { lanes[i]->prof.clear(); lanes[i]->ev_used = 0; }
@@ -1682,6 +1799,8 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    h->pt_n_t1 = 0; h->pt_counts = nullptr;
+    if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     if (m <= h->cfg.min_obs_adapter) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
@@ -1754,6 +1873,16 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h);
             if (rc < 0) return rc;
+        }
+        // The truncation look (ADP_FLAG_TRUNCATED) comes behind all of that, on every read's final row: one more synchronisation for
+        // its T1 count, and T2 only where a tail window passed.
+        if (rc == 0 && trunc_wanted(flags, rows_out)) {
+            rc = trunc_finish(h, dsig, dlen, n_reads, m, merged, false, 0);
+            if (rc < 0) return rc;
+            if (rc == 0 && !out_dev) {
+                HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+            }
         }
         if (rc == 0) break;
         if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
@@ -1994,6 +2123,11 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         int32_t c[4] = {(int32_t)h->so_n_sel, 0, 0, 0};
         if (h->so_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->so_counts, 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 16); return ADP_OK; }
+    case 12: { // the truncation look of the last adp_detect_llr / adp_detect_cnn call: eligible reads, T1 passed, rows replaced
+        if (bytes < 12) return ADP_ERR_INVALID;
+        int32_t c[3] = {0, 0, 0};
+        if (h->pt_counts) { HIPCHK(hipMemcpyAsync(c, h->pt_counts, 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;
               HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg), bytes, 0, hipMemcpyDeviceToHost));

@@ -1067,7 +1067,8 @@ struct PartReq {
     int64_t a_s, a_e, p_e;
     float adapter_med, adapter_mad;
     int32_t have_adapter_medmad;
-    int32_t p_none;     // polya_end is None (mvs_detect_overwrite): poly(A) keeps its start only, the RNA partition is all None
+    int32_t p_none;     // bit 0: polya_end is None (mvs_detect_overwrite): poly(A) keeps its start only, the RNA partition is all None;
+                        // bit 1: Boundaries.polya_truncated (k_pt_preq, polya_truncated.h): the RNA partition is all None
 };
 
 // the three partitions of read r
@@ -1085,7 +1086,7 @@ static __device__ __forceinline__ void bs_partitions_of_read(const ROW sig, cons
         if (p == 2 && q.p_none) continue;
         if (threadIdx.x == 0) row->col[c_start[p]] = (double)st;
         present |= 1ull << c_start[p];
-        if (en <= st || (p == 1 && q.p_none)) continue;
+        if (en <= st || (p == 1 && (q.p_none & 1))) continue;
         long long a = st < S ? st : S, b = en < S ? en : S;
         int n = (int)(b - a);
         SegStats s;

@@ -216,6 +216,7 @@ static __device__ __forceinline__ RowF32 as_row(const float *p) { return RowF32{
 static __device__ __forceinline__ RowF32 as_row(float *p) { return RowF32{(const GLB float *)p}; }
 static __device__ __forceinline__ RowF32 as_row(RowF32 r) { return r; }
 static __device__ __forceinline__ RowI16 as_row(RowI16 r) { return r; }
+static __device__ __forceinline__ const LDS float *as_row(const LDS float *p) { return p; } // (a slice held in LDS is read where it lies)
 
 static __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

@@ -84,6 +84,11 @@ struct adp_handle {
     DevBuf so_sel, so_ws, so_rows;
     unsigned int so_n_sel = 0;              // reads the last adp_detect_cnn call selected for it
     unsigned int *so_counts = nullptr;      // device: [0] rows replaced, [1] re-validated and still failing, [2] minibatches without one (null: none ran)
+    // the truncation look (polya_truncated.h): the reads that passed T1 [reads of the call]; the verdicts and the counts; T2's
+    // per-subset arrays (carved by trunc_run_t2) and rows [selected reads]
+    DevBuf pt_sel, pt_ws, pt_b2, pt_rows;
+    unsigned int pt_n_t1 = 0;               // reads of the last call that passed T1
+    unsigned int *pt_counts = nullptr;      // device: [0] eligible reads, [1] T1 passed, [2] rows replaced (null: the last call did not look)
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;

@@ -174,10 +174,11 @@ static __device__ __noinline__ void bn_move_var(X a, int n, int w, float *out_)
 // The same two recurrences element by element, for k_validate's rare long-window path over int16 rows: the register
 // budget of anything k_validate can reach counts against its 6 waves per SIMD, and the eight-sample pipelines above need
 // 103 registers once each sample is also converted.  Same operations, same order.
-template <class X>
+// (O: where the series goes -- global memory, or LDS for polya_truncated.h's tail test)
+template <class X, class O = GLB float *>
 static __device__ __noinline__ void bn_move_slim(X a, int n, int w, float *out_, bool var)
 {
-    GLB float *out = (GLB float *)out_;
+    O out = (O)out_;
     float amean = 0.f, assqdm = 0.f, asum = 0.f;
     int count = 0;
     for (int i = 0; i < w; i++) {

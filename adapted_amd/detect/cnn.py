@@ -258,15 +258,30 @@ def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = 
 
 
 def _second_opinion_form(conv: str, fallback: str):
-    """the LLR second opinion runs inside adp_detect_cnn, behind the library's own conv stack and fallback: the host-side
-    variants of either have no such form"""
+    """the LLR second opinion and the truncation look run inside adp_detect_cnn, behind the library's own conv stack and
+    fallback: the host-side variants of either have no such form"""
     if conv != "hip":
-        raise ValueError('the LLR second opinion runs inside the library call: conv must be "hip"')
+        raise ValueError('the LLR second opinion / the truncation look runs inside the library call: conv must be "hip"')
     if _fallback_mode(fallback) != "device":
-        raise ValueError('the LLR second opinion runs inside the library call: fallback must be "device"')
+        raise ValueError('the LLR second opinion / the truncation look runs inside the library call: fallback must be "device"')
 
 
-def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+def detect_rows_truncated(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+    """detect_rows with the truncation look behind it (ADP_FLAG_TRUNCATED, include/adapted_hip.h): a read whose poly(A) runs into
+    the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
+    (``reserved_`` bit 1); every row carries bit 2.  An extension: the reference never sets ``polya_truncated``.  ONE library call."""
+    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, flag_truncated=True, second_opinion=False)
+
+
+def detect_rows_device_truncated(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
+                                 fallback: str = "device") -> np.ndarray:
+    """detect_rows_device with the truncation look behind it.  ONE library call over the resident batch."""
+    return detect_rows_device_second_opinion(eng, dsig, dlen, n, lens_host, model, spc, minibatch=minibatch, fallback=fallback,
+                                             flag_truncated=True, second_opinion=False)
+
+
+def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device",
+                               flag_truncated: bool = False, second_opinion: bool = True) -> np.ndarray:
     """detect_rows with the LLR second opinion (ADP_CNN_SECOND_LLR): a read whose row fails gets the row combined_detect_llr2
     returns for it on this batch, where that row passes (``reserved_`` bit 0 marks it; lib.rows_to_results names its primary
     columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call."""
@@ -275,19 +290,21 @@ def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, sp
     if int(spc.cnn_boundaries.polya_cand_k) < 1:
         raise ValueError("polya_cand_k must be >= 1")
     ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=True)[0]
+    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=second_opinion, flag_truncated=flag_truncated)[0]
 
 
 def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
-                                      fallback: str = "device") -> np.ndarray:
+                                      fallback: str = "device", flag_truncated: bool = False, second_opinion: bool = True) -> np.ndarray:
     """detect_rows_device with the LLR second opinion, per minibatch as combined_detect_llr2 would see it (its normalisation is
     the minibatch's).  ONE library call over the resident batch."""
     _second_opinion_form("hip", fallback)
     ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True, second_opinion=True)[0]
+    return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True, second_opinion=second_opinion,
+                               flag_truncated=flag_truncated)[0]
 
 
-def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0) -> List[DetectResults]:
+def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0,
+                            flag_truncated: bool = False) -> List[DetectResults]:
     """combined_detect_cnn, and for the reads it fails combined_detect_llr2 on the same batch where that passes (an extension;
     such results carry ``llr_adapter_end`` / ``llr_polya_end`` instead of the ``cnn_*`` pair).  Always a list."""
     from .combined import _as_batch, get_engine
@@ -299,13 +316,14 @@ def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.n
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = detect_rows_second_opinion(eng, sig, lens, model, spc)
+        rows = detect_rows_second_opinion(eng, sig, lens, model, spc, flag_truncated=flag_truncated)
     return lib.rows_to_results(rows, "cnn", consume=True)
 
 
 def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
-                        device: int = 0, conv: str = "hip") -> Union[List[DetectResults], DetectResults]:
-    """model: the nn.Sequential of load_cnn_model, a dict of weight arrays (load_cnn_weights), or None (the config's model)"""
+                        device: int = 0, conv: str = "hip", flag_truncated: bool = False) -> Union[List[DetectResults], DetectResults]:
+    """model: the nn.Sequential of load_cnn_model, a dict of weight arrays (load_cnn_weights), or None (the config's model).
+    flag_truncated: as combined_detect_llr2's (an extension, off by default)."""
     from .combined import _as_batch, get_engine
 
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
@@ -313,6 +331,6 @@ def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarr
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = detect_rows(eng, sig, lens, model, spc, conv=conv)
+        rows = (detect_rows_truncated if flag_truncated else detect_rows)(eng, sig, lens, model, spc, conv=conv)
     res = lib.rows_to_results(rows, "cnn", consume=True)
     return res if len(res) > 1 else res[0]

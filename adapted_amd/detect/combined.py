@@ -59,13 +59,16 @@ def _as_batch(batch_of_signals, full_signal_lens):
 
 
 def combined_detect_llr2(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, spc, device: int = 0,
-                         with_start_peak: bool = False) -> List[DetectResults]:
+                         with_start_peak: bool = False, flag_truncated: bool = False) -> List[DetectResults]:
+    """flag_truncated (an extension, off by default; the reference never sets ``polya_truncated``): reads whose poly(A) runs into
+    the end of the preloaded window come back with ``polya_truncated=True``, ``polya_end`` at the window's end and no RNA
+    partition; every other passing read with ``polya_truncated=False`` (include/adapted_hip.h, ADP_FLAG_TRUNCATED)."""
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
     n, m = sig.shape
     if n == 0:
         return []
     eng = get_engine(spc, n, m, device)
-    rows, mbs = eng.detect_llr_rows(sig, lens, n, n, with_start_peak=with_start_peak)
+    rows, mbs = eng.detect_llr_rows(sig, lens, n, n, with_start_peak=with_start_peak, flag_truncated=flag_truncated)
     if mbs[0] == lib.MB_MAD_ZERO:
         msg = "MAD normalization failed: scale is 0"
         logging.error(msg)
@@ -142,22 +145,24 @@ def validate_boundaries(signal: np.ndarray, boundaries: Boundaries, spc, full_si
     b[0, 1:1 + len(cands)] = cands
     if not none and len(cands) and cands[0] != int(boundaries.polya_end or 0):
         raise ValueError("polya_end_topk[0] must equal polya_end")
-    rows = eng.validate_rows(sig, np.array([eff_len], dtype=np.int32), 1, b, topk_none=none)
+    # (Boundaries.polya_truncated: no RNA partition, signal_partitions.py:74-77; the returned polya_truncated stays None, combined.py:606)
+    rows = eng.validate_rows(sig, np.array([eff_len], dtype=np.int32), 1, b, topk_none=none, polya_truncated=bool(boundaries.polya_truncated))
     if eff_len != int(full_signal_len) and int(rows[0]["present"]) & 1:
         rows[0]["col"][0] = float(full_signal_len)  # signal_len reports the read's true length
     return lib.rows_to_results(rows, spc.primary_method, consume=True)[0]
 
 
 def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
-                        device: int = 0, conv: str = "hip") -> Union[List[DetectResults], DetectResults]:
+                        device: int = 0, conv: str = "hip", flag_truncated: bool = False) -> Union[List[DetectResults], DetectResults]:
     from . import cnn as _cnn
 
-    return _cnn.combined_detect_cnn(batch_of_signals, full_signal_lens, model, spc, device=device, conv=conv)
+    return _cnn.combined_detect_cnn(batch_of_signals, full_signal_lens, model, spc, device=device, conv=conv, flag_truncated=flag_truncated)
 
 
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
                             device: int = 0) -> List[DetectResults]:
-    """The CNN operator with an LLR second opinion for the reads it fails (an extension: adapted_amd/detect/cnn.py)."""
+    """The CNN operator with an LLR second opinion for the reads it fails (an extension: adapted_amd/detect/cnn.py; that module's
+    function of the same name also takes ``flag_truncated`` -- this one keeps the parameters it was introduced with)."""
     from . import cnn as _cnn
 
     return _cnn.combined_detect_cnn_llr(batch_of_signals, full_signal_lens, model, spc, device=device)

@@ -26,7 +26,12 @@ MAX_OPEN_PORES = 16
 ADP_IN_DEVICE, ADP_OUT_DEVICE, ADP_WITH_START_PEAK, ADP_TOPK_NONE, ADP_BOUNDS_HOST, ADP_TAILS_NAN = 1, 2, 4, 8, 16, 32
 ADP_CNN_FALLBACK = 1 << 17  # adp_detect_cnn: the short-read LLR fallback inside the call
 ADP_CNN_SECOND_LLR = 1 << 18  # adp_detect_cnn: reads that fail get the LLR path's row where that one passes (row["reserved_"] bit 0)
-ROW_FROM_SECOND_LLR = 1  # bit of row["reserved_"]
+ADP_FLAG_TRUNCATED = 1 << 19  # adp_detect_llr / adp_detect_cnn: flag poly(A) tails cut off by the preload window (row["reserved_"] bits 1, 2)
+ADP_POLYA_TRUNCATED = 1 << 20  # adp_validate_candidates: Boundaries.polya_truncated is True -- no RNA partition
+ROW_FROM_SECOND_LLR = 1  # bits of row["reserved_"]
+ROW_POLYA_TRUNCATED = 2  # the poly(A) runs into the end of the preloaded window
+ROW_TRUNC_LOOKED = 4  # the call looked for that (every row of a call made with ADP_FLAG_TRUNCATED)
+ADP_ERR_UNSUPPORTED = -4
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
 COLS = ["signal_len", "preloaded", "adapter_start", "adapter_end", "adapter_len", "adapter_mean",
@@ -519,12 +524,34 @@ def fail_reason_of(row) -> Optional[str]:
     return fr
 
 
+_RNA_FIELDS = ("rna_preloaded_start", "rna_preloaded_len", "rna_preloaded_mean", "rna_preloaded_std", "rna_preloaded_med",
+               "rna_preloaded_mad")
+
+
+def truncation_unsupported(spc) -> Optional[str]:
+    """why the truncation look (ADP_FLAG_TRUNCATED) does not go with this configuration, or None (what the library refuses with
+    ADP_ERR_UNSUPPORTED, said without a GPU)"""
+    M = spc.mvs_polya
+    W = int(M.median_shift_window)
+    if not M.mvs_detect_check:
+        return "it needs mvs_polya.mvs_detect_check (its tests are the MVS check's)"
+    if M.mvs_detect_overwrite:
+        return "it does not go with mvs_polya.mvs_detect_overwrite"
+    if W > 4096:
+        return "mvs_polya.median_shift_window is longer than 4096"
+    if not (1 <= int(M.pA_var_window) <= W - 3 and 1 <= int(M.pA_mean_window) <= W - 3):
+        return "mvs_polya.pA_mean_window and pA_var_window must lie in [1, median_shift_window - 3]"
+    return None
+
+
 def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> List[DetectResults]:
     """adp_row[] -> DetectResults, value for value what the reference's validate_boundaries
     returns (types: python int / float, np.float32 where the reference keeps numpy scalars).
     consume: the rows are not needed again -- their overflow open_pores lists leave the registry (a long run converts
     every row exactly once: adapted_amd/main.py).
-    A row made by the CNN path's LLR second opinion (``reserved_`` bit 0) is named as the LLR path names it, whatever ``primary``."""
+    A row made by the CNN path's LLR second opinion (``reserved_`` bit 0) is named as the LLR path names it, whatever ``primary``.
+    ``polya_truncated`` (an extension: the reference never sets it): True for a row the truncation look replaced (bit 1; its six
+    ``rna_preloaded_*`` fields are None), False for a passing row of a call that looked (bit 2), None otherwise."""
     out = []
     names_of = {primary: [c.format(primary=primary) for c in COLS]}
     if rows.size and (rows["reserved_"] & ROW_FROM_SECOND_LLR).any():
@@ -563,6 +590,13 @@ def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> Li
                     raise HipLibraryError("a row with %d open pores lost its overflow list (rows from a device buffer? fetch them "
                                           "through Engine.attach_open_pores)" % no)
                 d.open_pores = more
+        res = int(r["reserved_"])
+        if res & ROW_POLYA_TRUNCATED:
+            d.polya_truncated = True
+            for name in _RNA_FIELDS:
+                setattr(d, name, None)
+        elif res & ROW_TRUNC_LOOKED and d.success:
+            d.polya_truncated = False
         d.mvs_llr_polya_end_adjust_ignored = False
         d.mvs_llr_polya_end_to_early_stop = bool(int(r["mvs_fail_mask"]) >> 8 & 1)  # (mvs_detect_overwrite only)
         fr = fail_reason_of(r)
@@ -745,13 +779,17 @@ class Engine:
         return out, out, 0
 
     def detect_llr_rows(self, signals, full_lens, n: int, minibatch: int, with_start_peak: bool = False,
-                        device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False):
+                        device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False, flag_truncated: bool = False):
         """-> (rows ndarray[ROW_DTYPE] or None when rows_dev is given, mb_status int32[n_mb]).
         tails_nan: the caller guarantees that every row is NaN from min(full_len, m) on (the reference's own padding,
-        adapted/file_proc.py:170-174); the streaming passes then skip the padding (ADP_TAILS_NAN)."""
+        adapted/file_proc.py:170-174); the streaming passes then skip the padding (ADP_TAILS_NAN).
+        flag_truncated: the call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension): a read whose poly(A) runs into
+        the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
+        (reserved_ bit 1); every row carries reserved_ bit 2."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         rows, rows_arg, out_flag = self._out(rows_dev, n)
         flags |= out_flag | (ADP_WITH_START_PEAK if with_start_peak else 0) | (ADP_TAILS_NAN if tails_nan else 0)
+        flags |= ADP_FLAG_TRUNCATED if flag_truncated else 0
         mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
         self._check(self.lib.adp_detect_llr(self._h, sig, lens, n, self.m, minibatch, flags, rows_arg, mbs))
         return self.attach_open_pores(rows), mbs
@@ -776,11 +814,14 @@ class Engine:
         return self.attach_open_pores(rows)
 
     def validate_rows(self, signals, full_lens, n: int, bounds: np.ndarray, device_ptrs: bool = False,
-                      topk_none: bool = False):
-        """bounds int64 [n, 1+k] (host) -> rows"""
+                      topk_none: bool = False, polya_truncated: bool = False):
+        """bounds int64 [n, 1+k] (host) -> rows.  polya_truncated: Boundaries.polya_truncated is True for every read -- the RNA
+        partition is all None (ADP_POLYA_TRUNCATED)"""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         if topk_none:
             flags |= ADP_TOPK_NONE
+        if polya_truncated:
+            flags |= ADP_POLYA_TRUNCATED
         b = np.ascontiguousarray(bounds, dtype=np.int64)
         rows = np.zeros(n, dtype=ROW_DTYPE)
         if device_ptrs:
@@ -1050,14 +1091,17 @@ class Engine:
         return out
 
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
-                        want_bounds: bool = True, fallback: bool = False, second_opinion: bool = False):
+                        want_bounds: bool = True, flag_truncated: bool = False, fallback: bool = False, second_opinion: bool = False):
         """combined_detect_cnn -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k]).  fallback: with the short-read
         fallback applied on the device (ADP_CNN_FALLBACK; where the configuration has it on); without it the rows are those in
         front of the fallback.  bounds: what cnn_detect returned, either way.  second_opinion: reads whose row fails get the
-        row of the LLR path on their minibatch where that one passes (ADP_CNN_SECOND_LLR; such rows carry reserved_ bit 0)."""
+        row of the LLR path on their minibatch where that one passes (ADP_CNN_SECOND_LLR; such rows carry reserved_ bit 0).
+        flag_truncated: the truncation look behind all of that, as in detect_llr_rows (ADP_FLAG_TRUNCATED)."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
         if fallback:
             flags |= ADP_CNN_FALLBACK
+        if flag_truncated:
+            flags |= ADP_FLAG_TRUNCATED
         if second_opinion:
             flags |= ADP_CNN_SECOND_LLR
         k = max(1, int(self.cfg.polya_cand_k))
@@ -1141,6 +1185,13 @@ class Engine:
         failing, minibatches with a selected read that gave none)"""
         a = np.zeros(4, dtype=np.int32)
         self._check(self.lib.adp_debug_fetch(self._h, 11, a, a.nbytes))
+        return tuple(int(v) for v in a)
+
+    def debug_truncated(self):
+        """the truncation look of the last detect_llr_rows / detect_cnn_rows call made with flag_truncated: (eligible reads, reads
+        whose tail window passed T1, rows replaced)"""
+        a = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.adp_debug_fetch(self._h, 12, a, a.nbytes))
         return tuple(int(v) for v in a)
 
     def debug_counters(self, n: int = 8):

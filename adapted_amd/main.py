@@ -36,6 +36,9 @@ def build_parser() -> argparse.ArgumentParser:
     d = sub.add_parser("detect", help="Detect adapter and poly(A) signal boundaries and calculate statistics.")
     c = sub.add_parser("continue", help="Continue processing from a previous incomplete run.")
     c.add_argument("continue_from", type=str)
+    t = sub.add_parser("truncated", help="(extension) List the reads whose poly(A) was cut off by the preload window "
+                                         "(runs made with --flag_truncated), for a rerun with a larger --max_obs_trace.")
+    t.add_argument("directory", type=str, help="a run directory, or the directory that holds its detected_boundaries_*.csv files")
     d.add_argument("-i", "--input", type=str, nargs="+", required=True, help="input files / directories (.pod5 or .npz bundles)")
     d.add_argument("-o", "--output", type=str, default=None)
     d.add_argument("--config", type=str, default=None, help="config TOML (overrides --chemistry)")
@@ -49,6 +52,9 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("--start_peak", action="store_true", help="(extension) also fill the start_peak_* columns on the LLR path")
     d.add_argument("--second_opinion", type=str, choices=["llr"], default=None,
                    help="(extension) CNN primary: reads it fails get the LLR detector's boundaries where those pass validation")
+    d.add_argument("--flag_truncated", action="store_true",
+                   help="(extension) fill the polya_truncated column: True where the poly(A) runs into the end of the preloaded "
+                        "signal (rerun those reads with a larger --max_obs_trace: `adapted truncated`), False on every other passing read")
     d.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     d.add_argument("--int16_ingest", action="store_true",
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
@@ -145,8 +151,59 @@ def _check_second_opinion(args):
             raise SystemExit("--second_opinion llr needs the CNN primary (cnn_boundaries.cnn_detect); this configuration's primary is %s." % primary)
 
 
+def _check_flag_truncated(args):
+    """--flag_truncated and what it does not go with: said before a GPU is touched"""
+    if getattr(args, "flag_truncated", False) and (args.config or args.chemistry):
+        spc = _load_spc(args)
+        if spc.primary_method not in ("llr", "cnn"):
+            raise SystemExit("--flag_truncated goes with the LLR and CNN primaries; this configuration's primary is %s." % spc.primary_method)
+        why = lib.truncation_unsupported(spc)
+        if why:
+            raise SystemExit("--flag_truncated does not go with this configuration: %s." % why)
+
+
+def list_truncated(directory: str) -> int:
+    """`adapted truncated`: the read ids whose polya_truncated column reads True, over all detected_boundaries_*.csv of the
+    directory (or of its boundaries/ folder) in file order, into truncated_read_ids.csv (header read_id) beside them -- what the
+    reference's scripts/get_truncated.sh does, with the column found by name.  -> the number of ids written"""
+    import csv
+    import re
+
+    where = directory
+    if os.path.isdir(os.path.join(directory, "boundaries")):
+        where = os.path.join(directory, "boundaries")
+    found = []
+    if os.path.isdir(where):
+        for f in os.listdir(where):
+            mt = re.fullmatch(r"detected_boundaries_(\d+)\.csv", f)
+            if mt:
+                found.append((int(mt.group(1)), f))
+    if not found:
+        print("No detected_boundaries_*.csv files found in {}".format(where))
+        raise SystemExit(1)
+    ids = []
+    for _, f in sorted(found):
+        with open(os.path.join(where, f), newline="") as fh:
+            rd = csv.reader(fh)
+            header = next(rd, None)
+            if header is None:
+                continue
+            if "read_id" not in header or "polya_truncated" not in header:
+                print("{}: no read_id / polya_truncated column".format(os.path.join(where, f)))
+                raise SystemExit(1)
+            ci, ct = header.index("read_id"), header.index("polya_truncated")
+            ids.extend(row[ci] for row in rd if len(row) > max(ci, ct) and row[ct] == "True")
+    out = os.path.join(where, "truncated_read_ids.csv")
+    with open(out, "w", newline="") as fh:
+        fh.write("read_id\n")
+        for rid in ids:
+            fh.write(rid + "\n")
+    print("Truncated read ids saved to {} ({} reads)".format(out, len(ids)))
+    return len(ids)
+
+
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None):
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False):
     rank, ws, local = parallel.world()
     if device is None:
         device = local
@@ -170,8 +227,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     # decodes only the groups of whole minibatches a GroupSharder assigns to it (balanced by preloaded samples).
     GROUP = 4  # minibatches per staging slot and detect call (normalisation stays per minibatch)
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
-                        model=model, int16_input=int16_ingest, group=GROUP, ragged=True, second_opinion=second_opinion)
+                        model=model, int16_input=int16_ingest, group=GROUP, ragged=True, second_opinion=second_opinion,
+                        flag_truncated=flag_truncated)
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
+    n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
     sharder = GroupSharder(ws, rank, m) if multi else None
     ordinals: List[int] = []  # stream index of the first read of every group this rank yields
 
@@ -193,6 +252,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             my_ord.extend(int(x) for x in tagged[:, 1])
         else:
             n_second[0] += int(((rows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
+            n_trunc[0] += int(((rows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             res = lib.rows_to_results(rows, primary, consume=True)
             writer.add([ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for rid, r in zip(tagged[:, 0], res)])
@@ -213,6 +273,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             ids = [x for part in lists for x in part[0]]
             order = np.argsort(np.array([x for part in lists for x in part[1]], dtype=np.int64), kind="stable")
             n_second[0] += int(((allrows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
+            n_trunc[0] += int(((allrows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
             writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for i, r in zip(order, res)])
@@ -225,6 +286,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             logging.info("Pass: %d (%.2f%%), fail: %d", writer.n[True], 100.0 * writer.n[True] / tot, writer.n[False])
         if second_opinion:
             logging.info("Second opinion (%s): %d of the passing reads", second_opinion, n_second[0])
+        if flag_truncated:
+            logging.info("Truncated poly(A) (polya_truncated): %d of the passing reads", n_trunc[0])
     if multi:
         dist.barrier()
         logging.info("process group: backend %s, %d rank(s); HIP runtimes mapped: %s", dist.get_backend(), ws, ", ".join(lib.hip_runtimes()))
@@ -232,6 +295,9 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.mode == "truncated":
+        list_truncated(args.directory)
+        return
     if args.mode == "continue":
         run_dir = args.continue_from
         try:
@@ -244,10 +310,12 @@ def main(argv=None):
             if not hasattr(args, k):
                 setattr(args, k, v)
         _check_second_opinion(args)
+        _check_flag_truncated(args)
     else:
         args.output = args.output or os.getcwd()
         run_dir = os.path.join(args.output, "adapted_" + __version__.replace(".", "_") + "_" + str(uuid.uuid4())[:8])
         _check_second_opinion(args)
+        _check_flag_truncated(args)
         dist = _init_dist(getattr(args, "device", None))
         if dist is not None:  # one run directory for all ranks: rank 0's name
             box = [run_dir]
@@ -284,7 +352,8 @@ def main(argv=None):
         logging.info("Found %d previously processed reads.", len(excl))
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
-               int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None))
+               int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
+               flag_truncated=getattr(args, "flag_truncated", False))
     logging.info("Done.")
 
 

@@ -30,9 +30,11 @@ from . import lib
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
-                 second_opinion: Optional[str] = None):
+                 flag_truncated: bool = False, second_opinion: Optional[str] = None):
         """second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
-        minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py)."""
+        minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py).
+        flag_truncated: every detect call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension; LLR and CNN
+        primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one."""
         """int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
         to float32 pA on the device (adp_calibrate_i16), so only 2 bytes per sample cross PCIe.  get_buffers() then hands
         out (raw, lengths, scale, offset) instead of (signals, lengths)."""
@@ -51,10 +53,17 @@ class HostPipeline:
         if second_opinion and primary != "cnn":
             raise ValueError("second_opinion needs the CNN primary")
         self.second_opinion = second_opinion
+        self.flag_truncated = bool(flag_truncated)
+        if self.flag_truncated:
+            if primary not in ("llr", "cnn"):
+                raise ValueError("flag_truncated goes with the LLR and CNN primaries")
+            why = lib.truncation_unsupported(spc)
+            if why:
+                raise ValueError("flag_truncated: " + why)
         self.eng = lib.Engine(spc, self.N, self.m, device=self.device)
         self.slots = []
         # int16 input + LLR primary: the kernels read the raw samples themselves (adp_detect_llr_i16) -- no float32 matrix is made
-        self.native_i16 = self.i16 and primary == "llr" and self.m % 4 == 0
+        self.native_i16 = self.i16 and primary == "llr" and self.m % 4 == 0 and not self.flag_truncated
         # the float32 minibatch made on the device (calibrated and / or laid out from packed reads); one: detect is serial
         # (native int16 + packed reads: the raw int16 matrix instead)
         self.dsig16 = None
@@ -139,14 +148,17 @@ class HostPipeline:
         if self.primary == "llr":
             # (the staging slots are NaN padded by the reader / the on-device calibration: the passes may stop at each read's end)
             rows, mbs = self.eng.detect_llr_rows(dsig, dlen, n, self.mb, with_start_peak=self.with_start_peak, device_ptrs=True,
-                                                 tails_nan=True)
+                                                 tails_nan=True, flag_truncated=self.flag_truncated)
             return rows, mbs
         if self.primary == "start_peak":
             return self.eng.detect_start_peak_rows(dsig, dlen, n, self.mb, device_ptrs=True), None
         from .detect import cnn as _cnn
 
         # (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
-        detect = _cnn.detect_rows_device_second_opinion if self.second_opinion else _cnn.detect_rows_device
+        if self.second_opinion:
+            return _cnn.detect_rows_device_second_opinion(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb,
+                                                          flag_truncated=self.flag_truncated), None
+        detect = _cnn.detect_rows_device_truncated if self.flag_truncated else _cnn.detect_rows_device
         return detect(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
 
     # -- driver -------------------------------------------------------------------------------

@@ -75,6 +75,10 @@ extern "C" {
                                       call, where cfg.fallback_to_llr_short_reads is set: the rows are combined_detect_cnn's */
 #define ADP_CNN_SECOND_LLR (1 << 18) /* adp_detect_cnn: a read whose row fails gets the row of combined_detect_llr2 on its minibatch, if
                                       that row passes (an extension; adp_row.reserved_ bit 0 marks such a row) */
+#define ADP_FLAG_TRUNCATED (1 << 19) /* adp_detect_llr / adp_detect_cnn: flag poly(A) tails cut off by the preload window (an extension,
+                                      see adp_detect_llr; adp_row.reserved_ bits 1 and 2) */
+#define ADP_POLYA_TRUNCATED (1 << 20) /* adp_validate_candidates: Boundaries.polya_truncated is True for every read -- the RNA partition
+                                      is all None (adapted/partition/signal_partitions.py:74-77) */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -154,9 +158,15 @@ typedef struct adp_row {
     int32_t open_pores[ADP_MAX_OPEN_PORES]; /* the first ADP_MAX_OPEN_PORES positions */
     int32_t open_pores_more;   /* n_open_pores > ADP_MAX_OPEN_PORES: the WHOLE list lies at this offset of the call's
                                   open-pore arena (adp_open_pores_arena); -1 otherwise */
-    int32_t reserved_;         /* bit 0: the row was made by the LLR second opinion of adp_detect_cnn (ADP_CNN_SECOND_LLR): its
-                                  primary columns are the LLR's.  0 in every other row of every call */
+    int32_t reserved_;         /* ADP_ROW_* bits.  bit 0: the row was made by the LLR second opinion of adp_detect_cnn
+                                  (ADP_CNN_SECOND_LLR): its primary columns are the LLR's.  bit 1: the poly(A) runs into the end of the
+                                  preloaded window (ADP_FLAG_TRUNCATED): polya_end is the window's end, the RNA partition all None.
+                                  bit 2: the call looked for that (set in EVERY row of a call made with ADP_FLAG_TRUNCATED, so that a
+                                  row says by itself whether "not truncated" was decided or never asked).  0 in every other row */
 } adp_row;
+#define ADP_ROW_FROM_SECOND_LLR 1
+#define ADP_ROW_POLYA_TRUNCATED 2
+#define ADP_ROW_TRUNC_LOOKED 4
 
 typedef struct adp_handle adp_handle;
 
@@ -198,7 +208,24 @@ int adp_synchronize(adp_handle *h);
  * MI355X the overlap buys no time (profiles/r03_overlap_*), a smaller workspace is what grouping is for.
  * N1 (the minibatch's median / MAD): minibatches of at least ADP_N1_FUSED_MIN samples (default 2^22 = minibatch x max_obs_trace;
  * the reference's defaults are 1000 x 16 000) take ONE verified pass over the signal, smaller ones three or four; the values are
- * the exact np.nanmedian / MAD either way. */
+ * the exact np.nanmedian / MAD either way.
+ * With ADP_FLAG_TRUNCATED in `flags` (rows_out given; an extension, off by default -- the reference ships the column
+ * polya_truncated and never sets it, combined.py:606) the call ends with a look at every read's final row: does the poly(A) run
+ * into the end of the preloaded window?  With obs_end = min(full_len, m), W = cfg.median_shift_window and ae = the row's primary
+ * adapter end, a read is ELIGIBLE when full_len > m (a read that simply ends inside its poly(A) was not cut by the preload), its
+ * row is neither an exception row nor one of a dropped minibatch, ae is present and > 0, adapter_med is present and
+ * ae + W <= obs_end.  T1, on the eligible reads: the last W observed samples look like poly(A) -- the first four entries (mean,
+ * var, med, range) of the check vector of mean_var_shift_polyA_check(signal[:obs_end], obs_end - W, obs_end, less_signal_ok =
+ * True) hold, with cfg.pA_mean_range, or pA_mean_adapter_med_scale_range x the row's adapter_med where that range is empty (a NaN
+ * in the window fails it).  T2, on the reads that passed T1: the call's own validation with the boundaries (ae, obs_end), k = 1
+ * and Boundaries.polya_truncated = True, i.e. the reference's gates decide whether everything observed behind the adapter is
+ * poly(A).  Where T2's row passes it REPLACES the read's row with bit 1 of adp_row.reserved_ set; the primary's poly(A) end, cand[],
+ * the start-peak columns and start_peak_type and bit 0 of reserved_ stay those of the first row.  Every other row keeps its
+ * bytes, apart from bit 2 of reserved_, which the flag sets in every row of the call.  T2's open-pore lists share the call's
+ * arena; adp_debug_fetch(12) has the counts.  ADP_ERR_UNSUPPORTED, before anything is launched: mvs_detect_check == 0,
+ * mvs_detect_overwrite != 0, ADP_LAYOUT_SINGLE_READ, adp_detect_llr_i16, adp_detect_start_peak, W > 4096, or a
+ * pA_mean_window / pA_var_window outside [1, W - 3] (T1 is the windowed form of the check).  Without the flag every row of every
+ * call keeps the bytes it had before the flag existed. */
 int adp_detect_llr(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
                    int minibatch, int flags, adp_row *rows_out, int32_t *mb_status);
 
@@ -258,11 +285,15 @@ int adp_cnn_topk(adp_handle *h, const float *scores_dev, const int64_t *adapter_
  * minibatch), then the validation with those boundaries (k = 1).  Where that row passes it REPLACES the read's row, with bit 0 of
  * adp_row.reserved_ set; otherwise the CNN path's row stays, byte for byte.  A minibatch whose LLR status is not ADP_MB_OK (where
  * combined_detect_llr2 raises) gives none of its reads a second opinion.  Rows of reads that pass the CNN path are never touched;
- * bounds_out stays what cnn_detect returned; the second rows' open-pore lists share the call's arena. */
+ * bounds_out stays what cnn_detect returned; the second rows' open-pore lists share the call's arena.
+ * ADP_FLAG_TRUNCATED: as for adp_detect_llr, on the rows behind all of the above (a second-opinion row that is flagged keeps
+ * bit 0 of reserved_). */
 int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
                    adp_row *rows_out, int64_t *bounds_out);
 /* Validate with explicit primary boundaries: bounds int64 [n_reads, 1 + k] = adapter_end, k poly(A)
- * candidates (0 terminates), exactly what cnn_detect_boundaries hands to validate_boundaries. */
+ * candidates (0 terminates), exactly what cnn_detect_boundaries hands to validate_boundaries.
+ * ADP_POLYA_TRUNCATED in `flags`: Boundaries.polya_truncated is True for every read, so its RNA partition is all None
+ * (ADP_ERR_UNSUPPORTED with mvs_detect_overwrite, where the reference's poly(A) end then takes another branch, combined.py:548-562). */
 int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
                             const int64_t *bounds, int k, int flags, adp_row *rows_out);
 
@@ -519,7 +550,9 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *         median / MAD misses, 22 / 23 N1 heavy keys / samples; the rest: phase cycles of -DADP_PHASE_TIMING builds
  *       10 int32[3], the fallback of the last adp_detect_cnn call: reads selected, exception rows made, rows re-validated
  *       11 int32[4], the LLR second opinion of the last adp_detect_cnn call: reads selected, rows replaced, rows re-validated and
- *          still failing, minibatches (with a selected read) that gave none */
+ *          still failing, minibatches (with a selected read) that gave none
+ *       12 int32[3], the truncation look of the last adp_detect_llr / adp_detect_cnn call made with ADP_FLAG_TRUNCATED: eligible
+ *          reads, reads whose tail window looks like poly(A) (T1), rows replaced */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
