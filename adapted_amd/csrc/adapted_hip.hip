@@ -1229,14 +1229,20 @@ int adp_cnn_predict(adp_handle *h, const float *scores_dev, int n_reads, int min
     return ADP_OK;
 }
 
-// C1 on the handle's stream: pooled values (k_cnn_pool), then their per-read median / MAD scaling in place (k_cnn_prepare)
-static int launch_cnn_prepare(adp_handle *h, const float *dsig, int n_reads, int m, int off, int ds, int Lc, float *dout)
+// C1 on the handle's stream: pooled values (k_cnn_pool), then their per-read median / MAD scaling in place (k_cnn_prepare).
+// sp_head (the fused start-peak scan of a detect call, else null): k_sp_head's state of these reads, which K1 riding the pooling
+// pass (k_cnn_pool<true>) completes for k_sp_tail
+static int launch_cnn_prepare(adp_handle *h, const float *dsig, int n_reads, int m, int off, int ds, int Lc, float *dout, SpHead *sp_head = nullptr)
 {
     if (h->npk.ensure((size_t)n_reads * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; } // (npk: unused on this path)
     int32_t *nan_cnt = h->npk.as<int32_t>();
     HIPCHK(hipMemsetAsync(nan_cnt, 0, (size_t)n_reads * 4, h->stream));
     { Scope s(h, "k_cnn_pool");
-      hipLaunchKernelGGL(k_cnn_pool, dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt); }
+      if (sp_head)
+          hipLaunchKernelGGL(k_cnn_pool<true>, dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt,
+                             sp_head, (float)h->cfg.open_pore_pa);
+      else
+          hipLaunchKernelGGL(k_cnn_pool<false>, dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt); }
     { Scope s(h, "k_cnn_prepare");
       hipLaunchKernelGGL(k_cnn_prepare, dim3(n_reads), dim3(64), 0, h->stream, n_reads, Lc, dout, (const int32_t *)nan_cnt); }
     return 0;
@@ -1538,8 +1544,20 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
 // copy engine's signal and the host for the kernel's).  so_select: the second opinion's selection, in the same place.
 static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride);
 static int cnn_second_select(adp_handle *h, int n, const adp_row *rows);
+// the start-peak overlay of the CNN path (ADP_WITH_START_PEAK): can K1 ride the pooling pass?
+static bool cnn_sp_fused(const adp_handle *h)
+{
+    const adp_cfg &c = h->cfg;
+    return c.sp_downscale_factor == c.downscale_factor && c.min_obs_adapter % c.downscale_factor == 0 && env_int("ADP_SP_FUSED", 1) != 0;
+}
+static void cnn_sp_decorate(adp_handle *h, const SpOut *sp, adp_row *rows, int n)
+{
+    hipLaunchKernelGGL(k_sp_decorate, dim3((n + 255) / 256), dim3(256), 0, h->stream, sp, rows, n, 0, (const int32_t *)nullptr);
+}
+// sp_out (ADP_WITH_START_PEAK, else null): K1's results of these reads -- a slice of the CALL's buffer, the owner handle's, because
+// the phases behind the first pass run there -- are computed beside the pass and overlaid on its rows (k_sp_decorate, mode 0).
 static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
-                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false, bool so_select = false)
+                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false, bool so_select = false, SpOut *sp_out = nullptr)
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     const int Lc = (m - off + ds - 1) / ds, L1 = (Lc - 1) / 3 + 1, Lo = 3 * L1 - 2;
@@ -1547,8 +1565,33 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     hipStream_t st = h->stream;
     int rc = alloc_all(h, n_reads, false);
     if (rc) return rc;
-    rc = launch_cnn_prepare(h, dsig, n_reads, m, off, ds, Lc, h->cnn_x.as<float>());
+    // K1 riding the pooling pass (k_cnn_pool<true>): when both pooling factors agree and min_obs_adapter is a multiple of them the
+    // start-peak scan costs no sweep of its own; else, and with ADP_SP_FUSED=0, the separate k_start_peak streams the signal on the
+    // side stream beside the conv stack (matrix cores, little HBM traffic)
+    const size_t sp_lds = (size_t)64 * h->cfg.sp_downscale_factor * 4;
+    const bool sp_fused = sp_out && cnn_sp_fused(h);
+    SpHead *sp_head = nullptr;
+    if (sp_fused) {
+        if (h->sphead.ensure((size_t)n_reads * sizeof(SpHead))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        sp_head = h->sphead.as<SpHead>();
+        Scope s(h, "k_sp_head");
+        hipLaunchKernelGGL(k_sp_head<SigF32>, dim3(n_reads), dim3(64), sp_lds, st, SigF32{dsig}, dlen, n_reads, m, h->cfg, off, sp_head);
+    }
+    rc = launch_cnn_prepare(h, dsig, n_reads, m, off, ds, Lc, h->cnn_x.as<float>(), sp_head);
     if (rc) return rc;
+    if (sp_fused) {
+        const int cov0 = off / ds, cov1 = cov0 + (m - off) / ds;
+        Scope s(h, "k_sp_tail");
+        hipLaunchKernelGGL(k_sp_tail<SigF32>, dim3(n_reads), dim3(64), sp_lds, st, SigF32{dsig}, dlen, n_reads, m, h->cfg, cov0, cov1, (const SpHead *)sp_head, sp_out);
+    } else if (sp_out) {
+        HIPCHK(hipEventRecord(h->ev_fork, st)); // (the signal is staged on this stream)
+        HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+        { Scope s(h, "k_start_peak", h->stream2);
+          hipLaunchKernelGGL(k_start_peak<SigF32>, dim3(n_reads), dim3(64), sp_lds, h->stream2, SigF32{dsig}, dlen, n_reads, m, h->cfg, sp_out); }
+        HIPCHK(hipEventRecord(h->ev_join, h->stream2));
+    }
+    // (from here on an error return must not leave the side stream's scan running into the caller's next use of sp_out)
+    struct SpJoin { hipStream_t side; bool armed; ~SpJoin() { if (armed) (void)hipStreamSynchronize(side); } } sp_join{h->stream2, sp_out && !sp_fused};
     rc = cnn_forward_dev(h, h->cnn_x.as<float>(), n_reads, Lc, h->cnn_sc.as<float>());
     if (rc) return rc;
     int kk = 1;
@@ -1558,6 +1601,10 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     HIPCHK(hipMemsetAsync(h->topk_none.p, 0, (size_t)n_reads, st));
     rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, kk, n_reads, false);
     if (rc) return rc;
+    if (sp_out) {
+        if (!sp_fused) { HIPCHK(hipStreamWaitEvent(st, h->ev_join, 0)); sp_join.armed = false; }
+        cnn_sp_decorate(h, sp_out, h->rows.as<adp_row>(), n_reads);
+    }
     if (fb_select) RCCHK(cnn_fallback_select(h, dlen, n_reads, h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk));
     if (so_select) RCCHK(cnn_second_select(h, n_reads, h->rows.as<adp_row>()));
     if (rows_dst) HIPCHK(hipMemcpyAsync(rows_dst, h->rows.p, (size_t)n_reads * sizeof(adp_row), (hipMemcpyKind)rows_kind, st));
@@ -1670,6 +1717,7 @@ static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dle
 
 // ---- the LLR second opinion for reads the CNN path fails (ADP_CNN_SECOND_LLR, cnn_second_opinion.h) ------------------------------
 static bool cnn_second_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_CNN_SECOND_LLR) && rows_out; }
+static bool cnn_sp_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_WITH_START_PEAK) && rows_out; }
 // rows: the CALL's device row buffer once every read's row of the CNN path is in it (behind the first pass, and again behind the
 // fallback's merge when that ran).  The count reaches the host in arena_end's copy.
 static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
@@ -1730,6 +1778,8 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     // the fallback runs once on this handle, over the call's device row buffer, when all lanes have drained: it needs the
     // predictions of all reads here whether the caller wants them or not
     const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out);
+    // K1's results of the whole call live in this handle's buffer (adp_detect_cnn sized it): the lanes write their slices
+    SpOut *sp = cnn_sp_wanted(flags, rows_out) ? h->sp.as<SpOut>() : nullptr;
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
     if ((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || ((bounds_out || fb) && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8))) {
         g_err = "device allocation failed"; return ADP_ERR_HIP;
@@ -1752,7 +1802,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
             const int r0 = g * mb_per_group * minibatch;
             const int ng = (n - r0) < mb_per_group * minibatch ? (n - r0) : mb_per_group * minibatch;
             rc = cnn_enqueue(l, dsig + (size_t)r0 * m, dlen + r0, ng, m, minibatch, rows_dev ? rows_dev + r0 : nullptr, hipMemcpyDeviceToDevice,
-                             bounds_dev ? bounds_dev + (size_t)r0 * (1 + kk) : nullptr, hipMemcpyDeviceToDevice);
+                             bounds_dev ? bounds_dev + (size_t)r0 * (1 + kk) : nullptr, hipMemcpyDeviceToDevice, false, false, sp ? sp + r0 : nullptr);
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
@@ -1765,6 +1815,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
         h->so_n_sel = 0; h->so_counts = nullptr;
         if (rc == 0 && n_sel) {
             RCCHK(cnn_fallback_run(h, dsig, dlen, m, rows_dev, bounds_dev, 1 + kk, (int)n_sel));
+            if (sp) cnn_sp_decorate(h, sp, rows_dev, n); // (re-validated rows come bare; idempotent on the others)
             if (so) RCCHK(cnn_second_select(h, n, rows_dev)); // (the merge changed rows: select again)
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
@@ -1773,6 +1824,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
         if (rc == 0 && n_so) {
             h->so_n_sel = n_so;
             RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows_dev, (int)n_so));
+            if (sp) cnn_sp_decorate(h, sp, rows_dev, n); // (the second opinion's rows come bare)
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h);
             if (rc < 0) return rc;
@@ -1807,6 +1859,8 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     h->cnn_redo_f32 = false;
     h->fb_n_sel = 0; h->fb_counts = nullptr;
     h->so_n_sel = 0; h->so_counts = nullptr;
+    // (K1's results of the whole call: sized here, before any phase's workspace call could move the buffer under them)
+    if (cnn_sp_wanted(flags, rows_out) && h->sp.ensure((size_t)n_reads * sizeof(SpOut))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
     if (rc) return rc;
@@ -1842,13 +1896,17 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     // first pass (and once more behind a fallback merge), its count comes back in the same copy, and a call whose reads all passed
     // ends there.  Its rows' open-pore lists depend on the LLR adapter end: they may want more than the first pass did, and the
     // counter is cumulative over the call -- attempt 1 can fall short in the first pass, attempt 2 in this phase, attempt 3 holds both.
+    // The start-peak overlay (ADP_WITH_START_PEAK): K1 runs beside the first pass and decorates its rows; the fallback and the second
+    // opinion deliver whole rows of their own validation, so the overlay is applied once more to the call's row buffer behind each
+    // (k_sp_decorate is idempotent); the truncation look's merge keeps the columns (k_pt_merge).
     const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    SpOut *sp = cnn_sp_wanted(flags, rows_out) ? h->sp.as<SpOut>() : nullptr;
     const int kk = h->cfg.polya_cand_k < 1 ? 1 : h->cfg.polya_cand_k; // (the stride of the predictions, as cnn_predict_dev lays them out)
     for (int attempt = 0; attempt < 3; attempt++) {
         rc = arena_begin(h);
         if (rc) return rc;
         rc = cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         bounds_out, hipMemcpyDeviceToHost, fb, so);
+                         bounds_out, hipMemcpyDeviceToHost, fb, so, sp);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
         unsigned int n_sel = 0, n_so = 0;
@@ -1860,6 +1918,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         adp_row *merged = out_dev ? rows_out : h->rows.as<adp_row>();
         if (rc == 0 && n_sel) {
             RCCHK(cnn_fallback_run(h, dsig, dlen, m, merged, h->bounds.as<int64_t>(), 1 + kk, (int)n_sel));
+            if (sp) cnn_sp_decorate(h, sp, merged, n_reads); // (re-validated rows come bare; idempotent on the others)
             if (so) RCCHK(cnn_second_select(h, n_reads, merged)); // (the merge changed rows: select again)
             if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -1869,6 +1928,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         if (rc == 0 && n_so) {
             h->so_n_sel = n_so;
             RCCHK(cnn_second_run(h, dsig, dlen, n_reads, m, minibatch, flags, merged, (int)n_so));
+            if (sp) cnn_sp_decorate(h, sp, merged, n_reads); // (the second opinion's rows come bare)
             if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             rc = arena_end(h);

@@ -1461,10 +1461,19 @@ __global__ void k_llr_bounds(const int32_t *__restrict__ adapter_idx, const int3
 // +-FLT_MAX).  Two kernels: k_cnn_pool (a 256-thread block per read; every wave pools tiles of 64 blocks staged in LDS with
 // coalesced 16-byte loads, numpy's summation order -- sp_pooled_tile; lane-strided scalar loads ran at 1.8 TB/s) and
 // k_cnn_prepare (a wave per read: the two medians and the scaling of the pooled values, in place).
+// SP (the start-peak scan of K1 rides this pass the way it rides k_norm_pool<SIG, true>, llr_stream.h): block j of this pass is
+// start_peak.py's pooled block j + off / ds bit for bit when both pooling factors agree and off is a multiple of them -- the same
+// helper over the same samples, the same zero-filled ragged last block at m -- and the wave's tile holds its raw samples.  Every
+// complete block is compared with the read's start-peak maximum (SpHead, left by k_sp_head): the first block above it inside
+// [a2, e0), and the first raw sample above the open-pore level before op_end.  Waves take tiles out of order, so both are minima:
+// per lane, per wave, then one LDS atomicMin per wave.  k_sp_tail finishes the row.  The plain instantiation has none of this.
+template <bool SP = false>
 __global__ void __launch_bounds__(256) k_cnn_pool(const float *__restrict__ sigs, int n_reads, int m, int off, int ds, int Lc,
-                                                   float *__restrict__ out, int32_t *__restrict__ nan_cnt)
+                                                   float *__restrict__ out, int32_t *__restrict__ nan_cnt,
+                                                   SpHead *__restrict__ sp_head = nullptr, float sp_thr = 0.f)
 {
     extern __shared__ __attribute__((aligned(16))) float cp_tiles_raw[]; // 4 waves x 64 * ds floats
+    __shared__ __attribute__((aligned(16))) int s_sp[2];                 // (SP only: the plain instantiation never names it)
     const int r = blockIdx.x;
     const int ln = lane_id(), wv = threadIdx.x >> 6;
     LDS float *tile = (LDS float *)cp_tiles_raw + (size_t)wv * 64 * ds;
@@ -1472,13 +1481,41 @@ __global__ void __launch_bounds__(256) k_cnn_pool(const float *__restrict__ sigs
     const int Lseg = m - off;
     float *o = out + (size_t)r * Lc;
     int nn = 0;
+    // start-peak state of this read (SP)
+    float sp_mx = 0.f;
+    int sp_a2 = 0, sp_e0 = 0, sp_op_end = 0, sp_hit = 0x7fffffff, sp_op = 0x7fffffff;
+    const int sp_full = Lseg / ds; // complete pooled blocks of this pass: the ragged last one is left to k_sp_tail
+    const int sp_pb0 = off / ds;   // pooled index (start_peak.py's) of this pass's block 0
+    if constexpr (SP) {
+        const SpHead hd = sp_head[r];
+        sp_mx = hd.mx; sp_a2 = hd.valid ? hd.a2 : 0; sp_e0 = hd.valid ? hd.e0 : 0; sp_op_end = hd.op_end;
+        if (threadIdx.x < 2) s_sp[threadIdx.x] = 0x7fffffff;
+        __syncthreads();
+    }
     for (int j0 = wv * 64; j0 < Lc; j0 += 256) {
         const float v = sp_pooled_tile(row, Lseg, ds, j0, tile);
         const int j = j0 + ln;
         if (j < Lc) { o[j] = v; if (v != v) nn++; }
+        if constexpr (SP) {
+            if (j < sp_full) {
+                const int g = sp_pb0 + j;
+                if (g >= sp_a2 && g < sp_e0 && v > sp_mx && g < sp_hit) sp_hit = g;
+                const int i0 = off + j * ds; // raw index of the block's first sample
+                if (i0 < sp_op_end && sp_op == 0x7fffffff) {
+                    const LDS float *p = tile + ln * ds; // (the tile stays as sp_pooled_tile left it until the next one is staged)
+                    for (int k = 0; k < ds; k++) if (i0 + k < sp_op_end && p[k] > sp_thr) { sp_op = i0 + k; break; }
+                }
+            }
+        }
     }
     nn = wave_sum(nn);
     if (ln == 0 && nn) atomicAdd(&nan_cnt[r], nn);
+    if constexpr (SP) {
+        sp_hit = wave_min(sp_hit); sp_op = wave_min(sp_op);
+        if (ln == 0) { if (sp_hit != 0x7fffffff) atomicMin(&s_sp[0], sp_hit); if (sp_op != 0x7fffffff) atomicMin(&s_sp[1], sp_op); }
+        __syncthreads();
+        if (threadIdx.x == 0) { sp_head[r].hit = s_sp[0]; sp_head[r].op_body = s_sp[1]; }
+    }
 }
 
 __global__ void __launch_bounds__(64) k_cnn_prepare(int n_reads, int Lc, float *__restrict__ out, const int32_t *__restrict__ nan_cnt)

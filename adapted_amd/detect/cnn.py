@@ -199,6 +199,17 @@ def _fallback_mode(fallback: str) -> str:
     return fallback
 
 
+def _start_peak_form(with_start_peak: bool, conv: str, fallback: str):
+    """the start-peak overlay (ADP_WITH_START_PEAK) is applied inside adp_detect_cnn to the row the call finally delivers:
+    rows made or replaced on the host behind the call would come without it"""
+    if not with_start_peak:
+        return
+    if conv != "hip":
+        raise ValueError('with_start_peak runs inside the library call: conv must be "hip"')
+    if _fallback_mode(fallback) != "device":
+        raise ValueError('with_start_peak runs inside the library call: fallback must be "device"')
+
+
 def detect_rows_device(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
                        fallback: str = "device") -> np.ndarray:
     """combined_detect_cnn over a DEVICE-resident batch (pointers) -> adp_row[]; ONE library call (adp_detect_cnn), the
@@ -266,47 +277,71 @@ def _second_opinion_form(conv: str, fallback: str):
         raise ValueError('the LLR second opinion / the truncation look runs inside the library call: fallback must be "device"')
 
 
-def detect_rows_truncated(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+def detect_rows_start_peak(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+    """detect_rows with the start-peak overlay (ADP_WITH_START_PEAK, include/adapted_hip.h): every row is detect_rows' row with the
+    start-peak columns of detect_rna_start_peak and start_peak_type filled as combined_detect_llr2's option of that name fills
+    them.  An extension: the reference keeps one primary per run.  ONE library call, so neither conv = "torch" nor
+    fallback = "host".  (detect_rows itself keeps the parameters it was introduced with; the truncated / second-opinion forms
+    take ``with_start_peak``.)"""
+    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, second_opinion=False, with_start_peak=True)
+
+
+def detect_rows_device_start_peak(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
+                                  fallback: str = "device") -> np.ndarray:
+    """detect_rows_device with the start-peak overlay.  ONE library call over the resident batch."""
+    return detect_rows_device_second_opinion(eng, dsig, dlen, n, lens_host, model, spc, minibatch=minibatch, fallback=fallback,
+                                             second_opinion=False, with_start_peak=True)
+
+
+def detect_rows_truncated(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device",
+                          with_start_peak: bool = False) -> np.ndarray:
     """detect_rows with the truncation look behind it (ADP_FLAG_TRUNCATED, include/adapted_hip.h): a read whose poly(A) runs into
     the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
     (``reserved_`` bit 1); every row carries bit 2.  An extension: the reference never sets ``polya_truncated``.  ONE library call."""
-    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, flag_truncated=True, second_opinion=False)
+    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, flag_truncated=True, second_opinion=False,
+                                      with_start_peak=with_start_peak)
 
 
 def detect_rows_device_truncated(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
-                                 fallback: str = "device") -> np.ndarray:
+                                 fallback: str = "device", with_start_peak: bool = False) -> np.ndarray:
     """detect_rows_device with the truncation look behind it.  ONE library call over the resident batch."""
     return detect_rows_device_second_opinion(eng, dsig, dlen, n, lens_host, model, spc, minibatch=minibatch, fallback=fallback,
-                                             flag_truncated=True, second_opinion=False)
+                                             flag_truncated=True, second_opinion=False, with_start_peak=with_start_peak)
 
 
 def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device",
-                               flag_truncated: bool = False, second_opinion: bool = True) -> np.ndarray:
+                               flag_truncated: bool = False, second_opinion: bool = True, with_start_peak: bool = False) -> np.ndarray:
     """detect_rows with the LLR second opinion (ADP_CNN_SECOND_LLR): a read whose row fails gets the row combined_detect_llr2
     returns for it on this batch, where that row passes (``reserved_`` bit 0 marks it; lib.rows_to_results names its primary
-    columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call."""
+    columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call.
+    with_start_peak: the overlay of detect_rows_start_peak on the rows this call delivers, the rescued ones included."""
+    _start_peak_form(with_start_peak, conv, fallback)
     _second_opinion_form(conv, fallback)
     n = sig.shape[0]
     if int(spc.cnn_boundaries.polya_cand_k) < 1:
         raise ValueError("polya_cand_k must be >= 1")
     ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=second_opinion, flag_truncated=flag_truncated)[0]
+    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=second_opinion, flag_truncated=flag_truncated,
+                               with_start_peak=with_start_peak)[0]
 
 
 def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
-                                      fallback: str = "device", flag_truncated: bool = False, second_opinion: bool = True) -> np.ndarray:
+                                      fallback: str = "device", flag_truncated: bool = False, second_opinion: bool = True,
+                                      with_start_peak: bool = False) -> np.ndarray:
     """detect_rows_device with the LLR second opinion, per minibatch as combined_detect_llr2 would see it (its normalisation is
-    the minibatch's).  ONE library call over the resident batch."""
+    the minibatch's).  ONE library call over the resident batch.  with_start_peak: as detect_rows_second_opinion's."""
+    _start_peak_form(with_start_peak, "hip", fallback)
     _second_opinion_form("hip", fallback)
     ensure_weights(eng, model, spc)
     return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True, second_opinion=second_opinion,
-                               flag_truncated=flag_truncated)[0]
+                               flag_truncated=flag_truncated, with_start_peak=with_start_peak)[0]
 
 
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0,
-                            flag_truncated: bool = False) -> List[DetectResults]:
+                            flag_truncated: bool = False, with_start_peak: bool = False) -> List[DetectResults]:
     """combined_detect_cnn, and for the reads it fails combined_detect_llr2 on the same batch where that passes (an extension;
-    such results carry ``llr_adapter_end`` / ``llr_polya_end`` instead of the ``cnn_*`` pair).  Always a list."""
+    such results carry ``llr_adapter_end`` / ``llr_polya_end`` instead of the ``cnn_*`` pair).  Always a list.
+    with_start_peak: as combined_detect_cnn's."""
     from .combined import _as_batch, get_engine
 
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
@@ -316,21 +351,29 @@ def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.n
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = detect_rows_second_opinion(eng, sig, lens, model, spc, flag_truncated=flag_truncated)
+        rows = detect_rows_second_opinion(eng, sig, lens, model, spc, flag_truncated=flag_truncated, with_start_peak=with_start_peak)
     return lib.rows_to_results(rows, "cnn", consume=True)
 
 
 def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
-                        device: int = 0, conv: str = "hip", flag_truncated: bool = False) -> Union[List[DetectResults], DetectResults]:
+                        device: int = 0, conv: str = "hip", flag_truncated: bool = False,
+                        with_start_peak: bool = False) -> Union[List[DetectResults], DetectResults]:
     """model: the nn.Sequential of load_cnn_model, a dict of weight arrays (load_cnn_weights), or None (the config's model).
-    flag_truncated: as combined_detect_llr2's (an extension, off by default)."""
+    flag_truncated: as combined_detect_llr2's (an extension, off by default).
+    with_start_peak: the ``start_peak_*`` fields of detect_rna_start_peak on every result, as combined_detect_llr2's option of
+    that name fills them (an extension, off by default: the reference keeps one primary per run); conv must be "hip"."""
     from .combined import _as_batch, get_engine
 
+    _start_peak_form(with_start_peak, conv, "device")
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
     n, m = sig.shape
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = (detect_rows_truncated if flag_truncated else detect_rows)(eng, sig, lens, model, spc, conv=conv)
+        if flag_truncated or with_start_peak:
+            rows = detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, flag_truncated=flag_truncated, second_opinion=False,
+                                              with_start_peak=with_start_peak)
+        else:
+            rows = detect_rows(eng, sig, lens, model, spc, conv=conv)
     res = lib.rows_to_results(rows, "cnn", consume=True)
     return res if len(res) > 1 else res[0]

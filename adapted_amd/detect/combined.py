@@ -153,16 +153,18 @@ def validate_boundaries(signal: np.ndarray, boundaries: Boundaries, spc, full_si
 
 
 def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
-                        device: int = 0, conv: str = "hip", flag_truncated: bool = False) -> Union[List[DetectResults], DetectResults]:
+                        device: int = 0, conv: str = "hip", flag_truncated: bool = False,
+                        with_start_peak: bool = False) -> Union[List[DetectResults], DetectResults]:
     from . import cnn as _cnn
 
-    return _cnn.combined_detect_cnn(batch_of_signals, full_signal_lens, model, spc, device=device, conv=conv, flag_truncated=flag_truncated)
+    return _cnn.combined_detect_cnn(batch_of_signals, full_signal_lens, model, spc, device=device, conv=conv, flag_truncated=flag_truncated,
+                                    with_start_peak=with_start_peak)
 
 
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
                             device: int = 0) -> List[DetectResults]:
     """The CNN operator with an LLR second opinion for the reads it fails (an extension: adapted_amd/detect/cnn.py; that module's
-    function of the same name also takes ``flag_truncated`` -- this one keeps the parameters it was introduced with)."""
+    function of the same name also takes ``flag_truncated`` and ``with_start_peak`` -- this one keeps the parameters it was introduced with)."""
     from . import cnn as _cnn
 
     return _cnn.combined_detect_cnn_llr(batch_of_signals, full_signal_lens, model, spc, device=device)

@@ -1091,13 +1091,18 @@ class Engine:
         return out
 
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
-                        want_bounds: bool = True, flag_truncated: bool = False, fallback: bool = False, second_opinion: bool = False):
+                        want_bounds: bool = True, flag_truncated: bool = False, with_start_peak: bool = False, fallback: bool = False,
+                        second_opinion: bool = False):
         """combined_detect_cnn -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k]).  fallback: with the short-read
         fallback applied on the device (ADP_CNN_FALLBACK; where the configuration has it on); without it the rows are those in
         front of the fallback.  bounds: what cnn_detect returned, either way.  second_opinion: reads whose row fails get the
         row of the LLR path on their minibatch where that one passes (ADP_CNN_SECOND_LLR; such rows carry reserved_ bit 0).
-        flag_truncated: the truncation look behind all of that, as in detect_llr_rows (ADP_FLAG_TRUNCATED)."""
+        flag_truncated: the truncation look behind all of that, as in detect_llr_rows (ADP_FLAG_TRUNCATED).
+        with_start_peak: the start-peak columns of detect_rna_start_peak overlaid on the row the call delivers, whichever phase
+        made it, as in detect_llr_rows (ADP_WITH_START_PEAK); nothing else of any row changes."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
+        if with_start_peak:
+            flags |= ADP_WITH_START_PEAK
         if fallback:
             flags |= ADP_CNN_FALLBACK
         if flag_truncated:

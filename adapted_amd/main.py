@@ -49,7 +49,7 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-j", "--num_proc", type=int, default=None, help="accepted for compatibility; the GPU engine does not use a process pool")
     d.add_argument("-b", "--batch_size", type=int, default=4000, help="Number of reads per output file.")
     d.add_argument("-s", "--minibatch_size", type=int, default=1000, help="Number of reads per minibatch (normalisation unit).")
-    d.add_argument("--start_peak", action="store_true", help="(extension) also fill the start_peak_* columns on the LLR path")
+    d.add_argument("--start_peak", action="store_true", help="(extension) LLR and CNN primaries: also fill the start_peak_* columns and start_peak_open_pore_type of every read")
     d.add_argument("--second_opinion", type=str, choices=["llr"], default=None,
                    help="(extension) CNN primary: reads it fails get the LLR detector's boundaries where those pass validation")
     d.add_argument("--flag_truncated", action="store_true",

@@ -31,7 +31,9 @@ class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
                  flag_truncated: bool = False, second_opinion: Optional[str] = None):
-        """second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
+        """with_start_peak: the start-peak columns on every row of the LLR and CNN primaries (an extension; the start-peak primary
+        fills them anyway).
+        second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
         minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py).
         flag_truncated: every detect call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension; LLR and CNN
         primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one."""
@@ -155,11 +157,11 @@ class HostPipeline:
         from .detect import cnn as _cnn
 
         # (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
-        if self.second_opinion:
+        if self.second_opinion or self.flag_truncated or self.with_start_peak:
             return _cnn.detect_rows_device_second_opinion(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb,
-                                                          flag_truncated=self.flag_truncated), None
-        detect = _cnn.detect_rows_device_truncated if self.flag_truncated else _cnn.detect_rows_device
-        return detect(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
+                                                          flag_truncated=self.flag_truncated, second_opinion=bool(self.second_opinion),
+                                                          with_start_peak=bool(self.with_start_peak)), None
+        return _cnn.detect_rows_device(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
 
     # -- driver -------------------------------------------------------------------------------
     def run(self, fill: Callable[[Callable[[], Tuple[np.ndarray, np.ndarray]]], Iterable[Tuple[int, object]]],

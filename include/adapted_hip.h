@@ -65,7 +65,7 @@ extern "C" {
 /* memory-kind flags */
 #define ADP_IN_DEVICE 1            /* signals / full_len are device pointers */
 #define ADP_OUT_DEVICE 2           /* rows_out is a device pointer */
-#define ADP_WITH_START_PEAK 4      /* LLR path: also fill the start_peak_* columns (extension) */
+#define ADP_WITH_START_PEAK 4      /* adp_detect_llr / adp_detect_cnn: also fill the start_peak_* columns (extension) */
 #define ADP_TOPK_NONE 8            /* adp_validate_candidates: polya_end_topk is None (k must be 1) */
 #define ADP_BOUNDS_HOST 16         /* adp_validate_candidates: `bounds` is host memory even though ADP_IN_DEVICE is set */
 #define ADP_TAILS_NAN 32           /* adp_detect_llr: the caller guarantees that row r is NaN from min(full_len[r], m) on (the
@@ -287,7 +287,16 @@ int adp_cnn_topk(adp_handle *h, const float *scores_dev, const int64_t *adapter_
  * combined_detect_llr2 raises) gives none of its reads a second opinion.  Rows of reads that pass the CNN path are never touched;
  * bounds_out stays what cnn_detect returned; the second rows' open-pore lists share the call's arena.
  * ADP_FLAG_TRUNCATED: as for adp_detect_llr, on the rows behind all of the above (a second-opinion row that is flagged keeps
- * bit 0 of reserved_). */
+ * bit 0 of reserved_).
+ * ADP_WITH_START_PEAK (rows_out given; an extension, the reference keeps one primary per run): every read's row is exactly the row
+ * of the call without the flag, with the result of detect_rna_start_peak (adapted/detect/start_peak.py:7-119, the rna_start_peak
+ * numbers of cfg) overlaid as on the LLR path: a row made for an exception the reference raises (ADP_F_IS_EXCEPTION) stays bare; a
+ * read whose start-peak result is not valid gets nothing; every other read gets start_peak_idx / _pa / _next_max_idx / _next_max_pa
+ * with their `present` bits, start_peak_open_pore_idx only when the read is flagged, and start_peak_type.  No other byte of a row
+ * changes -- success and fail_code included: failing on a flag is the start-peak primary's -- and neither does bounds_out.  This
+ * holds for the row the call finally delivers, whichever phase made it (first pass, fallback, second opinion, truncation look).
+ * The scan rides the pooling pass of prepare_data when cfg.sp_downscale_factor == cfg.downscale_factor and min_obs_adapter is a
+ * multiple of it (ADP_SP_FUSED=0 in the environment: never), else it streams the signal once more beside the conv stack. */
 int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
                    adp_row *rows_out, int64_t *bounds_out);
 /* Validate with explicit primary boundaries: bounds int64 [n_reads, 1 + k] = adapter_end, k poly(A)
