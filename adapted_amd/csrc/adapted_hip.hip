@@ -256,8 +256,9 @@ hipEvent_t next_event(adp_handle *h)
     return h->ev_pool[h->ev_used++];
 }
 
-// what a call reports through adp_kernel_times starts empty (the repeats of a call reset it too)
-static void reset_profile(adp_handle *h) { h->prof.clear(); h->ev_used = 0; h->last_grouped = false; }
+// what a call reports through adp_kernel_times starts empty (a handle's or a lane's; the repeats of a call drop it too)
+static void drop_profile(adp_handle *h) { h->prof.clear(); h->ev_used = 0; }
+static void reset_profile(adp_handle *h) { drop_profile(h); h->last_grouped = false; }
 // a call that works on the device: the handle's device current, reset_profile
 int begin_call(adp_handle *h) { HIPCHK(hipSetDevice(h->device)); reset_profile(h); return ADP_OK; }
 
@@ -335,11 +336,16 @@ static int env_int(const char *name, int dflt)
 // ---- the open-pore arena of one API call --------------------------------------------------
 // arena_begin: allocated, counter zeroed (on the handle's stream, ahead of every kernel of the call).  arena_end (the call's
 // stream(s) drained): how much the call wanted; > capacity = lists were dropped: grow and tell the caller to run again.
+// op_used: [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read
+// fallback, [3] reads selected for its LLR second opinion, [4] reads whose tail window passed the truncation look's T1 -- zeroed by
+// arena_begin, read by arena_end.  Behind them the phases' counts for adp_debug_fetch (10 / 11 / 12), zeroed by the phase that runs:
+// the fallback's [0] exception rows made, [1] rows re-validated; the second opinion's [0] rows replaced, [1] re-validated and still
+// failing, [2] minibatches without one; the truncation look's [0] eligible reads, [1] T1 passed, [2] rows replaced
+enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_END = 13 };
+static unsigned int *phase_counts(adp_handle *h, int opw) { return h->op_used.as<unsigned int>() + opw; }
 static int arena_begin(adp_handle *h)
 {
-    if (h->op_used.ensure(32) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    // [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read fallback,
-    // [3] reads selected for its LLR second opinion, [4] reads whose tail window passed the truncation look's T1 (ADP_FLAG_TRUNCATED)
+    if (h->op_used.ensure(OPW_END * 4) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     HIPCHK(hipMemsetAsync(h->op_used.p, 0, 20, h->stream));
     return 0;
 }
@@ -368,6 +374,44 @@ static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = null
     if ((size_t)used * 4 <= h->op_arena.cap) return 0;
     if (h->op_arena.ensure((size_t)used * 8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     return 1;
+}
+
+// A call's attempts on the arena: attempt() runs behind arena_begin -> 0 done, 1 run the call again (arena_end grew the arena, or
+// the conv stack goes to float32), < 0 error.  A repeat drops what the attempt recorded in the handle's profile and its lanes'.
+template <class F>
+static int call_attempts(adp_handle *h, adp_handle *const *lanes, int n_lanes, F &&attempt)
+{
+    for (int a = 0; a < 3; a++) {
+        RCCHK(arena_begin(h));
+        const int rc = attempt();
+        if (rc <= 0) return rc;
+        drop_profile(h);
+        for (int i = 0; i < n_lanes; i++) drop_profile(lanes[i]);
+    }
+    g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short";
+    return ADP_ERR_CAPACITY;
+}
+
+// a phase's per-subset arrays, carved from the handle's sub_ws in 16-byte aligned pieces: `pieces(Carve &)` lists them once and runs
+// twice -- first to add up the sizes (the buffer grows before anything of the phase is enqueued), then to hand out the pointers
+struct Carve {
+    char *base = nullptr;
+    size_t off = 0;
+    template <class T> T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += (count * sizeof(T) + 15) & ~(size_t)15;
+        return p;
+    }
+};
+template <class F> static int sub_carve(adp_handle *h, F &&pieces)
+{
+    Carve c;
+    pieces(c);
+    if (h->sub_ws.ensure(c.off)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    c = Carve{h->sub_ws.as<char>(), 0};
+    pieces(c);
+    return 0;
 }
 
 template <int THREADS, int HB, int U>
@@ -745,7 +789,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
 }
 
 // ---- the truncation look (ADP_FLAG_TRUNCATED, polya_truncated.h) --------------------------------------------------------------
-static bool trunc_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_FLAG_TRUNCATED) && rows_out; }
+static bool trunc_wanted(int flags, const adp_row *rows) { return (flags & ADP_FLAG_TRUNCATED) && rows; }
 // what the flag cannot go with, said before anything is launched
 static int trunc_supported(const adp_handle *h)
 {
@@ -764,17 +808,16 @@ static int trunc_supported(const adp_handle *h)
 // host in arena_end's copy (n_pt).
 static int trunc_enqueue_t1(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows)
 {
-    // verdicts n | counts 16 (8-byte aligned behind the verdicts)
-    const size_t voff = ((size_t)n + 15) & ~(size_t)15;
-    if (h->pt_sel.ensure((size_t)n * 4) || h->pt_ws.ensure(voff + 16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    int8_t *verdict = h->pt_ws.as<int8_t>();
-    unsigned int *counts = reinterpret_cast<unsigned int *>(verdict + voff);
-    h->pt_counts = counts; h->pt_n_t1 = 0;
-    HIPCHK(hipMemsetAsync(counts, 0, 16, h->stream));
+    int8_t *verdict;
+    if (h->pt_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    RCCHK(sub_carve(h, [&](Carve &c) { verdict = c.take<int8_t>(n); }));
+    unsigned int *counts = phase_counts(h, OPW_PT);
+    h->pt_looked = true;
+    HIPCHK(hipMemsetAsync(counts, 0, 12, h->stream));
     { Scope s(h, "k_pt_t1");
       hipLaunchKernelGGL(k_pt_t1, dim3(n), dim3(64), (size_t)3 * h->cfg.median_shift_window * 4, h->stream, dsig, dlen, n, m, h->cfg, rows, verdict); }
     { Scope s(h, "k_pt_select");
-      hipLaunchKernelGGL(k_pt_select, dim3(1), dim3(PT_SEL_THREADS), 0, h->stream, (const int8_t *)verdict, n, h->pt_sel.as<int32_t>(),
+      hipLaunchKernelGGL(k_pt_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, (const int8_t *)verdict, n, h->pt_sel.as<int32_t>(),
                          h->op_used.as<unsigned int>() + 4, counts); }
     return 0;
 }
@@ -785,38 +828,41 @@ static int trunc_run_t2(adp_handle *h, const float *dsig, const int32_t *dlen, i
     int rc = alloc_all(h, n_t1, false);
     if (rc) return rc;
     const size_t N = (size_t)n_t1;
-    // bounds of the validation 16 N | full_len 4 N | topk_none N
-    if (h->pt_b2.ensure(N * 21) || h->pt_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    int64_t *b2 = h->pt_b2.as<int64_t>();
-    int32_t *dlen_sub = reinterpret_cast<int32_t *>(b2 + 2 * N);
-    int8_t *tsub = reinterpret_cast<int8_t *>(dlen_sub + N);
+    int64_t *b2; int32_t *dlen_sub; int8_t *tsub; adp_row *rows2;
+    RCCHK(sub_carve(h, [&](Carve &c) { // (T1's verdicts are spent)
+        b2 = c.take<int64_t>(2 * N); dlen_sub = c.take<int32_t>(N); tsub = c.take<int8_t>(N); rows2 = c.take<adp_row>(N);
+    }));
     const int32_t *sel = h->pt_sel.as<int32_t>();
     { Scope s(h, "k_pt_gather");
       hipLaunchKernelGGL(k_pt_gather, dim3((n_t1 + 255) / 256), dim3(256), 0, h->stream, sel, n_t1, m, dlen, (const adp_row *)rows, dlen_sub, b2, tsub); }
-    const ValBufs vb{b2, tsub, h->pt_rows.as<adp_row>()};
+    const ValBufs vb{b2, tsub, rows2};
     rc = launch_validate(h, SigIdx{dsig, sel}, dlen_sub, n_t1, m, 1, n_t1, false, &vb, true);
     if (rc) return rc;
     { Scope s(h, "k_pt_merge");
-      hipLaunchKernelGGL(k_pt_merge, dim3(n_t1), dim3(64), 0, h->stream, sel, n_t1, (const adp_row *)h->pt_rows.as<adp_row>(), rows, h->pt_counts); }
+      hipLaunchKernelGGL(k_pt_merge, dim3(n_t1), dim3(64), 0, h->stream, sel, n_t1, (const adp_row *)rows2, rows, phase_counts(h, OPW_PT)); }
     HIPCHK(hipGetLastError());
     return 0;
 }
-// The look behind a call whose rows are final in `rows` (device) and whose stream(s) have drained: -> 0 done, 1 run the call
-// again (arena grown), < 0 error.  t1_enqueued: the caller put trunc_enqueue_t1 in front of its own arena_end and hands the count in.
-static int trunc_finish(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows, bool t1_enqueued, unsigned int n_pt)
+// The look behind a call whose rows are final in `rows` (device) and whose lanes, if any, have drained: T1 and the selection in
+// front of the arena counter, which brings their count, then T2 where a tail window passed -> 0 done, 1 run the call again (arena
+// grown), < 0 error.
+static int trunc_finish(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows)
 {
-    int rc;
-    if (!t1_enqueued) {
-        RCCHK(trunc_enqueue_t1(h, dsig, dlen, n, m, rows));
-        rc = arena_end(h, false, nullptr, nullptr, &n_pt); // (with n_pt it copies the counter and waits for the stream)
-        if (rc) return rc;
-    }
-    h->pt_n_t1 = n_pt;
-    if (!n_pt) return 0;
+    unsigned int n_pt = 0;
+    RCCHK(trunc_enqueue_t1(h, dsig, dlen, n, m, rows));
+    const int rc = arena_end(h, false, nullptr, nullptr, &n_pt); // (with n_pt it copies the counter and waits for the stream)
+    if (rc || !n_pt) return rc;
     RCCHK(trunc_run_t2(h, dsig, dlen, m, rows, (int)n_pt));
     HIPCHK(hipStreamSynchronize(h->stream));
     return arena_end(h);
 }
+// What the LLR path does behind llr_enqueue's last group, in both execution forms: the arena counter and, with look, the truncation
+// look on the rows (float32 signals only: adp_detect_llr_i16 refuses the flag) -> as arena_end
+static int llr_after_first_pass(adp_handle *h, SigF32 dsig, const int32_t *dlen, int n, int m, adp_row *rows, bool look)
+{
+    return look ? trunc_finish(h, dsig.base, dlen, n, m, rows) : arena_end(h);
+}
+static int llr_after_first_pass(adp_handle *h, SigI16, const int32_t *, int, int, adp_row *, bool) { return arena_end(h); }
 
 // how a call's minibatches are cut into groups: ADP_GROUPS (unset / 1: one group = the plain serial pipeline, 0: automatic = three
 // groups per lane, k: aim at k groups); ADP_LANES (streams the groups rotate over, default 2); ADP_STAGGER (bit p set: phase p of
@@ -858,14 +904,11 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     }
     adp_handle *lanes[ADP_MAX_LANES];
     for (int i = 0; i < n_lanes; i++) {
-        int rc = lane_get(h, i, mb_per_group * minibatch, &lanes[i]);
-        if (rc) return rc;
-        lanes[i]->prof.clear(); lanes[i]->ev_used = 0;
+        RCCHK(lane_get(h, i, mb_per_group * minibatch, &lanes[i]));
+        drop_profile(lanes[i]);
     }
     adp_row *rows_dev = rows_out ? (out_dev ? rows_out : h->rows.as<adp_row>()) : nullptr;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        int rc = arena_begin(h);
-        if (rc) return rc;
+    RCCHK(call_attempts(h, lanes, n_lanes, [&]() -> int {
         HIPCHK(hipEventRecord(h->ev_start, h->stream));      // (inputs staged on this stream, arena counter zeroed)
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamWaitEvent(lanes[i]->stream, h->ev_start, 0));
         for (int g = 0; g < G; g++) {
@@ -877,25 +920,13 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
                 ps.done[p] = h->ev_sync[(size_t)g * 3 + p];
                 if (g > 0 && (stagger >> p & 1)) ps.wait[p] = h->ev_sync[(size_t)(g - 1) * 3 + p];
             }
-            rc = llr_enqueue(l, sig_from(dsig, (size_t)r0, m), dlen + r0, ng, m, minibatch, flags, rows_dev ? rows_dev + r0 : nullptr,
-                             hipMemcpyDeviceToDevice, h->mbstat.as<int32_t>() + mb0, h->mbparams.as<double>() + 4 * (size_t)mb0, 8, &ps);
+            const int rc = llr_enqueue(l, sig_from(dsig, (size_t)r0, m), dlen + r0, ng, m, minibatch, flags, rows_dev ? rows_dev + r0 : nullptr,
+                                       hipMemcpyDeviceToDevice, h->mbstat.as<int32_t>() + mb0, h->mbparams.as<double>() + 4 * (size_t)mb0, 8, &ps);
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
-        const bool pt = trunc_wanted(flags, rows_out);
-        unsigned int n_pt = 0;
-        if constexpr (std::is_same<SIG, SigF32>::value) {
-            if (pt) RCCHK(trunc_enqueue_t1(h, dsig.base, dlen, n, m, rows_dev)); // (arena_end waits for this stream)
-        }
-        rc = arena_end(h, false, nullptr, nullptr, pt ? &n_pt : nullptr);
-        if (rc < 0) return rc;
-        if constexpr (std::is_same<SIG, SigF32>::value) {
-            if (rc == 0 && pt) { rc = trunc_finish(h, dsig.base, dlen, n, m, rows_dev, true, n_pt); if (rc < 0) return rc; }
-        }
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        for (int i = 0; i < n_lanes; i++) { lanes[i]->prof.clear(); lanes[i]->ev_used = 0; }
-    }
+        return llr_after_first_pass(h, dsig, dlen, n, m, rows_dev, trunc_wanted(flags, rows_dev));
+    }));
     if (rows_out && !out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
     if (mb_status) HIPCHK(hipMemcpyAsync(mb_status, h->mbstat.p, (size_t)n_mb * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -926,16 +957,9 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
     // ADP_FLAG_TRUNCATED: the look rides behind the validation on the device rows (the caller's, or the handle's -- host rows are
     // then delivered once, behind it); its T1 count comes back with the arena counter
     const bool pt = upto >= 8 && trunc_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        int rc = arena_begin(h);
-        if (rc) return rc;
-        rc = llr_enqueue(h, dsig, dlen, n, m, minibatch, flags, upto >= 8 && !(pt && !out_dev) ? rows_out : nullptr,
-                         out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, nullptr, nullptr, upto, nullptr);
-        if (rc) return rc;
-        adp_row *pt_rows = out_dev ? rows_out : h->rows.as<adp_row>();
-        if constexpr (std::is_same<SIG, SigF32>::value) {
-            if (pt) RCCHK(trunc_enqueue_t1(h, dsig.base, dlen, n, m, pt_rows));
-        }
+    return call_attempts(h, nullptr, 0, [&]() -> int {
+        RCCHK(llr_enqueue(h, dsig, dlen, n, m, minibatch, flags, upto >= 8 && !(pt && !out_dev) ? rows_out : nullptr,
+                          out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, nullptr, nullptr, upto, nullptr));
         if (mb_status) {
             // through a small device buffer -> host
             hipLaunchKernelGGL(k_mb_status_out, dim3((n_mb + 255) / 256), dim3(256), 0, h->stream, h->mbs.as<MbState>(), n_mb, h->gbelow.as<int32_t>());
@@ -943,25 +967,14 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (upto < 8) break;
-        unsigned int n_pt = 0;
-        rc = arena_end(h, false, nullptr, nullptr, pt ? &n_pt : nullptr);
-        if (rc < 0) return rc;
-        if constexpr (std::is_same<SIG, SigF32>::value) {
-            if (rc == 0 && pt) {
-                rc = trunc_finish(h, dsig.base, dlen, n, m, pt_rows, true, n_pt);
-                if (rc < 0) return rc;
-                if (rc == 0 && !out_dev) {
-                    HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
-                    HIPCHK(hipStreamSynchronize(h->stream));
-                }
-            }
+        if (upto < 8) return 0;
+        const int rc = llr_after_first_pass(h, dsig, dlen, n, m, out_dev ? rows_out : h->rows.as<adp_row>(), pt);
+        if (rc == 0 && pt && !out_dev) {
+            HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
         }
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        reset_profile(h);
-    }
-    return ADP_OK;
+        return rc;
+    });
 }
 
 static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full_len, int n, int m, int minibatch, int flags,
@@ -970,7 +983,7 @@ static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full
     if (!h || !signals || !full_len || n < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ && minibatch != 1) { g_err = "the single-read layout normalises every read on its own: minibatch must be 1"; return ADP_ERR_INVALID; }
-    h->pt_n_t1 = 0; h->pt_counts = nullptr;
+    h->pt_looked = false;
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
@@ -1086,9 +1099,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
     if (rc) return rc;
     // the pandas float-column quirk couples the reads of ONE minibatch: process minibatch by minibatch (one arena for the
     // whole call: the offsets in the rows of every minibatch stay valid until the next call)
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = arena_begin(h);
-        if (rc) return rc;
+    return call_attempts(h, nullptr, 0, [&]() -> int {
         for (int s0 = 0; s0 < n_reads; s0 += minibatch) {
             int n = n_reads - s0 < minibatch ? n_reads - s0 : minibatch;
             const float *sg = dsig + (size_t)s0 * m;
@@ -1098,8 +1109,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
               hipLaunchKernelGGL(k_start_peak<SigF32>, dim3(n), dim3(64), (size_t)64 * h->cfg.sp_downscale_factor * 4, st, SigF32{sg}, ln, n, m, h->cfg, h->sp.as<SpOut>()); }
             hipLaunchKernelGGL(k_sp_bounds, dim3((n + 255) / 256), dim3(256), 0, st, h->sp.as<SpOut>(), n, h->bounds.as<int64_t>(),
                                h->topk_none.as<int8_t>(), h->any_none.as<int32_t>());
-            rc = launch_validate(h, SigF32{sg}, ln, n, m, 1, minibatch, false);
-            if (rc) return rc;
+            RCCHK(launch_validate(h, SigF32{sg}, ln, n, m, 1, minibatch, false));
             hipLaunchKernelGGL(k_sp_decorate, dim3((n + 255) / 256), dim3(256), 0, st, h->sp.as<SpOut>(), h->rows.as<adp_row>(), n, 1,
                                h->any_none.as<int32_t>());
             if (rows_out) {
@@ -1109,13 +1119,8 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
             HIPCHK(hipStreamSynchronize(st));
         }
         HIPCHK(hipGetLastError());
-        rc = arena_end(h);
-        if (rc < 0) return rc;
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        reset_profile(h);
-    }
-    return ADP_OK;
+        return arena_end(h);
+    });
 }
 
 int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
@@ -1132,25 +1137,16 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
     hipStream_t st = h->stream;
     rc = alloc_all(h, n_reads, false);
     if (rc) return rc;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = arena_begin(h);
-        if (rc) return rc;
+    return call_attempts(h, nullptr, 0, [&]() -> int {
         HIPCHK(hipMemcpyAsync(h->bounds.p, bounds, (size_t)n_reads * (1 + k) * 8,
                               ((flags & ADP_IN_DEVICE) && !(flags & ADP_BOUNDS_HOST)) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(h->topk_none.p, (flags & ADP_TOPK_NONE) ? 1 : 0, (size_t)n_reads, st));
-        rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated);
-        if (rc) return rc;
-        rc = deliver_rows(h, n_reads, flags, rows_out);
-        if (rc) return rc;
+        RCCHK(launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated));
+        RCCHK(deliver_rows(h, n_reads, flags, rows_out));
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        rc = arena_end(h);
-        if (rc < 0) return rc;
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        reset_profile(h);
-    }
-    return ADP_OK;
+        return arena_end(h);
+    });
 }
 
 // C3 on the device: top-k behind given arg-maxes (dapos / dppos device int64 [n]) -> dcand / dcnt in ct_out (asynchronous)
@@ -1532,18 +1528,14 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
         HIPCHK(hipStreamSynchronize(h->stream));
         if (!flag) break;
         h->cnn_redo_f32 = true; // an activation left the float16 range: once more on the float32 kernels
-        h->prof.clear(); h->ev_used = 0;
+        drop_profile(h);
     }
     return ADP_OK;
 }
 
 // combined_detect_cnn up to (not including) the short-read fallback: C1 prepare -> C2 conv stack -> C3 predict -> V1 with the
 // k candidates, enqueued on the handle's stream without waiting for anything on the host.  bounds_dst (may be NULL): int64
-// [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.  fb_select: the fallback's selection over these reads rides
-// directly behind the validation kernels, in front of the row copy (kernel after kernel: behind the copy it would wait for the
-// copy engine's signal and the host for the kernel's).  so_select: the second opinion's selection, in the same place.
-static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride);
-static int cnn_second_select(adp_handle *h, int n, const adp_row *rows);
+// [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.
 // the start-peak overlay of the CNN path (ADP_WITH_START_PEAK): can K1 ride the pooling pass?
 static bool cnn_sp_fused(const adp_handle *h)
 {
@@ -1557,7 +1549,7 @@ static void cnn_sp_decorate(adp_handle *h, const SpOut *sp, adp_row *rows, int n
 // sp_out (ADP_WITH_START_PEAK, else null): K1's results of these reads -- a slice of the CALL's buffer, the owner handle's, because
 // the phases behind the first pass run there -- are computed beside the pass and overlaid on its rows (k_sp_decorate, mode 0).
 static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
-                       int rows_kind, int64_t *bounds_dst, int bounds_kind, bool fb_select = false, bool so_select = false, SpOut *sp_out = nullptr)
+                       int rows_kind, int64_t *bounds_dst, int bounds_kind, SpOut *sp_out = nullptr)
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     const int Lc = (m - off + ds - 1) / ds, L1 = (Lc - 1) / 3 + 1, Lo = 3 * L1 - 2;
@@ -1605,8 +1597,6 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
         if (!sp_fused) { HIPCHK(hipStreamWaitEvent(st, h->ev_join, 0)); sp_join.armed = false; }
         cnn_sp_decorate(h, sp_out, h->rows.as<adp_row>(), n_reads);
     }
-    if (fb_select) RCCHK(cnn_fallback_select(h, dlen, n_reads, h->rows.as<adp_row>(), h->bounds.as<int64_t>(), 1 + kk));
-    if (so_select) RCCHK(cnn_second_select(h, n_reads, h->rows.as<adp_row>()));
     if (rows_dst) HIPCHK(hipMemcpyAsync(rows_dst, h->rows.p, (size_t)n_reads * sizeof(adp_row), (hipMemcpyKind)rows_kind, st));
     HIPCHK(hipGetLastError());
     return ADP_OK;
@@ -1662,9 +1652,9 @@ static int refine_chain(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int
 } // extern "C++"
 
 // ---- the short-read fallback of combined_detect_cnn (combined.py:251-301) behind the first pass (cnn_fallback.h) -----------------
-static bool cnn_fallback_wanted(const adp_handle *h, int flags, const adp_row *rows_out)
+static bool cnn_fallback_wanted(const adp_handle *h, int flags, const adp_row *rows)
 {
-    return (flags & ADP_CNN_FALLBACK) && h->cfg.fallback_to_llr_short_reads && rows_out;
+    return (flags & ADP_CNN_FALLBACK) && h->cfg.fallback_to_llr_short_reads && rows;
 }
 // rows / bounds: the CALL's device row buffer and predictions (int64 [n, bstride]) once every read's first pass is in them.
 // Enqueues the selection on the handle's stream; the count reaches the host in arena_end's copy.
@@ -1672,7 +1662,7 @@ static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const 
 {
     if (h->fb_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     Scope s(h, "k_cnn_fb_select");
-    hipLaunchKernelGGL(k_cnn_fb_select, dim3(1), dim3(FB_SEL_THREADS), 0, h->stream, rows, bounds, bstride, dlen, n, 2ll * h->cfg.max_obs_adapter,
+    hipLaunchKernelGGL(k_cnn_fb_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, rows, bounds, bstride, dlen, n, 2ll * h->cfg.max_obs_adapter,
                        h->fb_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 2);
     return 0;
 }
@@ -1687,15 +1677,16 @@ static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dle
     int rc = alloc_all(h, n_sel, true);
     if (rc) return rc;
     const size_t N = (size_t)n_sel;
-    // ranges 16 N | new poly(A) ends 8 N | bounds of the re-validation 16 N | status 4 N | full_len 4 N | counts 8 | topk_none N
-    if (h->fb_ws.ensure(N * 49 + 8) || h->fb_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    int64_t *drng = h->fb_ws.as<int64_t>(), *dout = drng + 2 * N, *db2 = dout + N;
-    int32_t *dstat = reinterpret_cast<int32_t *>(db2 + 2 * N), *dlen_sub = dstat + N;
-    unsigned int *counts = reinterpret_cast<unsigned int *>(dlen_sub + N);
-    int8_t *topk = reinterpret_cast<int8_t *>(counts + 2);
+    int64_t *drng, *dout, *db2; int32_t *dstat, *dlen_sub; int8_t *topk; adp_row *rows2;
+    RCCHK(sub_carve(h, [&](Carve &c) { // ranges, new poly(A) ends, bounds of the re-validation, status, full_len, topk_none, rows
+        drng = c.take<int64_t>(2 * N); dout = c.take<int64_t>(N); db2 = c.take<int64_t>(2 * N);
+        dstat = c.take<int32_t>(N); dlen_sub = c.take<int32_t>(N); topk = c.take<int8_t>(N); rows2 = c.take<adp_row>(N);
+    }));
+    unsigned int *counts = phase_counts(h, OPW_FB);
     const int32_t *sel = h->fb_sel.as<int32_t>();
     const SigIdx sig{dsig, sel};
-    HIPCHK(hipMemsetAsync(counts, 0, 8 + N, st)); // (both counts and topk_none: polya_end_topk is given)
+    HIPCHK(hipMemsetAsync(counts, 0, 8, st));
+    HIPCHK(hipMemsetAsync(topk, 0, N, st)); // (polya_end_topk is given)
     { Scope s(h, "k_cnn_fb_gather");
       hipLaunchKernelGGL(k_cnn_fb_gather, dim3((n_sel + 255) / 256), dim3(256), 0, st, sel, n_sel, 0, bounds, bstride, dlen, dlen_sub, drng,
                          (const int64_t *)nullptr, (const int32_t *)nullptr, (int64_t *)nullptr); }
@@ -1704,64 +1695,117 @@ static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dle
     { Scope s(h, "k_cnn_fb_gather");
       hipLaunchKernelGGL(k_cnn_fb_gather, dim3((n_sel + 255) / 256), dim3(256), 0, st, sel, n_sel, 1, bounds, bstride, dlen, dlen_sub, drng,
                          (const int64_t *)dout, (const int32_t *)dstat, db2); }
-    const ValBufs vb{db2, topk, h->fb_rows.as<adp_row>()};
+    const ValBufs vb{db2, topk, rows2};
     rc = launch_validate(h, sig, dlen_sub, n_sel, m, 1, n_sel, false, &vb);
     if (rc) return rc;
     { Scope s(h, "k_cnn_fb_merge");
       hipLaunchKernelGGL(k_cnn_fb_merge, dim3(n_sel), dim3(64), 0, st, sel, n_sel, (const int64_t *)dout, (const int32_t *)dstat,
-                         (const adp_row *)h->fb_rows.as<adp_row>(), rows, counts); }
-    h->fb_counts = counts;
+                         (const adp_row *)rows2, rows, counts); }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 // ---- the LLR second opinion for reads the CNN path fails (ADP_CNN_SECOND_LLR, cnn_second_opinion.h) ------------------------------
-static bool cnn_second_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_CNN_SECOND_LLR) && rows_out; }
-static bool cnn_sp_wanted(int flags, const adp_row *rows_out) { return (flags & ADP_WITH_START_PEAK) && rows_out; }
+static bool cnn_second_wanted(int flags, const adp_row *rows) { return (flags & ADP_CNN_SECOND_LLR) && rows; }
+static bool cnn_sp_wanted(int flags, const adp_row *rows) { return (flags & ADP_WITH_START_PEAK) && rows; }
 // rows: the CALL's device row buffer once every read's row of the CNN path is in it (behind the first pass, and again behind the
 // fallback's merge when that ran).  The count reaches the host in arena_end's copy.
 static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
 {
     if (h->so_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     Scope s(h, "k_cnn_so_select");
-    hipLaunchKernelGGL(k_cnn_so_select, dim3(1), dim3(SO_SEL_THREADS), 0, h->stream, rows, n, h->so_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 3);
+    hipLaunchKernelGGL(k_cnn_so_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, rows, n, h->so_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 3);
     return 0;
 }
 
 // The second opinion for the n_so selected reads, enqueued on the handle's stream.  The LLR primary is the LLR path's own up to
 // k_polya_peak (llr_enqueue, stage 7) over ALL n reads in their minibatches -- N1 and the minibatch status are those
 // adp_detect_llr computes -- with its boundaries in a buffer of this phase (the handle's bounds / topk_none / rows hold the CNN
-// path's).  The validation (k = 1) reads the selected rows in place and leaves its rows in so_rows; the merge copies those that
-// passed into `rows`.  Open-pore lists of the second rows append to the call's arena: the caller looks at its counter once more.
+// path's).  The validation (k = 1) reads the selected rows in place and leaves its rows in the phase's own; the merge copies those
+// that passed into `rows`.  Open-pore lists of the second rows append to the call's arena: the caller looks at its counter once more.
 static int cnn_second_run(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so)
 {
     hipStream_t st = h->stream;
     int rc = llr_enqueue(h, SigF32{dsig}, dlen, n, m, minibatch, flags & ADP_TAILS_NAN, nullptr, 0, nullptr, nullptr, 7, nullptr);
     if (rc) return rc;
     const size_t R = (size_t)n, N = (size_t)n_so;
-    // LLR bounds of all reads 16 R | bounds of the validation 16 N | full_len 4 N | counts 16 | topk_none of all reads R | of the subset N
-    if (h->so_ws.ensure(R * 17 + N * 21 + 16) || h->so_rows.ensure(N * sizeof(adp_row))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    int64_t *ball = h->so_ws.as<int64_t>(), *b2 = ball + 2 * R;
-    int32_t *dlen_sub = reinterpret_cast<int32_t *>(b2 + 2 * N);
-    unsigned int *counts = reinterpret_cast<unsigned int *>(dlen_sub + N);
-    int8_t *tall = reinterpret_cast<int8_t *>(counts + 4), *tsub = tall + R;
+    int64_t *ball, *b2; int32_t *dlen_sub; int8_t *tall, *tsub; adp_row *rows2;
+    RCCHK(sub_carve(h, [&](Carve &c) { // LLR bounds and topk_none of all reads; of the subset: bounds of the validation, full_len, topk_none, rows
+        ball = c.take<int64_t>(2 * R); tall = c.take<int8_t>(R);
+        b2 = c.take<int64_t>(2 * N); dlen_sub = c.take<int32_t>(N); tsub = c.take<int8_t>(N); rows2 = c.take<adp_row>(N);
+    }));
+    unsigned int *counts = phase_counts(h, OPW_SO);
     const int32_t *sel = h->so_sel.as<int32_t>();
     const MbState *mbs = h->mbs.as<MbState>();
-    HIPCHK(hipMemsetAsync(counts, 0, 16, st));
+    HIPCHK(hipMemsetAsync(counts, 0, 12, st));
     if (h->L > 0) // (else every minibatch is ADP_MB_EMPTY_TRACE: k_cnn_so_gather reads no bounds)
         hipLaunchKernelGGL(k_llr_bounds, dim3((n + 255) / 256), dim3(256), 0, st, h->adapter_idx.as<int32_t>(), h->polya_idx.as<int32_t>(), n, h->ds,
                            h->pos_off, ball, tall, 0);
     { Scope s(h, "k_cnn_so_gather");
       hipLaunchKernelGGL(k_cnn_so_gather, dim3((n_so + 255) / 256), dim3(256), 0, st, sel, n_so, minibatch, mbs, dlen, (const int64_t *)ball,
                          (const int8_t *)tall, dlen_sub, b2, tsub); }
-    const ValBufs vb{b2, tsub, h->so_rows.as<adp_row>()};
+    const ValBufs vb{b2, tsub, rows2};
     rc = launch_validate(h, SigIdx{dsig, sel}, dlen_sub, n_so, m, 1, n_so, false, &vb);
     if (rc) return rc;
     { Scope s(h, "k_cnn_so_merge");
-      hipLaunchKernelGGL(k_cnn_so_merge, dim3(n_so), dim3(64), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)h->so_rows.as<adp_row>(), rows, counts); }
-    h->so_counts = counts;
+      hipLaunchKernelGGL(k_cnn_so_merge, dim3(n_so), dim3(64), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)rows2, rows, counts); }
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- what adp_detect_cnn does behind the first pass, in both execution forms ---------------------------------------------------------
+// Called once every read's first-pass row lies in `rows`, the CALL's device row buffer (null: the caller wants no rows), and its
+// predictions in `bounds` (int64 [n, bstride]); the lanes of a grouped call have drained.  sp (ADP_WITH_START_PEAK, else null): K1's
+// results of the call.  -> 0 done, 1 run the call again, < 0 error; *changed: a phase wrote to `rows` behind the first pass.
+//
+// The fallback: its selection's count comes back with the arena counter at the call's one synchronisation point -- a call without
+// selected reads (every call over full-length reads) ends there.  Otherwise the second phase follows and merges its rows over the
+// first ones.  Its re-validated rows append to the call's arena; a read's open-pore list depends on its adapter end alone, so the
+// second phase wants at most what the first one did and an arena grown for the first (to twice its demand) holds both: three
+// attempts are still enough.
+// The second opinion (ADP_CNN_SECOND_LLR) works the same way on the rows behind the fallback: its selection is enqueued with the
+// fallback's (and once more behind a fallback merge), its count comes back in the same copy, and a call whose reads all passed
+// ends there.  Its rows' open-pore lists depend on the LLR adapter end: they may want more than the first pass did, and the
+// counter is cumulative over the call -- attempt 1 can fall short in the first pass, attempt 2 in this phase, attempt 3 holds both.
+// The start-peak overlay: K1 ran beside the first pass and decorated its rows; the fallback and the second opinion deliver whole
+// rows of their own validation, so the overlay is applied once more to the call's row buffer behind each (k_sp_decorate is
+// idempotent); the truncation look's merge keeps the columns (k_pt_merge).
+// The truncation look (ADP_FLAG_TRUNCATED) comes behind all of that, on every read's final row: one more synchronisation for its
+// T1 count, and T2 only where a tail window passed.
+static int cnn_after_first_pass(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows,
+                                const int64_t *bounds, int bstride, const SpOut *sp, bool *changed)
+{
+    const bool fb = cnn_fallback_wanted(h, flags, rows), so = cnn_second_wanted(flags, rows);
+    *changed = false;
+    if (fb) RCCHK(cnn_fallback_select(h, dlen, n, rows, bounds, bstride));
+    if (so) RCCHK(cnn_second_select(h, n, rows));
+    unsigned int n_sel = 0, n_so = 0;
+    int rc = arena_end(h, true, fb ? &n_sel : nullptr, so ? &n_so : nullptr); // (with a count to read it waits for the stream)
+    if (rc < 0) return rc;
+    h->fb_n_sel = n_sel; h->so_n_sel = 0;
+    if (rc == 0 && n_sel) {
+        *changed = true;
+        RCCHK(cnn_fallback_run(h, dsig, dlen, m, rows, bounds, bstride, (int)n_sel));
+        if (sp) cnn_sp_decorate(h, sp, rows, n); // (re-validated rows come bare; idempotent on the others)
+        if (so) RCCHK(cnn_second_select(h, n, rows)); // (the merge changed rows: select again)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
+        if (rc < 0) return rc;
+    }
+    if (rc == 0 && n_so) {
+        *changed = true;
+        h->so_n_sel = n_so;
+        RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows, (int)n_so));
+        if (sp) cnn_sp_decorate(h, sp, rows, n); // (the second opinion's rows come bare)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        rc = arena_end(h);
+        if (rc < 0) return rc;
+    }
+    if (rc == 0 && trunc_wanted(flags, rows)) {
+        *changed = true; // (T1 marks every row)
+        rc = trunc_finish(h, dsig, dlen, n, m, rows);
+    }
+    return rc;
 }
 
 // Chunks of whole minibatches over two lanes, free-running: while one lane's chunk is in the conv stack (matrix cores, one
@@ -1777,7 +1821,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
     // the fallback runs once on this handle, over the call's device row buffer, when all lanes have drained: it needs the
     // predictions of all reads here whether the caller wants them or not
-    const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out);
+    const bool fb = cnn_fallback_wanted(h, flags, rows_out);
     // K1's results of the whole call live in this handle's buffer (adp_detect_cnn sized it): the lanes write their slices
     SpOut *sp = cnn_sp_wanted(flags, rows_out) ? h->sp.as<SpOut>() : nullptr;
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
@@ -1786,58 +1830,26 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     }
     adp_handle *lanes[ADP_MAX_LANES];
     for (int i = 0; i < n_lanes; i++) {
-        int rc = lane_get(h, i, mb_per_group * minibatch, &lanes[i]);
-        if (rc) return rc;
-        lanes[i]->prof.clear(); lanes[i]->ev_used = 0;
+        RCCHK(lane_get(h, i, mb_per_group * minibatch, &lanes[i]));
+        drop_profile(lanes[i]);
     }
     adp_row *rows_dev = rows_out ? (out_dev ? rows_out : h->rows.as<adp_row>()) : nullptr;
     int64_t *bounds_dev = (bounds_out || fb) ? h->bounds.as<int64_t>() : nullptr;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        int rc = arena_begin(h);
-        if (rc) return rc;
+    RCCHK(call_attempts(h, lanes, n_lanes, [&]() -> int {
         HIPCHK(hipEventRecord(h->ev_start, h->stream));
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamWaitEvent(lanes[i]->stream, h->ev_start, 0));
         for (int g = 0; g < G; g++) {
             adp_handle *l = lanes[g % n_lanes];
             const int r0 = g * mb_per_group * minibatch;
             const int ng = (n - r0) < mb_per_group * minibatch ? (n - r0) : mb_per_group * minibatch;
-            rc = cnn_enqueue(l, dsig + (size_t)r0 * m, dlen + r0, ng, m, minibatch, rows_dev ? rows_dev + r0 : nullptr, hipMemcpyDeviceToDevice,
-                             bounds_dev ? bounds_dev + (size_t)r0 * (1 + kk) : nullptr, hipMemcpyDeviceToDevice, false, false, sp ? sp + r0 : nullptr);
+            const int rc = cnn_enqueue(l, dsig + (size_t)r0 * m, dlen + r0, ng, m, minibatch, rows_dev ? rows_dev + r0 : nullptr, hipMemcpyDeviceToDevice,
+                                       bounds_dev ? bounds_dev + (size_t)r0 * (1 + kk) : nullptr, hipMemcpyDeviceToDevice, sp ? sp + r0 : nullptr);
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
-        if (fb) RCCHK(cnn_fallback_select(h, dlen, n, rows_dev, bounds_dev, 1 + kk));
-        if (so) RCCHK(cnn_second_select(h, n, rows_dev));
-        unsigned int n_sel = 0, n_so = 0;
-        rc = arena_end(h, true, fb ? &n_sel : nullptr, so ? &n_so : nullptr);
-        if (rc < 0) return rc;
-        h->fb_n_sel = n_sel; h->fb_counts = nullptr;
-        h->so_n_sel = 0; h->so_counts = nullptr;
-        if (rc == 0 && n_sel) {
-            RCCHK(cnn_fallback_run(h, dsig, dlen, m, rows_dev, bounds_dev, 1 + kk, (int)n_sel));
-            if (sp) cnn_sp_decorate(h, sp, rows_dev, n); // (re-validated rows come bare; idempotent on the others)
-            if (so) RCCHK(cnn_second_select(h, n, rows_dev)); // (the merge changed rows: select again)
-            HIPCHK(hipStreamSynchronize(h->stream));
-            rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
-            if (rc < 0) return rc;
-        }
-        if (rc == 0 && n_so) {
-            h->so_n_sel = n_so;
-            RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows_dev, (int)n_so));
-            if (sp) cnn_sp_decorate(h, sp, rows_dev, n); // (the second opinion's rows come bare)
-            HIPCHK(hipStreamSynchronize(h->stream));
-            rc = arena_end(h);
-            if (rc < 0) return rc;
-        }
-        if (rc == 0 && trunc_wanted(flags, rows_out)) { // (behind everything else: every read's final row)
-            rc = trunc_finish(h, dsig, dlen, n, m, rows_dev, false, 0);
-            if (rc < 0) return rc;
-        }
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        for (int i = 0; i < n_lanes; i++) { lanes[i]->prof.clear(); lanes[i]->ev_used = 0; }
-        h->prof.clear(); h->ev_used = 0;
-    }
+        bool changed;
+        return cnn_after_first_pass(h, dsig, dlen, n, m, minibatch, flags, rows_dev, bounds_dev, 1 + kk, sp, &changed);
+    }));
     if (rows_out && !out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
     if (bounds_out) HIPCHK(hipMemcpyAsync(bounds_out, h->bounds.p, (size_t)n * (1 + kk) * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1851,14 +1863,12 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    h->pt_n_t1 = 0; h->pt_counts = nullptr;
+    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     if (m <= h->cfg.min_obs_adapter) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
     h->cnn_redo_f32 = false;
-    h->fb_n_sel = 0; h->fb_counts = nullptr;
-    h->so_n_sel = 0; h->so_counts = nullptr;
     // (K1's results of the whole call: sized here, before any phase's workspace call could move the buffer under them)
     if (cnn_sp_wanted(flags, rows_out) && h->sp.ensure((size_t)n_reads * sizeof(SpOut))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
     const float *dsig; const int32_t *dlen;
@@ -1887,68 +1897,25 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         if (G < n_lanes) n_lanes = G;
         if (G >= 2) return cnn_grouped(h, dsig, dlen, n_reads, m, minibatch, flags, rows_out, bounds_out, per, n_lanes);
     }
-    // The fallback: the selection rides behind the first pass and its count comes back with the arena counter at the call's one
-    // synchronisation point -- a call without selected reads (every call over full-length reads) ends there, its rows delivered
-    // as before.  Otherwise the second phase follows and the merged rows are delivered over the first ones.  Its re-validated rows
-    // append to the call's arena; a read's open-pore list depends on its adapter end alone, so the second phase wants at most what
-    // the first one did and an arena grown for the first (to twice its demand) holds both: three attempts are still enough.
-    // The second opinion (ADP_CNN_SECOND_LLR) works the same way on the rows behind the fallback: its selection rides behind the
-    // first pass (and once more behind a fallback merge), its count comes back in the same copy, and a call whose reads all passed
-    // ends there.  Its rows' open-pore lists depend on the LLR adapter end: they may want more than the first pass did, and the
-    // counter is cumulative over the call -- attempt 1 can fall short in the first pass, attempt 2 in this phase, attempt 3 holds both.
-    // The start-peak overlay (ADP_WITH_START_PEAK): K1 runs beside the first pass and decorates its rows; the fallback and the second
-    // opinion deliver whole rows of their own validation, so the overlay is applied once more to the call's row buffer behind each
-    // (k_sp_decorate is idempotent); the truncation look's merge keeps the columns (k_pt_merge).
-    const bool fb = cnn_fallback_wanted(h, flags, rows_out), so = cnn_second_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    // One chunk: the first pass delivers the caller's rows in-stream, and a call whose later phases change nothing ends at its one
+    // synchronisation point.  Device rows are merged where the caller has them; host rows are merged in the handle's buffer and
+    // delivered once more behind the phases.
+    const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
     SpOut *sp = cnn_sp_wanted(flags, rows_out) ? h->sp.as<SpOut>() : nullptr;
     const int kk = h->cfg.polya_cand_k < 1 ? 1 : h->cfg.polya_cand_k; // (the stride of the predictions, as cnn_predict_dev lays them out)
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = arena_begin(h);
-        if (rc) return rc;
-        rc = cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                         bounds_out, hipMemcpyDeviceToHost, fb, so, sp);
-        if (rc) return rc;
+    return call_attempts(h, nullptr, 0, [&]() -> int {
+        RCCHK(cnn_enqueue(h, dsig, dlen, n_reads, m, minibatch, rows_out, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                          bounds_out, hipMemcpyDeviceToHost, sp));
         HIPCHK(hipStreamSynchronize(h->stream));
-        unsigned int n_sel = 0, n_so = 0;
-        rc = arena_end(h, true, fb ? &n_sel : nullptr, so ? &n_so : nullptr);
-        if (rc < 0) return rc;
-        h->fb_n_sel = n_sel; h->fb_counts = nullptr;
-        h->so_n_sel = 0; h->so_counts = nullptr;
-        // (device rows: merged where the caller has them; host rows: merged in the handle's buffer and delivered again)
-        adp_row *merged = out_dev ? rows_out : h->rows.as<adp_row>();
-        if (rc == 0 && n_sel) {
-            RCCHK(cnn_fallback_run(h, dsig, dlen, m, merged, h->bounds.as<int64_t>(), 1 + kk, (int)n_sel));
-            if (sp) cnn_sp_decorate(h, sp, merged, n_reads); // (re-validated rows come bare; idempotent on the others)
-            if (so) RCCHK(cnn_second_select(h, n_reads, merged)); // (the merge changed rows: select again)
-            if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
+        adp_row *rows_dev = rows_out ? (out_dev ? rows_out : h->rows.as<adp_row>()) : nullptr;
+        bool changed;
+        const int rc = cnn_after_first_pass(h, dsig, dlen, n_reads, m, minibatch, flags, rows_dev, h->bounds.as<int64_t>(), 1 + kk, sp, &changed);
+        if (rc == 0 && changed && !out_dev) {
+            HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
-            rc = arena_end(h, false, nullptr, so ? &n_so : nullptr);
-            if (rc < 0) return rc;
         }
-        if (rc == 0 && n_so) {
-            h->so_n_sel = n_so;
-            RCCHK(cnn_second_run(h, dsig, dlen, n_reads, m, minibatch, flags, merged, (int)n_so));
-            if (sp) cnn_sp_decorate(h, sp, merged, n_reads); // (the second opinion's rows come bare)
-            if (!out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            rc = arena_end(h);
-            if (rc < 0) return rc;
-        }
-        // The truncation look (ADP_FLAG_TRUNCATED) comes behind all of that, on every read's final row: one more synchronisation for
-        // its T1 count, and T2 only where a tail window passed.
-        if (rc == 0 && trunc_wanted(flags, rows_out)) {
-            rc = trunc_finish(h, dsig, dlen, n_reads, m, merged, false, 0);
-            if (rc < 0) return rc;
-            if (rc == 0 && !out_dev) {
-                HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n_reads * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-            }
-        }
-        if (rc == 0) break;
-        if (attempt == 2) { g_err = "the call's repeats (conv stack out of the float16 range, open-pore arena growth) are used up and the arena is still short"; return ADP_ERR_CAPACITY; }
-        reset_profile(h);
-    }
-    return ADP_OK;
+        return rc;
+    });
 }
 
 int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *full_len, int n, int m, const int64_t *ranges,
@@ -2176,17 +2143,17 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
     case 10: { // the last adp_detect_cnn call's fallback: reads selected, exception rows made, rows re-validated
         if (bytes < 12) return ADP_ERR_INVALID;
         int32_t c[3] = {(int32_t)h->fb_n_sel, 0, 0};
-        if (h->fb_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->fb_counts, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        if (h->fb_n_sel) { HIPCHK(hipMemcpyAsync(c + 1, phase_counts(h, OPW_FB), 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
     case 11: { // the last adp_detect_cnn call's LLR second opinion: reads selected, rows replaced, re-validated and still failing, minibatches without one
         if (bytes < 16) return ADP_ERR_INVALID;
         int32_t c[4] = {(int32_t)h->so_n_sel, 0, 0, 0};
-        if (h->so_counts) { HIPCHK(hipMemcpyAsync(c + 1, h->so_counts, 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        if (h->so_n_sel) { HIPCHK(hipMemcpyAsync(c + 1, phase_counts(h, OPW_SO), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 16); return ADP_OK; }
     case 12: { // the truncation look of the last adp_detect_llr / adp_detect_cnn call: eligible reads, T1 passed, rows replaced
         if (bytes < 12) return ADP_ERR_INVALID;
         int32_t c[3] = {0, 0, 0};
-        if (h->pt_counts) { HIPCHK(hipMemcpyAsync(c, h->pt_counts, 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        if (h->pt_looked) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_PT), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;

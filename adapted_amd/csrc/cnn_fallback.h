@@ -12,19 +12,14 @@
 #pragma once
 #include "common.h"
 
-#define FB_SEL_THREADS 1024
-
-// One workgroup walks the reads FB_SEL_THREADS at a time: ballot + prefix count inside a wave, one offset per wave across the
-// workgroup, the running total carried from step to step -- the list comes out in ascending read order.
+// One workgroup walks the reads SEL_THREADS at a time (sel_step, common.h): the list comes out in ascending read order.
 // bounds: int64 [n, bstride], adapter end and first poly(A) candidate in front.  limit = 2 * max_obs_adapter.
-__global__ void __launch_bounds__(FB_SEL_THREADS) k_cnn_fb_select(const adp_row *__restrict__ rows, const int64_t *__restrict__ bounds, int bstride,
-                                                                  const int32_t *__restrict__ full_len, int n, long long limit,
-                                                                  int32_t *__restrict__ sel, unsigned int *__restrict__ count_out)
+__global__ void __launch_bounds__(SEL_THREADS) k_cnn_fb_select(const adp_row *__restrict__ rows, const int64_t *__restrict__ bounds, int bstride,
+                                                               const int32_t *__restrict__ full_len, int n, long long limit,
+                                                               int32_t *__restrict__ sel, unsigned int *__restrict__ count_out)
 {
-    __shared__ __attribute__((aligned(16))) int s_wave[FB_SEL_THREADS / 64];
-    const int ln = lane_id(), w = threadIdx.x >> 6;
     int total = 0;
-    for (int r0 = 0; r0 < n; r0 += FB_SEL_THREADS) {
+    for (int r0 = 0; r0 < n; r0 += SEL_THREADS) {
         const int r = r0 + threadIdx.x;
         bool take = false;
         if (r < n) {
@@ -32,14 +27,7 @@ __global__ void __launch_bounds__(FB_SEL_THREADS) k_cnn_fb_select(const adp_row 
             const long long ae = bounds[(size_t)r * bstride], pe = bounds[(size_t)r * bstride + 1];
             take = rows[r].success == 0 && !ADP_F_IS_EXCEPTION(fc) && ae > 0 && pe > 0 && pe - ae > 1000 && (long long)full_len[r] < limit;
         }
-        const unsigned long long mk = __ballot(take);
-        if (ln == 0) s_wave[w] = __popcll(mk);
-        __syncthreads();
-        int before = 0, step = 0;
-        for (int i = 0; i < FB_SEL_THREADS / 64; i++) { const int c = s_wave[i]; if (i < w) before += c; step += c; }
-        if (take) sel[total + before + __popcll(mk & ((1ull << ln) - 1ull))] = r;
-        total += step;
-        __syncthreads();
+        sel_step(take, r, sel, total);
     }
     if (threadIdx.x == 0) *count_out = (unsigned int)total;
 }

@@ -16,27 +16,14 @@
 
 #include "common.h"
 
-#define SO_SEL_THREADS 1024
-
-// One workgroup walks the reads SO_SEL_THREADS at a time (as k_cnn_fb_select, cnn_fallback.h): ballot + prefix count inside a
-// wave, one offset per wave across the workgroup, the running total carried from step to step -- ascending read order.
-__global__ void __launch_bounds__(SO_SEL_THREADS) k_cnn_so_select(const adp_row *__restrict__ rows, int n, int32_t *__restrict__ sel,
-                                                                  unsigned int *__restrict__ count_out)
+// One workgroup walks the reads SEL_THREADS at a time (sel_step, common.h): ascending read order.
+__global__ void __launch_bounds__(SEL_THREADS) k_cnn_so_select(const adp_row *__restrict__ rows, int n, int32_t *__restrict__ sel,
+                                                               unsigned int *__restrict__ count_out)
 {
-    __shared__ __attribute__((aligned(16))) int s_wave[SO_SEL_THREADS / 64];
-    const int ln = lane_id(), w = threadIdx.x >> 6;
     int total = 0;
-    for (int r0 = 0; r0 < n; r0 += SO_SEL_THREADS) {
+    for (int r0 = 0; r0 < n; r0 += SEL_THREADS) {
         const int r = r0 + threadIdx.x;
-        const bool take = r < n && rows[r].success == 0;
-        const unsigned long long mk = __ballot(take);
-        if (ln == 0) s_wave[w] = __popcll(mk);
-        __syncthreads();
-        int before = 0, step = 0;
-        for (int i = 0; i < SO_SEL_THREADS / 64; i++) { const int c = s_wave[i]; if (i < w) before += c; step += c; }
-        if (take) sel[total + before + __popcll(mk & ((1ull << ln) - 1ull))] = r;
-        total += step;
-        __syncthreads();
+        sel_step(r < n && rows[r].success == 0, r, sel, total);
     }
     if (threadIdx.x == 0) *count_out = (unsigned int)total;
 }

@@ -274,6 +274,25 @@ static __device__ __forceinline__ int wave_scan_incl(int v)
     return v;
 }
 
+// One step of an ascending compaction by ONE workgroup of SEL_THREADS threads (k_cnn_fb_select, k_cnn_so_select, k_pt_select): thread t
+// offers read r = the step's first read + t when `take`.  Ballot + prefix count inside a wave, one offset per wave across the
+// workgroup, and `total` -- the reads taken so far, the same in every thread -- carried from step to step: sel comes out in
+// ascending read order.  Every thread of the workgroup calls it in every step.
+#define SEL_THREADS 1024
+static __device__ __forceinline__ void sel_step(bool take, int r, int32_t *__restrict__ sel, int &total)
+{
+    __shared__ __attribute__((aligned(16))) int s_wave[SEL_THREADS / 64];
+    const int ln = lane_id(), w = threadIdx.x >> 6;
+    const unsigned long long mk = __ballot(take);
+    if (ln == 0) s_wave[w] = __popcll(mk);
+    __syncthreads();
+    int before = 0, step = 0;
+    for (int i = 0; i < SEL_THREADS / 64; i++) { const int c = s_wave[i]; if (i < w) before += c; step += c; }
+    if (take) sel[total + before + __popcll(mk & ((1ull << ln) - 1ull))] = r;
+    total += step;
+    __syncthreads();
+}
+
 // numpy's pairwise float32 sum of n <= 128 values read through `get(i)` (sequential in one lane).
 // numpy/_core/src/umath/loops_utils.h.src (pairwise_sum): n < 8 plain loop; else 8 accumulators.
 template <class F>

@@ -74,21 +74,15 @@ struct adp_handle {
     // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
     DevBuf ws;              // the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): one call's staging and scratch (ws_carve)
-    // the CNN path's short-read fallback (cnn_fallback.h): the selected reads' indices [reads of the call]; the per-subset arrays
-    // of its chain and re-validation (carved by cnn_fallback_run) and the re-validated rows [selected reads]
-    DevBuf fb_sel, fb_ws, fb_rows;
-    unsigned int fb_n_sel = 0;              // reads the last adp_detect_cnn call selected
-    unsigned int *fb_counts = nullptr;      // device: [0] exception rows made, [1] rows re-validated by that call (null: it ran no second phase)
-    // the CNN path's LLR second opinion (cnn_second_opinion.h): the failed reads' indices [reads of the call]; the LLR bounds of all
-    // reads and the per-subset arrays of the validation (carved by cnn_second_run); the second rows [selected reads]
-    DevBuf so_sel, so_ws, so_rows;
-    unsigned int so_n_sel = 0;              // reads the last adp_detect_cnn call selected for it
-    unsigned int *so_counts = nullptr;      // device: [0] rows replaced, [1] re-validated and still failing, [2] minibatches without one (null: none ran)
-    // the truncation look (polya_truncated.h): the reads that passed T1 [reads of the call]; the verdicts and the counts; T2's
-    // per-subset arrays (carved by trunc_run_t2) and rows [selected reads]
-    DevBuf pt_sel, pt_ws, pt_b2, pt_rows;
-    unsigned int pt_n_t1 = 0;               // reads of the last call that passed T1
-    unsigned int *pt_counts = nullptr;      // device: [0] eligible reads, [1] T1 passed, [2] rows replaced (null: the last call did not look)
+    // the phases behind a detect call's first pass (cnn_fallback.h, cnn_second_opinion.h, polya_truncated.h): the reads each one
+    // selected [reads of the call] -- fb_sel and so_sel are both live between the first pass and the counter read -- and the
+    // per-subset arrays and rows of the phase that is running (carved by it: each runs to completion before the next starts)
+    DevBuf fb_sel, so_sel, pt_sel, sub_ws;
+    // what adp_debug_fetch(10 / 11 / 12) reports beside the phases' device counts (the tail of op_used): the reads the last
+    // adp_detect_cnn call selected for the fallback / the second opinion (0: that phase did not run), and whether the last
+    // detect call looked for truncated tails
+    unsigned int fb_n_sel = 0, so_n_sel = 0;
+    bool pt_looked = false;
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;

@@ -26,7 +26,6 @@
 #include "validate.h"
 
 #define PT_WMAX 4096        // longest median_shift_window T1 holds in LDS (three arrays of W floats beside the wave's scratch)
-#define PT_SEL_THREADS 1024
 // k_pt_t1's verdict per read
 #define PT_INELIGIBLE 0
 #define PT_T1_FAILED 1
@@ -90,29 +89,20 @@ __global__ void __launch_bounds__(64) k_pt_t1(const float *__restrict__ sigs, co
     if (ln == 0) verdict[r] = ok ? PT_T1_PASSED : PT_T1_FAILED;
 }
 
-// One workgroup walks the verdicts PT_SEL_THREADS at a time (as k_cnn_so_select, cnn_second_opinion.h): ascending read order.
-// counts: [0] eligible reads, [1] reads that passed T1 (adp_debug_fetch what = 12)
-__global__ void __launch_bounds__(PT_SEL_THREADS) k_pt_select(const int8_t *__restrict__ verdict, int n, int32_t *__restrict__ sel,
-                                                              unsigned int *__restrict__ count_out, unsigned int *__restrict__ counts)
+// One workgroup walks the verdicts SEL_THREADS at a time (sel_step, common.h): ascending read order.
+// counts (adp_debug_fetch what = 12; zeroed by the host): [0] eligible reads -- every wave adds its own, [1] reads that passed T1
+__global__ void __launch_bounds__(SEL_THREADS) k_pt_select(const int8_t *__restrict__ verdict, int n, int32_t *__restrict__ sel,
+                                                           unsigned int *__restrict__ count_out, unsigned int *__restrict__ counts)
 {
-    __shared__ __attribute__((aligned(16))) int s_wave[PT_SEL_THREADS / 64];
-    __shared__ __attribute__((aligned(16))) int s_elig[PT_SEL_THREADS / 64];
-    const int ln = lane_id(), w = threadIdx.x >> 6;
     int total = 0, eligible = 0;
-    for (int r0 = 0; r0 < n; r0 += PT_SEL_THREADS) {
+    for (int r0 = 0; r0 < n; r0 += SEL_THREADS) {
         const int r = r0 + threadIdx.x;
         const int v = r < n ? verdict[r] : PT_INELIGIBLE;
-        const bool take = v == PT_T1_PASSED;
-        const unsigned long long mk = __ballot(take), me = __ballot(v != PT_INELIGIBLE);
-        if (ln == 0) { s_wave[w] = __popcll(mk); s_elig[w] = __popcll(me); }
-        __syncthreads();
-        int before = 0, step = 0;
-        for (int i = 0; i < PT_SEL_THREADS / 64; i++) { const int c = s_wave[i]; if (i < w) before += c; step += c; eligible += s_elig[i]; }
-        if (take) sel[total + before + __popcll(mk & ((1ull << ln) - 1ull))] = r;
-        total += step;
-        __syncthreads();
+        eligible += __popcll(__ballot(v != PT_INELIGIBLE));
+        sel_step(v == PT_T1_PASSED, r, sel, total);
     }
-    if (threadIdx.x == 0) { *count_out = (unsigned int)total; counts[0] = (unsigned int)eligible; counts[1] = (unsigned int)total; }
+    if (lane_id() == 0 && eligible) atomicAdd(counts, (unsigned int)eligible);
+    if (threadIdx.x == 0) { *count_out = (unsigned int)total; counts[1] = (unsigned int)total; }
 }
 
 __global__ void __launch_bounds__(256) k_pt_gather(const int32_t *__restrict__ sel, int n_sel, int m, const int32_t *__restrict__ full_len,

@@ -223,6 +223,35 @@ def test_compaction_edges(R, pattern, oracle_mod):
     eng.close()
 
 
+def test_compaction_carries_its_total_across_a_1024_read_step(oracle_mod):
+    """k_cnn_so_select walks the rows 1024 at a time and carries the reads taken so far from step to step: 1090 = 1024 + 64 + 2 copies of
+    the reads of _PATTERNS in one minibatch (5: selected and rescued, 6: selected and failing both ways, 0: never selected).  Reads
+    1023 and 1024 are selected (the step's border), the last read is, and the second wave of the first step (reads 64..127) holds
+    none; of the second step's waves only two hold reads at all."""
+    spc, sig, lens, _ = _case("rna004_cnn_default")
+    n = 1090
+    pick = [(5, 0, 6, 0)[i % 4] for i in range(n)]
+    pick[64:128] = [0] * 64
+    pick[1023] = 6
+    pick[n - 1] = 5
+    selected = [_CNN_FAILS_IT[r] for r in pick]
+    assert selected[1023] and selected[1024] and selected[n - 1] and not any(selected[64:128])
+    assert sum(selected) == 515 and sum(selected[:1024]) == 481
+    bs, bl = np.ascontiguousarray(sig[pick]), np.ascontiguousarray(lens[pick])
+    want, raised = _oracle_llr(oracle_mod, None, bs, bl, spc, n)
+    assert not raised
+    for i, r in enumerate(pick):  # precondition, LLR side (as in test_compaction_edges)
+        assert want[i]["success"] == (r != 6), (i, r, want[i]["fail_reason"])
+    eng = _engine(spc, n, sig.shape[1])
+    plain, got, counts = _both(eng, bs, bl, n)
+    assert [int(s) for s in plain["success"]] == [int(not s) for s in selected], "precondition, CNN side"
+    kinds = _check(plain, got, counts, want, raised, n, "1090 reads")
+    rescued = [i for i, r in enumerate(pick) if r == 5]
+    assert kinds["rescued"] == rescued
+    assert counts == (sum(selected), len(rescued), sum(r == 6 for r in pick), 0)
+    eng.close()
+
+
 def test_resident_input_and_device_rows_give_the_same_bytes(oracle_mod):
     import torch
 

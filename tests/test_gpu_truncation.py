@@ -122,6 +122,38 @@ def test_groups_and_lanes_give_the_same_rows(oracle_mod, monkeypatch):
     assert out[None] == out["2"]
 
 
+def test_selection_carries_its_total_across_a_1024_read_step(oracle_mod):
+    """k_pt_select walks the verdicts 1024 at a time and carries the reads taken so far from step to step: 1090 = 1024 + 64 + 2 reads in
+    one minibatch, copies of a flagged, a T1-failing and a T2-failing read of the file's batch and of an ineligible one (full_len == m).
+    Reads 1023 and 1024 pass T1 (the step's border), the last read does, and the second wave of the first step (reads 64..127) holds
+    none that does; of the second step's waves only two hold reads at all.  Kinds and counts come from the restated rule on this batch."""
+    from adapted_amd import lib
+
+    spc = tc.spc_of("llr")
+    m = spc.sig_preload_size
+    long_sig, long_len = tc.batch(m, 48)
+    short_sig, short_len = tc.batch(m, 24, full_len=m)
+    src = [(long_sig[3], long_len[3]), (long_sig[0], long_len[0]), (short_sig[3], short_len[3]), (long_sig[1], long_len[1])]
+    n = 1090
+    pick = [i % 4 for i in range(n)]
+    pick[64:128] = [1, 2] * 32
+    pick[n - 1] = 0
+    sig = np.stack([src[p][0] for p in pick])
+    lens = np.array([src[p][1] for p in pick], dtype=np.int32)
+    first = tr.llr_first_rows(oracle_mod, sig, lens, spc, n)
+    exp, counts, kinds = tr.look(oracle_mod, sig, lens, first, spc, "llr")
+    passed = [k in ("t2_failed", "flagged") for k in kinds]
+    print("1090 reads: counts %s, kinds %s" % (counts, {k: kinds.count(k) for k in set(kinds)}))
+    assert passed[1023] and passed[1024] and passed[n - 1] and not any(passed[64:128]), "precondition: the step's border, the last read, an empty wave"
+    assert set(kinds) == {"ineligible", "t1_failed", "t2_failed", "flagged"}, "precondition: reads of every outcome"
+    assert counts[1] == sum(passed) and sum(passed[:1024]) >= 3 and sum(passed[1024:]) >= 3
+    eng = lib.Engine(spc, n, m, device=0)
+    got, _ = eng.detect_llr_rows(sig, lens, n, n, flag_truncated=True)
+    assert eng.debug_truncated() == counts, (eng.debug_truncated(), counts)
+    _compare(got, exp, "llr", "1090 reads")
+    eng.close()
+
+
 @pytest.mark.parametrize("short_by", [0, 700])
 def test_a_read_that_ends_inside_its_polya_is_never_flagged(oracle_mod, short_by):
     """full_len == m and full_len < m: the poly(A) of a quarter of the reads reaches their end, the tail window of another quarter
