@@ -414,13 +414,17 @@ template <class F> static int sub_carve(adp_handle *h, F &&pieces)
     return 0;
 }
 
-template <int THREADS, int HB, int U>
-static int launch_cand_stats2(adp_handle *h, const float *sig, const int32_t *dlen, int n, int m, int kmax, int cap)
+// the resident matrix types of the detect calls' first passes: the whole matrix, one row per read of the launch (the long-slice
+// series kernels and the shared sweeps work on these; a subset read in place -- SigIdx, SigIdxI16 -- has one candidate per read)
+template <class SIG> struct sig_is_matrix { static constexpr bool value = std::is_same<SIG, SigF32>::value || std::is_same<SIG, SigI16>::value; };
+
+template <int THREADS, int HB, int U, class SIG>
+static int launch_cand_stats2(adp_handle *h, SIG sig, const int32_t *dlen, int n, int m, int kmax, int cap)
 {
     typedef Cs2Sh<HB> Sh;
-    const unsigned bit = THREADS >= 512 ? 4096u : 8192u;
-    if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_cand_stats2<THREADS, HB, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh))); h->attr_done |= bit; }
-    hipLaunchKernelGGL((k_cand_stats2<THREADS, HB, U>), dim3(n), dim3(THREADS), sizeof(Sh), h->stream, sig, dlen, n, m, h->bounds.as<int64_t>(), kmax, h->cfg,
+    const unsigned bit = (THREADS >= 512 ? 4096u : 8192u) << (std::is_same<SIG, SigF32>::value ? 0 : 6);
+    if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_cand_stats2<SIG, THREADS, HB, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh))); h->attr_done |= bit; }
+    hipLaunchKernelGGL((k_cand_stats2<SIG, THREADS, HB, U>), dim3(n), dim3(THREADS), sizeof(Sh), h->stream, sig, dlen, n, m, h->bounds.as<int64_t>(), kmax, h->cfg,
                        (const float *)h->series.as<float>(), cap, (const int8_t *)h->have_series.as<int8_t>(), h->cstat.as<CandStat>());
     return 0;
 }
@@ -444,7 +448,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     // several candidates per read (the CNN path): moving-window series up to the LARGEST candidate for every read (the
     // window, not MVS_CAP, bounds them), then the order statistics of all candidates in shared sweeps (cand_stats.h)
     // (two shapes of k_cand_stats: big workgroups and wide levels beyond a 32 k preload, small ones below: cand_stats.h)
-    const bool multi = std::is_same<SIG, SigF32>::value && kmax > 1 && h->cfg.mvs_detect_check && !h->cfg.mvs_detect_overwrite &&
+    const bool multi = sig_is_matrix<SIG>::value && !vb && kmax > 1 && h->cfg.mvs_detect_check && !h->cfg.mvs_detect_overwrite &&
                        h->cfg.pA_var_window <= MS_HIST && h->cfg.pA_mean_window <= MS_HIST;
     const int cap = multi ? h->vstride : MVS_CAP;
     if (multi && (h->series.ensure((size_t)n * 2 * cap * 4) || h->cstat.ensure((size_t)n * kmax * sizeof(CandStat)))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
@@ -454,14 +458,16 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
         // one candidate per read (the LLR path): the same pipeline of waves over the slice [adapter end, poly(A) end) where it takes the
         // windows (round 4; the lane-per-read kernel k_mvs_series waits on 64 scattered rows per load instruction); ADP_SERIES_PIPE_LLR=0: as before
         bool piped = false;
-        if constexpr (std::is_same<SIG, SigF32>::value) {
+        if constexpr (sig_is_matrix<SIG>::value) {
+        constexpr bool f32 = std::is_same<SIG, SigF32>::value; // (one candidate per read on int16 rows, the LLR path: k_mvs_series<SigI16>, as before)
         const bool pipe_ok = sp_takes(h->cfg.pA_var_window, h->cfg.pA_mean_window) && env_int("ADP_SERIES_PIPE", 1);
-        if (multi || (pipe_ok && kmax == 1 && env_int("ADP_SERIES_PIPE_LLR", 1))) {
+        if (multi || (f32 && pipe_ok && kmax == 1 && env_int("ADP_SERIES_PIPE_LLR", 1))) {
             piped = true;
             Scope s(h, multi ? "k_mvs_series_wave" : "k_mvs_series");
             auto ring = [](int w) { int rb = 128; while (rb < w + MS_CHUNK) rb <<= 1; return rb; };
             const size_t lds = (size_t)MS_G * (ring(h->cfg.pA_var_window) + 4 + ring(h->cfg.pA_mean_window) + 4 + 4 * (MS_CHUNK + 4)) * 4; // (two out halves per wave)
-            if (lds > h->lds_series_set) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->lds_series_set = lds; }
+            size_t &lds_set = f32 ? h->lds_series_set : h->lds_series_set_i16;
+            if (lds > lds_set) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_wave<SIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); lds_set = lds; }
             // the plan (slice starts / lengths, have[]) and the order by falling length (validate.h), then the chains
             if (h->series_plan.ensure((size_t)n * 12 + 2 * MS_NBKT * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
             int32_t *pa = h->series_plan.as<int32_t>(), *pn = pa + n, *pp = pn + n;
@@ -472,11 +478,12 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
             hipLaunchKernelGGL(k_series_order, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, cap, pn, pc, pc + MS_NBKT, pp);
             // round 4: the recurrences as a pipeline of waves (series_pipe.h) for the windows it takes; ADP_SERIES_PIPE=0: one wave per recurrence
             if (pipe_ok) {
-                if (!(h->attr_done & 32u)) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_pipe, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_FLOATS * 4)); h->attr_done |= 32u; }
-                hipLaunchKernelGGL(k_mvs_series_pipe, dim3((n + SP_G - 1) / SP_G), dim3(SP_THREADS), SP_LDS_FLOATS * 4, h->stream, dsig.base, n, m, pa, pn, pp,
+                const unsigned bit = f32 ? 32u : 1u << 20;
+                if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_pipe<SIG>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_FLOATS * 4)); h->attr_done |= bit; }
+                hipLaunchKernelGGL(k_mvs_series_pipe<SIG>, dim3((n + SP_G - 1) / SP_G), dim3(SP_THREADS), SP_LDS_FLOATS * 4, h->stream, dsig, n, m, pa, pn, pp,
                                    h->cfg.pA_var_window, h->cfg.pA_mean_window, h->series.as<float>(), cap, h->have_series.as<int8_t>());
             } else
-            hipLaunchKernelGGL(k_mvs_series_wave, dim3((n + MS_G - 1) / MS_G), dim3(128), lds, h->stream, dsig.base, n, m, pa, pn, pp, h->cfg,
+            hipLaunchKernelGGL(k_mvs_series_wave<SIG>, dim3((n + MS_G - 1) / MS_G), dim3(128), lds, h->stream, dsig, n, m, pa, pn, pp, h->cfg,
                                h->series.as<float>(), cap, h->have_series.as<int8_t>());
         }
         }
@@ -485,15 +492,15 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
             hipLaunchKernelGGL(k_mvs_series<SIG>, dim3((n + 63) / 64), dim3(64), 0, h->stream, dsig, dlen, n, m, bounds, kmax, h->cfg,
                                h->series.as<float>(), cap, h->have_series.as<int8_t>());
         }
-        if constexpr (std::is_same<SIG, SigF32>::value) {
+        if constexpr (sig_is_matrix<SIG>::value) {
         if (multi) {
             Scope s(h, "k_cand_stats");
             // two sweeps per array (cand_stats2.h)
             int rc;
                 // (shapes tried on one box, 24 000 reads at the 200 k window / 32 000 at the default one: 512 threads x 8 loads in flight 14.3 ms,
                 // x 4 14.7, 1024 threads 18.9-19.8; 256 threads x 4 3.5 ms, x 8 4.4, x 2 3.45, 128 threads 4.1-4.2)
-                rc = h->m > 32768 ? launch_cand_stats2<512, 12, 8>(h, dsig.base, dlen, n, m, kmax, cap)
-                                  : launch_cand_stats2<256, 10, 4>(h, dsig.base, dlen, n, m, kmax, cap);
+                rc = h->m > 32768 ? launch_cand_stats2<512, 12, 8>(h, dsig, dlen, n, m, kmax, cap)
+                                  : launch_cand_stats2<256, 10, 4>(h, dsig, dlen, n, m, kmax, cap);
             if (rc) return rc;
         }
         }
@@ -620,6 +627,9 @@ struct PhaseSync {
 
 static __device__ __host__ inline SigF32 sig_from(const SigF32 &s, size_t r0, int m) { return SigF32{s.base + r0 * (size_t)m}; }
 static __device__ __host__ inline SigI16 sig_from(const SigI16 &s, size_t r0, int m) { return SigI16{s.base + r0 * (size_t)m, s.scale + r0, s.offset + r0, s.full_len + r0}; }
+// the rows sel[0 .. ) of a matrix, read where they lie
+static inline SigIdx sig_subset(const SigF32 &s, const int32_t *sel) { return SigIdx{s.base, sel}; }
+static inline SigIdxI16 sig_subset(const SigI16 &s, const int32_t *sel) { return SigIdxI16{s.base, s.scale, s.offset, s.full_len, sel}; }
 
 // k_cumsum and k_cumsum_gather share the launch's waves (llr_stream.h; ADP_CUMSUM_GATHER=0: k_cumsum takes them all, same results)
 static void launch_cumsum(adp_handle *h, int n)
@@ -1227,22 +1237,25 @@ int adp_cnn_predict(adp_handle *h, const float *scores_dev, int n_reads, int min
 
 // C1 on the handle's stream: pooled values (k_cnn_pool), then their per-read median / MAD scaling in place (k_cnn_prepare).
 // sp_head (the fused start-peak scan of a detect call, else null): k_sp_head's state of these reads, which K1 riding the pooling
-// pass (k_cnn_pool<true>) completes for k_sp_tail
-static int launch_cnn_prepare(adp_handle *h, const float *dsig, int n_reads, int m, int off, int ds, int Lc, float *dout, SpHead *sp_head = nullptr)
+// pass (k_cnn_pool<SIG, true>) completes for k_sp_tail
+extern "C++" {
+template <class SIG>
+static int launch_cnn_prepare(adp_handle *h, SIG dsig, int n_reads, int m, int off, int ds, int Lc, float *dout, SpHead *sp_head = nullptr)
 {
     if (h->npk.ensure((size_t)n_reads * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; } // (npk: unused on this path)
     int32_t *nan_cnt = h->npk.as<int32_t>();
     HIPCHK(hipMemsetAsync(nan_cnt, 0, (size_t)n_reads * 4, h->stream));
     { Scope s(h, "k_cnn_pool");
       if (sp_head)
-          hipLaunchKernelGGL(k_cnn_pool<true>, dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt,
+          hipLaunchKernelGGL((k_cnn_pool<SIG, true>), dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt,
                              sp_head, (float)h->cfg.open_pore_pa);
       else
-          hipLaunchKernelGGL(k_cnn_pool<false>, dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt); }
+          hipLaunchKernelGGL((k_cnn_pool<SIG, false>), dim3(n_reads), dim3(256), (size_t)4 * 64 * ds * 4, h->stream, dsig, n_reads, m, off, ds, Lc, dout, nan_cnt); }
     { Scope s(h, "k_cnn_prepare");
       hipLaunchKernelGGL(k_cnn_prepare, dim3(n_reads), dim3(64), 0, h->stream, n_reads, Lc, dout, (const int32_t *)nan_cnt); }
     return 0;
 }
+} // extern "C++"
 
 int adp_cnn_prepare(adp_handle *h, const float *signals, int n_reads, int m, int flags, float *prepared_out)
 {
@@ -1263,7 +1276,7 @@ int adp_cnn_prepare(adp_handle *h, const float *signals, int n_reads, int m, int
         if (h->bounds_stage.ensure((size_t)n_reads * Lc * 4)) { g_err = "staging allocation failed"; return ADP_ERR_HIP; }
         dout = h->bounds_stage.as<float>();
     }
-    { int rc2 = launch_cnn_prepare(h, dsig, n_reads, m, off, ds, Lc, dout); if (rc2) return rc2; }
+    { int rc2 = launch_cnn_prepare(h, SigF32{dsig}, n_reads, m, off, ds, Lc, dout); if (rc2) return rc2; }
     if (!(flags & ADP_OUT_DEVICE))
         HIPCHK(hipMemcpyAsync(prepared_out, dout, (size_t)n_reads * Lc * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipGetLastError());
@@ -1537,6 +1550,8 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
 // k candidates, enqueued on the handle's stream without waiting for anything on the host.  bounds_dst (may be NULL): int64
 // [n, 1 + max(k, 1)] what cnn_detect returns, copied with bounds_kind.
 // the start-peak overlay of the CNN path (ADP_WITH_START_PEAK): can K1 ride the pooling pass?
+// (from here to adp_detect_cnn: templates on the matrix type -- SigF32 for adp_detect_cnn, SigI16 for adp_detect_cnn_i16)
+extern "C++" {
 static bool cnn_sp_fused(const adp_handle *h)
 {
     const adp_cfg &c = h->cfg;
@@ -1548,7 +1563,8 @@ static void cnn_sp_decorate(adp_handle *h, const SpOut *sp, adp_row *rows, int n
 }
 // sp_out (ADP_WITH_START_PEAK, else null): K1's results of these reads -- a slice of the CALL's buffer, the owner handle's, because
 // the phases behind the first pass run there -- are computed beside the pass and overlaid on its rows (k_sp_decorate, mode 0).
-static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
+template <class SIG>
+static int cnn_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n_reads, int m, int minibatch, adp_row *rows_dst,
                        int rows_kind, int64_t *bounds_dst, int bounds_kind, SpOut *sp_out = nullptr)
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
@@ -1557,7 +1573,7 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     hipStream_t st = h->stream;
     int rc = alloc_all(h, n_reads, false);
     if (rc) return rc;
-    // K1 riding the pooling pass (k_cnn_pool<true>): when both pooling factors agree and min_obs_adapter is a multiple of them the
+    // K1 riding the pooling pass (k_cnn_pool<SIG, true>): when both pooling factors agree and min_obs_adapter is a multiple of them the
     // start-peak scan costs no sweep of its own; else, and with ADP_SP_FUSED=0, the separate k_start_peak streams the signal on the
     // side stream beside the conv stack (matrix cores, little HBM traffic)
     const size_t sp_lds = (size_t)64 * h->cfg.sp_downscale_factor * 4;
@@ -1567,19 +1583,19 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
         if (h->sphead.ensure((size_t)n_reads * sizeof(SpHead))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
         sp_head = h->sphead.as<SpHead>();
         Scope s(h, "k_sp_head");
-        hipLaunchKernelGGL(k_sp_head<SigF32>, dim3(n_reads), dim3(64), sp_lds, st, SigF32{dsig}, dlen, n_reads, m, h->cfg, off, sp_head);
+        hipLaunchKernelGGL(k_sp_head<SIG>, dim3(n_reads), dim3(64), sp_lds, st, dsig, dlen, n_reads, m, h->cfg, off, sp_head);
     }
     rc = launch_cnn_prepare(h, dsig, n_reads, m, off, ds, Lc, h->cnn_x.as<float>(), sp_head);
     if (rc) return rc;
     if (sp_fused) {
         const int cov0 = off / ds, cov1 = cov0 + (m - off) / ds;
         Scope s(h, "k_sp_tail");
-        hipLaunchKernelGGL(k_sp_tail<SigF32>, dim3(n_reads), dim3(64), sp_lds, st, SigF32{dsig}, dlen, n_reads, m, h->cfg, cov0, cov1, (const SpHead *)sp_head, sp_out);
+        hipLaunchKernelGGL(k_sp_tail<SIG>, dim3(n_reads), dim3(64), sp_lds, st, dsig, dlen, n_reads, m, h->cfg, cov0, cov1, (const SpHead *)sp_head, sp_out);
     } else if (sp_out) {
         HIPCHK(hipEventRecord(h->ev_fork, st)); // (the signal is staged on this stream)
         HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
         { Scope s(h, "k_start_peak", h->stream2);
-          hipLaunchKernelGGL(k_start_peak<SigF32>, dim3(n_reads), dim3(64), sp_lds, h->stream2, SigF32{dsig}, dlen, n_reads, m, h->cfg, sp_out); }
+          hipLaunchKernelGGL(k_start_peak<SIG>, dim3(n_reads), dim3(64), sp_lds, h->stream2, dsig, dlen, n_reads, m, h->cfg, sp_out); }
         HIPCHK(hipEventRecord(h->ev_join, h->stream2));
     }
     // (from here on an error return must not leave the side stream's scan running into the caller's next use of sp_out)
@@ -1591,7 +1607,7 @@ static int cnn_enqueue(adp_handle *h, const float *dsig, const int32_t *dlen, in
     if (rc) return rc;
     if (bounds_dst) HIPCHK(hipMemcpyAsync(bounds_dst, h->bounds.p, (size_t)n_reads * (1 + kk) * 8, (hipMemcpyKind)bounds_kind, st));
     HIPCHK(hipMemsetAsync(h->topk_none.p, 0, (size_t)n_reads, st));
-    rc = launch_validate(h, SigF32{dsig}, dlen, n_reads, m, kk, n_reads, false);
+    rc = launch_validate(h, dsig, dlen, n_reads, m, kk, n_reads, false);
     if (rc) return rc;
     if (sp_out) {
         if (!sp_fused) { HIPCHK(hipStreamWaitEvent(st, h->ev_join, 0)); sp_join.armed = false; }
@@ -1671,7 +1687,8 @@ static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const 
 // polya_end_topk given) and the merge into `rows`.  The selected signal rows are read where they lie (SigIdx); the re-validated
 // rows and their candidates have buffers of their own -- the handle's hold the first pass (launch_validate's ValBufs).  Open-pore
 // lists of re-validated rows go to the same arena of the call: the caller looks at its counter once more.
-static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dlen, int m, adp_row *rows, const int64_t *bounds, int bstride, int n_sel)
+template <class SIG>
+static int cnn_fallback_run(adp_handle *h, SIG dsig, const int32_t *dlen, int m, adp_row *rows, const int64_t *bounds, int bstride, int n_sel)
 {
     hipStream_t st = h->stream;
     int rc = alloc_all(h, n_sel, true);
@@ -1684,7 +1701,7 @@ static int cnn_fallback_run(adp_handle *h, const float *dsig, const int32_t *dle
     }));
     unsigned int *counts = phase_counts(h, OPW_FB);
     const int32_t *sel = h->fb_sel.as<int32_t>();
-    const SigIdx sig{dsig, sel};
+    const auto sig = sig_subset(dsig, sel);
     HIPCHK(hipMemsetAsync(counts, 0, 8, st));
     HIPCHK(hipMemsetAsync(topk, 0, N, st)); // (polya_end_topk is given)
     { Scope s(h, "k_cnn_fb_gather");
@@ -1723,10 +1740,13 @@ static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
 // adp_detect_llr computes -- with its boundaries in a buffer of this phase (the handle's bounds / topk_none / rows hold the CNN
 // path's).  The validation (k = 1) reads the selected rows in place and leaves its rows in the phase's own; the merge copies those
 // that passed into `rows`.  Open-pore lists of the second rows append to the call's arena: the caller looks at its counter once more.
-static int cnn_second_run(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so)
+template <class SIG>
+static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so)
 {
     hipStream_t st = h->stream;
-    int rc = llr_enqueue(h, SigF32{dsig}, dlen, n, m, minibatch, flags & ADP_TAILS_NAN, nullptr, 0, nullptr, nullptr, 7, nullptr);
+    // (int16 rows: the padding is implied, so the passes always stop at a read's end -- as adp_detect_llr_i16 runs them)
+    const int tails = std::is_same<SIG, SigF32>::value ? (flags & ADP_TAILS_NAN) : ADP_TAILS_NAN;
+    int rc = llr_enqueue(h, dsig, dlen, n, m, minibatch, tails, nullptr, 0, nullptr, nullptr, 7, nullptr);
     if (rc) return rc;
     const size_t R = (size_t)n, N = (size_t)n_so;
     int64_t *ball, *b2; int32_t *dlen_sub; int8_t *tall, *tsub; adp_row *rows2;
@@ -1745,7 +1765,7 @@ static int cnn_second_run(adp_handle *h, const float *dsig, const int32_t *dlen,
       hipLaunchKernelGGL(k_cnn_so_gather, dim3((n_so + 255) / 256), dim3(256), 0, st, sel, n_so, minibatch, mbs, dlen, (const int64_t *)ball,
                          (const int8_t *)tall, dlen_sub, b2, tsub); }
     const ValBufs vb{b2, tsub, rows2};
-    rc = launch_validate(h, SigIdx{dsig, sel}, dlen_sub, n_so, m, 1, n_so, false, &vb);
+    rc = launch_validate(h, sig_subset(dsig, sel), dlen_sub, n_so, m, 1, n_so, false, &vb);
     if (rc) return rc;
     { Scope s(h, "k_cnn_so_merge");
       hipLaunchKernelGGL(k_cnn_so_merge, dim3(n_so), dim3(64), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)rows2, rows, counts); }
@@ -1772,7 +1792,8 @@ static int cnn_second_run(adp_handle *h, const float *dsig, const int32_t *dlen,
 // idempotent); the truncation look's merge keeps the columns (k_pt_merge).
 // The truncation look (ADP_FLAG_TRUNCATED) comes behind all of that, on every read's final row: one more synchronisation for its
 // T1 count, and T2 only where a tail window passed.
-static int cnn_after_first_pass(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows,
+template <class SIG>
+static int cnn_after_first_pass(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows,
                                 const int64_t *bounds, int bstride, const SpOut *sp, bool *changed)
 {
     const bool fb = cnn_fallback_wanted(h, flags, rows), so = cnn_second_wanted(flags, rows);
@@ -1801,9 +1822,11 @@ static int cnn_after_first_pass(adp_handle *h, const float *dsig, const int32_t 
         rc = arena_end(h);
         if (rc < 0) return rc;
     }
+    if constexpr (std::is_same<SIG, SigF32>::value) { // (a float32-row phase: adp_detect_cnn_i16 refuses the flag)
     if (rc == 0 && trunc_wanted(flags, rows)) {
         *changed = true; // (T1 marks every row)
-        rc = trunc_finish(h, dsig, dlen, n, m, rows);
+        rc = trunc_finish(h, dsig.base, dlen, n, m, rows);
+    }
     }
     return rc;
 }
@@ -1812,7 +1835,8 @@ static int cnn_after_first_pass(adp_handle *h, const float *dsig, const int32_t 
 // wave per SIMD, little HBM traffic), the other's is in the candidate validation -- the moving-window recurrences (latency of one
 // wave's instruction stream, ~11 ms per launch whatever the number of reads), the order-statistics sweeps (HBM), the partition
 // statistics.  Reads of different minibatches never interact on this path (find_peaks / row compaction are per minibatch).
-static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows_out,
+template <class SIG>
+static int cnn_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows_out,
                        int64_t *bounds_out, int mb_per_group, int n_lanes)
 {
     const int n_mb = (n + minibatch - 1) / minibatch;
@@ -1842,7 +1866,7 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
             adp_handle *l = lanes[g % n_lanes];
             const int r0 = g * mb_per_group * minibatch;
             const int ng = (n - r0) < mb_per_group * minibatch ? (n - r0) : mb_per_group * minibatch;
-            const int rc = cnn_enqueue(l, dsig + (size_t)r0 * m, dlen + r0, ng, m, minibatch, rows_dev ? rows_dev + r0 : nullptr, hipMemcpyDeviceToDevice,
+            const int rc = cnn_enqueue(l, sig_from(dsig, (size_t)r0, m), dlen + r0, ng, m, minibatch, rows_dev ? rows_dev + r0 : nullptr, hipMemcpyDeviceToDevice,
                                        bounds_dev ? bounds_dev + (size_t)r0 * (1 + kk) : nullptr, hipMemcpyDeviceToDevice, sp ? sp + r0 : nullptr);
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
         }
@@ -1856,24 +1880,21 @@ static int cnn_grouped(adp_handle *h, const float *dsig, const int32_t *dlen, in
     return ADP_OK;
 }
 
-// combined_detect_cnn in one call: up to its short-read fallback, or with ADP_CNN_FALLBACK (and cfg.fallback_to_llr_short_reads)
-// the whole of it.  bounds_out (host, may be NULL): int64 [n, 1 + max(k, 1)], what cnn_detect returns.
-int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
-                   adp_row *rows_out, int64_t *bounds_out)
+// what both detect calls of the CNN path refuse behind begin_call
+static int cnn_ready(const adp_handle *h, int m)
 {
-    if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
-    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
-    if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
-    RCCHK(begin_call(h));
     if (m <= h->cfg.min_obs_adapter) { g_err = "preload shorter than min_obs_adapter"; return ADP_ERR_INVALID; }
     if (!h->cnn_have_w) { g_err = "adp_cnn_set_weights has not been called"; return ADP_ERR_INVALID; }
+    return 0;
+}
+// A detect call of the CNN path over a resident matrix (its arguments checked, begin_call and cnn_ready done), in either execution form
+template <class SIG>
+static int cnn_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n_reads, int m, int minibatch, int flags, adp_row *rows_out,
+                          int64_t *bounds_out)
+{
     h->cnn_redo_f32 = false;
     // (K1's results of the whole call: sized here, before any phase's workspace call could move the buffer under them)
     if (cnn_sp_wanted(flags, rows_out) && h->sp.ensure((size_t)n_reads * sizeof(SpOut))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    const float *dsig; const int32_t *dlen;
-    int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
-    if (rc) return rc;
     // ADP_CNN_GROUPS (opt-in): unset / 1 = one chunk on one stream; 0 = automatic (chunks of about a quarter of the call, at most
     // what the conv stack's activation buffers hold, over two lanes); k = aim at k chunks.  Measured at the 200 k window (8000
     // reads, profiles/r03_cnn_chunks.txt): 4 chunks over 2 lanes 107.5 ms against 95.4 ms for one chunk -- the moving-window
@@ -1916,6 +1937,42 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
         }
         return rc;
     });
+}
+} // extern "C++"
+
+// combined_detect_cnn in one call: up to its short-read fallback, or with ADP_CNN_FALLBACK (and cfg.fallback_to_llr_short_reads)
+// the whole of it.  bounds_out (host, may be NULL): int64 [n, 1 + max(k, 1)], what cnn_detect returns.
+int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, int minibatch, int flags,
+                   adp_row *rows_out, int64_t *bounds_out)
+{
+    if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
+    if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
+    RCCHK(begin_call(h));
+    RCCHK(cnn_ready(h, m));
+    const float *dsig; const int32_t *dlen;
+    int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
+    if (rc) return rc;
+    return cnn_pipeline_t(h, SigF32{dsig}, dlen, n_reads, m, minibatch, flags, rows_out, bounds_out);
+}
+
+// The same over raw int16 rows (include/adapted_hip_i16.h): every kernel that touches the signal reads the ADC samples and forms pA
+// in registers; the phases, their order and their buffers are adp_detect_cnn's.
+int adp_detect_cnn_i16(adp_handle *h, const int16_t *raw, const int32_t *full_len, const float *scale, const float *offset, int n_reads,
+                       int m, int minibatch, int flags, adp_row *rows_out, int64_t *bounds_out)
+{
+    if (!h || !raw || !full_len || !scale || !offset || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!(flags & ADP_IN_DEVICE)) { g_err = "adp_detect_cnn_i16 takes device pointers (ADP_IN_DEVICE)"; return ADP_ERR_INVALID; }
+    if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "the single-read layout takes float32 input"; return ADP_ERR_UNSUPPORTED; }
+    if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_cnn)"; return ADP_ERR_UNSUPPORTED; }
+    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
+    RCCHK(begin_call(h));
+    RCCHK(cnn_ready(h, m));
+    // (samples at or beyond min(full_len, m) read as NaN: the padding is implied)
+    return cnn_pipeline_t(h, SigI16{raw, scale, offset, full_len}, full_len, n_reads, m, minibatch, flags, rows_out, bounds_out);
 }
 
 int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *full_len, int n, int m, const int64_t *ranges,

@@ -86,9 +86,44 @@ static __device__ __forceinline__ void cs2_sweep(const GLB float *p, int b0, int
     }
 }
 
+// the same over a row of the signal matrix: float32 rows are the array itself; int16 rows take 8-byte loads, as many per thread in
+// flight, and become pA on their way to f (the slice [b0, b1) lies inside the read: no padding among the samples)
+template <int THREADS, int CS2_U, class F>
+static __device__ __forceinline__ void cs2_sweep(const RowF32 &x, int b0, int b1, int tid, F f) { cs2_sweep<THREADS, CS2_U>(x.p, b0, b1, tid, f); }
+template <int THREADS, int CS2_U, class F>
+static __device__ __forceinline__ void cs2_sweep(const RowI16 &x, int b0, int b1, int tid, F f)
+{
+    if (b1 - b0 < 4) {
+        for (int i = b0 + tid; i < b1; i += THREADS) f(x.cal(x.p[i]), i);
+        return;
+    }
+    const int last = b1 - 4;
+    for (int base = b0 + tid * 4; base < b1; base += THREADS * 4 * CS2_U) {
+        adp_s4u v[CS2_U];
+#pragma unroll
+        for (int u = 0; u < CS2_U; u++) {
+            const int i = base + u * THREADS * 4;
+            const int ic = i < last ? i : last;
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const GLB adp_s4u *>(x.p + ic));
+        }
+#pragma unroll
+        for (int u = 0; u < CS2_U; u++) {
+            const int i = base + u * THREADS * 4;
+            if (i < b1) {
+                const int ic = i < last ? i : last;
+                if (ic >= i) f(x.cal(v[u].x), ic);
+                if (ic + 1 >= i) f(x.cal(v[u].y), ic + 1);
+                if (ic + 2 >= i) f(x.cal(v[u].z), ic + 2);
+                f(x.cal(v[u].w), ic + 3);
+            }
+        }
+    }
+}
+
 // grid = n reads; block = THREADS; dynamic LDS = sizeof(Cs2Sh<HB>).  Arguments and results as k_cand_stats (cand_stats.h).
-template <int THREADS, int HB, int CS2_U>
-__global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict__ sigs, const int32_t *__restrict__ full_len, int n_reads, int m,
+// SIG: the matrix type of the slices (SigF32, SigI16); the two series are float32 arrays either way.
+template <class SIG, int THREADS, int HB, int CS2_U>
+__global__ void __launch_bounds__(THREADS) k_cand_stats2(SIG sigs, const int32_t *__restrict__ full_len, int n_reads, int m,
                                                             const int64_t *__restrict__ bounds, int kmax, adp_cfg cfg,
                                                             const float *__restrict__ series, int cap, const int8_t *__restrict__ have,
                                                             CandStat *__restrict__ out)
@@ -109,8 +144,9 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
     if (a_e == 0 || (long long)S < a_e + cfg.median_shift_window) return;
     const int a = (int)(a_e < S ? a_e : S);
     const int wvw = cfg.pA_var_window, wmw = cfg.pA_mean_window;
+    const typename SIG::Row x0 = sigs.row(r, m) + a; // array 0, the slice
     const GLB float *arr[3];
-    arr[0] = (const GLB float *)sigs + (size_t)r * m + a;
+    arr[0] = nullptr;
     arr[2] = (const GLB float *)series + (size_t)r * 2 * cap; // moving mean
     arr[1] = arr[2] + cap;                                    // moving variance
     int ncand = 0;
@@ -167,7 +203,8 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
             for (int j = 0; j < 3; j++) {
                 const int w1 = j == 0 ? 0 : (j == 1 ? wvw - 1 : wmw - 1);
                 const int la = n_all - w1, lf = n_first - w1;
-                const float v1 = arr[j][(int)(((long long)tid * la) / THREADS)], v2 = arr[j][(int)(((long long)tid * lf) / THREADS)];
+                const int i1 = (int)(((long long)tid * la) / THREADS), i2 = (int)(((long long)tid * lf) / THREADS);
+                const float v1 = j == 0 ? x0[i1] : arr[j][i1], v2 = j == 0 ? x0[i2] : arr[j][i2];
                 uint32_t mn = 0xffffffffu, mx = 0u;
                 if (v1 == v1) { const uint32_t k = f2key(v1); mn = k; mx = k; }
                 if (v2 == v2) { const uint32_t k = f2key(v2); mn = k < mn ? k : mn; mx = k > mx ? k : mx; }
@@ -207,14 +244,17 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
                     LDS uint32_t *h = (LDS uint32_t *)sh->hist + j * NB;
                     const uint32_t kl = klo[j]; const int sf = shf[j];
                     int nm = nanmin[j];
-                    if (!ABLATED(1 << 23))
-                    cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, [&](float v, int i) {
+                    auto count = [&](float v, int i) {
                         if (v != v) { nm = i < nm ? i : nm; return; }
                         const uint32_t key = f2key(v);
                         uint32_t b = ((key > kl ? key : kl) - kl) >> sf;
                         b = b < (uint32_t)(NB - 1) ? b : (uint32_t)(NB - 1);
                         __hip_atomic_fetch_add(&h[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    });
+                    };
+                    if (!ABLATED(1 << 23)) {
+                        if (j == 0) cs2_sweep<THREADS, CS2_U>(x0, b0, b1, tid, count);
+                        else cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, count);
+                    }
                     nanmin[j] = nm;
                 }
                 prev = hi;
@@ -319,8 +359,7 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
                     const LDS uint8_t *lut = (const LDS uint8_t *)sh->lut + j * NB;
                     const uint32_t kl = klo[j]; const int sf = shf[j];
                     const uint32_t lowmask = sf ? ((1u << sf) - 1u) : 0u;
-                    if (!ABLATED(1 << 21))
-                    cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, [&](float v, int i) {
+                    auto collect = [&](float v, int i) {
                         (void)i;
                         if (v != v) return;
                         const uint32_t key = f2key(v);
@@ -337,7 +376,11 @@ __global__ void __launch_bounds__(THREADS) k_cand_stats2(const float *__restrict
                             const int p = __hip_atomic_fetch_add(&sh->s_fill[sl], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             if (p < sh->s_total[sl]) pool[sh->s_off[sl] + p] = ((uint32_t)s << CS2_SEGSH) | low;
                         }
-                    });
+                    };
+                    if (!ABLATED(1 << 21)) {
+                        if (j == 0) cs2_sweep<THREADS, CS2_U>(x0, b0, b1, tid, collect);
+                        else cs2_sweep<THREADS, CS2_U>(arr[j], b0, b1, tid, collect);
+                    }
                 }
                 prev = hi;
             }

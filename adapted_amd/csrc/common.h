@@ -113,6 +113,10 @@ struct RowF32 {
     static constexpr int PREFETCH = 1;
     __device__ __forceinline__ Raw4 raw4u_in(long long i) const { return f4u(i); }
     __device__ __forceinline__ float4 cook4(const Raw4 &v) const { return v; }
+    // raw1 / cook1: the same split for ONE sample through the caches (the moving-window chains keep a chunk's loads in flight)
+    typedef float Raw1;
+    __device__ __forceinline__ Raw1 raw1(long long i) const { return p[i]; }
+    __device__ __forceinline__ float cook1(Raw1 v) const { return v; }
     __device__ __forceinline__ bool vec_ok() const { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
     __device__ __forceinline__ uintptr_t key() const { return reinterpret_cast<uintptr_t>(p); }
     __device__ __forceinline__ long long diff(const RowF32 &o) const { return p - o.p; }
@@ -171,6 +175,9 @@ struct RowI16 {
         return w;
     }
     __device__ __forceinline__ float4 cook4(const Raw4 &v) const { return cal4(v); }
+    typedef short Raw1; // (raw1 / cook1 are for samples the caller knows to exist: no padding check)
+    __device__ __forceinline__ Raw1 raw1(long long i) const { return p[i]; }
+    __device__ __forceinline__ float cook1(Raw1 v) const { return cal(v); }
     __device__ __forceinline__ bool vec_ok() const { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
     __device__ __forceinline__ uintptr_t key() const { return reinterpret_cast<uintptr_t>(p); }
     __device__ __forceinline__ long long diff(const RowI16 &o) const { return p - o.p; }
@@ -202,6 +209,22 @@ struct SigIdx {
     const int32_t *idx;
     __device__ __forceinline__ Row row(long long j, int m) const { return Row{(const GLB float *)base + (size_t)idx[j] * m}; }
     __device__ __forceinline__ bool vec_ok(int m) const { return (m & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0; }
+};
+// the same subset of resident int16 rows (adp_detect_cnn_i16's fallback and second opinion): scale, offset and length are the
+// matrix's, taken at idx[j]
+struct SigIdxI16 {
+    typedef RowI16 Row;
+    const int16_t *base;
+    const float *scale, *offset;
+    const int32_t *full_len;
+    const int32_t *idx;
+    __device__ __forceinline__ Row row(long long j, int m) const
+    {
+        const int r = idx[j];
+        const int fl = full_len[r];
+        return Row{(const GLB int16_t *)base + (size_t)r * m, scale[r], offset[r], fl < m ? (fl > 0 ? fl : 0) : m};
+    }
+    __device__ __forceinline__ bool vec_ok(int m) const { return (m & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 7) == 0; }
 };
 // plain float arrays (series, pooled values, copies) go through the same helpers as rows
 // x[i] if ok, else some valid element's value or 0 (the caller does not use it): the load pattern each row type is fastest with

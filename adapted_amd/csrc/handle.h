@@ -106,7 +106,7 @@ struct adp_handle {
     // launch attributes already requested through this handle (hipFuncSetAttribute per kernel instantiation and device; kept per
     // handle -- a handle is used by one thread at a time -- instead of in process-wide statics)
     unsigned attr_done = 0;
-    size_t lds_series_set = 0;
+    size_t lds_series_set = 0, lds_series_set_i16 = 0;
 #ifdef ADP_ABLATE
     int ablate = 0;   // the mask this handle last copied to its device (sync_ablate)
 #endif

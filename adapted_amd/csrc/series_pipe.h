@@ -10,6 +10,7 @@
 // serial: the mean (one add per step) and the clamped sum of squares (add, compare, select).  Here they run in DIFFERENT waves of a
 // workgroup, on different SIMDs, each with nothing else to issue:
 //     wave 0  loader      coalesced 16-byte loads of the next chunk (4 reads per instruction) -> the reads' LDS rings
+//                         (int16 rows: 8 bytes per lane, converted with the read's calibration on the way into the ring)
 //     wave 1  mean        move_mean: asum += a_i - a_old                                    -> outm
 //     wave 2  var, part 1 delta, the mean chain, t = (a_i' + a_old') * delta                -> tbuf     (7 instructions per step)
 //     wave 3  var, part 2 ssq = max0(ssq + t), out = ssq * (1/w), one chunk behind part 1   -> outv     (4 instructions per step)
@@ -55,8 +56,22 @@ static __device__ inline long long sp_now() { long long t; asm volatile("s_waitc
 #define SP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #endif
 
+// what the loader keeps in flight per lane and read -- four RAW samples from any position (a slice's start is only aligned to a
+// sample) -- and their conversion when they go to the ring.  A slice lies inside its read (k_series_plan): no padding to look for.
+template <class ROW> struct SpRaw;
+template <> struct SpRaw<RowF32> { typedef sp_f4u T; };
+template <> struct SpRaw<RowI16> { typedef adp_s4u T; };
+static __device__ __forceinline__ sp_f4u sp_ld4(const RowF32 &x, int i) { return *reinterpret_cast<const GLB sp_f4u *>(x.p + i); }
+static __device__ __forceinline__ adp_s4u sp_ld4(const RowI16 &x, int i) { return *reinterpret_cast<const GLB adp_s4u *>(x.p + i); }
+static __device__ __forceinline__ adp_v4f sp_cook4(const RowF32 &, const sp_f4u &v) { return (adp_v4f){v.x, v.y, v.z, v.w}; }
+static __device__ __forceinline__ adp_v4f sp_cook4(const RowI16 &x, const adp_s4u &v)
+{
+    return (adp_v4f){x.cal(v.x), x.cal(v.y), x.cal(v.z), x.cal(v.w)};
+}
+
 // grid = ceil(n_reads / SP_G); block = SP_THREADS; dynamic LDS = SP_LDS_FLOATS floats.  a_plan / n_plan / perm: k_series_plan, k_series_order
-__global__ void __launch_bounds__(SP_THREADS) k_mvs_series_pipe(const float *__restrict__ sigs, int n_reads, int m, const int32_t *__restrict__ a_plan,
+template <class SIG>
+__global__ void __launch_bounds__(SP_THREADS) k_mvs_series_pipe(SIG sigs, int n_reads, int m, const int32_t *__restrict__ a_plan,
                                                                 const int32_t *__restrict__ n_plan, const int32_t *__restrict__ perm, int wv, int wm,
                                                                 float *__restrict__ series, int cap, int8_t *__restrict__ have)
 {
@@ -101,31 +116,33 @@ __global__ void __launch_bounds__(SP_THREADS) k_mvs_series_pipe(const float *__r
     if (wave == 0) {
         // ---- loader: instruction u of a chunk brings 64 samples of the reads 4u .. 4u + 3, 16 lanes x 16 bytes each
         const int sub = ln & 15;
-        const GLB float *xb[NU];
+        typedef typename SIG::Row Row;
+        typedef typename SpRaw<Row>::T Raw;
+        Row xb[NU]; // (int16 rows: the read's scale and offset ride in the loader's registers with its pointer)
         int last[NU], nend[NU];
 #pragma unroll
         for (int u = 0; u < NU; u++) {
             const int q = 4 * u + (ln >> 4);
-            xb[u] = (const GLB float *)sigs + (size_t)rid_of[q] * m + a_of[q];
+            xb[u] = sigs.row(rid_of[q], m) + a_of[q];
             const int nq = n_of[q];
             last[u] = nq >= 4 ? nq - 4 : 0; // (what lies behind a slice's end is never used: any readable address will do)
             nend[u] = nq;
         }
         // a chunk's loads are issued a WHOLE iteration before their samples go to LDS (two register sets in turn): issued at the end
         // of one iteration and consumed at the start of the next, every chunk waited a memory round trip (~2 us against ~0.8 us of chains)
-        sp_f4u preA[NU], preB[NU];
-        auto fetch = [&](int c, sp_f4u (&pre)[NU]) {
+        Raw preA[NU], preB[NU];
+        auto fetch = [&](int c, Raw (&pre)[NU]) {
 #pragma unroll
             for (int u = 0; u < NU; u++) {
                 const int i = c * SP_CH + 4 * sub;
 #if defined(SP_ABL) && (SP_ABL & 1) // (timing only: no global loads)
-                pre[u] = (sp_f4u){(float)i, 1.f, 2.f, 3.f};
+                pre[u] = (Raw){(decltype(pre[u].x))i, 1, 2, 3};
 #else
-                pre[u] = *reinterpret_cast<const GLB sp_f4u *>(xb[u] + (i < last[u] ? i : last[u]));
+                pre[u] = sp_ld4(xb[u], i < last[u] ? i : last[u]);
 #endif
             }
         };
-        auto put = [&](int c, const sp_f4u (&pre)[NU]) {
+        auto put = [&](int c, const Raw (&pre)[NU]) {
 #pragma unroll
             for (int u = 0; u < NU; u++) {
                 const int q = 4 * u + (ln >> 4), i = c * SP_CH + 4 * sub;
@@ -133,11 +150,12 @@ __global__ void __launch_bounds__(SP_THREADS) k_mvs_series_pipe(const float *__r
                 // the vector that straddles the end: its leading samples are rebuilt below)
                 LDS float *dst = ring + q * SP_S + (i & MASK);
                 const int lim = last[u];
-                if (i <= lim) *reinterpret_cast<LDS adp_v4f *>(dst) = (adp_v4f){pre[u].x, pre[u].y, pre[u].z, pre[u].w};
+                const adp_v4f cv = sp_cook4(xb[u], pre[u]);
+                if (i <= lim) *reinterpret_cast<LDS adp_v4f *>(dst) = cv;
                 else if (i < nend[u]) { // (a vector wholly behind the end: nothing reads its cells -- the lanes of ended reads pass)
                     // the load was taken at `lim` instead of i: sample i + j sits at position i + j - lim of the vector, if inside it
                     const int sh = i - lim;
-                    const float v[4] = {pre[u].x, pre[u].y, pre[u].z, pre[u].w};
+                    const float v[4] = {cv.x, cv.y, cv.z, cv.w};
 #pragma unroll
                     for (int j = 0; j < 4; j++) { const int s = sh + j; float val = 0.f;
 #pragma unroll

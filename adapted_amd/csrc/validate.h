@@ -685,8 +685,8 @@ static __device__ __forceinline__ void ms_var4(const float (&a)[4], const float 
     assqdm = p3;
 }
 
-template <bool VAR>
-static __device__ void ms_chains(const float *__restrict__ sigs, int m, const LDS int32_t *a_of, const LDS int32_t *n_of,
+template <bool VAR, class SIG>
+static __device__ void ms_chains(SIG sigs, int m, const LDS int32_t *a_of, const LDS int32_t *n_of,
                                  const LDS int32_t *rid_of, int w, float *__restrict__ series, int cap, LDS float *buf, LDS float *out,
                                  int8_t *__restrict__ have)
 {
@@ -705,22 +705,25 @@ static __device__ void ms_chains(const float *__restrict__ sigs, int m, const LD
     LDS float *mybuf = buf + g * S;
     const bool vec = (w & 3) == 0;
     // lengths and slice starts of the wave's reads in registers (wave-uniform values)
+    // (int16 rows: the slice lies inside the read -- k_series_plan --, so the samples are converted without a padding check,
+    // and only when they go to LDS: the raw values are what stays in flight during the chains)
+    typedef typename SIG::Row Row;
     int nq[MS_G];
-    const GLB float *xq[MS_G];
+    Row xq[MS_G];
 #pragma unroll
     for (int q = 0; q < MS_G; q++) {
         nq[q] = n_of[q];
-        xq[q] = (const GLB float *)sigs + (size_t)rid_of[q] * m + a_of[q];
+        xq[q] = sigs.row(rid_of[q], m) + a_of[q];
     }
     // the samples of the NEXT chunk are requested before the chains of the current one run (one load per read, all in
     // flight together; waiting for them one by one cost 8 us per chunk) and land in LDS after it.  The loads are
     // UNCONDITIONAL (index clamped into the slice; what lies behind a slice's end is not copied to LDS): behind a
     // condition the compiler joins the two paths right after the load -- s_waitcnt vmcnt(0) BEFORE the chains, i.e. a full
     // memory round trip (2.5 us, 16 streams with a page each) per chunk of 1.6 us of arithmetic
-    float pre[MS_G];
+    typename Row::Raw1 pre[MS_G];
     auto fetch = [&](int i0) {
 #pragma unroll
-        for (int q = 0; q < MS_G; q++) { const int i = i0 + ln, last = nq[q] > 0 ? nq[q] - 1 : 0; pre[q] = xq[q][i < last ? i : last]; }
+        for (int q = 0; q < MS_G; q++) { const int i = i0 + ln, last = nq[q] > 0 ? nq[q] - 1 : 0; pre[q] = xq[q].raw1(i < last ? i : last); }
     };
     // out[q][i - i0] is read q's series value at index i - w + 1 (defined from i = w - 1 on): coalesced stores per read,
     // issued a chunk LATE, from the other half of the out buffer, right behind the next chunk's loads: gfx950 counts loads
@@ -739,7 +742,7 @@ static __device__ void ms_chains(const float *__restrict__ sigs, int m, const LD
     for (int i0 = 0; i0 < nmax; i0 += MS_CHUNK, par ^= 1) {
         ws_sync();
 #pragma unroll
-        for (int q = 0; q < MS_G; q++) buf[q * S + ((i0 + ln) & MASK)] = pre[q]; // (behind a slice's end: cells no chain reads)
+        for (int q = 0; q < MS_G; q++) buf[q * S + ((i0 + ln) & MASK)] = xq[q].cook1(pre[q]); // (behind a slice's end: cells no chain reads)
         ws_sync();
         fetch(i0 + MS_CHUNK); // (also behind the last chunk: clamped indices, values not used -- no second path to join)
         if (i0 > 0) store_chunk(i0 - MS_CHUNK, out + (par ^ 1) * MS_G * SO);
@@ -882,7 +885,8 @@ __global__ void __launch_bounds__(256) k_series_order(int n_reads, int cap, cons
 }
 
 // grid = ceil(n_reads / MS_G); block = 128 (wave 0: MS_G moving variances, wave 1: MS_G moving means); dynamic LDS
-__global__ void __launch_bounds__(128) k_mvs_series_wave(const float *__restrict__ sigs, int n_reads, int m, const int32_t *__restrict__ a_plan,
+template <class SIG>
+__global__ void __launch_bounds__(128) k_mvs_series_wave(SIG sigs, int n_reads, int m, const int32_t *__restrict__ a_plan,
                                                          const int32_t *__restrict__ n_plan, const int32_t *__restrict__ perm, adp_cfg cfg,
                                                          float *__restrict__ series, int cap, int8_t *__restrict__ have)
 {
@@ -902,8 +906,8 @@ __global__ void __launch_bounds__(128) k_mvs_series_wave(const float *__restrict
     const int Sv = ms_ring(cfg.pA_var_window) + 4, Sm = ms_ring(cfg.pA_mean_window) + 4;
     LDS float *base = (LDS float *)ms_raw;
     LDS float *buf_v = base, *out_v = buf_v + MS_G * Sv, *buf_m = out_v + 2 * MS_G * (MS_CHUNK + 4), *out_m = buf_m + MS_G * Sm; // (out: two halves)
-    if (wave == 0) ms_chains<true>(sigs, m, a_of, n_of, rid_of, cfg.pA_var_window, series, cap, buf_v, out_v, have);
-    else ms_chains<false>(sigs, m, a_of, n_of, rid_of, cfg.pA_mean_window, series, cap, buf_m, out_m, have);
+    if (wave == 0) ms_chains<true, SIG>(sigs, m, a_of, n_of, rid_of, cfg.pA_var_window, series, cap, buf_v, out_v, have);
+    else ms_chains<false, SIG>(sigs, m, a_of, n_of, rid_of, cfg.pA_mean_window, series, cap, buf_m, out_m, have);
 }
 
 static __device__ void row_clear(adp_row *row)
@@ -1467,8 +1471,8 @@ __global__ void k_llr_bounds(const int32_t *__restrict__ adapter_idx, const int3
 // complete block is compared with the read's start-peak maximum (SpHead, left by k_sp_head): the first block above it inside
 // [a2, e0), and the first raw sample above the open-pore level before op_end.  Waves take tiles out of order, so both are minima:
 // per lane, per wave, then one LDS atomicMin per wave.  k_sp_tail finishes the row.  The plain instantiation has none of this.
-template <bool SP = false>
-__global__ void __launch_bounds__(256) k_cnn_pool(const float *__restrict__ sigs, int n_reads, int m, int off, int ds, int Lc,
+template <class SIG, bool SP = false>
+__global__ void __launch_bounds__(256) k_cnn_pool(SIG sigs, int n_reads, int m, int off, int ds, int Lc,
                                                    float *__restrict__ out, int32_t *__restrict__ nan_cnt,
                                                    SpHead *__restrict__ sp_head = nullptr, float sp_thr = 0.f)
 {
@@ -1477,7 +1481,7 @@ __global__ void __launch_bounds__(256) k_cnn_pool(const float *__restrict__ sigs
     const int r = blockIdx.x;
     const int ln = lane_id(), wv = threadIdx.x >> 6;
     LDS float *tile = (LDS float *)cp_tiles_raw + (size_t)wv * 64 * ds;
-    const RowF32 row = RowF32{(const GLB float *)sigs + (size_t)r * m + off};
+    const typename SIG::Row row = sigs.row(r, m) + off; // (int16 rows: converted on the way into the tile, NaN from the read's end on)
     const int Lseg = m - off;
     float *o = out + (size_t)r * Lc;
     int nn = 0;

@@ -337,6 +337,21 @@ def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_ho
                                flag_truncated=flag_truncated, with_start_peak=with_start_peak)[0]
 
 
+def detect_rows_device_i16(eng, draw: int, dlen: int, dscale: int, doffset: int, n: int, lens_host: np.ndarray, model, spc,
+                           minibatch: Optional[int] = None, with_start_peak: bool = False, second_opinion: bool = False,
+                           fallback: str = "device", conv: str = "hip") -> np.ndarray:
+    """detect_rows_device over RAW int16 samples resident on the device (draw int16 [n, m], dscale / doffset float32 [n], dlen
+    int32 [n]: pointers): the CNN primary reads the ADC samples itself (adp_detect_cnn_i16) -- no float32 matrix is made -- with
+    the short-read fallback on the device where the configuration has it, and the two options as
+    detect_rows_device_second_opinion has them.  The rows are those of calibrate_i16 + that function, byte for byte.  ONE library
+    call: there is no host-fallback and no torch-conv form (and no truncation look: that phase reads float32 rows)."""
+    if conv != "hip" or _fallback_mode(fallback) != "device":
+        raise ValueError('int16 rows are read inside the library call: conv must be "hip" and fallback "device"')
+    ensure_weights(eng, model, spc)
+    return eng.detect_cnn_rows_i16(draw, dlen, dscale, doffset, n, minibatch or n, want_bounds=False, fallback=True,
+                                   second_opinion=second_opinion, with_start_peak=with_start_peak)[0]
+
+
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0,
                             flag_truncated: bool = False, with_start_peak: bool = False) -> List[DetectResults]:
     """combined_detect_cnn, and for the reads it fails combined_detect_llr2 on the same batch where that passes (an extension;

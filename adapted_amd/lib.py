@@ -265,7 +265,7 @@ def load():
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
     try:
-        for name, proto in list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()):
+        for name, proto in list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items()):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -423,6 +423,11 @@ MODULE_PROTOTYPES = {
     "adp_sizeof_adapter_start_args": "int:",
     "adp_start_peak": "int: adp_handle* void* int32* int int adp_start_peak_args* int int32* double*",
     "adp_adapter_start": "int: adp_handle* void* int32* int int adp_adapter_start_args* int int32* int64* int64* double*",
+}
+# include/adapted_hip_i16.h (the header adapted_hip.h includes for the CNN primary over raw int16 rows; adp_detect_llr_i16, the LLR
+# primary's twin, stays in PROTOTYPES); tests/test_cnn_i16_cpu.py holds this table against its header
+I16_PROTOTYPES = {
+    "adp_detect_cnn_i16": "int: adp_handle* int16* int32* float* float* int int int int adp_row* int64*",
 }
 
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
@@ -1113,6 +1118,28 @@ class Engine:
         bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
         rows, rows_arg, out_flag = self._out(rows_dev, n)
         self._check(self.lib.adp_detect_cnn(self._h, sig, lens, n, self.m, int(minibatch), flags | out_flag, rows_arg, bounds))
+        return self.attach_open_pores(rows), bounds
+
+    def detect_cnn_rows_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, minibatch: int,
+                            rows_dev: Optional[int] = None, want_bounds: bool = True, with_start_peak: bool = False, fallback: bool = False,
+                            second_opinion: bool = False):
+        """detect_cnn_rows over RAW int16 samples resident on the device (adp_detect_cnn_i16: the per-read calibration applied in
+        registers, no float32 matrix) -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k] or None).  The options
+        are detect_cnn_rows'; the rows are those of calibrate_i16 + detect_cnn_rows, byte for byte.  m must be a multiple of 4;
+        the truncation look has no int16 form."""
+        flags = ADP_IN_DEVICE
+        if with_start_peak:
+            flags |= ADP_WITH_START_PEAK
+        if fallback:
+            flags |= ADP_CNN_FALLBACK
+        if second_opinion:
+            flags |= ADP_CNN_SECOND_LLR
+        k = max(1, int(self.cfg.polya_cand_k))
+        bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        _check_runtime_once_torch_is_here()
+        self._check(self.lib.adp_detect_cnn_i16(self._h, int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev), n, self.m,
+                                                int(minibatch), flags | out_flag, rows_arg, bounds))
         return self.attach_open_pores(rows), bounds
 
     def cnn_set_weights(self, state):

@@ -58,7 +58,8 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     d.add_argument("--int16_ingest", action="store_true",
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
-                        "(pA = scale * (float32(adc) + offset)); .pod5 inputs or .npz bundles with raw/scale/offset")
+                        "(pA = scale * (float32(adc) + offset)): both primaries, LLR and CNN, read the raw samples on the GPU and "
+                        "no float32 copy of the signal is made there; .pod5 inputs or .npz bundles with raw/scale/offset")
     return p
 
 
@@ -227,7 +228,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     # decodes only the groups of whole minibatches a GroupSharder assigns to it (balanced by preloaded samples).
     GROUP = 4  # minibatches per staging slot and detect call (normalisation stays per minibatch)
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
-                        model=model, int16_input=int16_ingest, group=GROUP, ragged=True, second_opinion=second_opinion,
+                        model=model, int16_input="native" if int16_ingest else False, group=GROUP, ragged=True, second_opinion=second_opinion,
                         flag_truncated=flag_truncated)
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)

@@ -27,6 +27,18 @@ import numpy as np
 from . import lib
 
 
+def native_int16_plan(primary: str, int16_input, m: int, flag_truncated: bool) -> bool:
+    """Do the detect kernels read the raw int16 rows themselves (no float32 matrix on the device)?  int16_input: False, True
+    (the LLR primary natively, the CNN primary through the calibrated float32 matrix) or "native" (the CNN primary natively as
+    well: adp_detect_cnn_i16).  Never for rows that are not 8-byte aligned (m % 4), with the truncation look (a float32-row
+    phase) or for the start-peak primary."""
+    if not int16_input or m % 4 != 0 or flag_truncated:
+        return False
+    if primary == "llr":
+        return True
+    return primary == "cnn" and int16_input == "native"
+
+
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
@@ -39,7 +51,8 @@ class HostPipeline:
         primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one."""
         """int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
         to float32 pA on the device (adp_calibrate_i16), so only 2 bytes per sample cross PCIe.  get_buffers() then hands
-        out (raw, lengths, scale, offset) instead of (signals, lengths)."""
+        out (raw, lengths, scale, offset) instead of (signals, lengths).  True: the LLR primary reads the raw rows itself, the
+        CNN primary the calibrated matrix; "native": the CNN primary reads them itself as well (native_int16_plan)."""
         """group: minibatches per staging slot and per detect call (a call over several minibatches fills the GPU better
         than one over 1000 reads; normalisation stays per minibatch)."""
         """ragged: the staging slots hold the reads packed back to back (flat array + offsets int64 [N + 1]); only the samples
@@ -50,6 +63,8 @@ class HostPipeline:
         self.N = self.mb * max(1, int(group))  # reads per slot
         self.primary, self.with_start_peak, self.model, self.i16 = primary, with_start_peak, model, bool(int16_input)
         self.ragged = bool(ragged)
+        if int16_input not in (False, True, "native"):
+            raise ValueError('int16_input must be False, True or "native"')
         if second_opinion not in (None, "llr"):
             raise ValueError('second_opinion must be None or "llr"')
         if second_opinion and primary != "cnn":
@@ -64,8 +79,9 @@ class HostPipeline:
                 raise ValueError("flag_truncated: " + why)
         self.eng = lib.Engine(spc, self.N, self.m, device=self.device)
         self.slots = []
-        # int16 input + LLR primary: the kernels read the raw samples themselves (adp_detect_llr_i16) -- no float32 matrix is made
-        self.native_i16 = self.i16 and primary == "llr" and self.m % 4 == 0 and not self.flag_truncated
+        # int16 input + LLR primary (or the CNN primary with "native"): the kernels read the raw samples themselves
+        # (adp_detect_llr_i16, adp_detect_cnn_i16) -- no float32 matrix is made
+        self.native_i16 = native_int16_plan(primary, int16_input, self.m, self.flag_truncated)
         # the float32 minibatch made on the device (calibrated and / or laid out from packed reads); one: detect is serial
         # (native int16 + packed reads: the raw int16 matrix instead)
         self.dsig16 = None
@@ -137,6 +153,12 @@ class HostPipeline:
             if self.ragged:
                 self.eng.expand_ragged_i16(dsig, s["do"], dlen, n, self.dsig16)
                 dsig = self.dsig16
+            if self.primary == "cnn":
+                from .detect import cnn as _cnn
+
+                return _cnn.detect_rows_device_i16(self.eng, dsig, dlen, s["dcal"], s["dcal"] + self.N * 4, n, s["lens"][:n], self.model,
+                                                   self.spc, minibatch=self.mb, with_start_peak=bool(self.with_start_peak),
+                                                   second_opinion=bool(self.second_opinion)), None
             return self.eng.detect_llr_rows_i16(dsig, dlen, s["dcal"], s["dcal"] + self.N * 4, n, self.mb, with_start_peak=self.with_start_peak)
         if self.ragged:  # packed reads (-> calibrated) -> float32 [n, m], NaN beyond each read
             if self.i16:

@@ -235,7 +235,8 @@ int adp_detect_llr(adp_handle *h, const float *signals, const int32_t *full_len,
  * signal forms pA = scale * (float32(adc) + offset) in registers (both operations rounded to float32, never fused --
  * bit-identical to adp_calibrate_i16's output) and treats samples at or beyond min(full_len, m) as the NaN padding of
  * adapted/file_proc.py:170-174, so rows are identical to adp_calibrate_i16 + adp_detect_llr while every streaming pass
- * moves 2 bytes per sample instead of 4.  m must be a multiple of 4. */
+ * moves 2 bytes per sample instead of 4.  m must be a multiple of 4.  The CNN primary has the same twin, adp_detect_cnn_i16,
+ * declared in adapted_hip_i16.h. */
 int adp_detect_llr_i16(adp_handle *h, const int16_t *raw, const int32_t *full_len, const float *scale, const float *offset,
                        int n_reads, int m, int minibatch, int flags, adp_row *rows_out, int32_t *mb_status);
 
@@ -543,6 +544,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 /* The reference's start-peak and adapter-start modules (adp_start_peak, adp_adapter_start): the part of this ABI that is declared
  * in a header of its own, with its own prototype table in adapted_amd/lib.py (MODULE_PROTOTYPES). */
 #include "adapted_hip_startmods.h"
+
+/* The CNN primary over raw int16 rows, adp_detect_cnn_i16: declared in a header of its own as well, with its prototype table in
+ * adapted_amd/lib.py, I16_PROTOTYPES. */
+#include "adapted_hip_i16.h"
 
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
