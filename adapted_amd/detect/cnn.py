@@ -199,38 +199,6 @@ def _fallback_mode(fallback: str) -> str:
     return fallback
 
 
-def _start_peak_form(with_start_peak: bool, conv: str, fallback: str):
-    """the start-peak overlay (ADP_WITH_START_PEAK) is applied inside adp_detect_cnn to the row the call finally delivers:
-    rows made or replaced on the host behind the call would come without it"""
-    if not with_start_peak:
-        return
-    if conv != "hip":
-        raise ValueError('with_start_peak runs inside the library call: conv must be "hip"')
-    if _fallback_mode(fallback) != "device":
-        raise ValueError('with_start_peak runs inside the library call: fallback must be "device"')
-
-
-def detect_rows_device(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
-                       fallback: str = "device") -> np.ndarray:
-    """combined_detect_cnn over a DEVICE-resident batch (pointers) -> adp_row[]; ONE library call (adp_detect_cnn), the
-    short-read fallback included.  minibatch: reads per call of the reference (its find_peaks and row compaction work on one
-    minibatch); default: the whole batch.  fallback = "host": the fallback applied here instead, on host copies of the
-    affected reads (same rows)."""
-    ensure_weights(eng, model, spc)
-    m = eng.m
-    if _fallback_mode(fallback) == "device":
-        return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True)[0]
-    rows, bounds = eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True)
-    if spc.cnn_boundaries.fallback_to_llr_short_reads:
-        idx = _need_fallback(rows, bounds, lens_host, spc)
-        if idx.size:
-            sub = np.zeros((idx.size, m), dtype=np.float32)
-            for j, i in enumerate(idx):
-                eng.d2h(sub[j], dsig + int(i) * m * 4)
-            _apply_fallback(eng, rows, idx, sub, np.asarray(lens_host)[idx], bounds, spc)
-    return rows
-
-
 def _apply_fallback(eng, rows, idx, sig_sub, lens_sub, bounds, spc):
     new_pe, status = eng.llr_refine_polya(sig_sub, lens_sub, idx.size, bounds[idx, :2])
     for j, i in enumerate(idx):
@@ -244,37 +212,86 @@ def _apply_fallback(eng, rows, idx, sig_sub, lens_sub, bounds, spc):
         rows[ii] = eng.validate_rows(sig_sub[redo], lens_sub[redo], len(ii), b2)
 
 
-def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
-    """combined_detect_cnn over one batch -> adp_row[] (reference adapted/detect/combined.py:230-309).
-    conv = "torch": the conv stack through PyTorch-ROCm instead of the library's own (cross-check; its fallback is the host's).
-    fallback = "host": the short-read fallback applied here, behind the library call, instead of inside it (same rows)."""
-    n = sig.shape[0]
-    if int(spc.cnn_boundaries.polya_cand_k) < 1:
-        raise ValueError("polya_cand_k must be >= 1")
-    if conv == "hip" and _fallback_mode(fallback) == "device":
-        ensure_weights(eng, model, spc)
-        return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True)[0]
+def _refuse_host_forms(conv: str, fallback: str, with_start_peak: bool, host_forms: bool, int16: bool = False, flag_truncated: bool = False):
+    """What runs inside the library call has no host-side form: the start-peak overlay (applied to the row the call finally
+    delivers), the LLR second opinion and the truncation look (behind the library's own conv stack and fallback) and int16 rows
+    (read by the kernels themselves).  Rows made (conv = "torch") or replaced (fallback = "host") behind the call would come
+    without them.  host_forms: the entry has those two forms.  Looks at nothing but its arguments, so it comes before an engine,
+    a model or the configuration is touched."""
+    if int16:
+        if conv != "hip" or _fallback_mode(fallback) != "device":
+            raise ValueError('int16 rows are read inside the library call: conv must be "hip" and fallback "device"')
+        if flag_truncated:
+            raise ValueError("the truncation look reads float32 rows: there is none over int16 rows")
+        return
+    for applies, what in ((with_start_peak, "with_start_peak"), (not host_forms, "the LLR second opinion / the truncation look")):
+        if applies and conv != "hip":
+            raise ValueError('%s runs inside the library call: conv must be "hip"' % what)
+        if applies and _fallback_mode(fallback) != "device":
+            raise ValueError('%s runs inside the library call: fallback must be "device"' % what)
+
+
+# The one path behind every detect_rows* entry; their parameter lists are what callers and tests pin.  Kept as it was found:
+#   - only the host-batch entries refuse polya_cand_k < 1 here, the resident ones leave it to the library;
+#   - conv = "torch" never looks at ``fallback``: its fallback is the host's whatever that says;
+#   - inside the library the fallback is always asked for (ADP_CNN_FALLBACK): the library applies it where the configuration has it;
+#   - host_forms is the entry's, not the options': the _start_peak / _truncated / _second_opinion entries refuse conv = "torch"
+#     and fallback = "host" with every option off as well;
+#   - the resident forms run lib's check of the HIP runtime (Engine._in, detect_cnn_rows_i16); Engine.detect_llr_rows_i16 does not;
+#   - combined_detect_cnn hands n == 0 to the engine and a single read's result back bare; combined_detect_cnn_llr returns [] and a list.
+def _detect_rows(eng, sig, lens, model, spc, dlen: Optional[int] = None, n: Optional[int] = None, calibration=None, conv: str = "hip",
+                 fallback: str = "device", second_opinion: bool = False, flag_truncated: bool = False, with_start_peak: bool = False,
+                 minibatch: Optional[int] = None, host_forms: bool = False) -> np.ndarray:
+    """combined_detect_cnn over one batch -> adp_row[]: ONE library call -- or, with conv = "torch" / fallback = "host", the
+    predictions made / the short-read fallback applied here, behind it.  The batch: sig float32 [n, m] and lens int32 [n] on the
+    host; or resident rows, sig and dlen (int32 [n]) pointers, n given and lens the host's copy of the lengths -- float32 rows,
+    or with calibration = (dscale, doffset) pointers raw int16 rows (adp_detect_cnn_i16)."""
+    resident, int16 = dlen is not None, calibration is not None
+    _refuse_host_forms(conv, fallback, with_start_peak, host_forms, int16, flag_truncated)
+    if not resident:
+        n = sig.shape[0]
+        if int(spc.cnn_boundaries.polya_cand_k) < 1:
+            raise ValueError("polya_cand_k must be >= 1")
+    on_host = conv != "hip" or _fallback_mode(fallback) == "host"  # the fallback, and with it the predictions it selects by
     if conv == "hip":
         ensure_weights(eng, model, spc)
-        rows, bounds = eng.detect_cnn_rows(sig, lens, n, n)
+        options = dict(want_bounds=on_host, fallback=not on_host, second_opinion=second_opinion, with_start_peak=with_start_peak)
+        if int16:
+            rows, bounds = eng.detect_cnn_rows_i16(sig, dlen, *calibration, n, minibatch or n, **options)
+        else:
+            rows, bounds = eng.detect_cnn_rows(sig, dlen if resident else lens, n, minibatch or n, device_ptrs=resident,
+                                               flag_truncated=flag_truncated, **options)
     else:
         preds = cnn_detect(sig, model, spc.cnn_boundaries, spc.core, spc=spc, engine=eng, conv=conv)
         bounds = np.ascontiguousarray(preds, dtype=np.int64)
         rows = eng.validate_rows(sig, lens, n, bounds)
-    if spc.cnn_boundaries.fallback_to_llr_short_reads:
+    if on_host and spc.cnn_boundaries.fallback_to_llr_short_reads:
         idx = _need_fallback(rows, bounds, lens, spc)
         if idx.size:
-            _apply_fallback(eng, rows, idx, sig[idx], lens[idx], bounds, spc)
+            if resident:  # the selected reads over PCIe, one row each
+                sub = np.zeros((idx.size, eng.m), dtype=np.float32)
+                for j, i in enumerate(idx):
+                    eng.d2h(sub[j], sig + int(i) * eng.m * 4)
+            else:
+                sub = sig[idx]
+            _apply_fallback(eng, rows, idx, sub, np.asarray(lens)[idx], bounds, spc)
     return rows
 
 
-def _second_opinion_form(conv: str, fallback: str):
-    """the LLR second opinion and the truncation look run inside adp_detect_cnn, behind the library's own conv stack and
-    fallback: the host-side variants of either have no such form"""
-    if conv != "hip":
-        raise ValueError('the LLR second opinion / the truncation look runs inside the library call: conv must be "hip"')
-    if _fallback_mode(fallback) != "device":
-        raise ValueError('the LLR second opinion / the truncation look runs inside the library call: fallback must be "device"')
+def detect_rows(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
+    """combined_detect_cnn over one batch -> adp_row[] (reference adapted/detect/combined.py:230-309).
+    conv = "torch": the conv stack through PyTorch-ROCm instead of the library's own (cross-check; its fallback is the host's).
+    fallback = "host": the short-read fallback applied here, behind the library call, instead of inside it (same rows)."""
+    return _detect_rows(eng, sig, lens, model, spc, conv=conv, fallback=fallback, host_forms=True)
+
+
+def detect_rows_device(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
+                       fallback: str = "device") -> np.ndarray:
+    """combined_detect_cnn over a DEVICE-resident batch (pointers) -> adp_row[]; ONE library call (adp_detect_cnn), the
+    short-read fallback included.  minibatch: reads per call of the reference (its find_peaks and row compaction work on one
+    minibatch); default: the whole batch.  fallback = "host": the fallback applied here instead, on host copies of the
+    affected reads (same rows)."""
+    return _detect_rows(eng, dsig, lens_host, model, spc, dlen, n, fallback=fallback, minibatch=minibatch, host_forms=True)
 
 
 def detect_rows_start_peak(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device") -> np.ndarray:
@@ -283,14 +300,13 @@ def detect_rows_start_peak(eng, sig: np.ndarray, lens: np.ndarray, model, spc, c
     them.  An extension: the reference keeps one primary per run.  ONE library call, so neither conv = "torch" nor
     fallback = "host".  (detect_rows itself keeps the parameters it was introduced with; the truncated / second-opinion forms
     take ``with_start_peak``.)"""
-    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, second_opinion=False, with_start_peak=True)
+    return _detect_rows(eng, sig, lens, model, spc, conv=conv, fallback=fallback, with_start_peak=True)
 
 
 def detect_rows_device_start_peak(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
                                   fallback: str = "device") -> np.ndarray:
     """detect_rows_device with the start-peak overlay.  ONE library call over the resident batch."""
-    return detect_rows_device_second_opinion(eng, dsig, dlen, n, lens_host, model, spc, minibatch=minibatch, fallback=fallback,
-                                             second_opinion=False, with_start_peak=True)
+    return _detect_rows(eng, dsig, lens_host, model, spc, dlen, n, fallback=fallback, minibatch=minibatch, with_start_peak=True)
 
 
 def detect_rows_truncated(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device",
@@ -298,15 +314,14 @@ def detect_rows_truncated(eng, sig: np.ndarray, lens: np.ndarray, model, spc, co
     """detect_rows with the truncation look behind it (ADP_FLAG_TRUNCATED, include/adapted_hip.h): a read whose poly(A) runs into
     the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
     (``reserved_`` bit 1); every row carries bit 2.  An extension: the reference never sets ``polya_truncated``.  ONE library call."""
-    return detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, fallback=fallback, flag_truncated=True, second_opinion=False,
-                                      with_start_peak=with_start_peak)
+    return _detect_rows(eng, sig, lens, model, spc, conv=conv, fallback=fallback, flag_truncated=True, with_start_peak=with_start_peak)
 
 
 def detect_rows_device_truncated(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
                                  fallback: str = "device", with_start_peak: bool = False) -> np.ndarray:
     """detect_rows_device with the truncation look behind it.  ONE library call over the resident batch."""
-    return detect_rows_device_second_opinion(eng, dsig, dlen, n, lens_host, model, spc, minibatch=minibatch, fallback=fallback,
-                                             flag_truncated=True, second_opinion=False, with_start_peak=with_start_peak)
+    return _detect_rows(eng, dsig, lens_host, model, spc, dlen, n, fallback=fallback, minibatch=minibatch, flag_truncated=True,
+                        with_start_peak=with_start_peak)
 
 
 def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, spc, conv: str = "hip", fallback: str = "device",
@@ -315,14 +330,8 @@ def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, sp
     returns for it on this batch, where that row passes (``reserved_`` bit 0 marks it; lib.rows_to_results names its primary
     columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call.
     with_start_peak: the overlay of detect_rows_start_peak on the rows this call delivers, the rescued ones included."""
-    _start_peak_form(with_start_peak, conv, fallback)
-    _second_opinion_form(conv, fallback)
-    n = sig.shape[0]
-    if int(spc.cnn_boundaries.polya_cand_k) < 1:
-        raise ValueError("polya_cand_k must be >= 1")
-    ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows(sig, lens, n, n, want_bounds=False, fallback=True, second_opinion=second_opinion, flag_truncated=flag_truncated,
-                               with_start_peak=with_start_peak)[0]
+    return _detect_rows(eng, sig, lens, model, spc, conv=conv, fallback=fallback, second_opinion=second_opinion, flag_truncated=flag_truncated,
+                        with_start_peak=with_start_peak)
 
 
 def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_host: np.ndarray, model, spc, minibatch: Optional[int] = None,
@@ -330,11 +339,8 @@ def detect_rows_device_second_opinion(eng, dsig: int, dlen: int, n: int, lens_ho
                                       with_start_peak: bool = False) -> np.ndarray:
     """detect_rows_device with the LLR second opinion, per minibatch as combined_detect_llr2 would see it (its normalisation is
     the minibatch's).  ONE library call over the resident batch.  with_start_peak: as detect_rows_second_opinion's."""
-    _start_peak_form(with_start_peak, "hip", fallback)
-    _second_opinion_form("hip", fallback)
-    ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows(dsig, dlen, n, minibatch or n, device_ptrs=True, want_bounds=False, fallback=True, second_opinion=second_opinion,
-                               flag_truncated=flag_truncated, with_start_peak=with_start_peak)[0]
+    return _detect_rows(eng, dsig, lens_host, model, spc, dlen, n, fallback=fallback, minibatch=minibatch, second_opinion=second_opinion,
+                        flag_truncated=flag_truncated, with_start_peak=with_start_peak)
 
 
 def detect_rows_device_i16(eng, draw: int, dlen: int, dscale: int, doffset: int, n: int, lens_host: np.ndarray, model, spc,
@@ -345,11 +351,8 @@ def detect_rows_device_i16(eng, draw: int, dlen: int, dscale: int, doffset: int,
     the short-read fallback on the device where the configuration has it, and the two options as
     detect_rows_device_second_opinion has them.  The rows are those of calibrate_i16 + that function, byte for byte.  ONE library
     call: there is no host-fallback and no torch-conv form (and no truncation look: that phase reads float32 rows)."""
-    if conv != "hip" or _fallback_mode(fallback) != "device":
-        raise ValueError('int16 rows are read inside the library call: conv must be "hip" and fallback "device"')
-    ensure_weights(eng, model, spc)
-    return eng.detect_cnn_rows_i16(draw, dlen, dscale, doffset, n, minibatch or n, want_bounds=False, fallback=True,
-                                   second_opinion=second_opinion, with_start_peak=with_start_peak)[0]
+    return _detect_rows(eng, draw, lens_host, model, spc, dlen, n, (dscale, doffset), conv=conv, fallback=fallback, minibatch=minibatch,
+                        second_opinion=second_opinion, with_start_peak=with_start_peak)
 
 
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0,
@@ -366,7 +369,7 @@ def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.n
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = detect_rows_second_opinion(eng, sig, lens, model, spc, flag_truncated=flag_truncated, with_start_peak=with_start_peak)
+        rows = _detect_rows(eng, sig, lens, model, spc, second_opinion=True, flag_truncated=flag_truncated, with_start_peak=with_start_peak)
     return lib.rows_to_results(rows, "cnn", consume=True)
 
 
@@ -379,16 +382,14 @@ def combined_detect_cnn(batch_of_signals: np.ndarray, full_signal_lens: np.ndarr
     that name fills them (an extension, off by default: the reference keeps one primary per run); conv must be "hip"."""
     from .combined import _as_batch, get_engine
 
-    _start_peak_form(with_start_peak, conv, "device")
+    host_forms = not (flag_truncated or with_start_peak)
+    _refuse_host_forms(conv, "device", with_start_peak, host_forms)  # (here as well: before an engine is made)
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
     n, m = sig.shape
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        if flag_truncated or with_start_peak:
-            rows = detect_rows_second_opinion(eng, sig, lens, model, spc, conv=conv, flag_truncated=flag_truncated, second_opinion=False,
-                                              with_start_peak=with_start_peak)
-        else:
-            rows = detect_rows(eng, sig, lens, model, spc, conv=conv)
+        rows = _detect_rows(eng, sig, lens, model, spc, conv=conv, flag_truncated=flag_truncated, with_start_peak=with_start_peak,
+                            host_forms=host_forms)
     res = lib.rows_to_results(rows, "cnn", consume=True)
     return res if len(res) > 1 else res[0]

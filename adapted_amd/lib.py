@@ -472,6 +472,15 @@ def _argtype(kind):
     return C.POINTER(_POINTEES[element]) if element in _POINTEES else _Pointer(element)
 
 
+# a detect call's options -> their bits of its flag word (include/adapted_hip.h)
+_OPTION_FLAGS = {"with_start_peak": ADP_WITH_START_PEAK, "tails_nan": ADP_TAILS_NAN, "flag_truncated": ADP_FLAG_TRUNCATED,
+                 "fallback": ADP_CNN_FALLBACK, "second_opinion": ADP_CNN_SECOND_LLR}
+
+
+def _flag_word(**options) -> int:
+    return sum(_OPTION_FLAGS[name] for name, on in options.items() if on)
+
+
 class MinibatchDropped(RuntimeError):
     """batch-level failure of one minibatch (the reference drops it and logs): status = ADP_MB_*"""
 
@@ -783,6 +792,13 @@ class Engine:
         out = np.zeros(shape, dtype=dtype)
         return out, out, 0
 
+    def _detect_llr(self, fn, head, n, minibatch, flags, rows_dev):
+        """adp_detect_llr / adp_detect_llr_i16 (fn) behind the batch's leading arguments (head)"""
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
+        self._check(fn(self._h, *head, n, self.m, minibatch, flags | out_flag, rows_arg, mbs))
+        return self.attach_open_pores(rows), mbs
+
     def detect_llr_rows(self, signals, full_lens, n: int, minibatch: int, with_start_peak: bool = False,
                         device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False, flag_truncated: bool = False):
         """-> (rows ndarray[ROW_DTYPE] or None when rows_dev is given, mb_status int32[n_mb]).
@@ -792,23 +808,16 @@ class Engine:
         the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
         (reserved_ bit 1); every row carries reserved_ bit 2."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
-        rows, rows_arg, out_flag = self._out(rows_dev, n)
-        flags |= out_flag | (ADP_WITH_START_PEAK if with_start_peak else 0) | (ADP_TAILS_NAN if tails_nan else 0)
-        flags |= ADP_FLAG_TRUNCATED if flag_truncated else 0
-        mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
-        self._check(self.lib.adp_detect_llr(self._h, sig, lens, n, self.m, minibatch, flags, rows_arg, mbs))
-        return self.attach_open_pores(rows), mbs
+        flags |= _flag_word(with_start_peak=with_start_peak, tails_nan=tails_nan, flag_truncated=flag_truncated)
+        return self._detect_llr(self.lib.adp_detect_llr, (sig, lens), n, minibatch, flags, rows_dev)
 
     def detect_llr_rows_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, minibatch: int,
                             with_start_peak: bool = False, rows_dev: Optional[int] = None):
         """adp_detect_llr over RAW int16 samples resident on the device (per-read calibration applied in registers):
         -> (rows or None when rows_dev is given, mb_status)"""
-        rows, rows_arg, out_flag = self._out(rows_dev, n)
-        flags = ADP_IN_DEVICE | out_flag | (ADP_WITH_START_PEAK if with_start_peak else 0)
-        mbs = np.zeros((n + minibatch - 1) // minibatch, dtype=np.int32)
-        self._check(self.lib.adp_detect_llr_i16(self._h, int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev), n, self.m,
-                                                minibatch, flags, rows_arg, mbs))
-        return self.attach_open_pores(rows), mbs
+        head = (int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev))
+        flags = ADP_IN_DEVICE | _flag_word(with_start_peak=with_start_peak)
+        return self._detect_llr(self.lib.adp_detect_llr_i16, head, n, minibatch, flags, rows_dev)
 
     def detect_start_peak_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False):
         """adp_detect_start_peak over n reads in ONE library call: the pandas float-column quirk couples the reads of a minibatch
@@ -1095,6 +1104,14 @@ class Engine:
         self._check(self.lib.adp_cnn_predict(self._h, int(scores_ptr), n, int(minibatch), int(Lo), out))
         return out
 
+    def _detect_cnn(self, fn, head, n, minibatch, flags, rows_dev, want_bounds):
+        """adp_detect_cnn / adp_detect_cnn_i16 (fn) behind the batch's leading arguments (head)"""
+        k = max(1, int(self.cfg.polya_cand_k))
+        bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
+        rows, rows_arg, out_flag = self._out(rows_dev, n)
+        self._check(fn(self._h, *head, n, self.m, int(minibatch), flags | out_flag, rows_arg, bounds))
+        return self.attach_open_pores(rows), bounds
+
     def detect_cnn_rows(self, signals, full_lens, n: int, minibatch: int, device_ptrs: bool = False, rows_dev: Optional[int] = None,
                         want_bounds: bool = True, flag_truncated: bool = False, with_start_peak: bool = False, fallback: bool = False,
                         second_opinion: bool = False):
@@ -1106,19 +1123,8 @@ class Engine:
         with_start_peak: the start-peak columns of detect_rna_start_peak overlaid on the row the call delivers, whichever phase
         made it, as in detect_llr_rows (ADP_WITH_START_PEAK); nothing else of any row changes."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
-        if with_start_peak:
-            flags |= ADP_WITH_START_PEAK
-        if fallback:
-            flags |= ADP_CNN_FALLBACK
-        if flag_truncated:
-            flags |= ADP_FLAG_TRUNCATED
-        if second_opinion:
-            flags |= ADP_CNN_SECOND_LLR
-        k = max(1, int(self.cfg.polya_cand_k))
-        bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
-        rows, rows_arg, out_flag = self._out(rows_dev, n)
-        self._check(self.lib.adp_detect_cnn(self._h, sig, lens, n, self.m, int(minibatch), flags | out_flag, rows_arg, bounds))
-        return self.attach_open_pores(rows), bounds
+        flags |= _flag_word(with_start_peak=with_start_peak, fallback=fallback, flag_truncated=flag_truncated, second_opinion=second_opinion)
+        return self._detect_cnn(self.lib.adp_detect_cnn, (sig, lens), n, minibatch, flags, rows_dev, want_bounds)
 
     def detect_cnn_rows_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, minibatch: int,
                             rows_dev: Optional[int] = None, want_bounds: bool = True, with_start_peak: bool = False, fallback: bool = False,
@@ -1127,20 +1133,10 @@ class Engine:
         registers, no float32 matrix) -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k] or None).  The options
         are detect_cnn_rows'; the rows are those of calibrate_i16 + detect_cnn_rows, byte for byte.  m must be a multiple of 4;
         the truncation look has no int16 form."""
-        flags = ADP_IN_DEVICE
-        if with_start_peak:
-            flags |= ADP_WITH_START_PEAK
-        if fallback:
-            flags |= ADP_CNN_FALLBACK
-        if second_opinion:
-            flags |= ADP_CNN_SECOND_LLR
-        k = max(1, int(self.cfg.polya_cand_k))
-        bounds = np.zeros((n, 1 + k), dtype=np.int64) if want_bounds else None
-        rows, rows_arg, out_flag = self._out(rows_dev, n)
         _check_runtime_once_torch_is_here()
-        self._check(self.lib.adp_detect_cnn_i16(self._h, int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev), n, self.m,
-                                                int(minibatch), flags | out_flag, rows_arg, bounds))
-        return self.attach_open_pores(rows), bounds
+        flags = ADP_IN_DEVICE | _flag_word(with_start_peak=with_start_peak, fallback=fallback, second_opinion=second_opinion)
+        head = (int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev))
+        return self._detect_cnn(self.lib.adp_detect_cnn_i16, head, n, minibatch, flags, rows_dev, want_bounds)
 
     def cnn_set_weights(self, state):
         """state: mapping with the reference's state-dict keys ("0.weight" ... "6.bias") -> float32 arrays (numpy, or anything

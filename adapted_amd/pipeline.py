@@ -48,14 +48,14 @@ class HostPipeline:
         second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
         minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py).
         flag_truncated: every detect call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension; LLR and CNN
-        primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one."""
-        """int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
+        primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one.
+        int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
         to float32 pA on the device (adp_calibrate_i16), so only 2 bytes per sample cross PCIe.  get_buffers() then hands
         out (raw, lengths, scale, offset) instead of (signals, lengths).  True: the LLR primary reads the raw rows itself, the
-        CNN primary the calibrated matrix; "native": the CNN primary reads them itself as well (native_int16_plan)."""
-        """group: minibatches per staging slot and per detect call (a call over several minibatches fills the GPU better
-        than one over 1000 reads; normalisation stays per minibatch)."""
-        """ragged: the staging slots hold the reads packed back to back (flat array + offsets int64 [N + 1]); only the samples
+        CNN primary the calibrated matrix; "native": the CNN primary reads them itself as well (native_int16_plan).
+        group: minibatches per staging slot and per detect call (a call over several minibatches fills the GPU better
+        than one over 1000 reads; normalisation stays per minibatch).
+        ragged: the staging slots hold the reads packed back to back (flat array + offsets int64 [N + 1]); only the samples
         that exist cross PCIe and the NaN-padded [N, m] minibatch is laid out on the device (adp_expand_ragged).  With
         heavy-tailed read lengths most of the padded matrix is padding.  get_buffers() hands out (flat, lengths, offsets)
         -- plus (scale, offset) with int16_input."""
@@ -149,6 +149,8 @@ class HostPipeline:
         s = self.slots[j]
         self.eng.copy_wait(j)  # this slot's copies only: the next slot's may still be in flight
         dsig, dlen = s["ds"], s["dl"]
+        # the CNN primary's options (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
+        options = dict(minibatch=self.mb, second_opinion=bool(self.second_opinion), with_start_peak=bool(self.with_start_peak))
         if self.native_i16:
             if self.ragged:
                 self.eng.expand_ragged_i16(dsig, s["do"], dlen, n, self.dsig16)
@@ -157,8 +159,7 @@ class HostPipeline:
                 from .detect import cnn as _cnn
 
                 return _cnn.detect_rows_device_i16(self.eng, dsig, dlen, s["dcal"], s["dcal"] + self.N * 4, n, s["lens"][:n], self.model,
-                                                   self.spc, minibatch=self.mb, with_start_peak=bool(self.with_start_peak),
-                                                   second_opinion=bool(self.second_opinion)), None
+                                                   self.spc, **options), None
             return self.eng.detect_llr_rows_i16(dsig, dlen, s["dcal"], s["dcal"] + self.N * 4, n, self.mb, with_start_peak=self.with_start_peak)
         if self.ragged:  # packed reads (-> calibrated) -> float32 [n, m], NaN beyond each read
             if self.i16:
@@ -178,12 +179,8 @@ class HostPipeline:
             return self.eng.detect_start_peak_rows(dsig, dlen, n, self.mb, device_ptrs=True), None
         from .detect import cnn as _cnn
 
-        # (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
-        if self.second_opinion or self.flag_truncated or self.with_start_peak:
-            return _cnn.detect_rows_device_second_opinion(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb,
-                                                          flag_truncated=self.flag_truncated, second_opinion=bool(self.second_opinion),
-                                                          with_start_peak=bool(self.with_start_peak)), None
-        return _cnn.detect_rows_device(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc, minibatch=self.mb), None
+        return _cnn.detect_rows_device_second_opinion(self.eng, dsig, dlen, n, s["lens"][:n], self.model, self.spc,
+                                                      flag_truncated=self.flag_truncated, **options), None
 
     # -- driver -------------------------------------------------------------------------------
     def run(self, fill: Callable[[Callable[[], Tuple[np.ndarray, np.ndarray]]], Iterable[Tuple[int, object]]],

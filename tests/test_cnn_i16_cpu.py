@@ -115,49 +115,35 @@ def test_pipeline_constructor_uses_the_plan(monkeypatch):
 
 
 @pytest.mark.parametrize("ragged", [False, True])
-def test_pipeline_hands_the_slot_and_the_options_to_the_int16_operator(monkeypatch, ragged):
-    """HostPipeline._detect of a bare object with native_i16 and the CNN primary (no engine: the operator is replaced)"""
-    from adapted_amd import pipeline
-    from adapted_amd.detect import cnn
+def test_pipeline_hands_the_slot_and_the_options_to_the_int16_operator(ragged):
+    """HostPipeline._detect of a bare object with native_i16 and the CNN primary, read where the library is called (a bare engine
+    whose library is a recorder, tests/call_recorder.py)"""
+    from adapted_amd import lib, pipeline
+    from adapted_amd.config import get_chemistry_specific_config
+    from call_recorder import detect_calls, names, recorder_engine
 
-    seen = {}
-
-    def fake(eng, draw, dlen, dscale, doffset, n, lens_host, model, spc, minibatch=None, **kw):
-        seen.update(kw, ptrs=(draw, dlen, dscale, doffset), n=n, lens=lens_host.tolist(), minibatch=minibatch)
-        return "rows"
-
-    def never(*a, **kw):
-        raise AssertionError("the float32 operators must not run on the native plan")
-
-    monkeypatch.setattr(cnn, "detect_rows_device_i16", fake)
-    monkeypatch.setattr(cnn, "detect_rows_device_second_opinion", never)
-    monkeypatch.setattr(cnn, "detect_rows_device", never)
+    spc = get_chemistry_specific_config("RNA004")
     p = pipeline.HostPipeline.__new__(pipeline.HostPipeline)
     p.primary, p.with_start_peak, p.second_opinion, p.flag_truncated = "cnn", True, "llr", False
     p.native_i16, p.i16, p.ragged = True, True, ragged
-    p.model = p.spc = None
+    p.model, p.spc = None, spc
     p.mb, p.N = 16, 32
     p.dsig16 = 7000 if ragged else None
-    calls = []
-
-    class Eng:
-        def copy_wait(self, j):
-            calls.append(("wait", j))
-
-        def expand_ragged_i16(self, *a):
-            calls.append(("expand",) + a)
-
-        def calibrate_i16(self, *a):
-            raise AssertionError("no calibration pass on the native plan")
-
-        expand_ragged = calibrate_i16
-
-    p.eng = Eng()
+    p.eng = recorder_engine(spc, 64)
     p.slots = [{"ds": 1000, "dl": 2000, "dcal": 3000, "do": 4000, "lens": np.arange(32, dtype=np.int32)}]
-    assert p._detect(0, 16) == ("rows", None)
-    assert seen == {"with_start_peak": True, "second_opinion": True, "ptrs": (7000 if ragged else 1000, 2000, 3000, 3000 + 32 * 4), "n": 16,
-                    "lens": list(range(16)), "minibatch": 16}
-    assert calls == [("wait", 0)] + ([("expand", 1000, 4000, 2000, 16, 7000)] if ragged else [])
+    rows, mbs = p._detect(0, 16)
+    assert rows.shape == (16,) and rows.dtype == lib.ROW_DTYPE and mbs is None
+    (c,) = detect_calls(p.eng)
+    assert c["fn"] == "adp_detect_cnn_i16", "the float32 operators must not run on the native plan"
+    # with_start_peak True, second_opinion True (and the fallback inside the call, the rows resident)
+    assert c["flags"] == lib.ADP_IN_DEVICE | lib.ADP_CNN_FALLBACK | lib.ADP_WITH_START_PEAK | lib.ADP_CNN_SECOND_LLR
+    assert c["head"] == (7000 if ragged else 1000, 2000, 3000, 3000 + 32 * 4) and (c["n"], c["m"], c["minibatch"]) == (16, 64, 16)
+    calls = p.eng.lib.calls
+    assert calls[0] == ("adp_copy_wait", (None, 0))
+    if ragged:
+        assert calls[1] == ("adp_expand_ragged_i16", (None, 1000, 4000, 2000, 16, 64, 7000))
+    assert names(p.eng) == ["adp_copy_wait"] + (["adp_expand_ragged_i16"] if ragged else []) + ["adp_cnn_set_weights", "adp_detect_cnn_i16"], \
+        "no calibration pass on the native plan"
 
 
 def test_the_llr_primary_keeps_its_int16_call(monkeypatch):

@@ -129,32 +129,27 @@ def test_the_keyword_through_the_layers():
     assert lib.ADP_WITH_START_PEAK == 4
 
 
-def test_pipeline_hands_the_option_to_the_cnn_primary(monkeypatch):
-    """HostPipeline._detect with the CNN primary passes with_start_peak down (no engine: the operator is replaced)"""
-    from adapted_amd import pipeline
-    from adapted_amd.detect import cnn
+def test_pipeline_hands_the_option_to_the_cnn_primary():
+    """HostPipeline._detect with the CNN primary passes with_start_peak down, and nothing else: read where the library is called (a
+    bare engine whose library is a recorder, tests/call_recorder.py)"""
+    from adapted_amd import lib, pipeline
+    from call_recorder import detect_calls, names, recorder_engine
 
-    seen = {}
-
-    def fake(eng, dsig, dlen, n, lens_host, model, spc, minibatch=None, **kw):
-        seen.update(kw, minibatch=minibatch)
-        return "rows"
-
-    monkeypatch.setattr(cnn, "detect_rows_device_second_opinion", fake)
+    spc = sc.inputs("default")[0]
     p = pipeline.HostPipeline.__new__(pipeline.HostPipeline)
     p.primary, p.with_start_peak, p.second_opinion, p.flag_truncated = "cnn", True, None, False
     p.native_i16 = p.ragged = p.i16 = False
-    p.model = p.spc = None
+    p.model, p.spc = None, spc
     p.mb = 16
-
-    class Eng:
-        def copy_wait(self, j):
-            pass
-
-    p.eng = Eng()
+    p.eng = recorder_engine(spc, 64)
     p.slots = [{"ds": 1, "dl": 2, "lens": np.zeros(16, np.int32)}]
-    assert p._detect(0, 16) == ("rows", None)
-    assert seen == {"flag_truncated": False, "second_opinion": False, "with_start_peak": True, "minibatch": 16}
+    rows, mbs = p._detect(0, 16)
+    assert rows.shape == (16,) and rows.dtype == lib.ROW_DTYPE and mbs is None
+    assert names(p.eng) == ["adp_copy_wait", "adp_cnn_set_weights", "adp_detect_cnn"]
+    (c,) = detect_calls(p.eng)
+    # flag_truncated False, second_opinion False, with_start_peak True; the fallback inside the call, the rows resident
+    assert c["flags"] == lib.ADP_IN_DEVICE | lib.ADP_CNN_FALLBACK | lib.ADP_WITH_START_PEAK
+    assert c["head"] == (1, 2) and (c["n"], c["m"], c["minibatch"]) == (16, 64, 16) and c["bounds"] is None
 
 
 def test_cli_help_names_both_primaries(capsys):

@@ -563,3 +563,48 @@ def test_conv_stack_flips_against_the_reference(name, tmp_path):
         with open(os.path.join(out, "conv_stack_flips_vs_reference_%s.txt" % name), "w") as fh:
             fh.write(text + "\n")
     assert flips_of["split"].size <= flips_of["f32"].size + 2, text
+
+
+def test_every_entry_point_is_the_one_library_call_with_its_flags_spelled_out():
+    """The nine detect_rows* entries of adapted_amd/detect/cnn.py on the reads of rna004_cnn_k3 (32 reads at its own window of 17 500
+    samples, 12 of them shorter than the window), each against a direct Engine.detect_cnn_rows / detect_cnn_rows_i16 call with the
+    flags written out here: rows byte for byte (registry token blanked) and equal overflow open-pore lists.  The resident forms get
+    the same reads as pointers, whole and in two minibatches; the int16 form the rows quantised as tests/test_gpu_cnn_i16.py
+    quantises them."""
+    from adapted_amd.detect import cnn
+    from test_gpu_cnn_fallback import _case
+    from test_gpu_cnn_i16 import _Dev, _quantised
+    from test_gpu_cnn_second_opinion import _per_row
+
+    spc, raw, scale, offset, lens = _quantised("rna004_cnn_k3")
+    sig = _case("rna004_cnn_k3")[1]
+    n, m = sig.shape
+    assert (n, m) == (32, 17500) and int((lens < m).sum()) == 12
+    dev = _Dev(spc, raw, scale, offset, lens, weights=False)
+    eng, dsig, dlen, cal = dev.eng, dev.d_f32, dev.d_len, (dev.d_cal, dev.d_cal + n * 4)
+    eng.h2d(dsig, sig)
+    options = {"": {}, "_start_peak": dict(with_start_peak=True), "_truncated": dict(flag_truncated=True), "_second_opinion": dict(second_opinion=True)}
+    try:
+        for name, flags in options.items():
+            kws = [{}] if name in ("", "_start_peak") else [{}, dict(with_start_peak=True)]
+            for kw in kws:
+                got = _per_row(getattr(cnn, "detect_rows" + name)(eng, sig, lens, None, spc, **kw))
+                want = _per_row(eng.detect_cnn_rows(sig, lens, n, n, fallback=True, **flags, **kw)[0])
+                assert got == want, ("detect_rows" + name, kw)
+                for mb in (None, 16):
+                    res = _per_row(getattr(cnn, "detect_rows_device" + name)(eng, dsig, dlen, n, lens, None, spc, mb, **kw))
+                    if mb is None:
+                        assert res == want, ("detect_rows_device" + name, kw, "the resident rows against the host batch")
+                    direct = _per_row(eng.detect_cnn_rows(dsig, dlen, n, mb or n, device_ptrs=True, fallback=True, **flags, **kw)[0])
+                    assert res == direct, ("detect_rows_device" + name, kw, mb)
+        plain = _per_row(eng.detect_cnn_rows(sig, lens, n, n, fallback=True)[0])
+        assert _per_row(cnn.detect_rows(eng, sig, lens, None, spc, "hip", "host")) == plain
+        assert _per_row(cnn.detect_rows_device(eng, dsig, dlen, n, lens, None, spc, None, "host")) == plain
+        assert any(a != b for a, b in zip(plain[0], want[0])), "precondition: an option changes rows"
+        for kw in ({}, dict(with_start_peak=True), dict(second_opinion=True), dict(with_start_peak=True, second_opinion=True)):
+            for mb in (None, 16):
+                got = _per_row(cnn.detect_rows_device_i16(eng, dev.d_raw, dlen, *cal, n, lens, None, spc, mb, **kw))
+                want = _per_row(eng.detect_cnn_rows_i16(dev.d_raw, dlen, *cal, n, mb or n, fallback=True, **kw)[0])
+                assert got == want, ("detect_rows_device_i16", kw, mb)
+    finally:
+        dev.close()
