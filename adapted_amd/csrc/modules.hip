@@ -1,8 +1,9 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak and the adapter start): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start and the event segmentation): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <initializer_list>
 #include <vector>
 
@@ -13,6 +14,7 @@
 #include "mvs_api.h"
 #include "sigstats_api.h"
 #include "startmods_api.h"
+#include "events_api.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -759,6 +761,77 @@ int adp_adapter_start(adp_handle *h, const void *sig, const int32_t *len, int n_
     RCCHK(d2h(h, out, dout, n * 8));
     RCCHK(d2h(h, cand_out, dcand, n * 8));
     RCCHK(d2h(h, diff_out, ddiff, n * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// ---- event segmentation of signal segments (an extension; events_api.h)
+
+int adp_sizeof_event_args(void) { return (int)sizeof(adp_event_args); }
+
+int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                       const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out)
+{
+    if (!h || !args || !info_out || !stats_out || cap < 0 || (cap > 0 && !pos_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
+    if (args->window < 2 || args->window > EV_WMAX) { g_err = "window must lie in [2, 64]"; return ADP_ERR_INVALID; }
+    if (args->min_distance < 1) { g_err = "min_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
+    if (!std::isfinite(args->threshold) || !(args->threshold > 0.0)) { g_err = "threshold must be finite and > 0"; return ADP_ERR_INVALID; }
+    if (!std::isfinite(args->var_floor) || !(args->var_floor > 0.0)) { g_err = "var_floor must be finite and > 0"; return ADP_ERR_INVALID; }
+    if (L >= (1 << 30)) { g_err = "rows of fewer than 2^30 samples"; return ADP_ERR_INVALID; } // (positions share a word with 2 state bits)
+    // the clipped slices (sigstats_api.h's ss_slice, on the host: len and segs are host arrays) and the longest one
+    std::vector<EvSeg> es(n_seg);
+    int lmax = 0;
+    for (int g = 0; g < n_seg; g++) {
+        const adp_seg &sg = segs[g];
+        es[g] = EvSeg{0, 0, 0};
+        if (sg.start < 0 || sg.end <= sg.start) continue;
+        const long long S = len[sg.row];
+        const long long a = sg.start < S ? sg.start : S, b = sg.end < S ? sg.end : S;
+        es[g] = EvSeg{(long long)sg.row * L + a, (int32_t)(b - a), 0};
+        if (es[g].n > lmax) lmax = es[g].n;
+    }
+    RCCHK(begin_call(h));
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
+    // a slot: the scores of one segment and its two lists of maxima; slots within a byte budget -- EV_SCRATCH_MIB, as the series
+    // kernels' (mv_slots), or ADP_EVENTS_SCRATCH_MIB from the environment, read per call -- and batches of slots
+    const size_t stride = ((size_t)(lmax > 0 ? lmax : 1) + 1) & ~(size_t)1, half = stride / 2 + 1;
+    long long mib = EV_SCRATCH_MIB;
+    if (const char *v = getenv("ADP_EVENTS_SCRATCH_MIB")) { mib = atoll(v); if (mib < 1 || mib > (1 << 20)) { g_err = "ADP_EVENTS_SCRATCH_MIB must lie in [1, 2^20]"; return ADP_ERR_INVALID; } }
+    size_t slots = ((size_t)mib << 20) / (stride * 8 + half * 8);
+    if (slots < 1) slots = 1;
+    if (slots > ns) slots = ns;
+    if (slots > 32768) slots = 32768;
+    void *s_sig; EvSeg *dsegs; int32_t *dnan; double *dscore, *dstats; uint32_t *pk, *wl; int64_t *dpos, *dinfo;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        dsegs = w.take<EvSeg>(ns); dnan = w.take<int32_t>(ns);
+        dpos = w.take<int64_t>(ns * cap); dinfo = w.take<int64_t>(ns * 2); dstats = w.take<double>(ns * 2);
+        dscore = w.take<double>(slots * stride); pk = w.take<uint32_t>(slots * half); wl = w.take<uint32_t>(slots * half);
+    }));
+    const void *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(h2d(h, dsegs, es.data(), ns * sizeof(EvSeg)));
+    HIPCHK(hipMemsetAsync(dnan, 0, ns * 4, h->stream));
+    const adp_event_args &a = *args;
+    for (size_t g0 = 0; g0 < ns; g0 += slots) {
+        const size_t nb = ns - g0 < slots ? ns - g0 : slots;
+        int bmax = 0;
+        for (size_t g = g0; g < g0 + nb; g++) if (es[g].n > bmax) bmax = es[g].n;
+        const int ntile = (bmax + EV_TILE - 1) / EV_TILE;
+        if (ntile > 0) {
+            Scope s(h, "k_ev_scores");
+            if (f64) hipLaunchKernelGGL(k_ev_scores<double>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, (const double *)ds, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan);
+            else hipLaunchKernelGGL(k_ev_scores<float>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, (const float *)ds, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan);
+        }
+        { Scope s(h, "k_ev_bounds");
+          hipLaunchKernelGGL(k_ev_bounds, dim3((unsigned)nb), dim3(64), 0, h->stream, dscore, stride, dsegs, (int)g0, a.window, a.min_distance, a.threshold, cap, pk, wl, (int)half, dnan, dpos, dinfo, dstats); }
+    }
+    HIPCHK(hipGetLastError());
+    if (cap > 0) RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
+    RCCHK(d2h(h, info_out, dinfo, ns * 16));
+    RCCHK(d2h(h, stats_out, dstats, ns * 16));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }

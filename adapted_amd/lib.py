@@ -265,7 +265,8 @@ def load():
         raise HipLibraryError("libadapted_hip.so is required (hipcc build or load failed): %s" % e) from e
     assert_one_runtime()
     try:
-        for name, proto in list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items()):
+        for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
+                            + list(EVENT_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -276,7 +277,8 @@ def load():
             or lib.adp_sizeof_mvs_args() != C.sizeof(AdpMvsArgs) or lib.adp_sizeof_seg() != SEG_DTYPE.itemsize
             or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)
             or lib.adp_sizeof_start_peak_args() != C.sizeof(AdpStartPeakArgs)
-            or lib.adp_sizeof_adapter_start_args() != C.sizeof(AdpAdapterStartArgs)):
+            or lib.adp_sizeof_adapter_start_args() != C.sizeof(AdpAdapterStartArgs)
+            or lib.adp_sizeof_event_args() != C.sizeof(AdpEventArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     _LIB = lib
     return lib
@@ -325,6 +327,24 @@ class AdpStartPeakArgs(C.Structure):
 class AdpAdapterStartArgs(C.Structure):
     """struct adp_adapter_start_args (include/adapted_hip.h): MMAdapterStartConfig's parameters"""
     _fields_ = [(k, C.c_double) for k in ("min_shift", "min_pA_current")] + [(k, C.c_int32) for k in ("window", "min_obs_adapter")]
+
+
+class AdpEventArgs(C.Structure):
+    """struct adp_event_args (include/adapted_hip_events.h): the parameters of the event segmentation"""
+    _fields_ = [(k, C.c_double) for k in ("threshold", "var_floor")] + [(k, C.c_int32) for k in ("window", "min_distance")]
+
+
+# the event segmentation's tile (EV_TILE: positions per workgroup of k_ev_scores) and the default byte budget, in MiB, of a call's batch
+# of slots (EV_SCRATCH_MIB; ADP_EVENTS_SCRATCH_MIB in the environment replaces it, read per call) -- adapted_amd/csrc/events_api.h;
+# tests/test_events_cpu.py holds both against that header
+EVENTS_TILE = 1024
+EVENTS_SCRATCH_MIB = 512
+
+
+def events_slot_bytes(longest: int) -> int:
+    """the scratch one segment takes in adp_segment_events when the call's longest clipped segment has ``longest`` samples"""
+    stride = (max(int(longest), 1) + 1) & ~1
+    return stride * 8 + (stride // 2 + 1) * 8
 
 
 # the chunk length of k_adapter_start's LDS staging (ASC_CHUNK, adapted_amd/csrc/startmods_api.h): its chains change path there
@@ -430,12 +450,19 @@ I16_PROTOTYPES = {
     "adp_detect_cnn_i16": "int: adp_handle* int16* int32* float* float* int int int int adp_row* int64*",
 }
 
+# include/adapted_hip_events.h (the header adapted_hip.h includes for the event segmentation, an extension);
+# tests/test_events_cpu.py holds this table against its header
+EVENT_PROTOTYPES = {
+    "adp_sizeof_event_args": "int:",
+    "adp_segment_events": "int: adp_handle* void* int32* int int adp_seg* int adp_event_args* int int int64* int64* double*",
+}
+
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
 _RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
 _SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
 _POINTEES = {"adp_cfg": AdpCfg, "adp_trace_args": AdpTraceArgs, "adp_peak_args": AdpPeakArgs, "adp_spike_args": AdpSpikeArgs,
             "adp_mvs_args": AdpMvsArgs, "adp_real_range_args": AdpRealRangeArgs, "adp_start_peak_args": AdpStartPeakArgs,
-            "adp_adapter_start_args": AdpAdapterStartArgs, "adp_handle*": _VoidP, "void*": _VoidP,
+            "adp_adapter_start_args": AdpAdapterStartArgs, "adp_event_args": AdpEventArgs, "adp_handle*": _VoidP, "void*": _VoidP,
             "char*": C.c_char_p}
 _ELEMENTS = {"float": np.float32, "double": np.float64, "int16": np.int16, "int32": np.int32, "int64": np.int64, "uint32": np.uint32,
              "uint64": np.uint64, "void": None, "adp_row": ROW_DTYPE, "adp_seg": SEG_DTYPE}
@@ -1089,6 +1116,24 @@ class Engine:
         self._check(self.lib.adp_adapter_start(self._h, sig, self._per_read(lens, n, "lens"), n, L, C.byref(args), flags, info, out,
                                                cand, diff))
         return info, out, cand, diff
+
+    def segment_events(self, sig, lens, rows, starts, ends, args: "AdpEventArgs", cap: int = 0, n: Optional[int] = None,
+                       L: Optional[int] = None, f64: bool = False):
+        """adp_segment_events: signals float32 / float64 [n, L] (a device pointer: float64 with ``f64``), lens, and per segment its
+        row, start and end -> (pos int64 [n_seg, cap]: the boundaries between the events, from the clipped segment's start,
+        padded with -1; info int64 [n_seg, 2]: the number of boundaries (also past cap), status (0; 1 a NaN in the slice; 2 the
+        slice is shorter than two windows); stats float64 [n_seg, 2]: median and MAD of the gaps between boundaries)"""
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
+        cap = int(cap)
+        if segs.size == 0:  # (the library wants a segment: an empty batch has an empty answer)
+            return np.zeros((0, cap), dtype=np.int64), np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2))
+        pos = np.zeros((segs.size, cap), dtype=np.int64)
+        info = np.zeros((segs.size, 2), dtype=np.int64)
+        stats = np.zeros((segs.size, 2))
+        self._check(self.lib.adp_segment_events(self._h, sig, lens, n, L, segs, segs.size, C.byref(args), flags, cap,
+                                                pos if cap > 0 else None, info, stats))
+        return pos, info, stats
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

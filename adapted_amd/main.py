@@ -20,6 +20,7 @@ import uuid
 from typing import List, Set
 
 import numpy as np
+import pandas as pd
 
 from . import lib, parallel
 from ._version import __version__
@@ -60,6 +61,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
                         "(pA = scale * (float32(adc) + offset)): both primaries, LLR and CNN, read the raw samples on the GPU and "
                         "no float32 copy of the signal is made there; .pod5 inputs or .npz bundles with raw/scale/offset")
+    d.add_argument("--polya_length", type=str, choices=["events", "adapter"], default=None,
+                   help="(extension) estimate the poly(A) length in bases of every passing read, into polya_length/polya_length_<k>.csv: "
+                        "poly(A) samples divided by the read's translocation speed in samples per base.  events: the speed is the "
+                        "median length of the events a segmentation of the adapter signal finds (on the GPU); adapter: the adapter's "
+                        "samples divided by --adapter_nt.  One GPU, LLR and CNN primaries, float32 ingestion")
+    d.add_argument("--adapter_nt", type=float, default=None, help="(extension) the adapter's length in bases (--polya_length adapter)")
+    d.add_argument("--event_params", type=str, default=None, metavar="WINDOW,MIN_DISTANCE,THRESHOLD",
+                   help="(extension) the event segmentation's parameters (default 8,8,16.0: untuned, chosen on synthetic signals)")
     return p
 
 
@@ -78,12 +87,36 @@ def scan_processed_reads(run_dir: str):
     return done, mx["boundaries"], mx["failed_reads"]
 
 
+POLYA_LENGTH_COLUMNS = ["read_id", "adapter_len", "polya_len", "n_events", "event_len_med", "event_len_mad", "samples_per_nt", "polya_nt",
+                        "polya_truncated"]
+
+
+def polya_length_records(read_ids, results, events, method: str, adapter_nt=None) -> List[dict]:
+    """one polya_length_<k>.csv line (POLYA_LENGTH_COLUMNS) per read: its DetectResults and its entry of the pipeline's
+    EVENT_DTYPE array -> lengths in samples, the adapter's events, the speed and the poly(A) length in bases"""
+    from .polya_length import estimate_polya_length
+
+    med = np.asarray(events["med"], dtype=np.float64)
+    nt, spn = estimate_polya_length([r.adapter_start for r in results], [r.adapter_end for r in results], [r.polya_end for r in results],
+                                    method=method, event_len_med=med if method == "events" else None, adapter_nt=adapter_nt)
+    out = []
+    for i, (rid, r) in enumerate(zip(read_ids, results)):
+        nb = int(events["n_bound"][i])
+        out.append({"read_id": str(rid), "adapter_len": r.adapter_len, "polya_len": r.polya_len,
+                    "n_events": max(nb - 1, 0) if nb >= 0 else None, "event_len_med": float(med[i]), "event_len_mad": float(events["mad"][i]),
+                    "samples_per_nt": float(spn[i]), "polya_nt": float(nt[i]), "polya_truncated": r.polya_truncated})
+    return out
+
+
 class _Writer:
     """Accumulates pass / fail results and flushes CSV files of `batch` reads each."""
 
-    def __init__(self, run_dir: str, batch: int, bidx_pass: int = 0, bidx_fail: int = 0):
+    def __init__(self, run_dir: str, batch: int, bidx_pass: int = 0, bidx_fail: int = 0, polya_length: bool = False):
+        """polya_length: every detected_boundaries_<k>.csv gets a polya_length/polya_length_<k>.csv beside it, one line per read
+        from the `polya_length` record its ReadResult carries (polya_length_records)"""
         self.dirs = {True: os.path.join(run_dir, "boundaries"), False: os.path.join(run_dir, "failed_reads")}
-        for d in self.dirs.values():
+        self.polya_dir = os.path.join(run_dir, "polya_length") if polya_length else None
+        for d in list(self.dirs.values()) + ([self.polya_dir] if polya_length else []):
             os.makedirs(d, exist_ok=True)
         self.names = {True: "detected_boundaries", False: "failed_reads"}
         self.bidx = {True: bidx_pass, False: bidx_fail}
@@ -102,6 +135,9 @@ class _Writer:
     def _flush(self, ok: bool, items: List[ReadResult]):
         fn = os.path.join(self.dirs[ok], "%s_%d.csv" % (self.names[ok], self.bidx[ok]))
         save_detected_boundaries(items, fn, save_fail_reasons=not ok)
+        if ok and self.polya_dir:
+            pd.DataFrame([r.polya_length for r in items], columns=POLYA_LENGTH_COLUMNS).round(3).to_csv(
+                os.path.join(self.polya_dir, "polya_length_%d.csv" % self.bidx[ok]), index=False)
         self.bidx[ok] += 1
         self.n[ok] += len(items)
 
@@ -163,6 +199,35 @@ def _check_flag_truncated(args):
             raise SystemExit("--flag_truncated does not go with this configuration: %s." % why)
 
 
+def _check_polya_length(args):
+    """--polya_length and what it does not go with: said before a GPU is touched"""
+    method = getattr(args, "polya_length", None)
+    if not method:
+        if getattr(args, "adapter_nt", None) is not None or getattr(args, "event_params", None):
+            raise SystemExit("--adapter_nt and --event_params go with --polya_length.")
+        return
+    if getattr(args, "int16_ingest", False):
+        raise SystemExit("--polya_length does not go with --int16_ingest: the event segmentation reads the float32 signal on the GPU, "
+                         "and that plan keeps none there.")
+    if parallel.world()[1] > 1:
+        raise SystemExit("--polya_length runs on one GPU: the polya_length files are not gathered from several ranks.")
+    if method == "adapter" and getattr(args, "adapter_nt", None) is None:
+        raise SystemExit("--polya_length adapter needs --adapter_nt, the adapter's length in bases.")
+    if getattr(args, "adapter_nt", None) is not None and not args.adapter_nt > 0:
+        raise SystemExit("--adapter_nt must be > 0.")
+    if getattr(args, "event_params", None):
+        from .polya_length import EventParams
+
+        try:
+            EventParams.parse(args.event_params)
+        except ValueError as e:
+            raise SystemExit("--event_params: %s." % e)
+    if args.config or args.chemistry:
+        primary = _load_spc(args).primary_method
+        if primary not in ("llr", "cnn"):
+            raise SystemExit("--polya_length goes with the LLR and CNN primaries; this configuration's primary is %s." % primary)
+
+
 def list_truncated(directory: str) -> int:
     """`adapted truncated`: the read ids whose polya_truncated column reads True, over all detected_boundaries_*.csv of the
     directory (or of its boundaries/ folder) in file order, into truncated_read_ids.csv (header read_id) beside them -- what the
@@ -204,7 +269,10 @@ def list_truncated(directory: str) -> int:
 
 
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False):
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, polya_length=None, adapter_nt=None,
+               event_params=None):
+    """polya_length: None, "events" or "adapter" (--polya_length: polya_length/polya_length_<k>.csv beside boundaries/);
+    adapter_nt: the adapter's bases for "adapter"; event_params: "WINDOW,MIN_DISTANCE,THRESHOLD" or None"""
     rank, ws, local = parallel.world()
     if device is None:
         device = local
@@ -215,7 +283,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     primary = spc.primary_method
     model = None  # CNN primary: the weights named in the config go to the engine on first use (no PyTorch module needed)
     m = spc.sig_preload_size
-    writer = _Writer(run_dir, batch_out, bidx_pass, bidx_fail) if rank == 0 else None
+    if polya_length and (ws > 1 or int16_ingest or primary not in ("llr", "cnn")):
+        raise ValueError("polya_length: one GPU, the LLR or CNN primary, no int16 ingest")
+    writer = (_Writer(run_dir, batch_out, bidx_pass, bidx_fail, polya_length=True) if polya_length
+              else _Writer(run_dir, batch_out, bidx_pass, bidx_fail)) if rank == 0 else None
     t0 = time.time()
     my_rows, my_ids, my_ord = [], [], []
     dropped_text = {1: "MAD normalization failed: scale is 0", 2: "a read has no signal after min_obs_adapter"}
@@ -230,6 +301,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
                         model=model, int16_input="native" if int16_ingest else False, group=GROUP, ragged=True, second_opinion=second_opinion,
                         flag_truncated=flag_truncated)
+    if polya_length:
+        from .polya_length import EventParams
+
+        pipe.enable_polya_length(EventParams.parse(event_params) if event_params else None)
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
     sharder = GroupSharder(ws, rank, m) if multi else None
@@ -246,7 +321,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             tagged[:, 1] = np.arange(ordinals[-1], ordinals[-1] + k)
             yield k, tagged
 
-    def on_rows(tagged, rows):
+    def on_rows(tagged, rows, events=None):
         if multi:
             my_rows.append(rows)
             my_ids.extend(tagged[:, 0].tolist())
@@ -255,8 +330,12 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_second[0] += int(((rows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             n_trunc[0] += int(((rows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             res = lib.rows_to_results(rows, primary, consume=True)
-            writer.add([ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
-                        for rid, r in zip(tagged[:, 0], res)])
+            out = [ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
+                   for rid, r in zip(tagged[:, 0], res)]
+            if events is not None:
+                for rr, rec in zip(out, polya_length_records(tagged[:, 0], res, events, polya_length, adapter_nt)):
+                    rr.polya_length = rec
+            writer.add(out)
 
     def on_dropped(tagged, status):
         logging.error("minibatch of %d reads dropped: %s", len(tagged), dropped_text.get(status, status))
@@ -312,11 +391,13 @@ def main(argv=None):
                 setattr(args, k, v)
         _check_second_opinion(args)
         _check_flag_truncated(args)
+        _check_polya_length(args)
     else:
         args.output = args.output or os.getcwd()
         run_dir = os.path.join(args.output, "adapted_" + __version__.replace(".", "_") + "_" + str(uuid.uuid4())[:8])
         _check_second_opinion(args)
         _check_flag_truncated(args)
+        _check_polya_length(args)
         dist = _init_dist(getattr(args, "device", None))
         if dist is not None:  # one run directory for all ranks: rank 0's name
             box = [run_dir]
@@ -354,7 +435,8 @@ def main(argv=None):
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
                int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
-               flag_truncated=getattr(args, "flag_truncated", False))
+               flag_truncated=getattr(args, "flag_truncated", False), polya_length=getattr(args, "polya_length", None),
+               adapter_nt=getattr(args, "adapter_nt", None), event_params=getattr(args, "event_params", None))
     logging.info("Done.")
 
 

@@ -39,6 +39,11 @@ def native_int16_plan(primary: str, int16_input, m: int, flag_truncated: bool) -
     return primary == "cnn" and int16_input == "native"
 
 
+# what enable_polya_length adds to a slot's rows, one entry per read (-1 / NaN for a read that did not pass): the boundaries
+# between the events of its adapter, the segmentation's status, median and MAD of the event lengths (adp_segment_events)
+EVENT_DTYPE = np.dtype([("n_bound", "<i8"), ("status", "<i8"), ("med", "<f8"), ("mad", "<f8")])
+
+
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
@@ -95,6 +100,40 @@ class HostPipeline:
         self.free: "queue.Queue[int]" = queue.Queue()
         for i in range(len(self.slots)):
             self.free.put(i)
+
+    def enable_polya_length(self, params=None):
+        """(extension) After every detect call, while the slot's float32 matrix is still resident, segment the adapter
+        [adapter_start, adapter_end) of every passing read into events in one adp_segment_events call
+        (adapted_amd/polya_length.py); run() then hands on_rows a third argument, an EVENT_DTYPE array beside the rows.
+        params: polya_length.EventParams (None: its untuned defaults).  Not on the native int16 plan (no float32 matrix
+        exists there) and not with the start-peak primary."""
+        from .polya_length import EventParams
+
+        if self.native_i16:
+            raise ValueError("polya_length needs the float32 matrix on the device: not with int16 input read natively")
+        if self.primary not in ("llr", "cnn"):
+            raise ValueError("polya_length goes with the LLR and CNN primaries")
+        params = params or EventParams()
+        params.check()
+        self.event_args = params.args()
+
+    def _adapter_events(self, j: int, n: int, rows: np.ndarray, mbs) -> np.ndarray:
+        """the events of the passing reads' adapters, from the matrix the detect call of slot j just read"""
+        ev = np.zeros(n, dtype=EVENT_DTYPE)
+        ev["n_bound"], ev["status"], ev["med"], ev["mad"] = -1, -1, np.nan, np.nan
+        ok = rows["success"][:n] != 0
+        if mbs is not None:  # (the rows of a dropped minibatch mean nothing)
+            ok &= np.repeat(np.asarray(mbs) == lib.MB_OK, self.mb)[:n]
+        idx = np.flatnonzero(ok)
+        if idx.size:
+            col, present = rows["col"][idx], rows["present"][idx]
+            starts = np.where(present >> np.uint64(2) & np.uint64(1), col[:, 2], 0).astype(np.int64)
+            ends = np.where(present >> np.uint64(3) & np.uint64(1), col[:, 3], 0).astype(np.int64)
+            lens = np.minimum(self.slots[j]["lens"][:n], self.m).astype(np.int32)
+            _, info, stats = self.eng.segment_events(self._resident, lens, idx, starts, ends, self.event_args, cap=0, n=n, L=self.m)
+            ev["n_bound"][idx], ev["status"][idx] = info[:, 0], info[:, 1]
+            ev["med"][idx], ev["mad"][idx] = stats[:, 0], stats[:, 1]
+        return ev
 
     def _slot(self, j: int):
         if self.slots[j] is None:
@@ -170,6 +209,7 @@ class HostPipeline:
         elif self.i16:  # raw ADC -> float32 pA, NaN beyond the read, on the engine's stream ahead of the detect kernels
             self.eng.calibrate_i16(dsig, dlen, s["dcal"], s["dcal"] + self.N * 4, n, self.dsig16)
             dsig = self.dsig16
+        self._resident = dsig  # the float32 [n, m] matrix this call reads (it stays until the next slot's call)
         if self.primary == "llr":
             # (the staging slots are NaN padded by the reader / the on-device calibration: the passes may stop at each read's end)
             rows, mbs = self.eng.detect_llr_rows(dsig, dlen, n, self.mb, with_start_peak=self.with_start_peak, device_ptrs=True,
@@ -253,15 +293,17 @@ class HostPipeline:
                 if pending is not None:
                     j, n, ids = pending
                     rows, mbs = self._detect(j, n)
+                    # (with enable_polya_length: a third item travels with the rows, sliced as they are)
+                    more = (self._adapter_events(j, n, rows, mbs),) if getattr(self, "event_args", None) is not None else ()
                     if mbs is None or (mbs == lib.MB_OK).all():
-                        done.put((ids, rows))
+                        done.put((ids, rows) + more)
                         total += n
                     else:  # some minibatch of the group was dropped (the reference logs it and goes on)
                         for q, st in enumerate(mbs):
                             a, b = q * self.mb, min(n, (q + 1) * self.mb)
                             sub = ids[a:b] if hasattr(ids, "__getitem__") and not isinstance(ids, tuple) else ids
                             if st == lib.MB_OK:
-                                done.put((sub, rows[a:b]))
+                                done.put((sub, rows[a:b]) + tuple(e[a:b] for e in more))
                                 total += b - a
                             elif on_dropped:
                                 on_dropped(sub, int(st))

@@ -549,6 +549,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * adapted_amd/lib.py, I16_PROTOTYPES. */
 #include "adapted_hip_i16.h"
 
+/* Event segmentation of signal segments and the statistics of the event lengths -- adp_segment_events, an extension --: declared in
+ * a header of its own, with its prototype table in adapted_amd/lib.py, EVENT_PROTOTYPES. */
+#include "adapted_hip_events.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
