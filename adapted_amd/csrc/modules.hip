@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start and the event segmentation): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation and the event fingerprints): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 #include "sigstats_api.h"
 #include "startmods_api.h"
 #include "events_api.h"
+#include "fingerprint_api.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -769,10 +770,15 @@ int adp_adapter_start(adp_handle *h, const void *sig, const int32_t *len, int n_
 
 int adp_sizeof_event_args(void) { return (int)sizeof(adp_event_args); }
 
-int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
-                       const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out)
+// what adp_event_levels asks of a segmentation call beside adp_segment_events' outputs (fingerprint_api.h): the widest event
+// table and where its pieces go -- count and fp to device memory with ADP_OUT_DEVICE, lengths / levels / norm nowhere when NULL
+struct EvLevels { int E; int32_t *count, *fpstatus, *lengths; double *levels, *fp, *norm; };
+
+// adp_segment_events and, with `lv`, adp_event_levels: the same checks, slots and batches; k_ev_levels behind k_ev_bounds
+static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                      const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out,
+                      const EvLevels *lv)
 {
-    if (!h || !args || !info_out || !stats_out || cap < 0 || (cap > 0 && !pos_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
     if (args->window < 2 || args->window > EV_WMAX) { g_err = "window must lie in [2, 64]"; return ADP_ERR_INVALID; }
     if (args->min_distance < 1) { g_err = "min_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
@@ -804,12 +810,21 @@ int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n
     if (slots > ns) slots = ns;
     if (slots > 32768) slots = 32768;
     void *s_sig; EvSeg *dsegs; int32_t *dnan; double *dscore, *dstats; uint32_t *pk, *wl; int64_t *dpos, *dinfo;
+    // (the event tables: in the workspace, but for the two that stay on the device with ADP_OUT_DEVICE)
+    const bool lv_dev = lv && (flags & ADP_OUT_DEVICE);
+    const size_t E = lv ? lv->E : 0;
+    int32_t *dcount = nullptr, *dfst = nullptr, *dlens = nullptr; double *dlev = nullptr, *dfp = nullptr, *dnorm = nullptr;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
         dsegs = w.take<EvSeg>(ns); dnan = w.take<int32_t>(ns);
         dpos = w.take<int64_t>(ns * cap); dinfo = w.take<int64_t>(ns * 2); dstats = w.take<double>(ns * 2);
         dscore = w.take<double>(slots * stride); pk = w.take<uint32_t>(slots * half); wl = w.take<uint32_t>(slots * half);
+        if (lv) {
+            dcount = w.take<int32_t>(ns, !lv_dev); dfst = w.take<int32_t>(ns); dlens = w.take<int32_t>(ns * E);
+            dlev = w.take<double>(ns * E); dfp = w.take<double>(ns * E, !lv_dev); dnorm = w.take<double>(ns * 2);
+        }
     }));
+    if (lv_dev) { dcount = lv->count; dfp = lv->fp; }
     const void *ds;
     RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
     RCCHK(h2d(h, dsegs, es.data(), ns * sizeof(EvSeg)));
@@ -827,11 +842,95 @@ int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n
         }
         { Scope s(h, "k_ev_bounds");
           hipLaunchKernelGGL(k_ev_bounds, dim3((unsigned)nb), dim3(64), 0, h->stream, dscore, stride, dsegs, (int)g0, a.window, a.min_distance, a.threshold, cap, pk, wl, (int)half, dnan, dpos, dinfo, dstats); }
+        if (lv) {
+            Scope s(h, "k_ev_levels");
+            if (f64) hipLaunchKernelGGL(k_ev_levels<double>, dim3((unsigned)nb), dim3(64), 0, h->stream, (const double *)ds, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, dcount, dfst, dlens, dlev, dfp, dnorm);
+            else hipLaunchKernelGGL(k_ev_levels<float>, dim3((unsigned)nb), dim3(64), 0, h->stream, (const float *)ds, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, dcount, dfst, dlens, dlev, dfp, dnorm);
+        }
     }
     HIPCHK(hipGetLastError());
     if (cap > 0) RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
     RCCHK(d2h(h, info_out, dinfo, ns * 16));
     RCCHK(d2h(h, stats_out, dstats, ns * 16));
+    if (lv) {
+        RCCHK(d2h(h, lv->fpstatus, dfst, ns * 4));
+        if (!lv_dev) { RCCHK(d2h(h, lv->count, dcount, ns * 4)); RCCHK(d2h(h, lv->fp, dfp, ns * E * 8)); }
+        if (lv->lengths) RCCHK(d2h(h, lv->lengths, dlens, ns * E * 4));
+        if (lv->levels) RCCHK(d2h(h, lv->levels, dlev, ns * E * 8));
+        if (lv->norm) RCCHK(d2h(h, lv->norm, dnorm, ns * 16));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                       const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out)
+{
+    if (!h || !args || !info_out || !stats_out || cap < 0 || (cap > 0 && !pos_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    return ev_segment(h, sig, len, n_reads, L, segs, n_seg, args, flags, cap, pos_out, info_out, stats_out, nullptr);
+}
+
+// ---- adapter event fingerprints and their DTW distances to templates (an extension; fingerprint_api.h)
+
+int adp_event_levels(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                     const adp_event_args *args, int flags, int max_events, int64_t *info_out, double *stats_out, int32_t *count_out,
+                     int32_t *fpstatus_out, int32_t *lengths_out, double *levels_out, double *fp_out, double *norm_out)
+{
+    if (!h || !args || !info_out || !stats_out || !count_out || !fpstatus_out || !fp_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (max_events < 2 || max_events > FP_EMAX) { g_err = "max_events must lie in [2, 512]"; return ADP_ERR_INVALID; }
+    const EvLevels lv{max_events, count_out, fpstatus_out, lengths_out, levels_out, fp_out, norm_out};
+    return ev_segment(h, sig, len, n_reads, L, segs, n_seg, args, flags, 0, nullptr, info_out, stats_out, &lv);
+}
+
+int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int nq, int Eq, const double *t, const int32_t *t_count,
+                   int nt, int Et, int band, int flags, double *dist_out, int32_t *best_out, double *bestdist_out)
+{
+    if (!h || !q || !q_count || !t || !t_count || !best_out || !bestdist_out || nq < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (Eq < 1 || Eq > FP_EMAX || Et < 1 || Et > FP_EMAX) { g_err = "Eq and Et must lie in [1, 512]"; return ADP_ERR_INVALID; }
+    if (nt < 1 || nt > DTW_NT_MAX) { g_err = "nt must lie in [1, 4096]"; return ADP_ERR_INVALID; }
+    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
+    for (int k = 0; k < nt; k++) {
+        if (t_count[k] < 1 || t_count[k] > Et) { g_err = "need 1 <= t_count <= Et for every template"; return ADP_ERR_INVALID; }
+        for (int j = 0; j < t_count[k]; j++)
+            if (!std::isfinite(t[(size_t)k * Et + j])) { g_err = "template values inside their count must be finite"; return ADP_ERR_INVALID; }
+    }
+    // the distance matrix of a batch of queries within a byte budget: DTW_SCRATCH_MIB, or ADP_DTW_SCRATCH_MIB from the environment,
+    // read per call
+    long long mib = DTW_SCRATCH_MIB;
+    if (const char *v = getenv("ADP_DTW_SCRATCH_MIB")) { mib = atoll(v); if (mib < 1 || mib > (1 << 20)) { g_err = "ADP_DTW_SCRATCH_MIB must lie in [1, 2^20]"; return ADP_ERR_INVALID; } }
+    const size_t nqs = nq, nts = nt;
+    size_t rows = ((size_t)mib << 20) / (nts * 8);
+    if (rows < 1) rows = 1;
+    if (rows > nqs) rows = nqs;
+    if (rows > (size_t)0x7fffffff / nts) rows = (size_t)0x7fffffff / nts; // (a workgroup per pair of the batch)
+    RCCHK(begin_call(h));
+    double *s_q, *dt, *ddist, *dbd; int32_t *s_qc, *dtc, *dbest;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_q = w.take<double>(nqs * Eq, !(flags & ADP_IN_DEVICE)); s_qc = w.take<int32_t>(nqs, !(flags & ADP_IN_DEVICE));
+        dt = w.take<double>(nts * Et); dtc = w.take<int32_t>(nts);
+        ddist = w.take<double>(rows * nts); dbest = w.take<int32_t>(nqs * 2); dbd = w.take<double>(nqs * 2);
+    }));
+    const double *dq; const int32_t *dqc;
+    RCCHK(stage_in(h, flags, q, s_q, nqs * Eq * 8, &dq));
+    RCCHK(stage_in(h, flags, q_count, s_qc, nqs * 4, &dqc));
+    RCCHK(h2d(h, dt, t, nts * Et * 8));
+    RCCHK(h2d(h, dtc, t_count, nts * 4));
+    const int C = (Et + 63) / 64;
+    for (size_t p0 = 0; p0 < nqs; p0 += rows) {
+        const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
+        const dim3 grid((unsigned)(nb * nts)), block(64);
+        { Scope s(h, "k_dtw");
+          if (C <= 1) hipLaunchKernelGGL(k_dtw<1>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
+          else if (C <= 2) hipLaunchKernelGGL(k_dtw<2>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
+          else if (C <= 4) hipLaunchKernelGGL(k_dtw<4>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
+          else hipLaunchKernelGGL(k_dtw<8>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist); }
+        { Scope s(h, "k_dtw_best");
+          hipLaunchKernelGGL(k_dtw_best, dim3((unsigned)((nb + 63) / 64)), block, 0, h->stream, ddist, (int)nb, nt, dbest + p0 * 2, dbd + p0 * 2); }
+        if (dist_out) RCCHK(d2h(h, dist_out + p0 * nts, ddist, nb * nts * 8));
+    }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, best_out, dbest, nqs * 8));
+    RCCHK(d2h(h, bestdist_out, dbd, nqs * 16));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }

@@ -266,7 +266,7 @@ def load():
     assert_one_runtime()
     try:
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
-                            + list(EVENT_PROTOTYPES.items())):
+                            + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -346,6 +346,13 @@ def events_slot_bytes(longest: int) -> int:
     stride = (max(int(longest), 1) + 1) & ~1
     return stride * 8 + (stride // 2 + 1) * 8
 
+
+# the widest event table of adp_event_levels, the longest query / template and the most templates of adp_dtw_assign, and the default
+# byte budget, in MiB, of that call's distance matrix (ADP_DTW_SCRATCH_MIB in the environment replaces it, read per call) --
+# FP_EMAX, DTW_NT_MAX and DTW_SCRATCH_MIB of adapted_amd/csrc/fingerprint_api.h; tests/test_fingerprint_cpu.py holds them against it
+FINGERPRINT_MAX_EVENTS = 512
+DTW_MAX_TEMPLATES = 4096
+DTW_SCRATCH_MIB = 512
 
 # the chunk length of k_adapter_start's LDS staging (ASC_CHUNK, adapted_amd/csrc/startmods_api.h): its chains change path there
 ADAPTER_START_CHUNK = 512
@@ -455,6 +462,14 @@ I16_PROTOTYPES = {
 EVENT_PROTOTYPES = {
     "adp_sizeof_event_args": "int:",
     "adp_segment_events": "int: adp_handle* void* int32* int int adp_seg* int adp_event_args* int int int64* int64* double*",
+}
+
+# include/adapted_hip_fingerprint.h (the header adapted_hip.h includes for the adapter event fingerprints and their DTW
+# distances to templates, an extension); tests/test_fingerprint_cpu.py holds this table against its header
+FINGERPRINT_PROTOTYPES = {
+    "adp_event_levels": "int: adp_handle* void* int32* int int adp_seg* int adp_event_args* int int int64* double* int32* int32* int32* "
+                        "double* double* double*",
+    "adp_dtw_assign": "int: adp_handle* double* int32* int int double* int32* int int int int double* int32* double*",
 }
 
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
@@ -1134,6 +1149,60 @@ class Engine:
         self._check(self.lib.adp_segment_events(self._h, sig, lens, n, L, segs, segs.size, C.byref(args), flags, cap,
                                                 pos if cap > 0 else None, info, stats))
         return pos, info, stats
+
+    def event_levels(self, sig, lens, rows, starts, ends, args: "AdpEventArgs", max_events: int, n: Optional[int] = None,
+                     L: Optional[int] = None, f64: bool = False, fp_ptr: Optional[int] = None, count_ptr: Optional[int] = None):
+        """adp_event_levels: the inputs of segment_events -> a dict: info int64 [n_seg, 2] and stats float64 [n_seg, 2] as
+        segment_events'; count int32 [n_seg]; status int32 [n_seg] (0; 1 / 2 as the segmentation's; 4: the MAD of the levels is 0,
+        or median / MAD are not finite); lengths int32 / levels float64 / fingerprints float64 [n_seg, max_events] (0 / NaN at and
+        beyond count); norm float64 [n_seg, 2]: median and MAD of the levels.  With ``fp_ptr`` and ``count_ptr`` (device buffers
+        of n_seg * max_events * 8 and n_seg * 4 bytes, dev_alloc) the fingerprints and counts stay on the device for dtw_assign and
+        are None here"""
+        sig, flags, n, L, _ = self._sig_in(sig, n, L, f64)
+        lens, segs = self._per_read(lens, n, "lens"), self._segs(rows, starts, ends)
+        E, ns = int(max_events), segs.size
+        if (fp_ptr is None) != (count_ptr is None):
+            raise ValueError("fp_ptr and count_ptr go together")
+        on_dev = fp_ptr is not None
+        out = {"info": np.zeros((ns, 2), dtype=np.int64), "stats": np.zeros((ns, 2)), "count": None if on_dev else np.zeros(ns, dtype=np.int32),
+               "status": np.zeros(ns, dtype=np.int32), "lengths": np.zeros((ns, max(E, 0)), dtype=np.int32), "levels": np.zeros((ns, max(E, 0))),
+               "fingerprints": None if on_dev else np.zeros((ns, max(E, 0))), "norm": np.zeros((ns, 2))}
+        if ns == 0:  # (the library wants a segment: an empty batch has an empty answer)
+            return out
+        self._check(self.lib.adp_event_levels(self._h, sig, lens, n, L, segs, ns, C.byref(args), flags | (ADP_OUT_DEVICE if on_dev else 0), E,
+                                              out["info"], out["stats"], int(count_ptr) if on_dev else out["count"], out["status"],
+                                              out["lengths"], out["levels"], int(fp_ptr) if on_dev else out["fingerprints"], out["norm"]))
+        return out
+
+    def dtw_assign(self, q, q_count, t, t_count, band: int = 0, nq: Optional[int] = None, Eq: Optional[int] = None,
+                   want_dist: bool = True):
+        """adp_dtw_assign: queries float64 [nq, Eq] with their counts (host arrays, or two device pointers with ``nq`` and ``Eq``:
+        event_levels' fp_ptr and count_ptr), templates float64 [nt, Et] with their counts (host) -> (dist float64 [nq, nt], or
+        None without ``want_dist``; best int32 [nq, 2]: the nearest and the second nearest template, -1 where there is none;
+        bestdist float64 [nq, 2], NaN where -1)"""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError("templates: a float64 [nt, Et] array")
+        nt, Et = t.shape
+        t_count = self._per_read(t_count, nt, "t_count")
+        if isinstance(q, int):
+            if nq is None or Eq is None or not isinstance(q_count, int):
+                raise ValueError("device queries need a device pointer to their counts, nq and Eq")
+            _check_runtime_once_torch_is_here()
+            flags, nq, Eq = ADP_IN_DEVICE, int(nq), int(Eq)
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.ndim != 2:
+                raise ValueError("queries: a float64 [nq, Eq] array")
+            flags, (nq, Eq) = 0, q.shape
+            q_count = self._per_read(q_count, nq, "q_count")
+        dist = np.zeros((nq, nt)) if want_dist else None
+        best = np.full((nq, 2), -1, dtype=np.int32)
+        bestdist = np.full((nq, 2), np.nan)
+        if nq == 0:  # (the library wants a query: an empty batch has an empty answer)
+            return dist, best, bestdist
+        self._check(self.lib.adp_dtw_assign(self._h, q, q_count, nq, Eq, t, t_count, nt, Et, int(band), flags, dist, best, bestdist))
+        return dist, best, bestdist
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

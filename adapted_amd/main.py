@@ -69,6 +69,14 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("--adapter_nt", type=float, default=None, help="(extension) the adapter's length in bases (--polya_length adapter)")
     d.add_argument("--event_params", type=str, default=None, metavar="WINDOW,MIN_DISTANCE,THRESHOLD",
                    help="(extension) the event segmentation's parameters (default 8,8,16.0: untuned, chosen on synthetic signals)")
+    d.add_argument("--fingerprints", type=int, default=None, metavar="E",
+                   help="(extension) the event table and a normalised fingerprint of at most E events (2 .. 512) of every passing read's "
+                        "adapter, into fingerprints/fingerprints_<k>.npz beside each detected_boundaries_<k>.csv (on the GPU; untuned, and "
+                        "not validated on real barcodes).  One GPU, LLR and CNN primaries, float32 ingestion")
+    d.add_argument("--barcode_templates", type=str, default=None, metavar="FILE.npz",
+                   help="(extension, with --fingerprints) templates (adapted_amd.fingerprint.save_templates): every fingerprint's DTW "
+                        "distance to each and the nearest two, into fingerprints/barcodes_<k>.csv")
+    d.add_argument("--dtw_band", type=int, default=None, metavar="R", help="(extension, with --barcode_templates) the DTW's band (default 0: none)")
     return p
 
 
@@ -108,6 +116,25 @@ def polya_length_records(read_ids, results, events, method: str, adapter_nt=None
     return out
 
 
+BARCODE_COLUMNS = ["read_id", "n_events", "barcode", "dtw_dist", "barcode_second", "dtw_dist_second", "dtw_margin"]
+
+
+def fingerprint_records(read_ids, fp, names=None) -> List[dict]:
+    """one record per read from the pipeline's AdapterFingerprints: its entries of fingerprints_<k>.npz and, with the templates'
+    ``names``, its barcodes_<k>.csv line (BARCODE_COLUMNS) under its "barcode" key"""
+    out = []
+    for i, rid in enumerate(read_ids):
+        rec = {"read_id": str(rid), "count": fp.count[i], "status": fp.status[i], "lengths": fp.lengths[i], "levels": fp.levels[i],
+               "fingerprints": fp.fingerprints[i]}
+        if names is not None:
+            b, b2 = int(fp.best[i, 0]), int(fp.best[i, 1])
+            d, d2 = float(fp.bestdist[i, 0]), float(fp.bestdist[i, 1])
+            rec["barcode"] = {"read_id": str(rid), "n_events": int(fp.count[i]), "barcode": names[b] if b >= 0 else None, "dtw_dist": d,
+                              "barcode_second": names[b2] if b2 >= 0 else None, "dtw_dist_second": d2, "dtw_margin": d2 - d}
+        out.append(rec)
+    return out
+
+
 class _Writer:
     """Accumulates pass / fail results and flushes CSV files of `batch` reads each."""
 
@@ -123,6 +150,14 @@ class _Writer:
         self.pending = {True: [], False: []}
         self.batch = batch
         self.n = {True: 0, False: 0}
+        self.fp_dir, self.fp_width, self.barcodes = None, 0, False
+
+    def enable_fingerprints(self, run_dir: str, width: int, barcodes: bool = False):
+        """every detected_boundaries_<k>.csv gets a fingerprints/fingerprints_<k>.npz beside it (read_id, count, status, lengths,
+        levels, fingerprints: one entry per read, in the CSV's order) and, with ``barcodes``, a fingerprints/barcodes_<k>.csv, from
+        the `fingerprint` record its ReadResult carries (fingerprint_records).  Distances are written in full precision."""
+        self.fp_dir, self.fp_width, self.barcodes = os.path.join(run_dir, "fingerprints"), int(width), bool(barcodes)
+        os.makedirs(self.fp_dir, exist_ok=True)
 
     def add(self, results: List[ReadResult]):
         for r in results:
@@ -138,6 +173,17 @@ class _Writer:
         if ok and self.polya_dir:
             pd.DataFrame([r.polya_length for r in items], columns=POLYA_LENGTH_COLUMNS).round(3).to_csv(
                 os.path.join(self.polya_dir, "polya_length_%d.csv" % self.bidx[ok]), index=False)
+        if ok and self.fp_dir:
+            recs, E = [r.fingerprint for r in items], self.fp_width
+            with open(os.path.join(self.fp_dir, "fingerprints_%d.npz" % self.bidx[ok]), "wb") as fh:
+                np.savez(fh, read_id=np.asarray([r["read_id"] for r in recs], dtype=str),
+                         count=np.asarray([r["count"] for r in recs], dtype=np.int32), status=np.asarray([r["status"] for r in recs], dtype=np.int32),
+                         lengths=np.asarray([r["lengths"] for r in recs], dtype=np.int32).reshape(len(recs), E),
+                         levels=np.asarray([r["levels"] for r in recs], dtype=np.float64).reshape(len(recs), E),
+                         fingerprints=np.asarray([r["fingerprints"] for r in recs], dtype=np.float64).reshape(len(recs), E))
+            if self.barcodes:
+                pd.DataFrame([r["barcode"] for r in recs], columns=BARCODE_COLUMNS).to_csv(
+                    os.path.join(self.fp_dir, "barcodes_%d.csv" % self.bidx[ok]), index=False)
         self.bidx[ok] += 1
         self.n[ok] += len(items)
 
@@ -199,11 +245,50 @@ def _check_flag_truncated(args):
             raise SystemExit("--flag_truncated does not go with this configuration: %s." % why)
 
 
+def _check_fingerprints(args):
+    """--fingerprints and what it does not go with: said before a GPU is touched.  -> the templates of --barcode_templates, or None"""
+    E = getattr(args, "fingerprints", None)
+    if E is None:
+        if getattr(args, "barcode_templates", None) or getattr(args, "dtw_band", None) is not None:
+            raise SystemExit("--barcode_templates and --dtw_band go with --fingerprints.")
+        return None
+    from .fingerprint import FingerprintParams, load_templates
+    from .polya_length import EventParams
+
+    if not 2 <= E <= lib.FINGERPRINT_MAX_EVENTS:
+        raise SystemExit("--fingerprints: the number of events must lie in [2, %d]." % lib.FINGERPRINT_MAX_EVENTS)
+    if getattr(args, "int16_ingest", False):
+        raise SystemExit("--fingerprints does not go with --int16_ingest: the event segmentation reads the float32 signal on the GPU, "
+                         "and that plan keeps none there.")
+    if parallel.world()[1] > 1:
+        raise SystemExit("--fingerprints runs on one GPU: the fingerprint files are not gathered from several ranks.")
+    band = getattr(args, "dtw_band", None)
+    if band is not None and not getattr(args, "barcode_templates", None):
+        raise SystemExit("--dtw_band goes with --barcode_templates.")
+    if band is not None and band < 0:
+        raise SystemExit("--dtw_band must be >= 0.")
+    try:
+        FingerprintParams(E, EventParams.parse(args.event_params) if getattr(args, "event_params", None) else EventParams(), band or 0).check()
+    except ValueError as e:
+        raise SystemExit("--event_params: %s." % e)
+    templates = None
+    if getattr(args, "barcode_templates", None):
+        try:
+            templates = load_templates(args.barcode_templates)
+        except ValueError as e:
+            raise SystemExit("--barcode_templates: %s." % e)
+    if args.config or args.chemistry:
+        primary = _load_spc(args).primary_method
+        if primary not in ("llr", "cnn"):
+            raise SystemExit("--fingerprints goes with the LLR and CNN primaries; this configuration's primary is %s." % primary)
+    return templates
+
+
 def _check_polya_length(args):
     """--polya_length and what it does not go with: said before a GPU is touched"""
     method = getattr(args, "polya_length", None)
     if not method:
-        if getattr(args, "adapter_nt", None) is not None or getattr(args, "event_params", None):
+        if getattr(args, "adapter_nt", None) is not None or (getattr(args, "event_params", None) and getattr(args, "fingerprints", None) is None):
             raise SystemExit("--adapter_nt and --event_params go with --polya_length.")
         return
     if getattr(args, "int16_ingest", False):
@@ -269,9 +354,11 @@ def list_truncated(directory: str) -> int:
 
 
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, polya_length=None, adapter_nt=None,
-               event_params=None):
-    """polya_length: None, "events" or "adapter" (--polya_length: polya_length/polya_length_<k>.csv beside boundaries/);
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, fingerprints=None, polya_length=None,
+               adapter_nt=None, event_params=None):
+    """fingerprints: None, or (E, templates or None, band) (--fingerprints: fingerprints/fingerprints_<k>.npz and, with templates,
+    fingerprints/barcodes_<k>.csv beside boundaries/; the events' parameters are event_params);
+    polya_length: None, "events" or "adapter" (--polya_length: polya_length/polya_length_<k>.csv beside boundaries/);
     adapter_nt: the adapter's bases for "adapter"; event_params: "WINDOW,MIN_DISTANCE,THRESHOLD" or None"""
     rank, ws, local = parallel.world()
     if device is None:
@@ -285,8 +372,12 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     m = spc.sig_preload_size
     if polya_length and (ws > 1 or int16_ingest or primary not in ("llr", "cnn")):
         raise ValueError("polya_length: one GPU, the LLR or CNN primary, no int16 ingest")
+    if fingerprints and (ws > 1 or int16_ingest or primary not in ("llr", "cnn")):
+        raise ValueError("fingerprints: one GPU, the LLR or CNN primary, no int16 ingest")
     writer = (_Writer(run_dir, batch_out, bidx_pass, bidx_fail, polya_length=True) if polya_length
               else _Writer(run_dir, batch_out, bidx_pass, bidx_fail)) if rank == 0 else None
+    if fingerprints and writer is not None:
+        writer.enable_fingerprints(run_dir, fingerprints[0], barcodes=fingerprints[1] is not None)
     t0 = time.time()
     my_rows, my_ids, my_ord = [], [], []
     dropped_text = {1: "MAD normalization failed: scale is 0", 2: "a read has no signal after min_obs_adapter"}
@@ -305,6 +396,12 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
         from .polya_length import EventParams
 
         pipe.enable_polya_length(EventParams.parse(event_params) if event_params else None)
+    if fingerprints:
+        from .fingerprint import FingerprintParams
+        from .polya_length import EventParams
+
+        pipe.enable_fingerprints(FingerprintParams(int(fingerprints[0]), EventParams.parse(event_params) if event_params else EventParams(),
+                                                   int(fingerprints[2] or 0)), fingerprints[1])
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
     sharder = GroupSharder(ws, rank, m) if multi else None
@@ -321,7 +418,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             tagged[:, 1] = np.arange(ordinals[-1], ordinals[-1] + k)
             yield k, tagged
 
-    def on_rows(tagged, rows, events=None):
+    def on_rows(tagged, rows, events=None, fp=None):
         if multi:
             my_rows.append(rows)
             my_ids.extend(tagged[:, 0].tolist())
@@ -335,6 +432,9 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             if events is not None:
                 for rr, rec in zip(out, polya_length_records(tagged[:, 0], res, events, polya_length, adapter_nt)):
                     rr.polya_length = rec
+            if fp is not None:
+                for rr, rec in zip(out, fingerprint_records(tagged[:, 0], fp, fingerprints[1].names if fingerprints[1] is not None else None)):
+                    rr.fingerprint = rec
             writer.add(out)
 
     def on_dropped(tagged, status):
@@ -392,12 +492,14 @@ def main(argv=None):
         _check_second_opinion(args)
         _check_flag_truncated(args)
         _check_polya_length(args)
+        templates = _check_fingerprints(args)
     else:
         args.output = args.output or os.getcwd()
         run_dir = os.path.join(args.output, "adapted_" + __version__.replace(".", "_") + "_" + str(uuid.uuid4())[:8])
         _check_second_opinion(args)
         _check_flag_truncated(args)
         _check_polya_length(args)
+        templates = _check_fingerprints(args)
         dist = _init_dist(getattr(args, "device", None))
         if dist is not None:  # one run directory for all ranks: rank 0's name
             box = [run_dir]
@@ -435,7 +537,9 @@ def main(argv=None):
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
                int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
-               flag_truncated=getattr(args, "flag_truncated", False), polya_length=getattr(args, "polya_length", None),
+               flag_truncated=getattr(args, "flag_truncated", False),
+               fingerprints=(args.fingerprints, templates, getattr(args, "dtw_band", None)) if getattr(args, "fingerprints", None) is not None else None,
+               polya_length=getattr(args, "polya_length", None),
                adapter_nt=getattr(args, "adapter_nt", None), event_params=getattr(args, "event_params", None))
     logging.info("Done.")
 

@@ -44,6 +44,30 @@ def native_int16_plan(primary: str, int16_input, m: int, flag_truncated: bool) -
 EVENT_DTYPE = np.dtype([("n_bound", "<i8"), ("status", "<i8"), ("med", "<f8"), ("mad", "<f8")])
 
 
+class AdapterFingerprints:
+    """What enable_fingerprints adds to a slot's rows, one entry per read (count / status -1, lengths 0, NaN for a read that did
+    not pass): the event table and fingerprint of its adapter (adp_event_levels) and, with templates, the nearest two templates
+    and their DTW distances (adp_dtw_assign; best None without templates).  Sliced as the rows are."""
+    FIELDS = ("count", "status", "lengths", "levels", "fingerprints", "best", "bestdist")
+
+    def __init__(self, n: int, E: int, templates: bool):
+        self.count, self.status = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+        self.lengths = np.zeros((n, E), dtype=np.int32)
+        self.levels, self.fingerprints = np.full((n, E), np.nan), np.full((n, E), np.nan)
+        self.best = np.full((n, 2), -1, dtype=np.int32) if templates else None
+        self.bestdist = np.full((n, 2), np.nan) if templates else None
+
+    def __len__(self):
+        return self.count.size
+
+    def __getitem__(self, sl):
+        out = AdapterFingerprints.__new__(AdapterFingerprints)
+        for k in self.FIELDS:
+            v = getattr(self, k)
+            setattr(out, k, None if v is None else v[sl])
+        return out
+
+
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
@@ -115,25 +139,90 @@ class HostPipeline:
             raise ValueError("polya_length goes with the LLR and CNN primaries")
         params = params or EventParams()
         params.check()
+        other = getattr(self, "fp_args", None)
+        if other is not None and bytes(other) != bytes(params.args()):
+            raise ValueError("fingerprints and polya_length share one segmentation: give both the same event parameters")
         self.event_args = params.args()
 
-    def _adapter_events(self, j: int, n: int, rows: np.ndarray, mbs) -> np.ndarray:
-        """the events of the passing reads' adapters, from the matrix the detect call of slot j just read"""
-        ev = np.zeros(n, dtype=EVENT_DTYPE)
-        ev["n_bound"], ev["status"], ev["med"], ev["mad"] = -1, -1, np.nan, np.nan
+    def enable_fingerprints(self, params=None, templates=None):
+        """(extension) After every detect call, while the slot's float32 matrix is still resident, the event table and the
+        fingerprint of the adapter [adapter_start, adapter_end) of every passing read in one adp_event_levels call and, with
+        ``templates`` (fingerprint.Templates), their DTW distances to the templates in one adp_dtw_assign call on the fingerprints
+        the first call left on the device (adapted_amd/fingerprint.py); run() then hands on_rows a third and a fourth argument:
+        the EVENT_DTYPE array of enable_polya_length, or None without it, and an AdapterFingerprints.  With enable_polya_length
+        as well there is still one segmentation per detect call: both take the same event parameters.
+        params: fingerprint.FingerprintParams (None: its untuned defaults).  Not on the native int16 plan and not with the
+        start-peak primary."""
+        from .fingerprint import FingerprintParams, template_arrays
+
+        if self.native_i16:
+            raise ValueError("fingerprints need the float32 matrix on the device: not with int16 input read natively")
+        if self.primary not in ("llr", "cnn"):
+            raise ValueError("fingerprints go with the LLR and CNN primaries")
+        params = params or FingerprintParams()
+        params.check()
+        args = params.events.args()
+        other = getattr(self, "event_args", None)
+        if other is not None and bytes(other) != bytes(args):
+            raise ValueError("fingerprints and polya_length share one segmentation: give both the same event parameters")
+        self.fp_templates = template_arrays(templates) if templates is not None else None
+        self.fp_params, self.fp_args = params, args
+        self._fp_dev = None  # (fingerprints and counts of a slot's passing reads, on the device between the two calls)
+
+    def _passing_adapters(self, j: int, n: int, rows: np.ndarray, mbs):
+        """the passing reads of undropped minibatches of slot j -> (their indices, adapter starts, adapter ends)"""
         ok = rows["success"][:n] != 0
         if mbs is not None:  # (the rows of a dropped minibatch mean nothing)
             ok &= np.repeat(np.asarray(mbs) == lib.MB_OK, self.mb)[:n]
         idx = np.flatnonzero(ok)
+        col, present = rows["col"][idx], rows["present"][idx]
+        starts = np.where(present >> np.uint64(2) & np.uint64(1), col[:, 2], 0).astype(np.int64)
+        ends = np.where(present >> np.uint64(3) & np.uint64(1), col[:, 3], 0).astype(np.int64)
+        return idx, starts, ends
+
+    @staticmethod
+    def _no_events(n: int) -> np.ndarray:
+        ev = np.zeros(n, dtype=EVENT_DTYPE)
+        ev["n_bound"], ev["status"], ev["med"], ev["mad"] = -1, -1, np.nan, np.nan
+        return ev
+
+    def _adapter_events(self, j: int, n: int, rows: np.ndarray, mbs) -> np.ndarray:
+        """the events of the passing reads' adapters, from the matrix the detect call of slot j just read"""
+        ev = self._no_events(n)
+        idx, starts, ends = self._passing_adapters(j, n, rows, mbs)
         if idx.size:
-            col, present = rows["col"][idx], rows["present"][idx]
-            starts = np.where(present >> np.uint64(2) & np.uint64(1), col[:, 2], 0).astype(np.int64)
-            ends = np.where(present >> np.uint64(3) & np.uint64(1), col[:, 3], 0).astype(np.int64)
             lens = np.minimum(self.slots[j]["lens"][:n], self.m).astype(np.int32)
             _, info, stats = self.eng.segment_events(self._resident, lens, idx, starts, ends, self.event_args, cap=0, n=n, L=self.m)
             ev["n_bound"][idx], ev["status"][idx] = info[:, 0], info[:, 1]
             ev["med"][idx], ev["mad"][idx] = stats[:, 0], stats[:, 1]
         return ev
+
+    def _adapter_fingerprints(self, j: int, n: int, rows: np.ndarray, mbs):
+        """-> (the EVENT_DTYPE array of _adapter_events, or None without enable_polya_length; AdapterFingerprints): one
+        adp_event_levels call -- its info / stats are adp_segment_events' --, then adp_dtw_assign on what it left on the device"""
+        E, tm = int(self.fp_params.max_events), self.fp_templates
+        ev = self._no_events(n) if getattr(self, "event_args", None) is not None else None
+        fp = AdapterFingerprints(n, E, tm is not None)
+        idx, starts, ends = self._passing_adapters(j, n, rows, mbs)
+        if idx.size:
+            lens = np.minimum(self.slots[j]["lens"][:n], self.m).astype(np.int32)
+            if tm is not None and self._fp_dev is None:
+                self._fp_dev = (self.eng.dev_alloc(self.N * E * 8), self.eng.dev_alloc(self.N * 4))
+            dev = dict(fp_ptr=self._fp_dev[0], count_ptr=self._fp_dev[1]) if tm is not None else {}
+            r = self.eng.event_levels(self._resident, lens, idx, starts, ends, self.fp_args, E, n=n, L=self.m, **dev)
+            if tm is not None:
+                _, best, bestdist = self.eng.dtw_assign(self._fp_dev[0], self._fp_dev[1], tm[0], tm[1], int(self.fp_params.band),
+                                                        nq=idx.size, Eq=E, want_dist=False)
+                fp.best[idx], fp.bestdist[idx] = best, bestdist
+                r["fingerprints"], r["count"] = np.zeros((idx.size, E)), np.zeros(idx.size, dtype=np.int32)
+                self.eng.d2h(r["fingerprints"], self._fp_dev[0])
+                self.eng.d2h(r["count"], self._fp_dev[1])
+            for k in ("count", "status", "lengths", "levels", "fingerprints"):
+                getattr(fp, k)[idx] = r[k]
+            if ev is not None:
+                ev["n_bound"][idx], ev["status"][idx] = r["info"][:, 0], r["info"][:, 1]
+                ev["med"][idx], ev["mad"][idx] = r["stats"][:, 0], r["stats"][:, 1]
+        return ev, fp
 
     def _slot(self, j: int):
         if self.slots[j] is None:
@@ -167,6 +256,10 @@ class HostPipeline:
         if self.dsig16:
             self.eng.dev_free(self.dsig16)
             self.dsig16 = None
+        if getattr(self, "_fp_dev", None):
+            for ptr in self._fp_dev:
+                self.eng.dev_free(ptr)
+            self._fp_dev = None
         self.slots = []
         self.eng.close()
 
@@ -294,7 +387,11 @@ class HostPipeline:
                     j, n, ids = pending
                     rows, mbs = self._detect(j, n)
                     # (with enable_polya_length: a third item travels with the rows, sliced as they are)
-                    more = (self._adapter_events(j, n, rows, mbs),) if getattr(self, "event_args", None) is not None else ()
+                    # (with enable_fingerprints: the events, or None, and the fingerprints)
+                    if getattr(self, "fp_params", None) is not None:
+                        more = self._adapter_fingerprints(j, n, rows, mbs)
+                    else:
+                        more = (self._adapter_events(j, n, rows, mbs),) if getattr(self, "event_args", None) is not None else ()
                     if mbs is None or (mbs == lib.MB_OK).all():
                         done.put((ids, rows) + more)
                         total += n
@@ -303,7 +400,7 @@ class HostPipeline:
                             a, b = q * self.mb, min(n, (q + 1) * self.mb)
                             sub = ids[a:b] if hasattr(ids, "__getitem__") and not isinstance(ids, tuple) else ids
                             if st == lib.MB_OK:
-                                done.put((sub, rows[a:b]) + tuple(e[a:b] for e in more))
+                                done.put((sub, rows[a:b]) + tuple(None if e is None else e[a:b] for e in more))
                                 total += b - a
                             elif on_dropped:
                                 on_dropped(sub, int(st))

@@ -553,6 +553,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * a header of its own, with its prototype table in adapted_amd/lib.py, EVENT_PROTOTYPES. */
 #include "adapted_hip_events.h"
 
+/* Adapter event fingerprints and their comparison by dynamic time warping -- adp_event_levels and adp_dtw_assign, an extension --:
+ * a header of its own again, with its prototype table in adapted_amd/lib.py, FINGERPRINT_PROTOTYPES. */
+#include "adapted_hip_fingerprint.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
