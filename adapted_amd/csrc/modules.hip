@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation and the event fingerprints): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints and the adapter-front post-pass): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "startmods_api.h"
 #include "events_api.h"
 #include "fingerprint_api.h"
+#include "adapter_front.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -933,6 +934,95 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
     RCCHK(d2h(h, bestdist_out, dbd, nqs * 16));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
+}
+
+} // extern "C"
+
+// ---- the adapter's front boundary over the rows of a detect call (an extension; adapter_front.h)
+
+// what both forms check before anything is launched
+static int af_check(adp_handle *h, const void *sig, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args,
+                    const int32_t *info_out, const int64_t *shift_out, const int64_t *cand_out, const double *diff_out)
+{
+    if (!h || !sig || !rows || !args || !info_out || !shift_out || !cand_out || !diff_out || n_reads < 1 || m < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (args->window < 1) { g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID; }
+    if (args->min_obs_adapter < 0 || args->min_adapter_len < 0) { g_err = "min_obs_adapter and min_adapter_len must be >= 0"; return ADP_ERR_INVALID; }
+    if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "adp_adapter_front: not with ADP_LAYOUT_SINGLE_READ"; return ADP_ERR_UNSUPPORTED; }
+    return ADP_OK;
+}
+
+// a call's pieces of the workspace behind its staged signal: the rows (host rows only), the side outputs, the segments and their
+// statistics, and the detector's slots ([2, m] floats each, the series kernels' byte budget: mv_slots)
+struct AfBufs { adp_row *rows; int32_t *info; int64_t *shift, *cand, *cnt; double *diff, *stats; SsSeg *segs; float *scr; size_t slots; };
+static void af_pieces(Carve &w, AfBufs &b, int n_reads, int m, bool rows_dev)
+{
+    const size_t n = n_reads;
+    b.slots = mv_slots(n_reads, m, 4);
+    b.rows = w.take<adp_row>(n, !rows_dev);
+    b.info = w.take<int32_t>(n * 4); b.shift = w.take<int64_t>(n); b.cand = w.take<int64_t>(n); b.diff = w.take<double>(n);
+    b.segs = w.take<SsSeg>(n); b.stats = w.take<double>(n * 4); b.cnt = w.take<int64_t>(n);
+    b.scr = w.take<float>(b.slots * 2 * m);
+}
+
+// the three kernels over a resident matrix of either kind, and the results back
+template <class Sig>
+static int af_run(adp_handle *h, Sig sig, int n_reads, int m, adp_row *rows, const adp_adapter_front_args *args, int flags, const AfBufs &b,
+                  int32_t *info_out, int64_t *shift_out, int64_t *cand_out, double *diff_out)
+{
+    const size_t n = n_reads;
+    const bool rows_dev = (flags & ADP_OUT_DEVICE) != 0;
+    adp_row *drows = rows_dev ? rows : b.rows;
+    if (!rows_dev) RCCHK(h2d(h, drows, rows, n * sizeof(adp_row)));
+    { Scope s(h, "k_adapter_front");
+      hipLaunchKernelGGL(k_adapter_front<Sig>, dim3((unsigned)b.slots), dim3(64), 0, h->stream, sig, n_reads, m, drows, *args, b.scr, b.info, b.shift, b.cand, b.diff, b.segs); }
+    { Scope s(h, "k_seg_stats_sig");
+      hipLaunchKernelGGL(k_seg_stats_sig<Sig>, dim3(n_reads), dim3(SS_BLOCK), 0, h->stream, sig, n_reads, m, b.segs, n_reads, b.stats, b.cnt); }
+    { Scope s(h, "k_adapter_front_patch");
+      hipLaunchKernelGGL(k_adapter_front_patch, dim3((n_reads + 255) / 256), dim3(256), 0, h->stream, drows, n_reads, b.segs, b.stats); }
+    HIPCHK(hipGetLastError());
+    if (!rows_dev) RCCHK(d2h(h, rows, drows, n * sizeof(adp_row)));
+    RCCHK(d2h(h, info_out, b.info, n * 16));
+    RCCHK(d2h(h, shift_out, b.shift, n * 8));
+    RCCHK(d2h(h, cand_out, b.cand, n * 8));
+    RCCHK(d2h(h, diff_out, b.diff, n * 8));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+extern "C" {
+
+int adp_sizeof_adapter_front_args(void) { return (int)sizeof(adp_adapter_front_args); }
+
+int adp_adapter_front(adp_handle *h, const float *sig, const int32_t *full_len, int n_reads, int m, adp_row *rows,
+                      const adp_adapter_front_args *args, int flags, int32_t *info_out, int64_t *shift_out, int64_t *cand_out,
+                      double *diff_out)
+{
+    (void)full_len; // (the matrix is read as it lies)
+    RCCHK(af_check(h, sig, n_reads, m, rows, args, info_out, shift_out, cand_out, diff_out));
+    RCCHK(begin_call(h));
+    AfBufs b;
+    float *s_sig;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<float>((size_t)m * n_reads, !(flags & ADP_IN_DEVICE));
+        af_pieces(w, b, n_reads, m, (flags & ADP_OUT_DEVICE) != 0);
+    }));
+    const float *ds;
+    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)m * 4 * n_reads, &ds));
+    return af_run(h, SigF32{ds}, n_reads, m, rows, args, flags, b, info_out, shift_out, cand_out, diff_out);
+}
+
+int adp_adapter_front_i16(adp_handle *h, const int16_t *raw, const int32_t *full_len, const float *scale, const float *offset,
+                          int n_reads, int m, adp_row *rows, const adp_adapter_front_args *args, int flags, int32_t *info_out,
+                          int64_t *shift_out, int64_t *cand_out, double *diff_out)
+{
+    RCCHK(af_check(h, raw, n_reads, m, rows, args, info_out, shift_out, cand_out, diff_out));
+    if (!full_len || !scale || !offset) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!(flags & ADP_IN_DEVICE)) { g_err = "adp_adapter_front_i16 takes device pointers (ADP_IN_DEVICE)"; return ADP_ERR_INVALID; }
+    if (m % 4 != 0) { g_err = "adp_adapter_front_i16: m must be a multiple of 4"; return ADP_ERR_UNSUPPORTED; }
+    RCCHK(begin_call(h));
+    AfBufs b;
+    RCCHK(ws_carve(h, [&](Carve &w) { af_pieces(w, b, n_reads, m, (flags & ADP_OUT_DEVICE) != 0); }));
+    return af_run(h, SigI16{raw, scale, offset, full_len}, n_reads, m, rows, args, flags, b, info_out, shift_out, cand_out, diff_out);
 }
 
 } // extern "C"

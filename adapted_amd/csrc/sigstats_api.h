@@ -84,9 +84,10 @@ static __device__ __forceinline__ void ss_pick(const LDS uint32_t *hist, int kk,
 // `skipnan` of the keys that are not NaN (np.nanmedian's view); k0 < 0: the two middles of the keys counted, (cnt - 1) / 2 and
 // cnt / 2.  cnt: the keys counted; nan: a key was NaN.  With cnt == 0 the values are NaN.  Uniform call of the whole workgroup
 // (whole waves); every thread gets the results: each wave picks the bins from the workgroup's histograms by itself.
+// x: anything that gives x[i] as a T -- a pointer, or a Row of common.h (adapter_front.h: raw int16 samples calibrated on load).
 template <class T> struct SsPair { T v0, v1; int cnt; bool nan; };
-template <class T, class F>
-static __device__ SsPair<T> ss_select2(const T *__restrict__ x, int n, int k0, int k1, bool skipnan, F f, LDS SsLds *s)
+template <class T, class F, class X>
+static __device__ SsPair<T> ss_select2(const X x, int n, int k0, int k1, bool skipnan, F f, LDS SsLds *s)
 {
     typedef typename SsKey<T>::type K;
     constexpr int NB = (int)sizeof(K);
@@ -134,29 +135,29 @@ static __device__ SsPair<T> ss_select2(const T *__restrict__ x, int n, int k0, i
 
 // np.median of f(x[0, n)) -- np.nanmedian with `skipnan`: NaN when nothing is counted, or when a key is NaN and counted; the
 // mean (a + b) / 2 of the two middles of an even count
-template <class T, class F>
-static __device__ __forceinline__ T ss_median(const T *x, int n, bool skipnan, F f, LDS SsLds *s)
+template <class T, class F, class X>
+static __device__ __forceinline__ T ss_median(const X x, int n, bool skipnan, F f, LDS SsLds *s)
 {
-    const SsPair<T> p = ss_select2<T, F>(x, n, -1, -1, skipnan, f, s);
+    const SsPair<T> p = ss_select2<T, F, X>(x, n, -1, -1, skipnan, f, s);
     if (p.cnt == 0 || (p.nan && !skipnan)) return (T)__builtin_nan("");
     return (p.cnt & 1) ? p.v1 : (p.v0 + p.v1) / (T)2;
 }
 
 // median and MAD (the median of |x - median|) of x[0, n), n >= 0
-template <class T>
-static __device__ __forceinline__ void ss_med_mad(const T *x, int n, bool skipnan, LDS SsLds *s, T &med, T &mad)
+template <class T, class X>
+static __device__ __forceinline__ void ss_med_mad(const X x, int n, bool skipnan, LDS SsLds *s, T &med, T &mad)
 {
-    med = n > 0 ? ss_median<T, SsIdent<T>>(x, n, skipnan, SsIdent<T>(), s) : (T)__builtin_nan("");
+    med = n > 0 ? ss_median<T, SsIdent<T>, X>(x, n, skipnan, SsIdent<T>(), s) : (T)__builtin_nan("");
     // (a NaN median: every deviation is NaN, and so is their median)
-    mad = med != med ? med : ss_median<T, SsAbsDev<T>>(x, n, skipnan, SsAbsDev<T>{med}, s);
+    mad = med != med ? med : ss_median<T, SsAbsDev<T>, X>(x, n, skipnan, SsAbsDev<T>{med}, s);
 }
 
 // np.add.reduce(x[0, n)) and np.add.reduce((x - mu)^2) in numpy's order
-template <class T> static __device__ __forceinline__ T ss_sum(const T *x, int n, LDS NpSumLdsT<T> *ws)
+template <class T, class X> static __device__ __forceinline__ T ss_sum(const X x, int n, LDS NpSumLdsT<T> *ws)
 {
     return np_sum_wave(n, [&](long k) { return x[k]; }, ws);
 }
-template <class T> static __device__ __forceinline__ T ss_sum_sqdev(const T *x, int n, T mu, LDS NpSumLdsT<T> *ws)
+template <class T, class X> static __device__ __forceinline__ T ss_sum_sqdev(const X x, int n, T mu, LDS NpSumLdsT<T> *ws)
 {
     return np_sum_wave(n, [&](long k) { const T d = x[k] - mu; return d * d; }, ws);
 }
@@ -184,6 +185,21 @@ static __device__ __forceinline__ const T *ss_slice(const T *sig, const int32_t 
 // mean, std, median, MAD of each segment as the reference's calc_partition_stats computes them -> stats[seg, 4] (float64
 // carrying the value of the working type exactly) and count[seg], the number of samples of the clipped slice.  An empty slice
 // gives NaN x 4 (numpy's mean and median of nothing).  One workgroup per segment.
+// the four statistics of x[0, n) -> o[0..3], n -> *cnt: the whole workgroup, x through any accessor (ss_select2)
+template <class T, class X>
+static __device__ __forceinline__ void ss_stats4(const X x, int n, LDS NpSumLdsT<T> *ws, LDS SsLds *sl, double *o, int64_t *cnt)
+{
+    if (n == 0) {
+        if (threadIdx.x == 0) { o[0] = o[1] = o[2] = o[3] = __builtin_nan(""); *cnt = 0; }
+        return;
+    }
+    const T mean = ss_sum<T>(x, n, ws) / (T)n;
+    const T sd = ss_sqrt(ss_sum_sqdev<T>(x, n, mean, ws) / (T)n);
+    T med, mad;
+    ss_med_mad<T>(x, n, false, sl, med, mad);
+    if (threadIdx.x == 0) { o[0] = (double)mean; o[1] = (double)sd; o[2] = (double)med; o[3] = (double)mad; *cnt = n; }
+}
+
 template <class T>
 __global__ void __launch_bounds__(SS_BLOCK) k_seg_stats(const T *__restrict__ sig, const int32_t *__restrict__ len, int n_reads, int L,
                                                   const SsSeg *__restrict__ segs, int n_seg, double *__restrict__ stats,
@@ -196,16 +212,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_seg_stats(const T *__restrict__ si
     if (g >= n_seg) return;
     int n;
     const T *x = ss_slice(sig, len, n_reads, L, segs[g], n);
-    double *o = stats + (size_t)g * 4;
-    if (n == 0) {
-        if (threadIdx.x == 0) { o[0] = o[1] = o[2] = o[3] = __builtin_nan(""); count[g] = 0; }
-        return;
-    }
-    const T mean = ss_sum(x, n, ws) / (T)n;
-    const T sd = ss_sqrt(ss_sum_sqdev(x, n, mean, ws) / (T)n);
-    T med, mad;
-    ss_med_mad(x, n, false, sl, med, mad);
-    if (threadIdx.x == 0) { o[0] = (double)mean; o[1] = (double)sd; o[2] = (double)med; o[3] = (double)mad; count[g] = n; }
+    ss_stats4<T>(x, n, ws, sl, stats + (size_t)g * 4, count + g);
 }
 
 // ---------------------------------------------------------------- median and MAD of rows (normalize.py:15-22)
@@ -219,7 +226,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_row_med_mad(const T *__restrict__ 
     const int r = blockIdx.x;
     if (r >= n_reads) return;
     T med, mad;
-    ss_med_mad(sig + (size_t)r * L, (int)len[r], skipnan != 0, sl, med, mad);
+    ss_med_mad<T>(sig + (size_t)r * L, (int)len[r], skipnan != 0, sl, med, mad);
     if (threadIdx.x == 0) { medmad[2 * r] = (double)med; medmad[2 * r + 1] = (double)mad; }
 }
 
@@ -381,7 +388,7 @@ static __device__ __forceinline__ double ss_percentile(const T *x, int n, double
     int lo, hi;
     double g;
     ws_pct_ranks(n, q100, lo, hi, g);
-    const SsPair<T> p = ss_select2<T, SsIdent<T>>(x, n, lo, hi, false, SsIdent<T>(), s);
+    const SsPair<T> p = ss_select2<T, SsIdent<T>, const T *>(x, n, lo, hi, false, SsIdent<T>(), s);
     nan = p.nan;
     const T a = p.v0, b = p.v1, diff = b - a;
     double r = (double)a + (double)diff * g;
@@ -411,7 +418,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_real_range(const T *__restrict__ s
         if (threadIdx.x == 0) { oi[0] = 0; oi[1] = 0; ov[0] = ov[1] = ov[2] = 0.0; }
         return;
     }
-    const T m0 = ss_sum(x, w, ws) / (T)w, m1 = ss_sum(x + (n - w), w, ws) / (T)w;
+    const T m0 = ss_sum<T>(x, w, ws) / (T)w, m1 = ss_sum<T>(x + (n - w), w, ws) / (T)w;
     int ok = 0, stage = 1;
     double lr = 0.0;
     if (ss_in_range((double)m0, a.mean_start_range) && ss_in_range((double)m1, a.mean_end_range)) {

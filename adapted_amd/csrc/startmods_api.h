@@ -148,6 +148,132 @@ template <class T> struct AsLds {
     T sum[ASC_CHUNK];           // bsum of the chunk
 };
 
+// The detector for ONE read, by one wave (a uniform call): x[i], i in [0, N + min_obs_adapter), through any accessor that gives T
+// -- a pointer, or a Row of common.h (adapter_front.h: the slice of a resident row, float32 or raw int16) --, N = len -
+// min_obs_adapter.  wmean / wsum: the wave's slot of the workspace, N - w elements each.  What comes back is what k_adapter_start
+// writes: info (status, the exception's window and slice size, accepted), res (adapter_start), cand, dc (difference[cand]).
+struct AsOut {
+    int32_t status, window, size, accepted;
+    long long res, cand;
+    double dc;
+    // info[k] (a chain of selects: an array indexed by the lane would live in scratch memory)
+    __device__ __forceinline__ int32_t info(int k) const { return k == 0 ? status : k == 1 ? window : k == 2 ? size : accepted; }
+};
+template <class T, class X>
+static __device__ __forceinline__ AsOut as_detect(const X x, int N, const adp_adapter_start_args &p, T *wmean, T *wsum, LDS AsLds<T> *b)
+{
+    const int ln = lane_id();
+    const int w = p.window, half = p.window / 2, Ls = N - w;
+    const T level = (T)p.min_pA_current; // (numpy compares an array with a Python float in the array's type)
+    AsOut o = {AS_ST_OK, 0, 0, 0, 0, -1, 0.0};
+    long long cand = -1;
+    double dc = 0.0;
+    if (N < w) { o.status = AS_ST_VALUE; o.window = w; o.size = N > 0 ? N : 0; }
+    else if (Ls > 0) {
+        // ---- pass 1: p = N - 1 ... 0 is step k = N - 1 - p of move_mean(reversed x); steps k >= w are outputs, at i = p
+        BnMean<T> sm = {0, 0, 0};
+        T bs = (T)-0.0; // (-0 + y == y for every y: the first sum is the first mean itself, as cumsum's is)
+        for (int hi = N; hi > 0;) {
+            const int lo = ((hi - 1) / ASC_CHUNK) * ASC_CHUNK;
+            const int e = hi + ASC_HIST < N ? hi + ASC_HIST : N;
+            ws_sync();
+            bool bad = false;
+            for (int k = ln; k < e - lo; k += 64) { const T v = x[lo + k]; b->in[k] = v; bad |= v != v; }
+            // no NaN in the chunk's windows, all of them full and sliding (hi <= Ls), every old sample staged
+            const bool fast = !__any(bad) && hi <= Ls && w <= ASC_HIST;
+            ws_sync();
+            if (ln == 0) {
+                int q = hi - 1;
+                if (fast) {
+                    for (; q - 7 >= lo; q -= 8) {
+                        T an[8], om[8], rm[8], rs[8];
+#pragma unroll
+                        for (int j = 0; j < 8; j++) { an[j] = b->in[q - j - lo]; om[j] = b->in[q - j + w - lo]; }
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            sm.asum += an[j] - om[j];
+                            rm[j] = sm.asum * sm.inv;
+                            bs += rm[j];
+                            rs[j] = bs;
+                        }
+#pragma unroll
+                        for (int j = 0; j < 8; j++) { b->mean[q - j - lo] = rm[j]; b->sum[q - j - lo] = rs[j]; }
+                    }
+                }
+                for (; q >= lo; q--) {
+                    const int k = N - 1 - q;
+                    const T aold = k < w ? (T)0 : (q + w < e ? b->in[q + w - lo] : x[q + w]);
+                    const T y = bn_mean_step(sm, k, w, b->in[q - lo], aold);
+                    if (k >= w) { bs += y; b->mean[q - lo] = y; b->sum[q - lo] = bs; }
+                }
+            }
+            ws_sync();
+            const int top = hi < Ls ? hi : Ls;
+            for (int k = lo + ln; k < top; k += 64) { wmean[k] = b->mean[k - lo]; wsum[k] = b->sum[k - lo]; }
+            hi = lo;
+        }
+        __threadfence_block();
+        ws_sync();
+        // ---- pass 2: fsum, the differences, their maximum and the first minimum over i >= w
+        T fs = (T)-0.0;
+        double lmax = 0.0, lmin = 0.0;
+        int imin = -1;
+        bool hmax = false, anynan = false;
+        for (int c0 = 0; c0 < Ls; c0 += ASC_CHUNK) {
+            const int c1 = c0 + ASC_CHUNK < Ls ? c0 + ASC_CHUNK : Ls, nc = c1 - c0;
+            ws_sync();
+            for (int k = ln; k < nc; k += 64) { b->mean[k] = wmean[c0 + k]; b->sum[k] = wsum[c0 + k]; }
+            ws_sync();
+            if (ln == 0) {
+                int q = 0;
+                for (; q + 8 <= nc; q += 8) {
+                    T v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) v[j] = b->mean[q + j];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) { fs += v[j]; v[j] = fs; }
+#pragma unroll
+                    for (int j = 0; j < 8; j++) b->mean[q + j] = v[j];
+                }
+                for (; q < nc; q++) { fs += b->mean[q]; b->mean[q] = fs; }
+            }
+            ws_sync();
+            for (int k = ln; k < nc; k += 64) {
+                const int i = c0 + k;
+                const double d = (double)b->sum[k] / (double)(Ls - i) - (double)b->mean[k] / (double)(i + 1);
+                if (d != d) anynan = true;
+                else {
+                    if (!hmax || d > lmax) { lmax = d; hmax = true; }
+                    if (i >= w && (imin < 0 || d < lmin)) { lmin = d; imin = i; }
+                }
+            }
+        }
+        anynan = __any(anynan);
+        // the wave's maximum, and its minimum with the first index that holds it (lanes without an entry stand back)
+        double M = lmax, m2 = lmin;
+        bool hM = hmax, hm = imin >= 0;
+        for (int o = 32; o > 0; o >>= 1) {
+            const double oM = __shfl_xor(M, o), om = __shfl_xor(m2, o);
+            const bool ohM = __shfl_xor((int)hM, o) != 0, ohm = __shfl_xor((int)hm, o) != 0;
+            if (ohM && (!hM || oM > M)) { M = oM; hM = true; }
+            if (ohm && (!hm || om < m2)) { m2 = om; hm = true; }
+        }
+        const int i2 = wave_min((imin >= 0 && lmin == m2) ? imin : 0x7fffffff);
+        if (anynan) { cand = 0; dc = __builtin_nan(""); }
+        else if (hm && m2 < M) { cand = i2; dc = m2; }
+        else { cand = 0; dc = M; }
+        // ---- the accept: the shift, and a mean above the level within half a window of the candidate
+        if (dc < -p.min_shift) {
+            const int s0 = cand - half > 0 ? (int)cand - half : 0, s1 = cand + half < Ls ? (int)cand + half : Ls;
+            bool above = false;
+            for (int k = s0 + ln; k < s1; k += 64) above |= wmean[k] > level;
+            if (__any(above)) { o.accepted = 1; o.res = cand + half; }
+        }
+    }
+    o.cand = cand; o.dc = dc;
+    return o;
+}
+
 // info int32 [n, 4]: status, the exception's window and slice size, accepted.  out int64 [n]: adapter_start.  cand int64 [n]:
 // argmin (-1: difference is empty, or the exception).  diff float64 [n]: difference[cand].  ws: [gridDim.x, 2, L] of T.
 template <class T>
@@ -158,118 +284,10 @@ __global__ void __launch_bounds__(64) k_adapter_start(const T *__restrict__ sig,
     __shared__ __attribute__((aligned(16))) AsLds<T> b_;
     LDS AsLds<T> *b = (LDS AsLds<T> *)&b_;
     const int ln = lane_id();
-    const int w = p.window, half = p.window / 2;
     T *wmean = ws + (size_t)blockIdx.x * 2 * L, *wsum = wmean + L;
-    const T level = (T)p.min_pA_current; // (numpy compares an array with a Python float in the array's type)
     for (int r = blockIdx.x; r < n_reads; r += gridDim.x) {
-        const T *x = sig + (size_t)r * L;
-        const int N = len[r] - p.min_obs_adapter, Ls = N - w;
-        int32_t info[4] = {AS_ST_OK, 0, 0, 0};
-        long long res = 0, cand = -1;
-        double dc = 0.0;
-        if (N < w) { info[0] = AS_ST_VALUE; info[1] = w; info[2] = N > 0 ? N : 0; }
-        else if (Ls > 0) {
-            // ---- pass 1: p = N - 1 ... 0 is step k = N - 1 - p of move_mean(reversed x); steps k >= w are outputs, at i = p
-            BnMean<T> sm = {0, 0, 0};
-            T bs = (T)-0.0; // (-0 + y == y for every y: the first sum is the first mean itself, as cumsum's is)
-            for (int hi = N; hi > 0;) {
-                const int lo = ((hi - 1) / ASC_CHUNK) * ASC_CHUNK;
-                const int e = hi + ASC_HIST < N ? hi + ASC_HIST : N;
-                ws_sync();
-                bool bad = false;
-                for (int k = ln; k < e - lo; k += 64) { const T v = x[lo + k]; b->in[k] = v; bad |= v != v; }
-                // no NaN in the chunk's windows, all of them full and sliding (hi <= Ls), every old sample staged
-                const bool fast = !__any(bad) && hi <= Ls && w <= ASC_HIST;
-                ws_sync();
-                if (ln == 0) {
-                    int q = hi - 1;
-                    if (fast) {
-                        for (; q - 7 >= lo; q -= 8) {
-                            T an[8], om[8], rm[8], rs[8];
-#pragma unroll
-                            for (int j = 0; j < 8; j++) { an[j] = b->in[q - j - lo]; om[j] = b->in[q - j + w - lo]; }
-#pragma unroll
-                            for (int j = 0; j < 8; j++) {
-                                sm.asum += an[j] - om[j];
-                                rm[j] = sm.asum * sm.inv;
-                                bs += rm[j];
-                                rs[j] = bs;
-                            }
-#pragma unroll
-                            for (int j = 0; j < 8; j++) { b->mean[q - j - lo] = rm[j]; b->sum[q - j - lo] = rs[j]; }
-                        }
-                    }
-                    for (; q >= lo; q--) {
-                        const int k = N - 1 - q;
-                        const T aold = k < w ? (T)0 : (q + w < e ? b->in[q + w - lo] : x[q + w]);
-                        const T y = bn_mean_step(sm, k, w, b->in[q - lo], aold);
-                        if (k >= w) { bs += y; b->mean[q - lo] = y; b->sum[q - lo] = bs; }
-                    }
-                }
-                ws_sync();
-                const int top = hi < Ls ? hi : Ls;
-                for (int k = lo + ln; k < top; k += 64) { wmean[k] = b->mean[k - lo]; wsum[k] = b->sum[k - lo]; }
-                hi = lo;
-            }
-            __threadfence_block();
-            ws_sync();
-            // ---- pass 2: fsum, the differences, their maximum and the first minimum over i >= w
-            T fs = (T)-0.0;
-            double lmax = 0.0, lmin = 0.0;
-            int imin = -1;
-            bool hmax = false, anynan = false;
-            for (int c0 = 0; c0 < Ls; c0 += ASC_CHUNK) {
-                const int c1 = c0 + ASC_CHUNK < Ls ? c0 + ASC_CHUNK : Ls, nc = c1 - c0;
-                ws_sync();
-                for (int k = ln; k < nc; k += 64) { b->mean[k] = wmean[c0 + k]; b->sum[k] = wsum[c0 + k]; }
-                ws_sync();
-                if (ln == 0) {
-                    int q = 0;
-                    for (; q + 8 <= nc; q += 8) {
-                        T v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) v[j] = b->mean[q + j];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) { fs += v[j]; v[j] = fs; }
-#pragma unroll
-                        for (int j = 0; j < 8; j++) b->mean[q + j] = v[j];
-                    }
-                    for (; q < nc; q++) { fs += b->mean[q]; b->mean[q] = fs; }
-                }
-                ws_sync();
-                for (int k = ln; k < nc; k += 64) {
-                    const int i = c0 + k;
-                    const double d = (double)b->sum[k] / (double)(Ls - i) - (double)b->mean[k] / (double)(i + 1);
-                    if (d != d) anynan = true;
-                    else {
-                        if (!hmax || d > lmax) { lmax = d; hmax = true; }
-                        if (i >= w && (imin < 0 || d < lmin)) { lmin = d; imin = i; }
-                    }
-                }
-            }
-            anynan = __any(anynan);
-            // the wave's maximum, and its minimum with the first index that holds it (lanes without an entry stand back)
-            double M = lmax, m2 = lmin;
-            bool hM = hmax, hm = imin >= 0;
-            for (int o = 32; o > 0; o >>= 1) {
-                const double oM = __shfl_xor(M, o), om = __shfl_xor(m2, o);
-                const bool ohM = __shfl_xor((int)hM, o) != 0, ohm = __shfl_xor((int)hm, o) != 0;
-                if (ohM && (!hM || oM > M)) { M = oM; hM = true; }
-                if (ohm && (!hm || om < m2)) { m2 = om; hm = true; }
-            }
-            const int i2 = wave_min((imin >= 0 && lmin == m2) ? imin : 0x7fffffff);
-            if (anynan) { cand = 0; dc = __builtin_nan(""); }
-            else if (hm && m2 < M) { cand = i2; dc = m2; }
-            else { cand = 0; dc = M; }
-            // ---- the accept: the shift, and a mean above the level within half a window of the candidate
-            if (dc < -p.min_shift) {
-                const int s0 = cand - half > 0 ? (int)cand - half : 0, s1 = cand + half < Ls ? (int)cand + half : Ls;
-                bool above = false;
-                for (int k = s0 + ln; k < s1; k += 64) above |= wmean[k] > level;
-                if (__any(above)) { info[3] = 1; res = cand + half; }
-            }
-        }
-        if (ln < 4) info_out[(size_t)r * 4 + ln] = info[ln];
-        if (ln == 0) { out[r] = res; cand_out[r] = cand; diff_out[r] = dc; }
+        const AsOut o = as_detect<T>(sig + (size_t)r * L, len[r] - p.min_obs_adapter, p, wmean, wsum, b);
+        if (ln < 4) info_out[(size_t)r * 4 + ln] = o.info(ln);
+        if (ln == 0) { out[r] = o.res; cand_out[r] = o.cand; diff_out[r] = o.dc; }
     }
 }

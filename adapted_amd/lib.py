@@ -31,6 +31,7 @@ ADP_POLYA_TRUNCATED = 1 << 20  # adp_validate_candidates: Boundaries.polya_trunc
 ROW_FROM_SECOND_LLR = 1  # bits of row["reserved_"]
 ROW_POLYA_TRUNCATED = 2  # the poly(A) runs into the end of the preloaded window
 ROW_TRUNC_LOOKED = 4  # the call looked for that (every row of a call made with ADP_FLAG_TRUNCATED)
+ROW_ADAPTER_FRONT = 8  # adp_adapter_front moved adapter_start: adapter_start / _len / _mean / _std / _med / _mad are the trimmed adapter's
 ADP_ERR_UNSUPPORTED = -4
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
@@ -266,7 +267,8 @@ def load():
     assert_one_runtime()
     try:
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
-                            + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())):
+                            + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
+                            + list(ADAPTER_FRONT_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -278,7 +280,8 @@ def load():
             or lib.adp_sizeof_real_range_args() != C.sizeof(AdpRealRangeArgs)
             or lib.adp_sizeof_start_peak_args() != C.sizeof(AdpStartPeakArgs)
             or lib.adp_sizeof_adapter_start_args() != C.sizeof(AdpAdapterStartArgs)
-            or lib.adp_sizeof_event_args() != C.sizeof(AdpEventArgs)):
+            or lib.adp_sizeof_event_args() != C.sizeof(AdpEventArgs)
+            or lib.adp_sizeof_adapter_front_args() != C.sizeof(AdpAdapterFrontArgs)):
         raise HipLibraryError("ABI mismatch between adapted_amd/lib.py and libadapted_hip.so")
     _LIB = lib
     return lib
@@ -327,6 +330,12 @@ class AdpStartPeakArgs(C.Structure):
 class AdpAdapterStartArgs(C.Structure):
     """struct adp_adapter_start_args (include/adapted_hip.h): MMAdapterStartConfig's parameters"""
     _fields_ = [(k, C.c_double) for k in ("min_shift", "min_pA_current")] + [(k, C.c_int32) for k in ("window", "min_obs_adapter")]
+
+
+class AdpAdapterFrontArgs(C.Structure):
+    """struct adp_adapter_front_args (include/adapted_hip_adapter_front.h): adp_adapter_start_args, then the least adapter a patched
+    row may be left with"""
+    _fields_ = AdpAdapterStartArgs._fields_ + [(k, C.c_int32) for k in ("min_adapter_len", "pad")]
 
 
 class AdpEventArgs(C.Structure):
@@ -472,12 +481,22 @@ FINGERPRINT_PROTOTYPES = {
     "adp_dtw_assign": "int: adp_handle* double* int32* int int double* int32* int int int int double* int32* double*",
 }
 
+# include/adapted_hip_adapter_front.h (the header adapted_hip.h includes for the adapter-front post-pass over the rows of a detect
+# call, an extension); tests/test_adapter_front_cpu.py holds this table against its header
+ADAPTER_FRONT_PROTOTYPES = {
+    "adp_sizeof_adapter_front_args": "int:",
+    "adp_adapter_front": "int: adp_handle* float* int32* int int adp_row* adp_adapter_front_args* int int32* int64* int64* double*",
+    "adp_adapter_front_i16": "int: adp_handle* int16* int32* float* float* int int adp_row* adp_adapter_front_args* int int32* int64* "
+                             "int64* double*",
+}
+
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
 _RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
 _SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
 _POINTEES = {"adp_cfg": AdpCfg, "adp_trace_args": AdpTraceArgs, "adp_peak_args": AdpPeakArgs, "adp_spike_args": AdpSpikeArgs,
             "adp_mvs_args": AdpMvsArgs, "adp_real_range_args": AdpRealRangeArgs, "adp_start_peak_args": AdpStartPeakArgs,
-            "adp_adapter_start_args": AdpAdapterStartArgs, "adp_event_args": AdpEventArgs, "adp_handle*": _VoidP, "void*": _VoidP,
+            "adp_adapter_start_args": AdpAdapterStartArgs, "adp_event_args": AdpEventArgs,
+            "adp_adapter_front_args": AdpAdapterFrontArgs, "adp_handle*": _VoidP, "void*": _VoidP,
             "char*": C.c_char_p}
 _ELEMENTS = {"float": np.float32, "double": np.float64, "int16": np.int16, "int32": np.int32, "int64": np.int64, "uint32": np.uint32,
              "uint64": np.uint64, "void": None, "adp_row": ROW_DTYPE, "adp_seg": SEG_DTYPE}
@@ -1131,6 +1150,35 @@ class Engine:
         self._check(self.lib.adp_adapter_start(self._h, sig, self._per_read(lens, n, "lens"), n, L, C.byref(args), flags, info, out,
                                                cand, diff))
         return info, out, cand, diff
+
+    def _adapter_front(self, fn, head, rows, args, n, m):
+        """adp_adapter_front / adp_adapter_front_i16 (fn) behind the batch's leading arguments (head); rows: a host ROW_DTYPE array
+        [n], patched in place, or a device pointer (ADP_OUT_DEVICE) -> (info int32 [n, 4], shift, cand int64 [n], diff float64 [n])"""
+        flags = ADP_IN_DEVICE if isinstance(head[0], int) else 0  # (the signals: a device pointer, or a host array)
+        if isinstance(rows, int):
+            flags |= ADP_OUT_DEVICE
+        elif not (isinstance(rows, np.ndarray) and rows.dtype == ROW_DTYPE and rows.flags.c_contiguous and rows.flags.writeable
+                  and rows.shape == (n,)):
+            raise ValueError("rows: a writable C-contiguous ROW_DTYPE array with one row per read, or a device pointer")
+        info = np.zeros((n, 4), dtype=np.int32)
+        shift, cand, diff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
+        self._check(fn(self._h, *head, n, int(m), rows, C.byref(args), flags, info, shift, cand, diff))
+        return info, shift, cand, diff
+
+    def adapter_front(self, sig, full_lens, rows, args: "AdpAdapterFrontArgs", n: Optional[int] = None, m: Optional[int] = None):
+        """adp_adapter_front: the adapter-front post-pass over the rows of a detect call on ``sig``, the float32 [n, m] minibatch
+        that call took (a host array, or a device pointer with ``n``; ``m``: the engine's unless given).  full_lens is not read
+        (None will do).  rows: see _adapter_front -> (info, shift, cand, diff)"""
+        sig, _, n, m = self._rows_in(sig, n, self.m if m is None else m, (np.float32,), what="signals")
+        return self._adapter_front(self.lib.adp_adapter_front, (sig, None), rows, args, n, m)
+
+    def adapter_front_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, rows, args: "AdpAdapterFrontArgs", n: int,
+                          m: Optional[int] = None):
+        """adp_adapter_front_i16: the same over RAW int16 samples resident on the device with their per-read calibration, as
+        detect_llr_rows_i16 takes them (device pointers only; m a multiple of 4)"""
+        _check_runtime_once_torch_is_here()
+        head = (int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev))
+        return self._adapter_front(self.lib.adp_adapter_front_i16, head, rows, args, int(n), self.m if m is None else int(m))
 
     def segment_events(self, sig, lens, rows, starts, ends, args: "AdpEventArgs", cap: int = 0, n: Optional[int] = None,
                        L: Optional[int] = None, f64: bool = False):

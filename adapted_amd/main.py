@@ -76,6 +76,14 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("--barcode_templates", type=str, default=None, metavar="FILE.npz",
                    help="(extension, with --fingerprints) templates (adapted_amd.fingerprint.save_templates): every fingerprint's DTW "
                         "distance to each and the nearest two, into fingerprints/barcodes_<k>.csv")
+    d.add_argument("--adapter_front", action="store_true",
+                   help="(extension) trim the front of every passing read's adapter with the reference's moving-mean start detector, on "
+                        "the GPU, after validation: adapter_start, adapter_len and the adapter_mean / std / med / mad columns describe the "
+                        "trimmed adapter, which --polya_length and --fingerprints then use (validation is not repeated; untuned, nothing "
+                        "validated on real data).  LLR and CNN primaries")
+    d.add_argument("--adapter_front_params", type=str, default=None, metavar="WINDOW,MIN_OBS_ADAPTER,MIN_SHIFT,MIN_PA",
+                   help="(extension, with --adapter_front) the detector's parameters (default 100,2500,20,90: the reference's "
+                        "MMAdapterStartConfig, untuned for RNA004)")
     d.add_argument("--dtw_band", type=int, default=None, metavar="R", help="(extension, with --barcode_templates) the DTW's band (default 0: none)")
     return p
 
@@ -245,6 +253,27 @@ def _check_flag_truncated(args):
             raise SystemExit("--flag_truncated does not go with this configuration: %s." % why)
 
 
+def _check_adapter_front(args):
+    """--adapter_front and what it does not go with: said before a GPU is touched.  -> its AdapterFrontParams (min_adapter_len left
+    to run_detect, which knows the configuration), or None"""
+    text = getattr(args, "adapter_front_params", None)
+    if not getattr(args, "adapter_front", False):
+        if text:
+            raise SystemExit("--adapter_front_params goes with --adapter_front.")
+        return None
+    from .adapter_front import AdapterFrontParams
+
+    try:
+        params = AdapterFrontParams.parse(text) if text else AdapterFrontParams()
+    except ValueError as e:
+        raise SystemExit("--adapter_front_params: %s." % e)
+    if args.config or args.chemistry:
+        primary = _load_spc(args).primary_method
+        if primary not in ("llr", "cnn"):
+            raise SystemExit("--adapter_front goes with the LLR and CNN primaries; this configuration's primary is %s." % primary)
+    return params
+
+
 def _check_fingerprints(args):
     """--fingerprints and what it does not go with: said before a GPU is touched.  -> the templates of --barcode_templates, or None"""
     E = getattr(args, "fingerprints", None)
@@ -354,9 +383,11 @@ def list_truncated(directory: str) -> int:
 
 
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, fingerprints=None, polya_length=None,
-               adapter_nt=None, event_params=None):
-    """fingerprints: None, or (E, templates or None, band) (--fingerprints: fingerprints/fingerprints_<k>.npz and, with templates,
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, adapter_front=None,
+               fingerprints=None, polya_length=None, adapter_nt=None, event_params=None):
+    """adapter_front: None, or an adapter_front.AdapterFrontParams (--adapter_front: the adapter's front trimmed on the final rows of
+    every detect call, ahead of the two below; its min_adapter_len is set here to core.min_obs_adapter);
+    fingerprints: None, or (E, templates or None, band) (--fingerprints: fingerprints/fingerprints_<k>.npz and, with templates,
     fingerprints/barcodes_<k>.csv beside boundaries/; the events' parameters are event_params);
     polya_length: None, "events" or "adapter" (--polya_length: polya_length/polya_length_<k>.csv beside boundaries/);
     adapter_nt: the adapter's bases for "adapter"; event_params: "WINDOW,MIN_DISTANCE,THRESHOLD" or None"""
@@ -392,6 +423,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
                         model=model, int16_input="native" if int16_ingest else False, group=GROUP, ragged=True, second_opinion=second_opinion,
                         flag_truncated=flag_truncated)
+    if adapter_front is not None:
+        import dataclasses
+
+        pipe.enable_adapter_front(dataclasses.replace(adapter_front, min_adapter_len=int(spc.core.min_obs_adapter)))
     if polya_length:
         from .polya_length import EventParams
 
@@ -404,6 +439,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
                                                    int(fingerprints[2] or 0)), fingerprints[1])
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
+    n_front = [0]  # rows whose adapter_start the adapter-front pass moved (reserved_ bit 3)
     sharder = GroupSharder(ws, rank, m) if multi else None
     ordinals: List[int] = []  # stream index of the first read of every group this rank yields
 
@@ -426,6 +462,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
         else:
             n_second[0] += int(((rows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             n_trunc[0] += int(((rows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
+            n_front[0] += int(((rows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
             res = lib.rows_to_results(rows, primary, consume=True)
             out = [ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                    for rid, r in zip(tagged[:, 0], res)]
@@ -454,6 +491,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             order = np.argsort(np.array([x for part in lists for x in part[1]], dtype=np.int64), kind="stable")
             n_second[0] += int(((allrows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             n_trunc[0] += int(((allrows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
+            n_front[0] += int(((allrows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
             res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
             writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for i, r in zip(order, res)])
@@ -468,6 +506,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             logging.info("Second opinion (%s): %d of the passing reads", second_opinion, n_second[0])
         if flag_truncated:
             logging.info("Truncated poly(A) (polya_truncated): %d of the passing reads", n_trunc[0])
+        if adapter_front is not None:
+            logging.info("Adapter front (adapter_start moved): %d of the passing reads", n_front[0])
     if multi:
         dist.barrier()
         logging.info("process group: backend %s, %d rank(s); HIP runtimes mapped: %s", dist.get_backend(), ws, ", ".join(lib.hip_runtimes()))
@@ -492,6 +532,7 @@ def main(argv=None):
         _check_second_opinion(args)
         _check_flag_truncated(args)
         _check_polya_length(args)
+        front = _check_adapter_front(args)
         templates = _check_fingerprints(args)
     else:
         args.output = args.output or os.getcwd()
@@ -499,6 +540,7 @@ def main(argv=None):
         _check_second_opinion(args)
         _check_flag_truncated(args)
         _check_polya_length(args)
+        front = _check_adapter_front(args)
         templates = _check_fingerprints(args)
         dist = _init_dist(getattr(args, "device", None))
         if dist is not None:  # one run directory for all ranks: rank 0's name
@@ -537,7 +579,7 @@ def main(argv=None):
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
                int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
-               flag_truncated=getattr(args, "flag_truncated", False),
+               flag_truncated=getattr(args, "flag_truncated", False), adapter_front=front,
                fingerprints=(args.fingerprints, templates, getattr(args, "dtw_band", None)) if getattr(args, "fingerprints", None) is not None else None,
                polya_length=getattr(args, "polya_length", None),
                adapter_nt=getattr(args, "adapter_nt", None), event_params=getattr(args, "event_params", None))

@@ -169,6 +169,34 @@ class HostPipeline:
         self.fp_params, self.fp_args = params, args
         self._fp_dev = None  # (fingerprints and counts of a slot's passing reads, on the device between the two calls)
 
+    def enable_adapter_front(self, params=None):
+        """(extension) After every detect call, while the slot's signal is still resident, trim the front of every passing read's
+        adapter with the moving-mean start detector in one adp_adapter_front call on the call's rows (adapted_amd/adapter_front.py):
+        a patched row carries the new adapter_start, adapter_len and adapter statistics and reserved_ bit 3; validation is not
+        repeated.  It runs before the event segmentation of enable_polya_length / enable_fingerprints, which read the row's
+        adapter_start and so segment the trimmed adapter.  Every input plan: float32 padded or packed, int16 calibrated on the
+        device, int16 read natively (adp_adapter_front_i16).  params: adapter_front.AdapterFrontParams (None: the reference's
+        defaults, untuned for RNA004).  Not with the start-peak primary."""
+        from .adapter_front import AdapterFrontParams
+
+        if self.primary not in ("llr", "cnn"):
+            raise ValueError("adapter_front goes with the LLR and CNN primaries")
+        params = params or AdapterFrontParams()
+        params.check()
+        self.front_args = params.args()
+        self.front_patched = 0  # rows patched so far
+
+    def _adapter_front(self, j: int, n: int, rows: np.ndarray):
+        """the adapter-front pass over the rows of slot j's detect call, on the signal that call just read; rows are patched in
+        place (rows of a dropped minibatch have success 0: they are not looked at)"""
+        if self.native_i16:
+            raw, dlen, scale, offset = self._resident_i16
+            info = self.eng.adapter_front_i16(raw, dlen, scale, offset, rows, self.front_args, n=n, m=self.m)[0]
+        else:
+            info = self.eng.adapter_front(self._resident, None, rows, self.front_args, n=n, m=self.m)[0]
+        self.front_patched += int(info[:, 3].sum())
+        return rows
+
     def _passing_adapters(self, j: int, n: int, rows: np.ndarray, mbs):
         """the passing reads of undropped minibatches of slot j -> (their indices, adapter starts, adapter ends)"""
         ok = rows["success"][:n] != 0
@@ -287,6 +315,7 @@ class HostPipeline:
             if self.ragged:
                 self.eng.expand_ragged_i16(dsig, s["do"], dlen, n, self.dsig16)
                 dsig = self.dsig16
+            self._resident_i16 = (dsig, dlen, s["dcal"], s["dcal"] + self.N * 4)  # the raw matrix this call reads, and its calibration
             if self.primary == "cnn":
                 from .detect import cnn as _cnn
 
@@ -386,6 +415,8 @@ class HostPipeline:
                 if pending is not None:
                     j, n, ids = pending
                     rows, mbs = self._detect(j, n)
+                    if getattr(self, "front_args", None) is not None:  # (with enable_adapter_front: ahead of the event segmentation)
+                        rows = self._adapter_front(j, n, rows)
                     # (with enable_polya_length: a third item travels with the rows, sliced as they are)
                     # (with enable_fingerprints: the events, or None, and the fingerprints)
                     if getattr(self, "fp_params", None) is not None:

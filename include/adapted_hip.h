@@ -162,11 +162,14 @@ typedef struct adp_row {
                                   (ADP_CNN_SECOND_LLR): its primary columns are the LLR's.  bit 1: the poly(A) runs into the end of the
                                   preloaded window (ADP_FLAG_TRUNCATED): polya_end is the window's end, the RNA partition all None.
                                   bit 2: the call looked for that (set in EVERY row of a call made with ADP_FLAG_TRUNCATED, so that a
-                                  row says by itself whether "not truncated" was decided or never asked).  0 in every other row */
+                                  row says by itself whether "not truncated" was decided or never asked).  bit 3: adp_adapter_front moved
+                                  the row's adapter_start (adapted_hip_adapter_front.h): adapter_start, adapter_len and the four adapter
+                                  statistics are the trimmed adapter's, everything else the first validation's.  0 in every other row */
 } adp_row;
 #define ADP_ROW_FROM_SECOND_LLR 1
 #define ADP_ROW_POLYA_TRUNCATED 2
 #define ADP_ROW_TRUNC_LOOKED 4
+#define ADP_ROW_ADAPTER_FRONT 8
 
 typedef struct adp_handle adp_handle;
 
@@ -556,6 +559,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 /* Adapter event fingerprints and their comparison by dynamic time warping -- adp_event_levels and adp_dtw_assign, an extension --:
  * a header of its own again, with its prototype table in adapted_amd/lib.py, FINGERPRINT_PROTOTYPES. */
 #include "adapted_hip_fingerprint.h"
+
+/* The adapter's front boundary as a post-pass over the rows of a detect call -- adp_adapter_front and adp_adapter_front_i16, an
+ * extension --: a header of its own, with its prototype table in adapted_amd/lib.py, ADAPTER_FRONT_PROTOTYPES. */
+#include "adapted_hip_adapter_front.h"
 
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
