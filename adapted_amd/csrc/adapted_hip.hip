@@ -113,7 +113,7 @@ static int alloc_all(adp_handle *h, int reads, bool llr)
     bad |= h->npk.ensure(R * 4);
     bad |= h->mk.ensure((size_t)h->pslots * (Lp / 2 + 1) * 4);
     }
-    if (bad) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(bad);
     return 0;
 }
 
@@ -345,7 +345,7 @@ enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_END = 13 };
 static unsigned int *phase_counts(adp_handle *h, int opw) { return h->op_used.as<unsigned int>() + opw; }
 static int arena_begin(adp_handle *h)
 {
-    if (h->op_used.ensure(OPW_END * 4) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->op_used.ensure(OPW_END * 4) || (h->op_arena.cap == 0 && h->op_arena.ensure((size_t)65536 * 4)));
     HIPCHK(hipMemsetAsync(h->op_used.p, 0, 20, h->stream));
     return 0;
 }
@@ -372,7 +372,7 @@ static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = null
     const unsigned int used = w[0];
     h->op_last_used = used;
     if ((size_t)used * 4 <= h->op_arena.cap) return 0;
-    if (h->op_arena.ensure((size_t)used * 8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->op_arena.ensure((size_t)used * 8));
     return 1;
 }
 
@@ -392,28 +392,6 @@ static int call_attempts(adp_handle *h, adp_handle *const *lanes, int n_lanes, F
     return ADP_ERR_CAPACITY;
 }
 
-// a phase's per-subset arrays, carved from the handle's sub_ws in 16-byte aligned pieces: `pieces(Carve &)` lists them once and runs
-// twice -- first to add up the sizes (the buffer grows before anything of the phase is enqueued), then to hand out the pointers
-struct Carve {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T> T *take(size_t count)
-    {
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += (count * sizeof(T) + 15) & ~(size_t)15;
-        return p;
-    }
-};
-template <class F> static int sub_carve(adp_handle *h, F &&pieces)
-{
-    Carve c;
-    pieces(c);
-    if (h->sub_ws.ensure(c.off)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    c = Carve{h->sub_ws.as<char>(), 0};
-    pieces(c);
-    return 0;
-}
-
 // the resident matrix types of the detect calls' first passes: the whole matrix, one row per read of the launch (the long-slice
 // series kernels and the shared sweeps work on these; a subset read in place -- SigIdx, SigIdxI16 -- has one candidate per read)
 template <class SIG> struct sig_is_matrix { static constexpr bool value = std::is_same<SIG, SigF32>::value || std::is_same<SIG, SigI16>::value; };
@@ -422,8 +400,7 @@ template <int THREADS, int HB, int U, class SIG>
 static int launch_cand_stats2(adp_handle *h, SIG sig, const int32_t *dlen, int n, int m, int kmax, int cap)
 {
     typedef Cs2Sh<HB> Sh;
-    const unsigned bit = (THREADS >= 512 ? 4096u : 8192u) << (std::is_same<SIG, SigF32>::value ? 0 : 6);
-    if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_cand_stats2<SIG, THREADS, HB, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh))); h->attr_done |= bit; }
+    RCCHK(lds_attr_once(h, (const void *)k_cand_stats2<SIG, THREADS, HB, U>, sizeof(Sh)));
     hipLaunchKernelGGL((k_cand_stats2<SIG, THREADS, HB, U>), dim3(n), dim3(THREADS), sizeof(Sh), h->stream, sig, dlen, n, m, h->bounds.as<int64_t>(), kmax, h->cfg,
                        (const float *)h->series.as<float>(), cap, (const int8_t *)h->have_series.as<int8_t>(), h->cstat.as<CandStat>());
     return 0;
@@ -451,7 +428,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     const bool multi = sig_is_matrix<SIG>::value && !vb && kmax > 1 && h->cfg.mvs_detect_check && !h->cfg.mvs_detect_overwrite &&
                        h->cfg.pA_var_window <= MS_HIST && h->cfg.pA_mean_window <= MS_HIST;
     const int cap = multi ? h->vstride : MVS_CAP;
-    if (multi && (h->series.ensure((size_t)n * 2 * cap * 4) || h->cstat.ensure((size_t)n * kmax * sizeof(CandStat)))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(multi && (h->series.ensure((size_t)n * 2 * cap * 4) || h->cstat.ensure((size_t)n * kmax * sizeof(CandStat))));
     in.series = h->series.as<float>(); in.have_series = h->have_series.as<int8_t>(); in.series_cap = cap;
     in.cstat = multi ? h->cstat.as<CandStat>() : nullptr;
     if (h->cfg.mvs_detect_check && !h->cfg.mvs_detect_overwrite) {
@@ -469,7 +446,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
             size_t &lds_set = f32 ? h->lds_series_set : h->lds_series_set_i16;
             if (lds > lds_set) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_wave<SIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); lds_set = lds; }
             // the plan (slice starts / lengths, have[]) and the order by falling length (validate.h), then the chains
-            if (h->series_plan.ensure((size_t)n * 12 + 2 * MS_NBKT * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+            ALLOCCHK(h->series_plan.ensure((size_t)n * 12 + 2 * MS_NBKT * 4));
             int32_t *pa = h->series_plan.as<int32_t>(), *pn = pa + n, *pp = pn + n;
             uint32_t *pc = reinterpret_cast<uint32_t *>(pp + n);
             HIPCHK(hipMemsetAsync(pc, 0, 2 * MS_NBKT * 4, h->stream));
@@ -478,8 +455,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
             hipLaunchKernelGGL(k_series_order, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, cap, pn, pc, pc + MS_NBKT, pp);
             // round 4: the recurrences as a pipeline of waves (series_pipe.h) for the windows it takes; ADP_SERIES_PIPE=0: one wave per recurrence
             if (pipe_ok) {
-                const unsigned bit = f32 ? 32u : 1u << 20;
-                if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_mvs_series_pipe<SIG>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_FLOATS * 4)); h->attr_done |= bit; }
+                RCCHK(lds_attr_once(h, (const void *)k_mvs_series_pipe<SIG>, SP_LDS_FLOATS * 4));
                 hipLaunchKernelGGL(k_mvs_series_pipe<SIG>, dim3((n + SP_G - 1) / SP_G), dim3(SP_THREADS), SP_LDS_FLOATS * 4, h->stream, dsig, n, m, pa, pn, pp,
                                    h->cfg.pA_var_window, h->cfg.pA_mean_window, h->series.as<float>(), cap, h->have_series.as<int8_t>());
             } else
@@ -540,7 +516,7 @@ static int launch_n1(adp_handle *h, SIG dsig, int n, int m, int T, int minibatch
     uint32_t *gh = h->ghist.as<uint32_t>(), *gb = h->gbelow.as<uint32_t>();
     unsigned long long *gc = h->gcnt.as<unsigned long long>();
     const int collect = ((long long)minibatch * T >= (1ll << 24)) ? 1 : 0; // only worth it (and sized) for big minibatches
-    if (collect && h->cbuf.ensure((size_t)n_mb * N1_CB_CAP * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(collect && h->cbuf.ensure((size_t)n_mb * N1_CB_CAP * 4));
     uint32_t *cb = h->cbuf.as<uint32_t>();
     int bpm = 4096 / n_mb; if (bpm > 256) bpm = 256; if (bpm < 4) bpm = 4;
     dim3 hg(bpm, n_mb), pg(n_mb);
@@ -559,8 +535,8 @@ static int launch_n1(adp_handle *h, SIG dsig, int n, int m, int T, int minibatch
     // 96 000 reads.  A bracket that misses on a small minibatch costs the fused pass and falls through to those passes.)
     const long long fused_min = getenv("ADP_N1_FUSED_MIN") ? atoll(getenv("ADP_N1_FUSED_MIN")) : (1ll << 22);
     if ((long long)minibatch * T >= fused_min && T >= 64) {
-        if (h->cbuf.ensure((size_t)n_mb * N1_CB_CAP * 4) || h->fz.ensure((size_t)n_mb * sizeof(N1Fused)) ||
-            h->fcnt.ensure((size_t)n_mb * 8 * N1F_NCNT) || h->n1heavy.ensure((size_t)n_mb * N1H_WORDS * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        ALLOCCHK(h->cbuf.ensure((size_t)n_mb * N1_CB_CAP * 4) || h->fz.ensure((size_t)n_mb * sizeof(N1Fused)) ||
+                 h->fcnt.ensure((size_t)n_mb * 8 * N1F_NCNT) || h->n1heavy.ensure((size_t)n_mb * N1H_WORDS * 4));
         cb = h->cbuf.as<uint32_t>();
         N1Fused *fz = h->fz.as<N1Fused>();
         unsigned long long *fc = h->fcnt.as<unsigned long long>();
@@ -659,9 +635,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     int rc = 0;
     const int n_mb = (n + minibatch - 1) / minibatch;
     h->last_n = n; h->last_nmb = n_mb;
-    if (h->mbs.ensure((size_t)n_mb * sizeof(MbState)) || h->ghist.ensure((size_t)n_mb * N1_BINS * 4) || h->gbelow.ensure((size_t)n_mb * 8) || h->gcnt.ensure((size_t)n_mb * 8 * N1_NCNT)) {
-        g_err = "device allocation failed"; return ADP_ERR_HIP;
-    }
+    ALLOCCHK(h->mbs.ensure((size_t)n_mb * sizeof(MbState)) || h->ghist.ensure((size_t)n_mb * N1_BINS * 4) || h->gbelow.ensure((size_t)n_mb * 8) || h->gcnt.ensure((size_t)n_mb * 8 * N1_NCNT));
     rc = alloc_all(h, n, true);
     if (rc) return rc;
     hipStream_t st = h->stream;
@@ -689,7 +663,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         const bool sp_fused = upto >= 8 && (flags & ADP_WITH_START_PEAK) && h->layout == ADP_LAYOUT_MINIBATCH &&
                               h->cfg.sp_downscale_factor == h->ds && h->off % h->ds == 0 && T > h->off && env_int("ADP_SP_FUSED", 1) != 0;
         if (sp_fused) {
-            if (h->sphead.ensure((size_t)n * sizeof(SpHead))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+            ALLOCCHK(h->sphead.ensure((size_t)n * sizeof(SpHead)));
             Scope s(h, "k_sp_head");
             hipLaunchKernelGGL(k_sp_head<SIG>, dim3(n), dim3(64), (size_t)64 * h->cfg.sp_downscale_factor * 4, st, dsig, dlen, n, m, h->cfg, h->off, h->sphead.as<SpHead>());
         }
@@ -711,7 +685,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
             if (h->layout == ADP_LAYOUT_SINGLE_READ) {
                 // the reference pools the unpadded read: its last, ragged block is filled up with zeros at the READ's end
                 // (downscale.py:22-29), which is what the per-read range [0, min(T, full_len)) does here
-                if (h->rng0.ensure((size_t)n * 16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+                ALLOCCHK(h->rng0.ensure((size_t)n * 16));
                 std::vector<int64_t> hr((size_t)2 * n);
                 for (int i = 0; i < n; i++) { hr[2 * i] = 0; hr[2 * i + 1] = T; }
                 HIPCHK(hipMemcpyAsync(h->rng0.p, hr.data(), (size_t)n * 16, hipMemcpyHostToDevice, st));
@@ -819,7 +793,7 @@ static int trunc_supported(const adp_handle *h)
 static int trunc_enqueue_t1(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, adp_row *rows)
 {
     int8_t *verdict;
-    if (h->pt_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->pt_sel.ensure((size_t)n * 4));
     RCCHK(sub_carve(h, [&](Carve &c) { verdict = c.take<int8_t>(n); }));
     unsigned int *counts = phase_counts(h, OPW_PT);
     h->pt_looked = true;
@@ -904,9 +878,7 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     const int stagger = env_int("ADP_STAGGER", 1);
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
     const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
-    if (h->mbstat.ensure((size_t)n_mb * 4) || h->mbparams.ensure((size_t)n_mb * 32) || (rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row)))) {
-        g_err = "device allocation failed"; return ADP_ERR_HIP;
-    }
+    ALLOCCHK(h->mbstat.ensure((size_t)n_mb * 4) || h->mbparams.ensure((size_t)n_mb * 32) || (rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))));
     while (h->ev_sync.size() < (size_t)G * 3) {
         hipEvent_t e;
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1167,8 +1139,8 @@ static int cnn_topk_dev(adp_handle *h, const float *scores, const long long *dap
     const int wpr = (int)((half + 4 + 15) / 16 + 2);
     const size_t lds = (size_t)wpr * 4;
     if (lds > 60000) { g_err = "Lo too large for the LDS state of k_cnn_topk"; return ADP_ERR_UNSUPPORTED; }
-    if (h->ct_pk.ensure((size_t)n * 2 * half * 4) || h->ct_pv.ensure((size_t)n * half * 4) || h->ct_st.ensure((size_t)n * wpr * 4) ||
-        h->ct_lnz.ensure((size_t)n * 4) || h->ct_out.ensure(((size_t)n * (k + 1) + 1) * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->ct_pk.ensure((size_t)n * 2 * half * 4) || h->ct_pv.ensure((size_t)n * half * 4) || h->ct_st.ensure((size_t)n * wpr * 4) ||
+             h->ct_lnz.ensure((size_t)n * 4) || h->ct_out.ensure(((size_t)n * (k + 1) + 1) * 4));
     int32_t *dcand = h->ct_out.as<int32_t>(), *dcnt = dcand + (size_t)n * k;
     const int n_mb = (n + mbsize - 1) / mbsize;
     hipStream_t st = h->stream;
@@ -1203,7 +1175,7 @@ static int cnn_predict_dev(adp_handle *h, const float *scores, int n, int mbsize
     const int k = c.polya_cand_k, kk = k < 1 ? 1 : k;
     if (k > ADP_MAX_CAND) { g_err = "polya_cand_k too large"; return ADP_ERR_UNSUPPORTED; }
     if (n > h->max_reads) { g_err = "n_reads exceeds the handle's capacity"; return ADP_ERR_CAPACITY; }
-    if (h->ct_ap.ensure((size_t)n * 16) || h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->ct_ap.ensure((size_t)n * 16) || h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8));
     long long *dap = h->ct_ap.as<long long>(), *dpp = dap + n;
     const int na = (c.max_obs_adapter - c.min_obs_adapter) / c.downscale_factor;
     hipStream_t st = h->stream;
@@ -1242,7 +1214,7 @@ extern "C++" {
 template <class SIG>
 static int launch_cnn_prepare(adp_handle *h, SIG dsig, int n_reads, int m, int off, int ds, int Lc, float *dout, SpHead *sp_head = nullptr)
 {
-    if (h->npk.ensure((size_t)n_reads * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; } // (npk: unused on this path)
+    ALLOCCHK(h->npk.ensure((size_t)n_reads * 4)); // (npk: unused on this path)
     int32_t *nan_cnt = h->npk.as<int32_t>();
     HIPCHK(hipMemsetAsync(nan_cnt, 0, (size_t)n_reads * 4, h->stream));
     { Scope s(h, "k_cnn_pool");
@@ -1301,7 +1273,7 @@ int adp_cnn_set_weights(adp_handle *h, const float *w0, const float *b0, const f
 {
     if (!h || !w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
-    if (h->cnn_w.ensure((size_t)CNN_WTOTAL * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->cnn_w.ensure((size_t)CNN_WTOTAL * 4));
     std::vector<float> all((size_t)CNN_WTOTAL);
     memcpy(&all[CNN_W0], w0, sizeof(float) * CNN_C * CNN_K); memcpy(&all[CNN_B0], b0, sizeof(float) * CNN_C);
     memcpy(&all[CNN_W1], w1, sizeof(float) * CNN_C * CNN_C * CNN_K); memcpy(&all[CNN_B1], b1, sizeof(float) * CNN_C);
@@ -1311,7 +1283,7 @@ int adp_cnn_set_weights(adp_handle *h, const float *w0, const float *b0, const f
     HIPCHK(hipMemcpyAsync(h->cnn_w.p, all.data(), (size_t)CNN_WTOTAL * 4, hipMemcpyHostToDevice, h->stream));
     // the 64 -> 64 layers once more as split float16 B fragments (cnn_conv_split.h), scaled by a power of two per layer so that the
     // largest weight lands in [2^13, 2^14)
-    if (h->cnn_wsp.ensure(((size_t)2 * CNS_WSP_LAYER + CNS_W3SP + CNS_W0SP) * 2)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->cnn_wsp.ensure(((size_t)2 * CNS_WSP_LAYER + CNS_W3SP + CNS_W0SP) * 2));
     for (int layer = 0; layer < 2; layer++) {
         const float *wl = &all[layer ? CNN_W2 : CNN_W1];
         float mx = 0.f;
@@ -1359,8 +1331,7 @@ template <int NT>
 static int launch_conv64(adp_handle *h, const float *in, float *out, const float *w, const float *b, int n, int L1, int Lpad, int tiles)
 {
     const size_t lds = (size_t)2 * CNN_C * (64 * NT + 8) * 4;
-    const unsigned bit = 4u << (NT - 2);
-    if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_cnn_conv64<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->attr_done |= bit; }
+    RCCHK(lds_attr_once(h, (const void *)k_cnn_conv64<NT>, lds));
     long long total = (long long)n * tiles;
     int grid = (int)(total < h->n_cu ? total : h->n_cu);
     hipLaunchKernelGGL(k_cnn_conv64<NT>, dim3(grid), dim3(256), lds, h->stream, in, out, w, b, n, L1, Lpad, tiles);
@@ -1376,8 +1347,7 @@ static int launch_conv64s(adp_handle *h, const _Float16 *in, _Float16 *out, cons
 {
     // (LAST: layer 3 in the epilogue -- tiles that advance by 64 NT - 2 positions, the taps' partial sums of a tile in LDS behind the two tile buffers)
     const size_t lds = (size_t)2 * (((size_t)(64 * NT + 6) * CNS_ROWB + 1023) / 1024 * 1024) + (LAST ? (size_t)2 * CNN_K * 64 * NT * 4 : 0);
-    const unsigned bit = (FIRST ? 16384u : LAST ? 512u : 64u) << (NT - 2);
-    if (!(h->attr_done & bit)) { HIPCHK(hipFuncSetAttribute((const void *)k_cnn_conv64s<NT, LAST, FIRST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->attr_done |= bit; }
+    RCCHK(lds_attr_once(h, (const void *)k_cnn_conv64s<NT, LAST, FIRST>, lds));
     long long total = (long long)n * tiles;
     if (total >= (1ll << 31)) { g_err = "too many tiles for one launch of k_cnn_conv64s"; return ADP_ERR_UNSUPPORTED; }
     int grid = (int)(total < h->n_cu ? total : h->n_cu);
@@ -1398,13 +1368,13 @@ static int cnn_forward_split(adp_handle *h, adp_handle *wh, const float *prepare
     int C = (int)((size_t)n_reads < cap_reads ? (size_t)n_reads : cap_reads);
     if (h->cnn_Lpad != Lrows || h->cnn_L1 != L1 || h->cnn_chunk < C) {
         for (int k = 0; k < 2; k++) {
-            if (h->cnn_act[k].ensure((size_t)C * per_read + CNS_SLACK)) { g_err = "device allocation failed"; return ADP_ERR_HIP; } // (+ what the tile DMAs read past the last read's rows)
+            ALLOCCHK(h->cnn_act[k].ensure((size_t)C * per_read + CNS_SLACK)); // (+ what the tile DMAs read past the last read's rows)
             HIPCHK(hipMemsetAsync(h->cnn_act[k].p, 0, h->cnn_act[k].cap, h->stream)); // the padding rows are never written again
         }
         h->cnn_Lpad = Lrows; h->cnn_L1 = L1; h->cnn_chunk = (int)((h->cnn_act[0].cap - CNS_SLACK) / per_read); if (h->cnn_chunk > 65535) h->cnn_chunk = 65535;
     }
     C = h->cnn_chunk < n_reads ? h->cnn_chunk : n_reads;
-    if (wh->op_used.ensure(16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(wh->op_used.ensure(16));
     int32_t *flag = wh->op_used.as<int32_t>() + 1;
     const float *W = wh->cnn_w.as<float>();
     const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
@@ -1496,7 +1466,7 @@ static int cnn_forward_dev(adp_handle *h, const float *prepared, int n_reads, in
     // call after it used to share one pair and cleared up to 2 x 4 GiB of padding on every change of kind)
     if (h->cnn_f_Lpad != Lpad || h->cnn_f_L1 != L1 || h->cnn_f_chunk < C) {
         for (int k = 0; k < 2; k++) {
-            if (h->cnn_actf[k].ensure((size_t)C * per_read)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+            ALLOCCHK(h->cnn_actf[k].ensure((size_t)C * per_read));
             HIPCHK(hipMemsetAsync(h->cnn_actf[k].p, 0, h->cnn_actf[k].cap, h->stream)); // the padding columns are never written again
         }
         h->cnn_f_Lpad = Lpad; h->cnn_f_L1 = L1; h->cnn_f_chunk = (int)(h->cnn_actf[0].cap / per_read); if (h->cnn_f_chunk > 65535) h->cnn_f_chunk = 65535;
@@ -1531,7 +1501,7 @@ int adp_cnn_forward(adp_handle *h, const float *prepared, int n_reads, int Lc, f
     RCCHK(begin_call(h));
     h->cnn_redo_f32 = false;
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (h->op_used.ensure(16)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        ALLOCCHK(h->op_used.ensure(16));
         HIPCHK(hipMemsetAsync(h->op_used.as<int32_t>() + 1, 0, 4, h->stream));
         int rc = cnn_forward_dev(h, prepared, n_reads, Lc, scores_out);
         if (rc) return rc;
@@ -1569,7 +1539,7 @@ static int cnn_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n_reads
 {
     const int off = h->cfg.min_obs_adapter, ds = h->cfg.downscale_factor;
     const int Lc = (m - off + ds - 1) / ds, L1 = (Lc - 1) / 3 + 1, Lo = 3 * L1 - 2;
-    if (h->cnn_x.ensure((size_t)n_reads * Lc * 4) || h->cnn_sc.ensure((size_t)n_reads * 2 * Lo * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->cnn_x.ensure((size_t)n_reads * Lc * 4) || h->cnn_sc.ensure((size_t)n_reads * 2 * Lo * 4));
     hipStream_t st = h->stream;
     int rc = alloc_all(h, n_reads, false);
     if (rc) return rc;
@@ -1580,7 +1550,7 @@ static int cnn_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n_reads
     const bool sp_fused = sp_out && cnn_sp_fused(h);
     SpHead *sp_head = nullptr;
     if (sp_fused) {
-        if (h->sphead.ensure((size_t)n_reads * sizeof(SpHead))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+        ALLOCCHK(h->sphead.ensure((size_t)n_reads * sizeof(SpHead)));
         sp_head = h->sphead.as<SpHead>();
         Scope s(h, "k_sp_head");
         hipLaunchKernelGGL(k_sp_head<SIG>, dim3(n_reads), dim3(64), sp_lds, st, dsig, dlen, n_reads, m, h->cfg, off, sp_head);
@@ -1639,9 +1609,7 @@ template <class SIG>
 static int refine_chain(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, const int64_t *drng, int64_t *dout, int32_t *dstat)
 {
     hipStream_t st = h->stream;
-    if (h->mbs.ensure((size_t)n * sizeof(MbState)) || h->ghist.ensure((size_t)n * N1_BINS * 4) || h->gbelow.ensure((size_t)n * 8) || h->gcnt.ensure((size_t)n * 8 * N1_NCNT)) {
-        g_err = "device allocation failed"; return ADP_ERR_HIP;
-    }
+    ALLOCCHK(h->mbs.ensure((size_t)n * sizeof(MbState)) || h->ghist.ensure((size_t)n * N1_BINS * 4) || h->gbelow.ensure((size_t)n * 8) || h->gcnt.ensure((size_t)n * 8 * N1_NCNT));
     MbState *mbs = h->mbs.as<MbState>();
     HIPCHK(hipMemsetAsync(mbs, 0, (size_t)n * sizeof(MbState), st));
     HIPCHK(hipMemsetAsync(h->ghist.p, 0, (size_t)n * N1_BINS * 4, st));
@@ -1676,7 +1644,7 @@ static bool cnn_fallback_wanted(const adp_handle *h, int flags, const adp_row *r
 // Enqueues the selection on the handle's stream; the count reaches the host in arena_end's copy.
 static int cnn_fallback_select(adp_handle *h, const int32_t *dlen, int n, const adp_row *rows, const int64_t *bounds, int bstride)
 {
-    if (h->fb_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->fb_sel.ensure((size_t)n * 4));
     Scope s(h, "k_cnn_fb_select");
     hipLaunchKernelGGL(k_cnn_fb_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, rows, bounds, bstride, dlen, n, 2ll * h->cfg.max_obs_adapter,
                        h->fb_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 2);
@@ -1729,7 +1697,7 @@ static bool cnn_sp_wanted(int flags, const adp_row *rows) { return (flags & ADP_
 // fallback's merge when that ran).  The count reaches the host in arena_end's copy.
 static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
 {
-    if (h->so_sel.ensure((size_t)n * 4)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->so_sel.ensure((size_t)n * 4));
     Scope s(h, "k_cnn_so_select");
     hipLaunchKernelGGL(k_cnn_so_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, rows, n, h->so_sel.as<int32_t>(), h->op_used.as<unsigned int>() + 3);
     return 0;
@@ -1849,9 +1817,7 @@ static int cnn_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
     // K1's results of the whole call live in this handle's buffer (adp_detect_cnn sized it): the lanes write their slices
     SpOut *sp = cnn_sp_wanted(flags, rows_out) ? h->sp.as<SpOut>() : nullptr;
     h->last_n = n; h->last_nmb = n_mb; h->last_grouped = true;
-    if ((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || ((bounds_out || fb) && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8))) {
-        g_err = "device allocation failed"; return ADP_ERR_HIP;
-    }
+    ALLOCCHK((rows_out && !out_dev && h->rows.ensure((size_t)n * sizeof(adp_row))) || ((bounds_out || fb) && h->bounds.ensure((size_t)n * (1 + ADP_MAX_CAND) * 8)));
     adp_handle *lanes[ADP_MAX_LANES];
     for (int i = 0; i < n_lanes; i++) {
         RCCHK(lane_get(h, i, mb_per_group * minibatch, &lanes[i]));
@@ -1894,7 +1860,7 @@ static int cnn_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n_re
 {
     h->cnn_redo_f32 = false;
     // (K1's results of the whole call: sized here, before any phase's workspace call could move the buffer under them)
-    if (cnn_sp_wanted(flags, rows_out) && h->sp.ensure((size_t)n_reads * sizeof(SpOut))) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(cnn_sp_wanted(flags, rows_out) && h->sp.ensure((size_t)n_reads * sizeof(SpOut)));
     // ADP_CNN_GROUPS (opt-in): unset / 1 = one chunk on one stream; 0 = automatic (chunks of about a quarter of the call, at most
     // what the conv stack's activation buffers hold, over two lanes); k = aim at k chunks.  Measured at the 200 k window (8000
     // reads, profiles/r03_cnn_chunks.txt): 4 chunks over 2 lanes 107.5 ms against 95.4 ms for one chunk -- the moving-window
@@ -1987,7 +1953,7 @@ int adp_llr_refine_polya(adp_handle *h, const float *signals, const int32_t *ful
     hipStream_t st = h->stream;
     rc = alloc_all(h, n, true);
     if (rc) return rc;
-    if (h->bounds_stage.ensure((size_t)n * 16 + (size_t)n * 12)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
+    ALLOCCHK(h->bounds_stage.ensure((size_t)n * 16 + (size_t)n * 12));
     int64_t *drng = h->bounds_stage.as<int64_t>();
     int64_t *dout = drng + 2 * (size_t)n;
     int32_t *dstat = reinterpret_cast<int32_t *>(dout + n);

@@ -1,5 +1,6 @@
 // handle.h -- what the library's translation units (adapted_hip.hip: the detect path; modules.hip: the reference-module
-// drop-ins) share on the host: the error string, the handle and the start / profiling scope of a call.  Nothing here is exported.
+// drop-ins) share on the host: the error string, the handle, the pieces of its carved buffers (carve.h) and the start / profiling
+// scope of a call.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "adapted_hip.h"
+#include "carve.h"
 
 #define ADP_HIDDEN __attribute__((visibility("hidden")))
 
@@ -23,6 +25,8 @@ extern ADP_HIDDEN thread_local std::string g_err;
     } while (0)
 // a helper's non-zero return code (g_err already set) ends the caller
 #define RCCHK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+// device memory that did not grow (DevBuf::ensure, one or several joined with ||) ends the caller
+#define ALLOCCHK(failed) do { if (failed) { g_err = "device allocation failed"; return ADP_ERR_HIP; } } while (0)
 
 // grow-only device memory, released with its owner (not copyable: two owners would free it twice)
 struct DevBuf {
@@ -73,7 +77,7 @@ struct adp_handle {
     DevBuf rng0;      // per-read [0, T) ranges of the single-read layout
     // CNN head (cnn_conv.h): weights of the four layers, two activation buffers [chunk][64][Lpad]
     DevBuf cnn_w, cnn_act[2], cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
-    DevBuf ws;              // the module entry points (adp_c_llr_*, adp_llr_*, adp_mvs_*): one call's staging and scratch (ws_carve)
+    DevBuf ws;              // the module entry points (modules.hip): one call's staging and scratch (ws_carve)
     // the phases behind a detect call's first pass (cnn_fallback.h, cnn_second_opinion.h, polya_truncated.h): the reads each one
     // selected [reads of the call] -- fb_sel and so_sel are both live between the first pass and the counter read -- and the
     // per-subset arrays and rows of the phase that is running (carved by it: each runs to completion before the next starts)
@@ -104,13 +108,30 @@ struct adp_handle {
     hipEvent_t ev_start = nullptr;          // parent: inputs staged, arena counter reset
     bool last_grouped = false;
     // launch attributes already requested through this handle (hipFuncSetAttribute per kernel instantiation and device; kept per
-    // handle -- a handle is used by one thread at a time -- instead of in process-wide statics)
-    unsigned attr_done = 0;
+    // handle -- a handle is used by one thread at a time -- instead of in process-wide statics): the kernels lds_attr_once has
+    // seen, and the largest size asked for the two kernels whose need grows with the configuration
+    std::vector<const void *> lds_attr_set;
     size_t lds_series_set = 0, lds_series_set_i16 = 0;
 #ifdef ADP_ABLATE
     int ablate = 0;   // the mask this handle last copied to its device (sync_ablate)
 #endif
 };
+
+// ---- a call's pieces of the handle's two carved buffers (carve.h).  A module call completes before it returns, and a phase runs
+// to completion before the next starts, so the next one takes the same memory: each buffer holds the largest single need.
+// ws: the module entry points' staging and scratch, in 256-byte aligned pieces
+template <class F> static int ws_carve(adp_handle *h, F &&pieces) { ALLOCCHK(!carve_pieces(h->ws, 256, pieces)); return ADP_OK; }
+// sub_ws: the per-subset arrays of the phase that is running, in 16-byte aligned pieces
+template <class F> static int sub_carve(adp_handle *h, F &&pieces) { ALLOCCHK(!carve_pieces(h->sub_ws, 16, pieces)); return ADP_OK; }
+
+// a kernel's dynamic LDS size, requested once per handle and kernel instantiation (`kernel`: its address)
+static inline int lds_attr_once(adp_handle *h, const void *kernel, size_t bytes)
+{
+    for (const void *k : h->lds_attr_set) if (k == kernel) return ADP_OK;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    h->lds_attr_set.push_back(kernel);
+    return ADP_OK;
+}
 
 // ---- a call's start and its profiling scopes (adapted_hip.hip) --------------------------
 ADP_HIDDEN hipEvent_t next_event(adp_handle *h);

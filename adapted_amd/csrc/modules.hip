@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <initializer_list>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "handle.h"
@@ -20,44 +22,43 @@
 
 // ---- workspace, staging and per-read checks of the entry points
 
-// 256-byte aligned pieces of the handle's workspace `ws`; a Carve without a base only adds up their sizes
-struct Carve {
-    char *base = nullptr;
-    size_t off = 0;
-    // `count` elements of T -- none (nullptr) unless `want`
-    template <class T> T *take(size_t count, bool want = true)
-    {
-        if (!want) return nullptr;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
-// a call's pieces of the workspace: `pieces(Carve &)` takes them all and runs twice -- first to add up the sizes, so that ws
-// grows once, before anything is enqueued (ensure() moves the buffer), then to hand out the pointers.  Every module call
-// completes before it returns, so the next one takes the same memory: a process holds the largest single call's need.
-template <class F> static int ws_carve(adp_handle *h, F &&pieces)
+// copies on the handle's stream between a host array and a workspace piece (handle.h: ws_carve): the whole piece, or its first
+// `count` elements
+template <class T> static int h2d(adp_handle *h, Piece<T> dst, const void *src, size_t count)
 {
-    Carve c;
-    pieces(c);
-    if (h->ws.ensure(c.off)) { g_err = "device allocation failed"; return ADP_ERR_HIP; }
-    c = Carve{h->ws.as<char>(), 0};
-    pieces(c);
+    if (count > dst.n) { g_err = "internal error: a copy past its workspace piece"; return ADP_ERR_INVALID; }
+    HIPCHK(hipMemcpyAsync(dst.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
     return ADP_OK;
 }
-
-// copies on the handle's stream: a host array in, a result back
-static int h2d(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream)); return ADP_OK; }
-static int d2h(adp_handle *h, void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream)); return ADP_OK; }
+template <class T> static int d2h(adp_handle *h, void *dst, Piece<T> src, size_t count)
+{
+    if (count > src.n) { g_err = "internal error: a copy past its workspace piece"; return ADP_ERR_INVALID; }
+    HIPCHK(hipMemcpyAsync(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    return ADP_OK;
+}
+template <class T> static int h2d(adp_handle *h, Piece<T> dst, const void *src) { return h2d(h, dst, src, dst.n); }
+template <class T> static int d2h(adp_handle *h, void *dst, Piece<T> src) { return d2h(h, dst, src, src.n); }
+template <class T> static int zero(adp_handle *h, Piece<T> piece) { HIPCHK(hipMemsetAsync(piece.p, 0, piece.bytes(), h->stream)); return ADP_OK; }
 
 // the device pointer of an input that is device memory with ADP_IN_DEVICE, else host memory: then copied to `piece` (a
-// workspace piece taken for it only in that case)
-template <class T> static int stage_in(adp_handle *h, int flags, const T *src, T *piece, size_t bytes, const T **dev)
+// workspace piece taken for it only in that case; of bytes where the input's element type is a flag's)
+template <class S, class T> static int stage_in(adp_handle *h, int flags, const S *src, Piece<T> piece, const S **dev)
 {
     if (flags & ADP_IN_DEVICE) { *dev = src; return ADP_OK; }
-    *dev = piece;
-    return h2d(h, piece, src, bytes);
+    *dev = piece.p;
+    return h2d(h, piece, src);
+}
+
+// a signal whose element type is a flag's: fn(the typed pointer), for float64 with `f64`, else float32; elem_t names the type there
+template <class F> static auto by_elem(bool f64, const void *sig, F &&fn) { return f64 ? fn((const double *)sig) : fn((const float *)sig); }
+template <class P> using elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+// a byte budget in MiB: `dflt`, or what the environment holds under `name` (`value`: its getenv, read per call)
+static int scratch_mib(const char *name, const char *value, long long dflt, long long *mib)
+{
+    *mib = value ? atoll(value) : dflt;
+    if (value && (*mib < 1 || *mib > (1 << 20))) { g_err = std::string(name) + " must lie in [1, 2^20]"; return ADP_ERR_INVALID; }
+    return ADP_OK;
 }
 
 // the per-read checks (host arrays of n entries): lo <= a <= hi; 0 <= len <= L; 0 <= start <= end <= len; positions in [0, 2^40]
@@ -74,6 +75,24 @@ static bool spans_ok(const int32_t *start, const int32_t *end, const int32_t *le
 }
 static bool positions_ok(const int64_t *p, int n) { return all_in<int64_t>(p, n, 0, (int64_t)1 << 40); }
 
+// what the row modules start with, checks done: signals float32 / float64 [n_reads, L] (ADP_MVS_F64) and a length per read
+struct RowsIn { bool f64; size_t esz; Piece<char> s_sig; Piece<int32_t> dlen; const void *ds; };
+// begin_call; the pieces -- the staged signal, dlen, then the call's own (`more(Carve &)`, with in.f64 / in.esz set) --; the two in
+template <class F>
+static int rows_begin(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, int flags, RowsIn &in, F &&more)
+{
+    RCCHK(begin_call(h));
+    in.f64 = (flags & ADP_MVS_F64) != 0;
+    in.esz = in.f64 ? 8 : 4;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        in.s_sig = w.take<char>((size_t)L * in.esz * n_reads, !(flags & ADP_IN_DEVICE));
+        in.dlen = w.take<int32_t>(n_reads);
+        more(w);
+    }));
+    RCCHK(stage_in(h, flags, sig, in.s_sig, &in.ds));
+    return h2d(h, in.dlen, len);
+}
+
 // ---- the signal statistics modules (sigstats_api.h)
 
 // the segments of a call, checked: rows in [0, n_reads), positions <= 2^40
@@ -89,10 +108,20 @@ static int seg_check(const void *sig, const int32_t *len, int n_reads, int L, co
     return ADP_OK;
 }
 
+// what the segment modules start with, checks done (seg_check, then their own): the rows (rows_begin) and the segments behind them
+struct SegIn : RowsIn { Piece<SsSeg> dsegs; };
+template <class F>
+static int seg_begin(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg, int flags,
+                     SegIn &in, F &&more)
+{
+    RCCHK(rows_begin(h, sig, len, n_reads, L, flags, in, [&](Carve &w) { in.dsegs = w.take<SsSeg>(n_seg); more(w); }));
+    return h2d(h, in.dsegs, segs);
+}
+
 // median and MAD on the device -> dmm [rows, 2] ([1, 2] with ADP_SS_WHOLE; then dlen[0] holds n_reads * L)
 template <class T>
-static int ss_med_mad_dev(adp_handle *h, const T *ds, const int32_t *dlen, int n_reads, int L, int flags, double *dmm, SsPop *dst,
-                           uint32_t *dhist)
+static int ss_med_mad_dev(adp_handle *h, const T *ds, const int32_t *dlen, int n_reads, int L, int flags, double *dmm, Piece<SsPop> dst,
+                           Piece<uint32_t> dhist)
 {
     const int skip = (flags & ADP_SS_NANSKIP) != 0;
     if (!(flags & ADP_SS_WHOLE)) {
@@ -109,9 +138,9 @@ static int ss_med_mad_dev(adp_handle *h, const T *ds, const int32_t *dlen, int n
     }
     long long nb = (N + 4095) / 4096;
     if (nb > (long long)h->n_cu * 8) nb = (long long)h->n_cu * 8;
-    HIPCHK(hipMemsetAsync(dhist, 0, 512 * sizeof(uint32_t), h->stream));
+    RCCHK(zero(h, dhist));
     for (int sel = 0; sel < 2; sel++) {
-        HIPCHK(hipMemsetAsync(dst, 0, sizeof(SsPop), h->stream));
+        RCCHK(zero(h, dst));
         for (int pass = 0; pass < (int)sizeof(typename SsKey<T>::type); pass++) {
             { Scope s(h, "k_pop_hist");
               hipLaunchKernelGGL(k_pop_hist<T>, dim3((unsigned)nb), dim3(SS_POP_BLOCK), 0, h->stream, ds, N, sel ? dmm : (const double *)nullptr, pass, skip, dst, dhist); }
@@ -143,10 +172,10 @@ int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const 
     }
     if (!lens_ok(len, n_reads, L) || !spans_ok(start, end, len, n_reads)) { g_err = "need 0 <= start <= end <= len <= L for every read"; return ADP_ERR_INVALID; }
     RCCHK(begin_call(h));
-    const size_t cells = (size_t)L * n_reads, mat = cells * 8, n4 = (size_t)n_reads * 4;
+    const size_t cells = (size_t)L * n_reads;
     // the sums a raw call computes go to the caller's arrays when those are device outputs, else to the workspace
     const bool own_c = !from_sums && !(c_io && out_dev);
-    int32_t *dlen, *dstart, *dend; double *s_raw, *s_c, *s_c2, *w_c, *w_c2, *w_g;
+    Piece<int32_t> dlen, dstart, dend; Piece<double> s_raw, s_c, s_c2, w_c, w_c2, w_g;
     RCCHK(ws_carve(h, [&](Carve &w) {
         dlen = w.take<int32_t>(n_reads); dstart = w.take<int32_t>(n_reads); dend = w.take<int32_t>(n_reads);
         s_raw = w.take<double>(cells, !from_sums && !in_dev);
@@ -154,28 +183,28 @@ int adp_c_llr_trace(adp_handle *h, const double *raw, const int32_t *len, const 
         w_c = w.take<double>(cells, own_c); w_c2 = w.take<double>(cells, own_c);
         w_g = w.take<double>(cells, !out_dev);
     }));
-    RCCHK(h2d(h, dlen, len, n4)); RCCHK(h2d(h, dstart, start, n4)); RCCHK(h2d(h, dend, end, n4));
+    RCCHK(h2d(h, dlen, len)); RCCHK(h2d(h, dstart, start)); RCCHK(h2d(h, dend, end));
     const double *dc, *dc2;
     if (from_sums) {
-        RCCHK(stage_in(h, flags, c_io, s_c, mat, &dc));
-        RCCHK(stage_in(h, flags, c2_io, s_c2, mat, &dc2));
+        RCCHK(stage_in<double>(h, flags, c_io, s_c, &dc));
+        RCCHK(stage_in<double>(h, flags, c2_io, s_c2, &dc2));
     } else {
         const double *draw;
-        RCCHK(stage_in(h, flags, raw, s_raw, mat, &draw));
-        double *wc = own_c ? w_c : c_io, *wc2 = own_c ? w_c2 : c2_io;
+        RCCHK(stage_in(h, flags, raw, s_raw, &draw));
+        double *wc = own_c ? w_c.p : c_io, *wc2 = own_c ? w_c2.p : c2_io;
         { Scope s(h, "k_trace_cumsum");
           hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, draw, dlen, L, n_reads, wc, wc2); }
         dc = wc; dc2 = wc2;
     }
-    double *dg = out_dev ? gain_out : w_g;
+    double *dg = out_dev ? gain_out : w_g.p;
     TraceArgs ta = {a.min_obs, a.border_trim, a.stride, a.adapter_early_stopping, a.adapter_early_stop_window, a.adapter_early_stop_stride,
                     a.polya_early_stopping, a.polya_early_stop_window, a.polya_early_stop_stride};
     { Scope s(h, "k_trace_gains");
       hipLaunchKernelGGL(k_trace_gains, dim3(n_reads), dim3(64), 0, h->stream, dc, dc2, dlen, dstart, dend, L, ta, dg); }
     HIPCHK(hipGetLastError());
-    if (!out_dev) {
-        RCCHK(d2h(h, gain_out, dg, mat));
-        if (!from_sums && c_io) { RCCHK(d2h(h, c_io, dc, mat)); RCCHK(d2h(h, c2_io, dc2, mat)); }
+    if (!out_dev) { // (the sums of a raw call are then the workspace's: own_c)
+        RCCHK(d2h(h, gain_out, w_g));
+        if (!from_sums && c_io) { RCCHK(d2h(h, c_io, w_c)); RCCHK(d2h(h, c2_io, w_c2)); }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
@@ -204,7 +233,7 @@ int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const
     const bool in_dev = (flags & ADP_IN_DEVICE) != 0;
     RCCHK(begin_call(h));
     const size_t cells = (size_t)L * n_reads, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
-    double *s_c, *s_c2, *part_g, *st_g; int32_t *part_x, *st_x; CdSeg *dsegs;
+    Piece<double> s_c, s_c2, part_g, st_g; Piece<int32_t> part_x, st_x; Piece<CdSeg> dsegs;
     RCCHK(ws_carve(h, [&](Carve &w) {
         dsegs = w.take<CdSeg>(n_reads);
         part_g = w.take<double>(n_reads * nck); part_x = w.take<int32_t>(n_reads * nck);
@@ -212,8 +241,8 @@ int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const
         s_c = w.take<double>(cells, !in_dev); s_c2 = w.take<double>(cells, !in_dev);
     }));
     const double *dc, *dc2;
-    RCCHK(stage_in(h, flags, c, s_c, cells * 8, &dc));
-    RCCHK(stage_in(h, flags, c2, s_c2, cells * 8, &dc2));
+    RCCHK(stage_in(h, flags, c, s_c, &dc));
+    RCCHK(stage_in(h, flags, c2, s_c2, &dc2));
     std::vector<CdSeg> segs(n_reads);
     for (int r = 0; r < n_reads; r++) {
         long lo = (long)start[r] + offset_head[r], hi = (long)end[r] - offset_tail[r];
@@ -221,12 +250,12 @@ int adp_c_llr_best_split(adp_handle *h, const double *c, const double *c2, const
         if (hi < lo) hi = lo; // (an empty range: the reference's loop does not run)
         segs[r] = CdSeg{r, start[r], end[r], (int32_t)lo, (int32_t)hi, r};
     }
-    RCCHK(h2d(h, dsegs, segs.data(), segs.size() * sizeof(CdSeg)));
+    RCCHK(h2d(h, dsegs, segs.data()));
     cd_splits(h, dc, dc2, L, dsegs, n_reads, part_g, part_x, st_x, st_g);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> x(n_reads);
-    RCCHK(d2h(h, x.data(), st_x, (size_t)n_reads * 4));
-    RCCHK(d2h(h, gain_out, st_g, (size_t)n_reads * 8));
+    RCCHK(d2h(h, x.data(), st_x));
+    RCCHK(d2h(h, gain_out, st_g));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int r = 0; r < n_reads; r++) x_out[r] = x[r];
     return ADP_OK;
@@ -243,7 +272,7 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
     RCCHK(begin_call(h));
     const size_t n = n_reads, cells = (size_t)L * n, esz = f32 ? 4 : 8, nck = (size_t)(L + CD_CHUNK - 1) / CD_CHUNK;
     // the sums, the staged signal; segments (2 per read), chunk winners, the per-read state
-    double *dc, *dc2, *part_g, *st_g, *med; int32_t *part_x, *st_x, *res, *dlen; CdSeg *segs, *psegs; void *s_raw;
+    Piece<double> dc, dc2, part_g, st_g, med; Piece<int32_t> part_x, st_x, res, dlen; Piece<CdSeg> segs, psegs; Piece<char> s_raw;
     RCCHK(ws_carve(h, [&](Carve &w) {
         dc = w.take<double>(cells); dc2 = w.take<double>(cells); s_raw = w.take<char>(cells * esz, !in_dev);
         segs = w.take<CdSeg>(2 * n); psegs = w.take<CdSeg>(n);
@@ -252,13 +281,12 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
         dlen = w.take<int32_t>(n);
     }));
     const void *draw;
-    RCCHK(stage_in(h, flags, raw, s_raw, cells * esz, &draw));
-    RCCHK(h2d(h, dlen, len, n * 4));
+    RCCHK(stage_in(h, flags, raw, s_raw, &draw));
+    RCCHK(h2d(h, dlen, len));
     const CdArgs a = {min_obs_adapter, border_trim, min_obs_polya, polya ? 1 : 0};
     const int rb = (n_reads + 255) / 256;
     { Scope s(h, "k_trace_cumsum");
-      if (f32) hipLaunchKernelGGL(k_trace_cumsum<float>, dim3(n_reads), dim3(64), 0, h->stream, (const float *)draw, dlen, L, n_reads, dc, dc2);
-      else hipLaunchKernelGGL(k_trace_cumsum<double>, dim3(n_reads), dim3(64), 0, h->stream, (const double *)draw, dlen, L, n_reads, dc, dc2); }
+      by_elem(!f32, draw, [&](auto sig) { hipLaunchKernelGGL(k_trace_cumsum<elem_t<decltype(sig)>>, dim3(n_reads), dim3(64), 0, h->stream, sig, dlen, L, n_reads, dc, dc2); }); }
     { Scope s(h, "k_cd_plan");
       hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 0, dlen, n_reads, a, st_x, segs); }
     cd_splits(h, dc, dc2, L, segs, n_reads, part_g, part_x, st_x, st_g);
@@ -266,8 +294,7 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
       hipLaunchKernelGGL(k_cd_plan, dim3(rb), dim3(256), 0, h->stream, 1, dlen, n_reads, a, st_x, segs); }
     cd_splits(h, dc, dc2, L, segs, 2 * n_reads, part_g, part_x, st_x, st_g);
     { Scope s(h, "k_cd_medians");
-      if (f32) hipLaunchKernelGGL(k_cd_medians<float>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const float *)draw, dlen, L, a, st_x, st_g, res, med, psegs);
-      else hipLaunchKernelGGL(k_cd_medians<double>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, (const double *)draw, dlen, L, a, st_x, st_g, res, med, psegs); }
+      by_elem(!f32, draw, [&](auto sig) { hipLaunchKernelGGL(k_cd_medians<elem_t<decltype(sig)>>, dim3(n_reads), dim3(CD_MED_BLOCK), 0, h->stream, sig, dlen, L, a, st_x, st_g, res, med, psegs); }); }
     if (polya) {
         cd_splits(h, dc, dc2, L, psegs, n_reads, part_g, part_x, st_x, st_g);
         { Scope s(h, "k_cd_finish");
@@ -276,12 +303,12 @@ int adp_c_llr_detect(adp_handle *h, const void *raw, const int32_t *len, int n_r
     HIPCHK(hipGetLastError());
     std::vector<int32_t> hres(n * 4), sx;
     std::vector<double> sg, hmed;
-    RCCHK(d2h(h, hres.data(), res, n * 16));
-    if (splits_out) { sx.resize(n * 4); RCCHK(d2h(h, sx.data(), st_x, n * 16)); }
+    RCCHK(d2h(h, hres.data(), res));
+    if (splits_out) { sx.resize(n * 4); RCCHK(d2h(h, sx.data(), st_x)); }
     if (stats_out) {
         sg.resize(n * 4); hmed.resize(n * 4);
-        RCCHK(d2h(h, sg.data(), st_g, n * 32));
-        RCCHK(d2h(h, hmed.data(), med, n * 32));
+        RCCHK(d2h(h, sg.data(), st_g));
+        RCCHK(d2h(h, hmed.data(), med));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < hres.size(); i++) rows_out[i] = hres[i];
@@ -312,22 +339,22 @@ int adp_llr_trace_bounds(adp_handle *h, double *trace, const int32_t *len, const
     if (stride < 1) { g_err = "stride must be >= 1"; return ADP_ERR_INVALID; }
     if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
     RCCHK(begin_call(h));
-    const size_t n = n_reads, mat = (size_t)L * 8 * n;
-    double *s_tr; int32_t *dlen, *dmo, *dtt, *ds, *de, *des;
+    const size_t n = n_reads;
+    Piece<double> s_tr; Piece<int32_t> dlen, dmo, dtt, ds, de, des;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
         dlen = w.take<int32_t>(n); dmo = w.take<int32_t>(n); dtt = w.take<int32_t>(n);
         ds = w.take<int32_t>(n); de = w.take<int32_t>(n); des = w.take<int32_t>(n);
     }));
     const double *dtr;
-    RCCHK(stage_in(h, flags, trace, s_tr, mat, &dtr));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dmo, min_obs, n * 4)); RCCHK(h2d(h, dtt, tail_trim, n * 4));
+    RCCHK(stage_in<double>(h, flags, trace, s_tr, &dtr));
+    RCCHK(h2d(h, dlen, len)); RCCHK(h2d(h, dmo, min_obs)); RCCHK(h2d(h, dtt, tail_trim));
     const int interp = (flags & ADP_LLR_INTERP) && stride > 1;
     { Scope s(h, "k_trace_bounds");
       hipLaunchKernelGGL(k_trace_bounds, dim3(n_reads), dim3(64), 0, h->stream, const_cast<double *>(dtr), dlen, L, dmo, dtt, stride, interp, ds, de, des); }
     HIPCHK(hipGetLastError());
-    if (interp && !(flags & ADP_IN_DEVICE)) RCCHK(d2h(h, trace, dtr, mat));
-    RCCHK(d2h(h, start_out, ds, n * 4)); RCCHK(d2h(h, end_out, de, n * 4)); RCCHK(d2h(h, early_stop_out, des, n * 4));
+    if (interp && !(flags & ADP_IN_DEVICE)) RCCHK(d2h(h, trace, s_tr));
+    RCCHK(d2h(h, start_out, ds)); RCCHK(d2h(h, end_out, de)); RCCHK(d2h(h, early_stop_out, des));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -346,7 +373,7 @@ int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, 
     RCCHK(begin_call(h));
     const size_t n = n_reads;
     const int nsum = (L + SUMBLK - 1) / SUMBLK;
-    double *s_tr, *bx, *bn; int32_t *dlen, *dlo, *dhi; int64_t *dcnt, *dpk;
+    Piece<double> s_tr, bx, bn; Piece<int32_t> dlen, dlo, dhi; Piece<int64_t> dcnt, dpk;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
         dlen = w.take<int32_t>(n); dlo = w.take<int32_t>(n); dhi = w.take<int32_t>(n);
@@ -354,14 +381,14 @@ int adp_llr_trace_peaks(adp_handle *h, const double *trace, const int32_t *len, 
         bx = w.take<double>(nsum * n); bn = w.take<double>(nsum * n);
     }));
     const double *dtr;
-    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dlo, clip_lo, n * 4)); RCCHK(h2d(h, dhi, clip_hi, n * 4));
+    RCCHK(stage_in(h, flags, trace, s_tr, &dtr));
+    RCCHK(h2d(h, dlen, len)); RCCHK(h2d(h, dlo, clip_lo)); RCCHK(h2d(h, dhi, clip_hi));
     trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 0, bx, bn);
     { Scope s(h, "k_trace_peaks");
       hipLaunchKernelGGL(k_trace_peaks, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, dlo, dhi, bx, bn, nsum, a, given, cap, dpk, dcnt); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, count_out, dcnt, n * 8));
-    RCCHK(d2h(h, peaks_out, dpk, n * 8 * cap));
+    RCCHK(d2h(h, count_out, dcnt));
+    RCCHK(d2h(h, peaks_out, dpk));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -378,8 +405,8 @@ int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, i
     RCCHK(begin_call(h));
     const size_t n = n_reads;
     const int nsum = (L + SUMBLK - 1) / SUMBLK, half = L / 2 + 1;
-    double *s_tr, *bx, *bn; int32_t *dlen; int64_t *dres;
-    uint32_t *pk, *wl; // the maxima and the work lists of k_trace_spike, half entries per read each
+    Piece<double> s_tr, bx, bn; Piece<int32_t> dlen; Piece<int64_t> dres;
+    Piece<uint32_t> pk, wl; // the maxima and the work lists of k_trace_spike, half entries per read each
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_tr = w.take<double>((size_t)L * n, !(flags & ADP_IN_DEVICE));
         dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
@@ -387,13 +414,13 @@ int adp_llr_spike_peak(adp_handle *h, const double *trace, const int32_t *len, i
         pk = w.take<uint32_t>(half * n); wl = w.take<uint32_t>(half * n);
     }));
     const double *dtr;
-    RCCHK(stage_in(h, flags, trace, s_tr, (size_t)L * 8 * n, &dtr));
-    RCCHK(h2d(h, dlen, len, n * 4));
+    RCCHK(stage_in(h, flags, trace, s_tr, &dtr));
+    RCCHK(h2d(h, dlen, len));
     trace_blocksum(h, dtr, dlen, n_reads, L, nsum, 1, bx, bn);
     { Scope s(h, "k_trace_spike");
       hipLaunchKernelGGL(k_trace_spike, dim3(n_reads), dim3(64), 0, h->stream, dtr, dlen, L, bx, bn, nsum, a, dist, pk, wl, half, dres); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, out, dres, n * 8));
+    RCCHK(d2h(h, out, dres));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -430,25 +457,21 @@ int adp_mvs_check(adp_handle *h, const void *sig, const int32_t *len, const int6
 {
     if (!h || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(mv_check_args(sig, len, n_reads, L, args, {adapter_end, polya_end}));
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
-    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dae, *dpe; double *dvals;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dae = w.take<int64_t>(n); dpe = w.take<int64_t>(n);
+    const size_t n = n_reads;
+    RowsIn in; size_t slots; Piece<char> scr; Piece<int32_t> dinfo; Piece<int64_t> dae, dpe; Piece<double> dvals;
+    RCCHK(rows_begin(h, sig, len, n_reads, L, flags, in, [&](Carve &w) {
+        slots = mv_slots(n_reads, L, in.esz);
+        dae = w.take<int64_t>(n); dpe = w.take<int64_t>(n);
         dinfo = w.take<int32_t>(n * 8); dvals = w.take<double>(n * 5);
-        scr = w.take<char>(slots * 2 * L * esz);
+        scr = w.take<char>(slots * 2 * L * in.esz);
     }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dae, adapter_end, n * 8)); RCCHK(h2d(h, dpe, polya_end, n * 8));
+    RCCHK(h2d(h, dae, adapter_end)); RCCHK(h2d(h, dpe, polya_end));
     { Scope s(h, "k_mvs_check");
-      if (f64) hipLaunchKernelGGL(k_mvs_check<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dae, dpe, *args, (double *)scr, dinfo, dvals);
-      else hipLaunchKernelGGL(k_mvs_check<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dae, dpe, *args, (float *)scr, dinfo, dvals); }
+      by_elem(in.f64, in.ds, [&](auto sig) { using T = elem_t<decltype(sig)>;
+          hipLaunchKernelGGL(k_mvs_check<T>, dim3(slots), dim3(64), 0, h->stream, sig, in.dlen, n_reads, L, dae, dpe, *args, (T *)scr.p, dinfo, dvals); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, info_out, dinfo, n * 32));
-    RCCHK(d2h(h, vals_out, dvals, n * 40));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, vals_out, dvals));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -458,26 +481,22 @@ int adp_mvs_detect_at_loc(adp_handle *h, const void *sig, const int32_t *len, co
 {
     if (!h || !info_out || !idx_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(mv_check_args(sig, len, n_reads, L, args, {loc}));
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
-    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dloc, *didx; double *dvals;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dloc = w.take<int64_t>(n);
+    const size_t n = n_reads;
+    RowsIn in; size_t slots; Piece<char> scr; Piece<int32_t> dinfo; Piece<int64_t> dloc, didx; Piece<double> dvals;
+    RCCHK(rows_begin(h, sig, len, n_reads, L, flags, in, [&](Carve &w) {
+        slots = mv_slots(n_reads, L, in.esz);
+        dloc = w.take<int64_t>(n);
         dinfo = w.take<int32_t>(n * 8); didx = w.take<int64_t>(n); dvals = w.take<double>(n * 5);
-        scr = w.take<char>(slots * 2 * L * esz);
+        scr = w.take<char>(slots * 2 * L * in.esz);
     }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dloc, loc, n * 8));
+    RCCHK(h2d(h, dloc, loc));
     { Scope s(h, "k_mvs_at_loc");
-      if (f64) hipLaunchKernelGGL(k_mvs_at_loc<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dloc, *args, (double *)scr, dinfo, didx, dvals);
-      else hipLaunchKernelGGL(k_mvs_at_loc<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dloc, *args, (float *)scr, dinfo, didx, dvals); }
+      by_elem(in.f64, in.ds, [&](auto sig) { using T = elem_t<decltype(sig)>;
+          hipLaunchKernelGGL(k_mvs_at_loc<T>, dim3(slots), dim3(64), 0, h->stream, sig, in.dlen, n_reads, L, dloc, *args, (T *)scr.p, dinfo, didx, dvals); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, info_out, dinfo, n * 32));
-    RCCHK(d2h(h, idx_out, didx, n * 8));
-    RCCHK(d2h(h, vals_out, dvals, n * 40));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, idx_out, didx));
+    RCCHK(d2h(h, vals_out, dvals));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -490,24 +509,14 @@ int adp_mvs_detect(adp_handle *h, const void *sig, const int32_t *len, int n_rea
     if (args->min_obs_adapter < 0 || args->min_obs_post_loc < 0 || args->s_median_shift_window < 0 || args->s_polyA_window < 0) {
         g_err = "min_obs_adapter, min_obs_post_loc and the windows must be >= 0"; return ADP_ERR_INVALID;
     }
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, esz = f64 ? 8 : 4;
-    void *s_sig; int32_t *dlen; int64_t *dres;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dres = w.take<int64_t>(n);
-    }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4));
+    RowsIn in; Piece<int64_t> dres;
+    RCCHK(rows_begin(h, sig, len, n_reads, L, flags, in, [&](Carve &w) { dres = w.take<int64_t>(n_reads); }));
     // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
     const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
     { Scope s(h, "k_mvs_stream");
-      if (f64) hipLaunchKernelGGL(k_mvs_stream<double>, dim3(grid), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, *args, dres);
-      else hipLaunchKernelGGL(k_mvs_stream<float>, dim3(grid), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, *args, dres); }
+      by_elem(in.f64, in.ds, [&](auto sig) { hipLaunchKernelGGL(k_mvs_stream<elem_t<decltype(sig)>>, dim3(grid), dim3(64), 0, h->stream, sig, in.dlen, n_reads, L, *args, dres); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, out, dres, n * 8));
+    RCCHK(d2h(h, out, dres));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -521,24 +530,14 @@ int adp_seg_stats(adp_handle *h, const void *sig, const int32_t *len, int n_read
 {
     if (!h || !stats_out || !count_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
-    void *s_sig; int32_t *dlen; SsSeg *dsegs; double *dstats; int64_t *dcnt;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns);
-        dstats = w.take<double>(ns * 4); dcnt = w.take<int64_t>(ns);
-    }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    const size_t ns = n_seg;
+    SegIn in; Piece<double> dstats; Piece<int64_t> dcnt;
+    RCCHK(seg_begin(h, sig, len, n_reads, L, segs, n_seg, flags, in, [&](Carve &w) { dstats = w.take<double>(ns * 4); dcnt = w.take<int64_t>(ns); }));
     { Scope s(h, "k_seg_stats");
-      if (f64) hipLaunchKernelGGL(k_seg_stats<double>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, dstats, dcnt);
-      else hipLaunchKernelGGL(k_seg_stats<float>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, dstats, dcnt); }
+      by_elem(in.f64, in.ds, [&](auto sig) { hipLaunchKernelGGL(k_seg_stats<elem_t<decltype(sig)>>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, sig, in.dlen, n_reads, L, in.dsegs, n_seg, dstats, dcnt); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, stats_out, dstats, ns * 32));
-    RCCHK(d2h(h, count_out, dcnt, ns * 8));
+    RCCHK(d2h(h, stats_out, dstats));
+    RCCHK(d2h(h, count_out, dcnt));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -561,19 +560,18 @@ int adp_med_mad(adp_handle *h, const void *sig, const int32_t *len, int n_reads,
     RCCHK(begin_call(h));
     const bool f64 = (flags & ADP_MVS_F64) != 0, whole = (flags & ADP_SS_WHOLE) != 0;
     const size_t n = n_reads, esz = f64 ? 8 : 4, rows = whole ? 1 : n;
-    void *s_sig; int32_t *dlen; double *dmm; SsPop *dst; uint32_t *dhist;
+    Piece<char> s_sig; Piece<int32_t> dlen; Piece<double> dmm; Piece<SsPop> dst; Piece<uint32_t> dhist;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
         dlen = w.take<int32_t>(n); dmm = w.take<double>(rows * 2); dst = w.take<SsPop>(1); dhist = w.take<uint32_t>(512);
     }));
     const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
+    RCCHK(stage_in(h, flags, sig, s_sig, &ds));
     const int32_t total = (int32_t)((long long)n_reads * L * (whole ? 1 : 0));
-    if (whole) RCCHK(h2d(h, dlen, &total, 4)); else RCCHK(h2d(h, dlen, len, n * 4));
-    if (f64) RCCHK(ss_med_mad_dev(h, (const double *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
-    else RCCHK(ss_med_mad_dev(h, (const float *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
+    if (whole) RCCHK(h2d(h, dlen, &total, 1)); else RCCHK(h2d(h, dlen, len));
+    RCCHK(by_elem(f64, ds, [&](auto sig) { return ss_med_mad_dev(h, sig, dlen, n_reads, L, flags, dmm, dst, dhist); }));
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, out, dmm, rows * 16));
+    RCCHK(d2h(h, out, dmm));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -589,28 +587,27 @@ int adp_normalize(adp_handle *h, const void *sig, const int32_t *len, int n_read
     if ((long long)n_reads * nbx > 0x7fffffffLL) { g_err = "too many rows"; return ADP_ERR_INVALID; }
     RCCHK(begin_call(h));
     const size_t n = n_reads, esz = f64 ? 8 : 4, rows = whole ? 1 : n, mat = (size_t)L * esz * n;
-    void *s_sig, *w_out; int32_t *dlen, *dstat; double *dmm; SsPop *dst; uint32_t *dhist;
+    Piece<char> s_sig, w_out; Piece<int32_t> dlen, dstat; Piece<double> dmm; Piece<SsPop> dst; Piece<uint32_t> dhist;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_sig = w.take<char>(mat, !(flags & ADP_IN_DEVICE)); w_out = w.take<char>(mat, !out_dev);
         dlen = w.take<int32_t>(n); dstat = w.take<int32_t>(rows); dmm = w.take<double>(rows * 2); dst = w.take<SsPop>(1); dhist = w.take<uint32_t>(512);
     }));
     const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, mat, &ds));
+    RCCHK(stage_in(h, flags, sig, s_sig, &ds));
     const int32_t total = (int32_t)((long long)n_reads * L * (whole ? 1 : 0));
-    if (whole) RCCHK(h2d(h, dlen, &total, 4)); else RCCHK(h2d(h, dlen, len, n * 4));
-    if (clip) RCCHK(h2d(h, dmm, medmad_io, rows * 16));
-    else if (f64) RCCHK(ss_med_mad_dev(h, (const double *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
-    else RCCHK(ss_med_mad_dev(h, (const float *)ds, dlen, n_reads, L, flags, dmm, dst, dhist));
-    void *dout = out_dev ? out : w_out;
-    if (!out_dev) HIPCHK(hipMemsetAsync(dout, 0, mat, h->stream)); // (cells behind a read's end, rows of MAD 0: zeros on the host)
-    const int32_t *klen = whole ? nullptr : dlen;
+    if (whole) RCCHK(h2d(h, dlen, &total, 1)); else RCCHK(h2d(h, dlen, len));
+    if (clip) RCCHK(h2d(h, dmm, medmad_io));
+    else RCCHK(by_elem(f64, ds, [&](auto sig) { return ss_med_mad_dev(h, sig, dlen, n_reads, L, flags, dmm, dst, dhist); }));
+    void *dout = out_dev ? out : w_out.p;
+    if (!out_dev) RCCHK(zero(h, w_out)); // (cells behind a read's end, rows of MAD 0: zeros on the host)
+    const int32_t *klen = whole ? nullptr : dlen.p;
     { Scope s(h, "k_clip_scale");
-      if (f64) hipLaunchKernelGGL(k_clip_scale<double>, dim3((unsigned)(n * nbx)), dim3(256), 0, h->stream, (const double *)ds, klen, (long long)L, dmm, outlier_thresh, whole ? 1 : 0, clip ? 1 : 0, nbx, (double *)dout, dstat);
-      else hipLaunchKernelGGL(k_clip_scale<float>, dim3((unsigned)(n * nbx)), dim3(256), 0, h->stream, (const float *)ds, klen, (long long)L, dmm, outlier_thresh, whole ? 1 : 0, clip ? 1 : 0, nbx, (float *)dout, dstat); }
+      by_elem(f64, ds, [&](auto sig) { using T = elem_t<decltype(sig)>;
+          hipLaunchKernelGGL(k_clip_scale<T>, dim3((unsigned)(n * nbx)), dim3(256), 0, h->stream, sig, klen, (long long)L, dmm, outlier_thresh, whole ? 1 : 0, clip ? 1 : 0, nbx, (T *)dout, dstat); }); }
     HIPCHK(hipGetLastError());
-    if (!out_dev) RCCHK(d2h(h, out, dout, mat));
-    if (!clip) RCCHK(d2h(h, medmad_io, dmm, rows * 16));
-    RCCHK(d2h(h, status_out, dstat, rows * 4));
+    if (!out_dev) RCCHK(d2h(h, out, w_out));
+    if (!clip) RCCHK(d2h(h, medmad_io, dmm));
+    RCCHK(d2h(h, status_out, dstat));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -626,22 +623,22 @@ int adp_pool_mean(adp_handle *h, const void *data, int n_rows, int n_cols, int p
     if (grid > 0x7fffffffLL) { g_err = "too many outputs for one call"; return ADP_ERR_INVALID; }
     RCCHK(begin_call(h));
     const size_t esz = f64 ? 8 : 4, in_b = (size_t)n_rows * n_cols * esz, out_b = (size_t)n_rows * n_out * esz;
-    void *s_in, *w_out;
+    Piece<char> s_in, w_out;
     RCCHK(ws_carve(h, [&](Carve &w) { s_in = w.take<char>(in_b, !(flags & ADP_IN_DEVICE)); w_out = w.take<char>(out_b, !out_dev); }));
     const void *dd;
-    RCCHK(stage_in(h, flags, data, s_in, in_b, &dd));
-    void *dout = out_dev ? out : w_out;
+    RCCHK(stage_in(h, flags, data, s_in, &dd));
+    void *dout = out_dev ? out : w_out.p;
     if (pool_size <= 128) {
         Scope s(h, "k_pool_mean");
-        if (f64) hipLaunchKernelGGL(k_pool_mean<double>, dim3((unsigned)grid), dim3(256), 0, h->stream, (const double *)dd, n_rows, (long long)n_cols, pool_size, n_out, nbx, (double *)dout);
-        else hipLaunchKernelGGL(k_pool_mean<float>, dim3((unsigned)grid), dim3(256), 0, h->stream, (const float *)dd, n_rows, (long long)n_cols, pool_size, n_out, nbx, (float *)dout);
+        by_elem(f64, dd, [&](auto in) { using T = elem_t<decltype(in)>;
+            hipLaunchKernelGGL(k_pool_mean<T>, dim3((unsigned)grid), dim3(256), 0, h->stream, in, n_rows, (long long)n_cols, pool_size, n_out, nbx, (T *)dout); });
     } else {
         Scope s(h, "k_pool_mean_wave");
-        if (f64) hipLaunchKernelGGL(k_pool_mean_wave<double>, dim3((unsigned)grid), dim3(64), 0, h->stream, (const double *)dd, n_rows, (long long)n_cols, pool_size, n_out, (double *)dout);
-        else hipLaunchKernelGGL(k_pool_mean_wave<float>, dim3((unsigned)grid), dim3(64), 0, h->stream, (const float *)dd, n_rows, (long long)n_cols, pool_size, n_out, (float *)dout);
+        by_elem(f64, dd, [&](auto in) { using T = elem_t<decltype(in)>;
+            hipLaunchKernelGGL(k_pool_mean_wave<T>, dim3((unsigned)grid), dim3(64), 0, h->stream, in, n_rows, (long long)n_cols, pool_size, n_out, (T *)dout); });
     }
     HIPCHK(hipGetLastError());
-    if (!out_dev) RCCHK(d2h(h, out, dout, out_b));
+    if (!out_dev) RCCHK(d2h(h, out, w_out));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -652,23 +649,14 @@ int adp_real_range(adp_handle *h, const void *sig, const int32_t *len, int n_rea
     if (!h || !args || !info_out || !vals_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
     if (args->mean_window < 1 || args->max_obs_local_range < 1) { g_err = "mean_window and max_obs_local_range must be >= 1"; return ADP_ERR_INVALID; }
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
-    void *s_sig; int32_t *dlen, *dinfo; SsSeg *dsegs; double *dvals;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns); dinfo = w.take<int32_t>(ns * 2); dvals = w.take<double>(ns * 3);
-    }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    const size_t ns = n_seg;
+    SegIn in; Piece<int32_t> dinfo; Piece<double> dvals;
+    RCCHK(seg_begin(h, sig, len, n_reads, L, segs, n_seg, flags, in, [&](Carve &w) { dinfo = w.take<int32_t>(ns * 2); dvals = w.take<double>(ns * 3); }));
     { Scope s(h, "k_real_range");
-      if (f64) hipLaunchKernelGGL(k_real_range<double>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, *args, dinfo, dvals);
-      else hipLaunchKernelGGL(k_real_range<float>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, *args, dinfo, dvals); }
+      by_elem(in.f64, in.ds, [&](auto sig) { hipLaunchKernelGGL(k_real_range<elem_t<decltype(sig)>>, dim3(n_seg), dim3(SS_BLOCK), 0, h->stream, sig, in.dlen, n_reads, L, in.dsegs, n_seg, *args, dinfo, dvals); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, info_out, dinfo, ns * 8));
-    RCCHK(d2h(h, vals_out, dvals, ns * 24));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, vals_out, dvals));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -679,23 +667,14 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
     if (!h || !pos_out || !count_out || cap < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
     if (lo != lo || hi != hi || min_obs_diff != min_obs_diff) { g_err = "the range and min_obs_diff must be numbers"; return ADP_ERR_INVALID; }
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
-    void *s_sig; int32_t *dlen; SsSeg *dsegs; int64_t *dpos, *dcnt;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dsegs = w.take<SsSeg>(ns); dpos = w.take<int64_t>(ns * cap); dcnt = w.take<int64_t>(ns * 3);
-    }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4)); RCCHK(h2d(h, dsegs, segs, ns * sizeof(SsSeg)));
+    const size_t ns = n_seg;
+    SegIn in; Piece<int64_t> dpos, dcnt;
+    RCCHK(seg_begin(h, sig, len, n_reads, L, segs, n_seg, flags, in, [&](Carve &w) { dpos = w.take<int64_t>(ns * cap); dcnt = w.take<int64_t>(ns * 3); }));
     { Scope s(h, "k_open_pores");
-      if (f64) hipLaunchKernelGGL(k_open_pores<double>, dim3(n_seg), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, dsegs, n_seg, lo, hi, min_obs_diff, cap, dpos, dcnt);
-      else hipLaunchKernelGGL(k_open_pores<float>, dim3(n_seg), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, dsegs, n_seg, lo, hi, min_obs_diff, cap, dpos, dcnt); }
+      by_elem(in.f64, in.ds, [&](auto sig) { hipLaunchKernelGGL(k_open_pores<elem_t<decltype(sig)>>, dim3(n_seg), dim3(64), 0, h->stream, sig, in.dlen, n_reads, L, in.dsegs, n_seg, lo, hi, min_obs_diff, cap, dpos, dcnt); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
-    RCCHK(d2h(h, count_out, dcnt, ns * 24));
+    RCCHK(d2h(h, pos_out, dpos));
+    RCCHK(d2h(h, count_out, dcnt));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -712,25 +691,16 @@ int adp_start_peak(adp_handle *h, const void *sig, const int32_t *full_len, int 
     if (!all_in<int32_t>(full_len, n_reads, 0, INT32_MAX)) { g_err = "need full_len >= 0 for every read"; return ADP_ERR_INVALID; }
     if (args->downscale_factor < 1) { g_err = "downscale_factor must be >= 1"; return ADP_ERR_INVALID; }
     if (args->offset1 < 0 || args->offset2 < 0 || args->start_peak_max_idx < 0) { g_err = "offset1, offset2 and start_peak_max_idx must be >= 0"; return ADP_ERR_INVALID; }
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, esz = f64 ? 8 : 4;
-    void *s_sig; int32_t *dlen, *dinfo; double *dvals;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)m * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dinfo = w.take<int32_t>(n * 5); dvals = w.take<double>(n * 2);
-    }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)m * esz * n, &ds));
-    RCCHK(h2d(h, dlen, full_len, n * 4));
+    const size_t n = n_reads;
+    RowsIn in; Piece<int32_t> dinfo; Piece<double> dvals;
+    RCCHK(rows_begin(h, sig, full_len, n_reads, m, flags, in, [&](Carve &w) { dinfo = w.take<int32_t>(n * 5); dvals = w.take<double>(n * 2); }));
     // (one wave per read: a persistent grid of at most 16 waves per CU takes longer batches)
     const int grid = n_reads < h->n_cu * 16 ? n_reads : h->n_cu * 16;
     { Scope s(h, "k_startpeak_mod");
-      if (f64) hipLaunchKernelGGL(k_startpeak_mod<double>, dim3(grid), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, m, *args, dinfo, dvals);
-      else hipLaunchKernelGGL(k_startpeak_mod<float>, dim3(grid), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, m, *args, dinfo, dvals); }
+      by_elem(in.f64, in.ds, [&](auto sig) { hipLaunchKernelGGL(k_startpeak_mod<elem_t<decltype(sig)>>, dim3(grid), dim3(64), 0, h->stream, sig, in.dlen, n_reads, m, *args, dinfo, dvals); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, info_out, dinfo, n * 20));
-    RCCHK(d2h(h, vals_out, dvals, n * 16));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, vals_out, dvals));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -742,27 +712,21 @@ int adp_adapter_start(adp_handle *h, const void *sig, const int32_t *len, int n_
     if (!lens_ok(len, n_reads, L)) { g_err = "need 0 <= len <= L for every read"; return ADP_ERR_INVALID; }
     if (args->window < 1) { g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID; }
     if (args->min_obs_adapter < 0) { g_err = "min_obs_adapter must be >= 0"; return ADP_ERR_INVALID; }
-    RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    // (a slot holds both series of one read, as the MVS series kernels' do: the same byte budget)
-    const size_t n = n_reads, esz = f64 ? 8 : 4, slots = mv_slots(n_reads, L, esz);
-    void *s_sig, *scr; int32_t *dlen, *dinfo; int64_t *dout, *dcand; double *ddiff;
-    RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
-        dlen = w.take<int32_t>(n); dinfo = w.take<int32_t>(n * 4); dout = w.take<int64_t>(n); dcand = w.take<int64_t>(n); ddiff = w.take<double>(n);
-        scr = w.take<char>(slots * 2 * L * esz);
+    const size_t n = n_reads;
+    RowsIn in; size_t slots; Piece<char> scr; Piece<int32_t> dinfo; Piece<int64_t> dout, dcand; Piece<double> ddiff;
+    RCCHK(rows_begin(h, sig, len, n_reads, L, flags, in, [&](Carve &w) {
+        slots = mv_slots(n_reads, L, in.esz); // (a slot holds both series of one read, as the MVS series kernels' do: the same byte budget)
+        dinfo = w.take<int32_t>(n * 4); dout = w.take<int64_t>(n); dcand = w.take<int64_t>(n); ddiff = w.take<double>(n);
+        scr = w.take<char>(slots * 2 * L * in.esz);
     }));
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dlen, len, n * 4));
     { Scope s(h, "k_adapter_start");
-      if (f64) hipLaunchKernelGGL(k_adapter_start<double>, dim3(slots), dim3(64), 0, h->stream, (const double *)ds, dlen, n_reads, L, *args, (double *)scr, dinfo, dout, dcand, ddiff);
-      else hipLaunchKernelGGL(k_adapter_start<float>, dim3(slots), dim3(64), 0, h->stream, (const float *)ds, dlen, n_reads, L, *args, (float *)scr, dinfo, dout, dcand, ddiff); }
+      by_elem(in.f64, in.ds, [&](auto sig) { using T = elem_t<decltype(sig)>;
+          hipLaunchKernelGGL(k_adapter_start<T>, dim3(slots), dim3(64), 0, h->stream, sig, in.dlen, n_reads, L, *args, (T *)scr.p, dinfo, dout, dcand, ddiff); }); }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, info_out, dinfo, n * 16));
-    RCCHK(d2h(h, out, dout, n * 8));
-    RCCHK(d2h(h, cand_out, dcand, n * 8));
-    RCCHK(d2h(h, diff_out, ddiff, n * 8));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, out, dout));
+    RCCHK(d2h(h, cand_out, dcand));
+    RCCHK(d2h(h, diff_out, ddiff));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -804,17 +768,17 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
     // a slot: the scores of one segment and its two lists of maxima; slots within a byte budget -- EV_SCRATCH_MIB, as the series
     // kernels' (mv_slots), or ADP_EVENTS_SCRATCH_MIB from the environment, read per call -- and batches of slots
     const size_t stride = ((size_t)(lmax > 0 ? lmax : 1) + 1) & ~(size_t)1, half = stride / 2 + 1;
-    long long mib = EV_SCRATCH_MIB;
-    if (const char *v = getenv("ADP_EVENTS_SCRATCH_MIB")) { mib = atoll(v); if (mib < 1 || mib > (1 << 20)) { g_err = "ADP_EVENTS_SCRATCH_MIB must lie in [1, 2^20]"; return ADP_ERR_INVALID; } }
+    long long mib;
+    RCCHK(scratch_mib("ADP_EVENTS_SCRATCH_MIB", getenv("ADP_EVENTS_SCRATCH_MIB"), EV_SCRATCH_MIB, &mib));
     size_t slots = ((size_t)mib << 20) / (stride * 8 + half * 8);
     if (slots < 1) slots = 1;
     if (slots > ns) slots = ns;
     if (slots > 32768) slots = 32768;
-    void *s_sig; EvSeg *dsegs; int32_t *dnan; double *dscore, *dstats; uint32_t *pk, *wl; int64_t *dpos, *dinfo;
+    Piece<char> s_sig; Piece<EvSeg> dsegs; Piece<int32_t> dnan; Piece<double> dscore, dstats; Piece<uint32_t> pk, wl; Piece<int64_t> dpos, dinfo;
     // (the event tables: in the workspace, but for the two that stay on the device with ADP_OUT_DEVICE)
     const bool lv_dev = lv && (flags & ADP_OUT_DEVICE);
     const size_t E = lv ? lv->E : 0;
-    int32_t *dcount = nullptr, *dfst = nullptr, *dlens = nullptr; double *dlev = nullptr, *dfp = nullptr, *dnorm = nullptr;
+    Piece<int32_t> dcount, dfst, dlens; Piece<double> dlev, dfp, dnorm;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
         dsegs = w.take<EvSeg>(ns); dnan = w.take<int32_t>(ns);
@@ -825,11 +789,11 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
             dlev = w.take<double>(ns * E); dfp = w.take<double>(ns * E, !lv_dev); dnorm = w.take<double>(ns * 2);
         }
     }));
-    if (lv_dev) { dcount = lv->count; dfp = lv->fp; }
+    int32_t *kcount = lv_dev ? lv->count : dcount.p; double *kfp = lv_dev ? lv->fp : dfp.p; // (what k_ev_levels writes)
     const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)L * esz * n, &ds));
-    RCCHK(h2d(h, dsegs, es.data(), ns * sizeof(EvSeg)));
-    HIPCHK(hipMemsetAsync(dnan, 0, ns * 4, h->stream));
+    RCCHK(stage_in(h, flags, sig, s_sig, &ds));
+    RCCHK(h2d(h, dsegs, es.data()));
+    RCCHK(zero(h, dnan));
     const adp_event_args &a = *args;
     for (size_t g0 = 0; g0 < ns; g0 += slots) {
         const size_t nb = ns - g0 < slots ? ns - g0 : slots;
@@ -838,27 +802,25 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
         const int ntile = (bmax + EV_TILE - 1) / EV_TILE;
         if (ntile > 0) {
             Scope s(h, "k_ev_scores");
-            if (f64) hipLaunchKernelGGL(k_ev_scores<double>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, (const double *)ds, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan);
-            else hipLaunchKernelGGL(k_ev_scores<float>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, (const float *)ds, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan);
+            by_elem(f64, ds, [&](auto sig) { hipLaunchKernelGGL(k_ev_scores<elem_t<decltype(sig)>>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, sig, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan); });
         }
         { Scope s(h, "k_ev_bounds");
           hipLaunchKernelGGL(k_ev_bounds, dim3((unsigned)nb), dim3(64), 0, h->stream, dscore, stride, dsegs, (int)g0, a.window, a.min_distance, a.threshold, cap, pk, wl, (int)half, dnan, dpos, dinfo, dstats); }
         if (lv) {
             Scope s(h, "k_ev_levels");
-            if (f64) hipLaunchKernelGGL(k_ev_levels<double>, dim3((unsigned)nb), dim3(64), 0, h->stream, (const double *)ds, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, dcount, dfst, dlens, dlev, dfp, dnorm);
-            else hipLaunchKernelGGL(k_ev_levels<float>, dim3((unsigned)nb), dim3(64), 0, h->stream, (const float *)ds, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, dcount, dfst, dlens, dlev, dfp, dnorm);
+            by_elem(f64, ds, [&](auto sig) { hipLaunchKernelGGL(k_ev_levels<elem_t<decltype(sig)>>, dim3((unsigned)nb), dim3(64), 0, h->stream, sig, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, kcount, dfst, dlens, dlev, kfp, dnorm); });
         }
     }
     HIPCHK(hipGetLastError());
-    if (cap > 0) RCCHK(d2h(h, pos_out, dpos, ns * 8 * cap));
-    RCCHK(d2h(h, info_out, dinfo, ns * 16));
-    RCCHK(d2h(h, stats_out, dstats, ns * 16));
+    if (cap > 0) RCCHK(d2h(h, pos_out, dpos));
+    RCCHK(d2h(h, info_out, dinfo));
+    RCCHK(d2h(h, stats_out, dstats));
     if (lv) {
-        RCCHK(d2h(h, lv->fpstatus, dfst, ns * 4));
-        if (!lv_dev) { RCCHK(d2h(h, lv->count, dcount, ns * 4)); RCCHK(d2h(h, lv->fp, dfp, ns * E * 8)); }
-        if (lv->lengths) RCCHK(d2h(h, lv->lengths, dlens, ns * E * 4));
-        if (lv->levels) RCCHK(d2h(h, lv->levels, dlev, ns * E * 8));
-        if (lv->norm) RCCHK(d2h(h, lv->norm, dnorm, ns * 16));
+        RCCHK(d2h(h, lv->fpstatus, dfst));
+        if (!lv_dev) { RCCHK(d2h(h, lv->count, dcount)); RCCHK(d2h(h, lv->fp, dfp)); }
+        if (lv->lengths) RCCHK(d2h(h, lv->lengths, dlens));
+        if (lv->levels) RCCHK(d2h(h, lv->levels, dlev));
+        if (lv->norm) RCCHK(d2h(h, lv->norm, dnorm));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
@@ -897,25 +859,25 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
     }
     // the distance matrix of a batch of queries within a byte budget: DTW_SCRATCH_MIB, or ADP_DTW_SCRATCH_MIB from the environment,
     // read per call
-    long long mib = DTW_SCRATCH_MIB;
-    if (const char *v = getenv("ADP_DTW_SCRATCH_MIB")) { mib = atoll(v); if (mib < 1 || mib > (1 << 20)) { g_err = "ADP_DTW_SCRATCH_MIB must lie in [1, 2^20]"; return ADP_ERR_INVALID; } }
+    long long mib;
+    RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
     const size_t nqs = nq, nts = nt;
     size_t rows = ((size_t)mib << 20) / (nts * 8);
     if (rows < 1) rows = 1;
     if (rows > nqs) rows = nqs;
     if (rows > (size_t)0x7fffffff / nts) rows = (size_t)0x7fffffff / nts; // (a workgroup per pair of the batch)
     RCCHK(begin_call(h));
-    double *s_q, *dt, *ddist, *dbd; int32_t *s_qc, *dtc, *dbest;
+    Piece<double> s_q, dt, ddist, dbd; Piece<int32_t> s_qc, dtc, dbest;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_q = w.take<double>(nqs * Eq, !(flags & ADP_IN_DEVICE)); s_qc = w.take<int32_t>(nqs, !(flags & ADP_IN_DEVICE));
         dt = w.take<double>(nts * Et); dtc = w.take<int32_t>(nts);
         ddist = w.take<double>(rows * nts); dbest = w.take<int32_t>(nqs * 2); dbd = w.take<double>(nqs * 2);
     }));
     const double *dq; const int32_t *dqc;
-    RCCHK(stage_in(h, flags, q, s_q, nqs * Eq * 8, &dq));
-    RCCHK(stage_in(h, flags, q_count, s_qc, nqs * 4, &dqc));
-    RCCHK(h2d(h, dt, t, nts * Et * 8));
-    RCCHK(h2d(h, dtc, t_count, nts * 4));
+    RCCHK(stage_in(h, flags, q, s_q, &dq));
+    RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
+    RCCHK(h2d(h, dt, t));
+    RCCHK(h2d(h, dtc, t_count));
     const int C = (Et + 63) / 64;
     for (size_t p0 = 0; p0 < nqs; p0 += rows) {
         const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
@@ -927,11 +889,11 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
           else hipLaunchKernelGGL(k_dtw<8>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist); }
         { Scope s(h, "k_dtw_best");
           hipLaunchKernelGGL(k_dtw_best, dim3((unsigned)((nb + 63) / 64)), block, 0, h->stream, ddist, (int)nb, nt, dbest + p0 * 2, dbd + p0 * 2); }
-        if (dist_out) RCCHK(d2h(h, dist_out + p0 * nts, ddist, nb * nts * 8));
+        if (dist_out) RCCHK(d2h(h, dist_out + p0 * nts, ddist, nb * nts));
     }
     HIPCHK(hipGetLastError());
-    RCCHK(d2h(h, best_out, dbest, nqs * 8));
-    RCCHK(d2h(h, bestdist_out, dbd, nqs * 16));
+    RCCHK(d2h(h, best_out, dbest));
+    RCCHK(d2h(h, bestdist_out, dbd));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -953,7 +915,7 @@ static int af_check(adp_handle *h, const void *sig, int n_reads, int m, const ad
 
 // a call's pieces of the workspace behind its staged signal: the rows (host rows only), the side outputs, the segments and their
 // statistics, and the detector's slots ([2, m] floats each, the series kernels' byte budget: mv_slots)
-struct AfBufs { adp_row *rows; int32_t *info; int64_t *shift, *cand, *cnt; double *diff, *stats; SsSeg *segs; float *scr; size_t slots; };
+struct AfBufs { Piece<adp_row> rows; Piece<int32_t> info; Piece<int64_t> shift, cand, cnt; Piece<double> diff, stats; Piece<SsSeg> segs; Piece<float> scr; size_t slots; };
 static void af_pieces(Carve &w, AfBufs &b, int n_reads, int m, bool rows_dev)
 {
     const size_t n = n_reads;
@@ -969,10 +931,9 @@ template <class Sig>
 static int af_run(adp_handle *h, Sig sig, int n_reads, int m, adp_row *rows, const adp_adapter_front_args *args, int flags, const AfBufs &b,
                   int32_t *info_out, int64_t *shift_out, int64_t *cand_out, double *diff_out)
 {
-    const size_t n = n_reads;
     const bool rows_dev = (flags & ADP_OUT_DEVICE) != 0;
-    adp_row *drows = rows_dev ? rows : b.rows;
-    if (!rows_dev) RCCHK(h2d(h, drows, rows, n * sizeof(adp_row)));
+    adp_row *drows = rows_dev ? rows : b.rows.p;
+    if (!rows_dev) RCCHK(h2d(h, b.rows, rows));
     { Scope s(h, "k_adapter_front");
       hipLaunchKernelGGL(k_adapter_front<Sig>, dim3((unsigned)b.slots), dim3(64), 0, h->stream, sig, n_reads, m, drows, *args, b.scr, b.info, b.shift, b.cand, b.diff, b.segs); }
     { Scope s(h, "k_seg_stats_sig");
@@ -980,11 +941,11 @@ static int af_run(adp_handle *h, Sig sig, int n_reads, int m, adp_row *rows, con
     { Scope s(h, "k_adapter_front_patch");
       hipLaunchKernelGGL(k_adapter_front_patch, dim3((n_reads + 255) / 256), dim3(256), 0, h->stream, drows, n_reads, b.segs, b.stats); }
     HIPCHK(hipGetLastError());
-    if (!rows_dev) RCCHK(d2h(h, rows, drows, n * sizeof(adp_row)));
-    RCCHK(d2h(h, info_out, b.info, n * 16));
-    RCCHK(d2h(h, shift_out, b.shift, n * 8));
-    RCCHK(d2h(h, cand_out, b.cand, n * 8));
-    RCCHK(d2h(h, diff_out, b.diff, n * 8));
+    if (!rows_dev) RCCHK(d2h(h, rows, b.rows));
+    RCCHK(d2h(h, info_out, b.info));
+    RCCHK(d2h(h, shift_out, b.shift));
+    RCCHK(d2h(h, cand_out, b.cand));
+    RCCHK(d2h(h, diff_out, b.diff));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }
@@ -1001,13 +962,13 @@ int adp_adapter_front(adp_handle *h, const float *sig, const int32_t *full_len, 
     RCCHK(af_check(h, sig, n_reads, m, rows, args, info_out, shift_out, cand_out, diff_out));
     RCCHK(begin_call(h));
     AfBufs b;
-    float *s_sig;
+    Piece<float> s_sig;
     RCCHK(ws_carve(h, [&](Carve &w) {
         s_sig = w.take<float>((size_t)m * n_reads, !(flags & ADP_IN_DEVICE));
         af_pieces(w, b, n_reads, m, (flags & ADP_OUT_DEVICE) != 0);
     }));
     const float *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, (size_t)m * 4 * n_reads, &ds));
+    RCCHK(stage_in(h, flags, sig, s_sig, &ds));
     return af_run(h, SigF32{ds}, n_reads, m, rows, args, flags, b, info_out, shift_out, cand_out, diff_out);
 }
 
