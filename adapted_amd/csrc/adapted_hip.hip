@@ -2179,6 +2179,21 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         if (h->pt_looked) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_PT), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
+    // what the kernels of phase C hand to each other (llr_stream.h, peaks.h), each copy bounded by its buffer
+    case 13: src = h->ck.p; if (bytes > h->ck.cap) return ADP_ERR_INVALID; break;
+    case 14: src = h->tail.p; if (bytes > h->tail.cap) return ADP_ERR_INVALID; break;
+    case 15: src = h->bmax.p; if (bytes > h->bmax.cap) return ADP_ERR_INVALID; break;
+    case 16: src = h->bmin.p; if (bytes > h->bmin.cap) return ADP_ERR_INVALID; break;
+    case 17: src = h->gstat.p; if (bytes > h->gstat.cap) return ADP_ERR_INVALID; break;
+    case 18: src = h->npk.p; if (bytes > h->npk.cap) return ADP_ERR_INVALID; break;
+    case 19: src = h->pk.p; if (bytes > h->pk.cap) return ADP_ERR_INVALID; break;
+    case 20: // (a handle made with ADP_PK_VALUES=0 has no such buffer)
+        if (!h->pkv.p) { g_err = "this handle keeps no heights beside its maxima lists (ADP_PK_VALUES=0)"; return ADP_ERR_INVALID; }
+        src = h->pkv.p; if (bytes > h->pkv.cap) return ADP_ERR_INVALID; break;
+    case 21: { // the minibatches' status words (ADP_MB_*), as the kernels of the last plain call left them
+        if (h->last_grouped || !h->mbs.p || h->last_nmb < 1 || bytes > (uint64_t)h->last_nmb * 4 || h->gbelow.cap < (size_t)h->last_nmb * 4) return ADP_ERR_INVALID;
+        hipLaunchKernelGGL(k_mb_status_out, dim3((h->last_nmb + 255) / 256), dim3(256), 0, h->stream, h->mbs.as<MbState>(), h->last_nmb, h->gbelow.as<int32_t>());
+        src = h->gbelow.p; break; }
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;
               HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg), bytes, 0, hipMemcpyDeviceToHost));
               static unsigned long long tally[ADP_NTALLY][8];

@@ -1345,8 +1345,9 @@ class Engine:
         self._check(self.lib.adp_debug_log(self._h, x, y, x.size))
         return y
 
-    def debug_llr_upto(self, signals, full_lens, n, minibatch, stage):
+    def debug_llr_upto(self, signals, full_lens, n, minibatch, stage, tails_nan: bool = False):
         sig, lens, flags = self._in(signals, full_lens, n, False)
+        flags |= _flag_word(tails_nan=tails_nan)
         self._check(self.lib.adp_debug_llr_upto(self._h, sig, lens, n, self.m, int(minibatch), flags, int(stage)))
 
     def debug_fetch(self, what: int, n: int):
@@ -1355,8 +1356,12 @@ class Engine:
         Lp = int(lp[0])
         if what == 6:
             return Lp
+        # (the selectors are listed in include/adapted_hip.h; n: reads, or minibatches for 21)
         shapes = {1: ((n,), np.int32), 2: ((n, Lp), np.float32), 3: ((n, Lp), np.float64), 4: ((n,), np.int32),
-                  5: ((n,), np.int32), 7: ((n, 2), np.int32), 9: ((n,), np.int8)}
+                  5: ((n,), np.int32), 7: ((n, 2), np.int32), 9: ((n,), np.int8),
+                  13: ((n, Lp // 16, 2), np.float64), 14: ((n, 2), np.float64), 15: ((n, Lp // 64), np.float64),
+                  16: ((n, Lp // 64), np.float64), 17: ((n, 3), np.float64), 18: ((n,), np.int32),
+                  19: ((n, Lp // 2 + 1), np.int32), 20: ((n, Lp // 2 + 1), np.float64), 21: ((n,), np.int32)}
         if what == 0:
             raise ValueError("use debug_norm_params")
         shp, dt = shapes[what]

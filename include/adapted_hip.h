@@ -581,7 +581,17 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *       11 int32[4], the LLR second opinion of the last adp_detect_cnn call: reads selected, rows replaced, rows re-validated and
  *          still failing, minibatches (with a selected read) that gave none
  *       12 int32[3], the truncation look of the last adp_detect_llr / adp_detect_cnn call made with ADP_FLAG_TRUNCATED: eligible
- *          reads, reads whose tail window looks like poly(A) (T1), rows replaced */
+ *          reads, reads whose tail window looks like poly(A) (T1), rows replaced
+ *       9 int8[n], 1: the read's moving-window series were prepared by a series kernel
+ *       What phase C's kernels hand to each other (nck = Lp / 16, nsum = Lp / 64; a copy beyond the buffer is ADP_ERR_INVALID):
+ *       13 ck float64[n*nck*2]: (c, c2) in front of pooled sample 16 q, written for q < ceil(n_valid / 16);
+ *       14 tail float64[n*2]: (c, c2)[n_valid - 2]; 15 / 16 bmax / bmin float64[n*nsum]: the trace's maximum / minimum per 64
+ *       points, written for blocks below ceil(n_valid / 64) -- pass 1: NaN counts as +inf in bmax and is left out of bmin,
+ *       pass 2: of the np.nan_to_num trace; 17 gstat float64[n*3]: sum, sum of squares, NaN count of pass 1's trace;
+ *       18 npk int32[n]: strict local maxima of pass 2's sanitised trace, -1: a plateau was met (k_polya_peak recounts);
+ *       19 pk int32[n*(Lp/2+1)]: their positions; 20 pkv float64[n*(Lp/2+1)]: their heights (ADP_ERR_INVALID on a handle made
+ *       with ADP_PK_VALUES=0); 21 int32[n_minibatch]: the minibatches' status words.  Reads of a dropped minibatch and reads
+ *       whose pass did not run (no adapter candidate: pass 2) keep what an earlier call left. */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from golden_cases import CASES
+from llr_stream_oracle import t1 as oracle_start_end
 from util import INDEX_FIELDS, load_case, row_diffs
 
 pytestmark = pytest.mark.gpu
@@ -102,14 +103,6 @@ def test_llr_stages_vs_oracle(hip, oracle_mod, name):
         assert np.allclose(a[fin], b[fin], rtol=1e-9, atol=1e-9), k
         assert int(pidx[k]) == max(stages[k]["polya_idx"], 0), (k, int(pidx[k]), stages[k]["polya_idx"])
     eng.close()
-
-
-def oracle_start_end(g):
-    pos = ~(g <= 0)
-    if not pos.any():
-        return 0, g.size - 1
-    idx = np.flatnonzero(pos)
-    return int(idx[0]), int(idx[-1])
 
 
 @pytest.mark.parametrize("name", LLR_CASES)
