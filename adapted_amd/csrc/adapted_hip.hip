@@ -31,6 +31,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_fallback.h"
 #include "cnn_second_opinion.h"
 #include "polya_truncated.h"
+#include "adapter_front_revalidate.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -393,7 +394,8 @@ static int call_attempts(adp_handle *h, adp_handle *const *lanes, int n_lanes, F
 }
 
 // the resident matrix types of the detect calls' first passes: the whole matrix, one row per read of the launch (the long-slice
-// series kernels and the shared sweeps work on these; a subset read in place -- SigIdx, SigIdxI16 -- has one candidate per read)
+// series kernels and the shared sweeps work on these; a subset read in place -- SigIdx, SigIdxI16 -- has one candidate per read, or,
+// behind the re-validating front pass, the read's whole list without prepared statistics: k_validate's own series then)
 template <class SIG> struct sig_is_matrix { static constexpr bool value = std::is_same<SIG, SigF32>::value || std::is_same<SIG, SigI16>::value; };
 
 template <int THREADS, int HB, int U, class SIG>
@@ -410,9 +412,10 @@ static int launch_cand_stats2(adp_handle *h, SIG sig, const int32_t *dlen, int n
 // (the second phase of adp_detect_cnn, cnn_fallback_run)
 struct ValBufs { const int64_t *bounds; const int8_t *topk_none; adp_row *rows; };
 
-template <class SIG>
-static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int kmax, int mbsize,
-                           bool gate_mb, const ValBufs *vb = nullptr, bool polya_truncated = false)
+// (FROM: k_validate<SIG, true> with the reads' adapter starts -- device int64 [n], or nullptr -- the only thing the switch changes)
+template <bool FROM, class SIG>
+static int launch_validate_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int kmax, int mbsize,
+                             bool gate_mb, const ValBufs *vb, bool polya_truncated, const int64_t *starts)
 {
     const int64_t *bounds = vb ? vb->bounds : h->bounds.as<int64_t>();
     adp_row *rows = vb ? vb->rows : h->rows.as<adp_row>();
@@ -422,6 +425,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     in.kmax = kmax; in.n_reads = n; in.m = m; in.mbsize = mbsize;
     in.mbs = gate_mb ? h->mbs.as<MbState>() : nullptr;
     in.scratch = h->vscratch.as<float>(); in.scratch_stride = h->vstride;
+    in.starts = starts;
     // several candidates per read (the CNN path): moving-window series up to the LARGEST candidate for every read (the
     // window, not MVS_CAP, bounds them), then the order statistics of all candidates in shared sweeps (cand_stats.h)
     // (two shapes of k_cand_stats: big workgroups and wide levels beyond a 32 k preload, small ones below: cand_stats.h)
@@ -492,7 +496,7 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
     adp_handle *a = h->owner ? h->owner : h;
     in.op_arena = a->op_arena.as<int32_t>(); in.op_used = a->op_used.as<unsigned int>(); in.op_cap = (unsigned int)(a->op_arena.cap / 4);
     { Scope s(h, "k_validate");
-      hipLaunchKernelGGL(k_validate<SIG>, dim3(grid), dim3(64), 0, h->stream, in, h->cfg, rows, h->preq.as<PartReq>()); }
+      hipLaunchKernelGGL((k_validate<SIG, FROM>), dim3(grid), dim3(64), 0, h->stream, in, h->cfg, rows, h->preq.as<PartReq>()); }
     if (polya_truncated) { // (Boundaries.polya_truncated: no RNA partition, signal_partitions.py:74-77)
         Scope s(h, "k_pt_preq");
         hipLaunchKernelGGL(k_pt_preq, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->preq.as<PartReq>(), n);
@@ -503,6 +507,13 @@ static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, 
       hipLaunchKernelGGL((k_partition_stats<SIG, BS_THREADS, 5>), dim3(n), dim3(BS_THREADS), sizeof(BlockScratch), h->stream, dsig, m, h->preq.as<PartReq>(),
                          rows); }
     return 0;
+}
+
+template <class SIG>
+static int launch_validate(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int kmax, int mbsize,
+                           bool gate_mb, const ValBufs *vb = nullptr, bool polya_truncated = false)
+{
+    return launch_validate_t<false>(h, dsig, dlen, n, m, kmax, mbsize, gate_mb, vb, polya_truncated, nullptr);
 }
 
 // N1 for all minibatches (n1_select.h): sampled guess, then ONE verified full pass per statistic when the copied
@@ -1105,8 +1116,9 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
     });
 }
 
-int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
-                            const int64_t *bounds, int k, int flags, adp_row *rows_out)
+// adp_validate_candidates and adp_validate_candidates_from: starts == nullptr -- every start is 0, k_validate<SigF32, false>
+static int validate_candidates(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m, const int64_t *bounds,
+                               const int64_t *starts, int k, int flags, adp_row *rows_out)
 {
     if (!h || !signals || !full_len || !bounds || n_reads < 1 || k < 1 || k > ADP_MAX_CAND) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
@@ -1119,16 +1131,145 @@ int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *
     hipStream_t st = h->stream;
     rc = alloc_all(h, n_reads, false);
     if (rc) return rc;
+    ALLOCCHK(starts && h->bounds_stage.ensure((size_t)n_reads * 8)); // (the starts: nothing else of this call stages bounds)
     return call_attempts(h, nullptr, 0, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(h->bounds.p, bounds, (size_t)n_reads * (1 + k) * 8,
-                              ((flags & ADP_IN_DEVICE) && !(flags & ADP_BOUNDS_HOST)) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        const hipMemcpyKind kind = ((flags & ADP_IN_DEVICE) && !(flags & ADP_BOUNDS_HOST)) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        HIPCHK(hipMemcpyAsync(h->bounds.p, bounds, (size_t)n_reads * (1 + k) * 8, kind, st));
+        if (starts) HIPCHK(hipMemcpyAsync(h->bounds_stage.p, starts, (size_t)n_reads * 8, kind, st));
         HIPCHK(hipMemsetAsync(h->topk_none.p, (flags & ADP_TOPK_NONE) ? 1 : 0, (size_t)n_reads, st));
-        RCCHK(launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated));
+        if (starts) RCCHK(launch_validate_t<true>(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated, h->bounds_stage.as<int64_t>()));
+        else RCCHK(launch_validate(h, SigF32{dsig}, dlen, n_reads, m, k, n_reads, false, nullptr, truncated));
         RCCHK(deliver_rows(h, n_reads, flags, rows_out));
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         return arena_end(h);
     });
+}
+
+int adp_validate_candidates(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
+                            const int64_t *bounds, int k, int flags, adp_row *rows_out)
+{
+    return validate_candidates(h, signals, full_len, n_reads, m, bounds, nullptr, k, flags, rows_out);
+}
+
+int adp_validate_candidates_from(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
+                                 const int64_t *bounds, const int64_t *starts, int k, int flags, adp_row *rows_out)
+{
+    return validate_candidates(h, signals, full_len, n_reads, m, bounds, starts, k, flags, rows_out);
+}
+
+} // extern "C"
+
+// ---- the adapter's front boundary with its rows validated again (adapter_front_revalidate.h; the detector: modules.hip) ----
+// One group of selected reads: gather, the validation from the trimmed starts over the rows where they lie, merge.
+struct AfrBufs { Piece<int32_t> sel_a, sel_b, len_sub, reval; Piece<unsigned int> counts; Piece<int64_t> bounds, starts; Piece<int8_t> topk; Piece<adp_row> rows2; };
+template <class SIG>
+static int afr_group(adp_handle *h, SIG dsig, const int32_t *dlen, int m, const AfStaged &af, const AfrBufs &b, const int32_t *sel, int n_sel, bool truncated)
+{
+    const int kmax = truncated ? 1 : ADP_MAX_CAND;
+    { Scope s(h, "k_afr_gather");
+      hipLaunchKernelGGL(k_afr_gather, dim3((n_sel + 255) / 256), dim3(256), 0, h->stream, sel, n_sel, kmax, truncated ? 1 : 0, dlen, (const adp_row *)af.rows,
+                         (const int64_t *)af.shift, b.len_sub.p, b.bounds.p, b.topk.p, b.starts.p); }
+    const ValBufs vb{b.bounds.p, b.topk.p, b.rows2.p};
+    RCCHK(launch_validate_t<true>(h, sig_subset(dsig, sel), b.len_sub.p, n_sel, m, kmax, n_sel, false, &vb, truncated, b.starts.p));
+    { Scope s(h, "k_afr_merge");
+      hipLaunchKernelGGL(k_afr_merge, dim3(n_sel), dim3(64), 0, h->stream, sel, n_sel, (const adp_row *)b.rows2.p, af.rows, b.reval.p); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// what the re-validating forms refuse beyond af_check, before anything is launched
+static int afr_check(adp_handle *h, const int32_t *full_len, int n_reads, int m, const adp_adapter_front_args *args, int flags, const int32_t *reval_out)
+{
+    if (!full_len || !reval_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (args->min_adapter_len < 1) { g_err = "adp_adapter_front_revalidate: min_adapter_len must be >= 1 (an empty adapter slice has no median)"; return ADP_ERR_INVALID; }
+    if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    if (h->cfg.mvs_detect_check && h->cfg.mvs_detect_overwrite) { g_err = "adp_adapter_front_revalidate does not go with mvs_detect_overwrite"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_OUT_DEVICE) { g_err = "adp_adapter_front_revalidate takes host rows (the call opens its own open-pore arena)"; return ADP_ERR_UNSUPPORTED; }
+    return ADP_OK;
+}
+
+// dsig(af): the resident matrix once the detector has staged it
+template <class MK>
+static int afr_run(adp_handle *h, MK &&dsig_of, const float *sig, const int16_t *raw, const int32_t *full_len, const float *scale, const float *offset,
+                   int n_reads, int m, adp_row *rows, const adp_adapter_front_args *args, int flags, int32_t *info_out, int64_t *shift_out,
+                   int64_t *cand_out, double *diff_out, int32_t *reval_out)
+{
+    RCCHK(begin_call(h));
+    hipStream_t st = h->stream;
+    const int32_t *dlen = full_len;
+    if (!(flags & ADP_IN_DEVICE)) {
+        ALLOCCHK(h->len_stage.ensure((size_t)n_reads * 4));
+        HIPCHK(hipMemcpyAsync(h->len_stage.p, full_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
+        dlen = h->len_stage.as<int32_t>();
+    }
+    AfStaged af;
+    RCCHK(af_detect_staged(h, sig, raw, dlen, scale, offset, n_reads, m, rows, args, flags, &af));
+    RCCHK(alloc_all(h, n_reads, false));
+    const size_t N = (size_t)n_reads;
+    AfrBufs b;
+    RCCHK(sub_carve(h, [&](Carve &c) {
+        b.sel_a = c.take<int32_t>(N); b.sel_b = c.take<int32_t>(N); b.len_sub = c.take<int32_t>(N); b.reval = c.take<int32_t>(2 * N);
+        b.counts = c.take<unsigned int>(4); b.bounds = c.take<int64_t>(N * (1 + ADP_MAX_CAND)); b.starts = c.take<int64_t>(N);
+        b.topk = c.take<int8_t>(N); b.rows2 = c.take<adp_row>(N);
+    }));
+    const auto dsig = dsig_of(af);
+    bool first = true;
+    const int rc = call_attempts(h, nullptr, 0, [&]() -> int {
+        // (a repeat on a larger arena starts from the rows as they came: the merge wrote into the staged copy)
+        if (!first) HIPCHK(hipMemcpyAsync(af.rows, rows, N * sizeof(adp_row), hipMemcpyHostToDevice, st));
+        first = false;
+        { Scope s(h, "k_afr_select");
+          hipLaunchKernelGGL(k_afr_select, dim3(1), dim3(SEL_THREADS), 0, st, (const int32_t *)af.info, (const adp_row *)af.rows, n_reads, b.sel_a.p, b.sel_b.p,
+                             b.counts.p, b.reval.p); }
+        unsigned int cnt[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(cnt, b.counts.p, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (cnt[0] > (unsigned int)n_reads || cnt[1] > (unsigned int)n_reads) { g_err = "adp_adapter_front_revalidate: selection count out of range"; return ADP_ERR_HIP; }
+        if (cnt[0]) RCCHK(afr_group(h, dsig, dlen, m, af, b, b.sel_a.p, (int)cnt[0], false));
+        if (cnt[1]) RCCHK(afr_group(h, dsig, dlen, m, af, b, b.sel_b.p, (int)cnt[1], true));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return arena_end(h);
+    });
+    if (rc) return rc;
+    // (behind the attempts: a repeat selects by the detector's acceptance column, which this overwrites with "replaced")
+    hipLaunchKernelGGL(k_afr_info, dim3((n_reads + 255) / 256), dim3(256), 0, st, af.info, (const int32_t *)b.reval.p, n_reads);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rows, af.rows, N * sizeof(adp_row), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(reval_out, b.reval.p, N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info_out, af.info, N * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(shift_out, af.shift, N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cand_out, af.cand, N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(diff_out, af.diff, N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ADP_OK;
+}
+
+extern "C" {
+
+int adp_adapter_front_revalidate(adp_handle *h, const float *sig, const int32_t *full_len, int n_reads, int m, adp_row *rows,
+                                 const adp_adapter_front_args *args, int flags, int32_t *info_out, int64_t *shift_out,
+                                 int64_t *cand_out, double *diff_out, int32_t *reval_out)
+{
+    RCCHK(af_check(h, sig, n_reads, m, rows, args, info_out, shift_out, cand_out, diff_out));
+    RCCHK(afr_check(h, full_len, n_reads, m, args, flags, reval_out));
+    return afr_run(h, [](const AfStaged &af) { return SigF32{af.sig}; }, sig, nullptr, full_len, nullptr, nullptr, n_reads, m, rows, args, flags,
+                   info_out, shift_out, cand_out, diff_out, reval_out);
+}
+
+int adp_adapter_front_revalidate_i16(adp_handle *h, const int16_t *raw, const int32_t *full_len, const float *scale,
+                                     const float *offset, int n_reads, int m, adp_row *rows, const adp_adapter_front_args *args,
+                                     int flags, int32_t *info_out, int64_t *shift_out, int64_t *cand_out, double *diff_out,
+                                     int32_t *reval_out)
+{
+    RCCHK(af_check(h, raw, n_reads, m, rows, args, info_out, shift_out, cand_out, diff_out));
+    if (!full_len || !scale || !offset) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!(flags & ADP_IN_DEVICE)) { g_err = "adp_adapter_front_revalidate_i16 takes device pointers (ADP_IN_DEVICE)"; return ADP_ERR_INVALID; }
+    if (m % 4 != 0) { g_err = "adp_adapter_front_revalidate_i16: m must be a multiple of 4"; return ADP_ERR_UNSUPPORTED; }
+    RCCHK(afr_check(h, full_len, n_reads, m, args, flags, reval_out));
+    return afr_run(h, [=](const AfStaged &) { return SigI16{raw, scale, offset, full_len}; }, nullptr, raw, full_len, scale, offset, n_reads, m, rows,
+                   args, flags, info_out, shift_out, cand_out, diff_out, reval_out);
 }
 
 // C3 on the device: top-k behind given arg-maxes (dapos / dppos device int64 [n]) -> dcand / dcnt in ct_out (asynchronous)

@@ -150,3 +150,14 @@ struct Scope {
     }
     ~Scope() { if (b) (void)hipEventRecord(b, st); }
 };
+
+// ---- the front detector of adp_adapter_front(_i16) (modules.hip) for adp_adapter_front_revalidate(_i16) (adapted_hip.hip) ------
+// af_check: what every form checks before anything is launched.  af_detect_staged: the signal staged (float32 host signals) and
+// k_adapter_front over `rows` (host), which are staged in but NOT patched -- device pointers into the handle's module workspace,
+// good until the next module call: the matrix, the rows, the detector's side outputs.  raw != nullptr: the int16 form.
+struct AfStaged { const float *sig; adp_row *rows; int32_t *info; int64_t *shift, *cand; double *diff; };
+ADP_HIDDEN int af_check(adp_handle *h, const void *sig, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args,
+                        const int32_t *info_out, const int64_t *shift_out, const int64_t *cand_out, const double *diff_out);
+ADP_HIDDEN int af_detect_staged(adp_handle *h, const float *sig, const int16_t *raw, const int32_t *full_len, const float *scale,
+                                const float *offset, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args,
+                                int flags, AfStaged *out);

@@ -903,8 +903,8 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
 // ---- the adapter's front boundary over the rows of a detect call (an extension; adapter_front.h)
 
 // what both forms check before anything is launched
-static int af_check(adp_handle *h, const void *sig, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args,
-                    const int32_t *info_out, const int64_t *shift_out, const int64_t *cand_out, const double *diff_out)
+int af_check(adp_handle *h, const void *sig, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args,
+             const int32_t *info_out, const int64_t *shift_out, const int64_t *cand_out, const double *diff_out)
 {
     if (!h || !sig || !rows || !args || !info_out || !shift_out || !cand_out || !diff_out || n_reads < 1 || m < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (args->window < 1) { g_err = "moving windows must be >= 1"; return ADP_ERR_INVALID; }
@@ -947,6 +947,32 @@ static int af_run(adp_handle *h, Sig sig, int n_reads, int m, adp_row *rows, con
     RCCHK(d2h(h, cand_out, b.cand));
     RCCHK(d2h(h, diff_out, b.diff));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+// (handle.h) the detector alone for the re-validating forms: staged rows stay as they came, the patch is the validation's
+int af_detect_staged(adp_handle *h, const float *sig, const int16_t *raw, const int32_t *full_len, const float *scale,
+                     const float *offset, int n_reads, int m, const adp_row *rows, const adp_adapter_front_args *args, int flags,
+                     AfStaged *out)
+{
+    AfBufs b;
+    Piece<float> s_sig;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_sig = w.take<float>((size_t)m * n_reads, !raw && !(flags & ADP_IN_DEVICE));
+        af_pieces(w, b, n_reads, m, false);
+    }));
+    const float *ds = nullptr;
+    if (!raw) RCCHK(stage_in(h, flags, sig, s_sig, &ds));
+    RCCHK(h2d(h, b.rows, rows));
+    { Scope s(h, "k_adapter_front");
+      if (raw)
+          hipLaunchKernelGGL(k_adapter_front<SigI16>, dim3((unsigned)b.slots), dim3(64), 0, h->stream, SigI16{raw, scale, offset, full_len}, n_reads, m,
+                             (const adp_row *)b.rows.p, *args, b.scr, b.info, b.shift, b.cand, b.diff, b.segs);
+      else
+          hipLaunchKernelGGL(k_adapter_front<SigF32>, dim3((unsigned)b.slots), dim3(64), 0, h->stream, SigF32{ds}, n_reads, m,
+                             (const adp_row *)b.rows.p, *args, b.scr, b.info, b.shift, b.cand, b.diff, b.segs); }
+    HIPCHK(hipGetLastError());
+    *out = AfStaged{ds, b.rows.p, b.info.p, b.shift.p, b.cand.p, b.diff.p};
     return ADP_OK;
 }
 

@@ -43,6 +43,7 @@ struct ValidateInT {
     int32_t *op_arena;         // whole open_pores lists of the reads with more than ADP_MAX_OPEN_PORES entries
     unsigned int *op_used;     // entries handed out (may exceed op_cap: the host then grows the arena and repeats the kernel)
     unsigned int op_cap;
+    const int64_t *starts;     // k_validate<SIG, true> only: [n_reads] Boundaries.adapter_start, or nullptr (0 for every read)
 };
 
 static __device__ __forceinline__ bool in_range_d(double v, double lo, double hi) { return lo <= v && v <= hi; }
@@ -928,7 +929,13 @@ static __device__ void row_exception(adp_row *row, int code)
 #ifndef VAL_WPE
 #define VAL_WPE 6 // waves per SIMD of k_validate (512 / VAL_WPE vector registers each)
 #endif
-template <class SIG>
+// FROM: Boundaries.adapter_start = in.starts[r] (combined.py:363, 398-419): the adapter median / MAD and the open-pore scan work
+// on [start, min(adapter_end, S)), open-pore positions stay absolute.  A compile-time switch: k_validate<SIG, false> never reads
+// in.starts and is the kernel it was.  A read with an adapter end whose start does not lie in [0, min(adapter_end, S)) is not
+// validated -- the reference takes the median of an empty slice there -- and nothing of its row is read in front of 0 or behind
+// S: it gets the row of a read without an adapter (success 0, ADP_F_NO_ADAPTER, partitions from start 0).  Without an adapter end
+// the start only names the adapter partition's start (an empty partition): a negative one counts as 0.
+template <class SIG, bool FROM = false>
 __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_eu(VAL_WPE, VAL_WPE))) k_validate(ValidateInT<SIG> in, adp_cfg cfg, adp_row *__restrict__ rows,
                                                  PartReq *__restrict__ preq)
 {
@@ -950,7 +957,13 @@ __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_e
         const long long a_in = bd[0];
         const long long p_in = in.kmax > 0 ? bd[1] : 0;
         const bool topk_none = in.topk_none ? in.topk_none[r] != 0 : false;
-        long long a_s = 0, a_e = a_in, p_best = p_in;
+        long long a0 = 0; // (a constant 0 without FROM)
+        bool a0_bad = false;
+        if constexpr (FROM) {
+            if (in.starts) a0 = in.starts[r];
+            if (a_in != 0 ? !(a0 >= 0 && a0 < (a_in < S ? a_in : S)) : a0 < 0) { a0_bad = a_in != 0; a0 = 0; }
+        }
+        long long a_s = a0, a_e = a_in, p_best = p_in;
         bool p_none = false; // polya_end_best became None (mvs_detect_overwrite)
         int success = 1, fail = ADP_F_NONE, mvs_mask = 0;
         float adapter_med = 0.f, adapter_mad = 0.f;
@@ -958,11 +971,16 @@ __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_e
         RowW rw{row, 0ull};
         int n_open = -1;
 
-        if (a_e == 0) { success = 0; fail = ADP_F_NO_ADAPTER; }
+        if (a_e == 0 || (FROM && a0_bad)) { success = 0; fail = ADP_F_NO_ADAPTER; }
         else {
             int b = (int)(a_e < S ? a_e : S);
+            if constexpr (FROM) {
+                adapter_med = wave_median(sig + a0, b - (int)a0, 0, 0.f, ws, sc);
+                adapter_mad = wave_median(sig + a0, b - (int)a0, 1, adapter_med, ws, sc);
+            } else {
             adapter_med = wave_median(sig, b, 0, 0.f, ws, sc);
             adapter_mad = wave_median(sig, b, 1, adapter_med, ws, sc);
+            }
             have_med = true;
         }
         if (success && have_med && adapter_mad != 0.0f &&
@@ -973,7 +991,7 @@ __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_e
             // V2: positions >= 200 pA; keep pos[i] (i >= 1) with a gap >= 10 to pos[i-1]; none kept -> [pos[-1]]
             const int b = (int)(a_e < S ? a_e : S);
             int npos = 0, nvalid = 0, prev_last = -1, lastpos = -1, lastvalid = -1;
-            for (int base = 0; base < b; base += 64) {
+            for (int base = FROM ? (int)a0 : 0; base < b; base += 64) {
                 int i = base + ln;
                 bool f = (i < b) && (200.0f <= sig[i]);
                 unsigned long long mk = __ballot(f);
@@ -1005,7 +1023,7 @@ __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_e
                 off = __shfl(off, 0);
                 if ((unsigned long long)off + (unsigned long long)n_open <= in.op_cap) {
                     int np2 = 0, nv2 = 0, pl2 = -1;
-                    for (int base = 0; base < b; base += 64) {
+                    for (int base = FROM ? (int)a0 : 0; base < b; base += 64) {
                         const int i = base + ln;
                         const bool f = (i < b) && (200.0f <= sig[i]);
                         const unsigned long long mk = __ballot(f);
@@ -1136,7 +1154,7 @@ __global__ void __launch_bounds__(64, VAL_WPE) __attribute__((amdgpu_waves_per_e
             PartReq q;
             q.valid = 1; q.S = S; q.a_s = a_s; q.a_e = a_e; q.p_e = p_best;
             q.adapter_med = adapter_med; q.adapter_mad = adapter_mad;
-            q.have_adapter_medmad = (have_med && a_s == 0 && a_e == a_in) ? 1 : 0; q.p_none = p_none ? 1 : 0;
+            q.have_adapter_medmad = (have_med && a_s == (FROM ? a0 : 0) && a_e == a_in) ? 1 : 0; q.p_none = p_none ? 1 : 0;
             preq[r] = q;
         }
         rw.set(ADP_C_ADAPTER_END, (double)a_e);

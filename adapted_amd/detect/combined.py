@@ -146,7 +146,13 @@ def validate_boundaries(signal: np.ndarray, boundaries: Boundaries, spc, full_si
     if not none and len(cands) and cands[0] != int(boundaries.polya_end or 0):
         raise ValueError("polya_end_topk[0] must equal polya_end")
     # (Boundaries.polya_truncated: no RNA partition, signal_partitions.py:74-77; the returned polya_truncated stays None, combined.py:606)
-    rows = eng.validate_rows(sig, np.array([eff_len], dtype=np.int32), 1, b, topk_none=none, polya_truncated=bool(boundaries.polya_truncated))
+    lens = np.array([eff_len], dtype=np.int32)
+    start = int(getattr(boundaries, "adapter_start", 0) or 0)
+    if start == 0:  # (None or 0: the call there has always been)
+        rows = eng.validate_rows(sig, lens, 1, b, topk_none=none, polya_truncated=bool(boundaries.polya_truncated))
+    else:  # Boundaries.adapter_start (combined.py:363): the adapter slice, its gates and the open-pore scan begin there
+        rows = eng.validate_rows_from(sig, lens, 1, b, np.array([start], dtype=np.int64), topk_none=none,
+                                      polya_truncated=bool(boundaries.polya_truncated))
     if eff_len != int(full_signal_len) and int(rows[0]["present"]) & 1:
         rows[0]["col"][0] = float(full_signal_len)  # signal_len reports the read's true length
     return lib.rows_to_results(rows, spc.primary_method, consume=True)[0]

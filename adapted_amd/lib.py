@@ -32,6 +32,7 @@ ROW_FROM_SECOND_LLR = 1  # bits of row["reserved_"]
 ROW_POLYA_TRUNCATED = 2  # the poly(A) runs into the end of the preloaded window
 ROW_TRUNC_LOOKED = 4  # the call looked for that (every row of a call made with ADP_FLAG_TRUNCATED)
 ROW_ADAPTER_FRONT = 8  # adp_adapter_front moved adapter_start: adapter_start / _len / _mean / _std / _med / _mad are the trimmed adapter's
+ROW_REVALIDATED = 16  # adp_adapter_front_revalidate replaced the row by the validation from the trimmed start (beside ROW_ADAPTER_FRONT)
 ADP_ERR_UNSUPPORTED = -4
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
@@ -268,7 +269,7 @@ def load():
     try:
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
-                            + list(ADAPTER_FRONT_PROTOTYPES.items())):
+                            + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -488,6 +489,16 @@ ADAPTER_FRONT_PROTOTYPES = {
     "adp_adapter_front": "int: adp_handle* float* int32* int int adp_row* adp_adapter_front_args* int int32* int64* int64* double*",
     "adp_adapter_front_i16": "int: adp_handle* int16* int32* float* float* int int adp_row* adp_adapter_front_args* int int32* int64* "
                              "int64* double*",
+}
+
+# include/adapted_hip_revalidate.h (the header adapted_hip.h includes for the validation from a given adapter start and the
+# adapter-front pass that validates its trimmed rows again, an extension); tests/test_revalidate_cpu.py holds this table against it
+REVALIDATE_PROTOTYPES = {
+    "adp_validate_candidates_from": "int: adp_handle* float* int32* int int int64* int64* int int adp_row*",
+    "adp_adapter_front_revalidate": "int: adp_handle* float* int32* int int adp_row* adp_adapter_front_args* int int32* int64* int64* "
+                                    "double* int32*",
+    "adp_adapter_front_revalidate_i16": "int: adp_handle* int16* int32* float* float* int int adp_row* adp_adapter_front_args* int int32* "
+                                        "int64* int64* double* int32*",
 }
 
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
@@ -904,6 +915,27 @@ class Engine:
         self._check(self.lib.adp_validate_candidates(self._h, sig, lens, n, self.m, b, b.shape[1] - 1, flags, rows))
         return self.attach_open_pores(rows)
 
+    def validate_rows_from(self, signals, full_lens, n: int, bounds: np.ndarray, starts, device_ptrs: bool = False,
+                           topk_none: bool = False, polya_truncated: bool = False):
+        """validate_rows with Boundaries.adapter_start = starts[r] (adp_validate_candidates_from): starts int64 [n] (host), or None
+        for 0 everywhere -- the bytes of validate_rows"""
+        sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
+        if topk_none:
+            flags |= ADP_TOPK_NONE
+        if polya_truncated:
+            flags |= ADP_POLYA_TRUNCATED
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        st = None
+        if starts is not None:
+            st = np.ascontiguousarray(starts, dtype=np.int64)
+            if st.shape != (n,):
+                raise ValueError("starts: int64 [n]")
+        rows = np.zeros(n, dtype=ROW_DTYPE)
+        if device_ptrs:
+            flags |= ADP_BOUNDS_HOST  # the signals are resident, the candidate table and the starts come from the host
+        self._check(self.lib.adp_validate_candidates_from(self._h, sig, lens, n, self.m, b, st, b.shape[1] - 1, flags, rows))
+        return self.attach_open_pores(rows)
+
     # -- the reference's modules (adp_c_llr_*, adp_llr_*, adp_mvs_*): one input path ----------------------------------------
     def _rows_in(self, x, n=None, L=None, dtypes=(np.float64,), convert=False, what="signals"):
         """a module call's [n, L] input: a device pointer (int) with n and L given, or a host C-contiguous array of one of
@@ -1179,6 +1211,46 @@ class Engine:
         _check_runtime_once_torch_is_here()
         head = (int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev))
         return self._adapter_front(self.lib.adp_adapter_front_i16, head, rows, args, int(n), self.m if m is None else int(m))
+
+    def _adapter_front_revalidate(self, fn, head, rows, args, n, m):
+        """adp_adapter_front_revalidate / _i16 (fn) behind the batch's leading arguments (head); rows: a host ROW_DTYPE array [n]
+        -> (info, shift, cand, diff, reval int32 [n, 2]).  The REPLACED rows alone get their whole open-pore lists out of this
+        call's arena, and their old lists leave the registry: every other row's open_pores_more is a registry token already."""
+        flags = ADP_IN_DEVICE if isinstance(head[0], int) else 0
+        if not (isinstance(rows, np.ndarray) and rows.dtype == ROW_DTYPE and rows.flags.c_contiguous and rows.flags.writeable
+                and rows.shape == (n,)):
+            raise ValueError("rows: a writable C-contiguous ROW_DTYPE array with one row per read (host rows only)")
+        info, reval = np.zeros((n, 4), dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+        shift, cand, diff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
+        n_before, token_before = rows["n_open_pores"].copy(), rows["open_pores_more"].copy()
+        self._check(fn(self._h, *head, n, int(m), rows, C.byref(args), flags, info, shift, cand, diff, reval))
+        replaced = np.flatnonzero(reval[:, 0] == 1)
+        for i in replaced[n_before[replaced] > MAX_OPEN_PORES]:
+            _OPEN_PORES_MORE.pop(int(token_before[i]), None)
+        big = replaced[rows["n_open_pores"][replaced] > MAX_OPEN_PORES]
+        if big.size:
+            sub = rows[big]  # (a copy: attach_open_pores swaps offsets for tokens in it)
+            rows[big] = self.attach_open_pores(sub)
+        return info, shift, cand, diff, reval
+
+    def adapter_front_revalidate(self, sig, full_lens, rows, args: "AdpAdapterFrontArgs", n: Optional[int] = None,
+                                 m: Optional[int] = None):
+        """adp_adapter_front_revalidate: adapter_front whose accepted reads are validated again from the trimmed start; a read whose
+        validation fails keeps its row (the trim is rejected).  full_lens IS read: int32 [n] on the host beside host signals, a
+        device pointer beside a device pointer -> (info, shift, cand, diff, reval)"""
+        sig, _, n, m = self._rows_in(sig, n, self.m if m is None else m, (np.float32,), what="signals")
+        lens = int(full_lens) if isinstance(sig, int) else np.ascontiguousarray(full_lens, dtype=np.int32)
+        if not isinstance(lens, int) and lens.shape != (n,):
+            raise ValueError("full_lens must be int32 [n]")
+        return self._adapter_front_revalidate(self.lib.adp_adapter_front_revalidate, (sig, lens), rows, args, n, m)
+
+    def adapter_front_revalidate_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, rows,
+                                     args: "AdpAdapterFrontArgs", n: int, m: Optional[int] = None):
+        """adp_adapter_front_revalidate_i16: the same over RAW int16 samples resident on the device (device pointers only)"""
+        _check_runtime_once_torch_is_here()
+        head = (int(raw_dev), int(len_dev), int(scale_dev), int(offset_dev))
+        return self._adapter_front_revalidate(self.lib.adp_adapter_front_revalidate_i16, head, rows, args, int(n),
+                                              self.m if m is None else int(m))
 
     def segment_events(self, sig, lens, rows, starts, ends, args: "AdpEventArgs", cap: int = 0, n: Optional[int] = None,
                        L: Optional[int] = None, f64: bool = False):

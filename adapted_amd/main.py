@@ -81,6 +81,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the GPU, after validation: adapter_start, adapter_len and the adapter_mean / std / med / mad columns describe the "
                         "trimmed adapter, which --polya_length and --fingerprints then use (validation is not repeated; untuned, nothing "
                         "validated on real data).  LLR and CNN primaries")
+    d.add_argument("--adapter_front_revalidate", action="store_true",
+                   help="(extension, with --adapter_front) validate every trimmed read again from the new adapter_start, in the same "
+                        "call: a row whose validation passes is replaced by it (adapter MAD gate, open pores, real-range check and the "
+                        "MVS mean gate are the trimmed adapter's), a read whose validation fails keeps its first row and its "
+                        "adapter_start (the trim is rejected).  Not with mvs_detect_overwrite; the detector is still untuned")
     d.add_argument("--adapter_front_params", type=str, default=None, metavar="WINDOW,MIN_OBS_ADAPTER,MIN_SHIFT,MIN_PA",
                    help="(extension, with --adapter_front) the detector's parameters (default 100,2500,20,90: the reference's "
                         "MMAdapterStartConfig, untuned for RNA004)")
@@ -257,9 +262,12 @@ def _check_adapter_front(args):
     """--adapter_front and what it does not go with: said before a GPU is touched.  -> its AdapterFrontParams (min_adapter_len left
     to run_detect, which knows the configuration), or None"""
     text = getattr(args, "adapter_front_params", None)
+    reval = bool(getattr(args, "adapter_front_revalidate", False))
     if not getattr(args, "adapter_front", False):
         if text:
             raise SystemExit("--adapter_front_params goes with --adapter_front.")
+        if reval:
+            raise SystemExit("--adapter_front_revalidate goes with --adapter_front.")
         return None
     from .adapter_front import AdapterFrontParams
 
@@ -271,6 +279,9 @@ def _check_adapter_front(args):
         primary = _load_spc(args).primary_method
         if primary not in ("llr", "cnn"):
             raise SystemExit("--adapter_front goes with the LLR and CNN primaries; this configuration's primary is %s." % primary)
+        if reval and bool(_load_spc(args).mvs_polya.mvs_detect_overwrite):
+            raise SystemExit("--adapter_front_revalidate does not go with mvs_polya.mvs_detect_overwrite.")
+    params.revalidate = reval
     return params
 
 
@@ -440,6 +451,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     n_second = [0]  # rows the LLR second opinion made (they say so themselves: reserved_ bit 0)
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
     n_front = [0]  # rows whose adapter_start the adapter-front pass moved (reserved_ bit 3)
+    n_reval = [0]  # ... that are the validation from the trimmed start (reserved_ bit 4: --adapter_front_revalidate)
+    n_rejected = [0]  # trims that validation rejected (the pipeline counts them: such a row says nothing)
     sharder = GroupSharder(ws, rank, m) if multi else None
     ordinals: List[int] = []  # stream index of the first read of every group this rank yields
 
@@ -463,6 +476,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_second[0] += int(((rows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             n_trunc[0] += int(((rows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             n_front[0] += int(((rows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
+            n_reval[0] += int(((rows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
             res = lib.rows_to_results(rows, primary, consume=True)
             out = [ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                    for rid, r in zip(tagged[:, 0], res)]
@@ -485,13 +499,18 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
         rows = np.concatenate(my_rows) if my_rows else np.zeros(0, dtype=lib.ROW_DTYPE)
         allrows = parallel.gather_rows(rows, dst=0, always=True)
         lists = [None] * ws if rank == 0 else None
-        dist.gather_object((my_ids, my_ord), lists, dst=0)
+        mine = (my_ids, my_ord)
+        if getattr(adapter_front, "revalidate", False):  # (the rejected trims: such a row says nothing)
+            mine += (int(pipe.front_rejected),)
+        dist.gather_object(mine, lists, dst=0)
         if rank == 0:
             ids = [x for part in lists for x in part[0]]
             order = np.argsort(np.array([x for part in lists for x in part[1]], dtype=np.int64), kind="stable")
             n_second[0] += int(((allrows["reserved_"] & lib.ROW_FROM_SECOND_LLR) != 0).sum())
             n_trunc[0] += int(((allrows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             n_front[0] += int(((allrows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
+            n_reval[0] += int(((allrows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
+            n_rejected[0] += sum(int(part[2]) for part in lists if len(part) > 2)
             res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
             writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                         for i, r in zip(order, res)])
@@ -508,6 +527,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             logging.info("Truncated poly(A) (polya_truncated): %d of the passing reads", n_trunc[0])
         if adapter_front is not None:
             logging.info("Adapter front (adapter_start moved): %d of the passing reads", n_front[0])
+            if getattr(adapter_front, "revalidate", False):
+                if not multi:
+                    n_rejected[0] = int(getattr(pipe, "front_rejected", 0))
+                logging.info("Adapter front re-validated: %d kept, %d trims rejected by validation", n_reval[0], n_rejected[0])
     if multi:
         dist.barrier()
         logging.info("process group: backend %s, %d rank(s); HIP runtimes mapped: %s", dist.get_backend(), ws, ", ".join(lib.hip_runtimes()))

@@ -176,19 +176,38 @@ class HostPipeline:
         repeated.  It runs before the event segmentation of enable_polya_length / enable_fingerprints, which read the row's
         adapter_start and so segment the trimmed adapter.  Every input plan: float32 padded or packed, int16 calibrated on the
         device, int16 read natively (adp_adapter_front_i16).  params: adapter_front.AdapterFrontParams (None: the reference's
-        defaults, untuned for RNA004).  Not with the start-peak primary."""
+        defaults, untuned for RNA004).  Not with the start-peak primary.
+        With ``params.revalidate`` the accepted reads are validated again from the trimmed start in the same call
+        (adp_adapter_front_revalidate / _i16): a row whose validation passes is replaced (reserved_ bits 3 and 4), a read whose
+        validation fails keeps its row -- counted in front_rejected.  Not with mvs_detect_overwrite; min_adapter_len >= 1."""
         from .adapter_front import AdapterFrontParams
 
         if self.primary not in ("llr", "cnn"):
             raise ValueError("adapter_front goes with the LLR and CNN primaries")
         params = params or AdapterFrontParams()
         params.check()
+        self.front_revalidate = bool(getattr(params, "revalidate", False))
+        if self.front_revalidate:
+            if int(params.min_adapter_len) < 1:
+                raise ValueError("adapter_front with revalidate needs min_adapter_len >= 1")
+            if bool(getattr(self.spc.mvs_polya, "mvs_detect_overwrite", False)):
+                raise ValueError("adapter_front with revalidate does not go with mvs_detect_overwrite")
         self.front_args = params.args()
         self.front_patched = 0  # rows patched so far
+        self.front_rejected = 0  # (revalidate) trims the validation rejected so far
 
     def _adapter_front(self, j: int, n: int, rows: np.ndarray):
         """the adapter-front pass over the rows of slot j's detect call, on the signal that call just read; rows are patched in
         place (rows of a dropped minibatch have success 0: they are not looked at)"""
+        if getattr(self, "front_revalidate", False):  # (the full lengths: the slot's, on the device beside the signal)
+            if self.native_i16:
+                raw, dlen, scale, offset = self._resident_i16
+                out = self.eng.adapter_front_revalidate_i16(raw, dlen, scale, offset, rows, self.front_args, n=n, m=self.m)
+            else:
+                out = self.eng.adapter_front_revalidate(self._resident, self.slots[j]["dl"], rows, self.front_args, n=n, m=self.m)
+            self.front_patched += int(out[0][:, 3].sum())
+            self.front_rejected += int((out[4][:, 0] == 0).sum())
+            return rows
         if self.native_i16:
             raw, dlen, scale, offset = self._resident_i16
             info = self.eng.adapter_front_i16(raw, dlen, scale, offset, rows, self.front_args, n=n, m=self.m)[0]

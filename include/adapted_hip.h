@@ -164,7 +164,9 @@ typedef struct adp_row {
                                   bit 2: the call looked for that (set in EVERY row of a call made with ADP_FLAG_TRUNCATED, so that a
                                   row says by itself whether "not truncated" was decided or never asked).  bit 3: adp_adapter_front moved
                                   the row's adapter_start (adapted_hip_adapter_front.h): adapter_start, adapter_len and the four adapter
-                                  statistics are the trimmed adapter's, everything else the first validation's.  0 in every other row */
+                                  statistics are the trimmed adapter's, everything else the first validation's.  bit 4 (beside bit 3):
+                                  adp_adapter_front_revalidate replaced the row by the validation from the trimmed start
+                                  (adapted_hip_revalidate.h).  0 in every other row */
 } adp_row;
 #define ADP_ROW_FROM_SECOND_LLR 1
 #define ADP_ROW_POLYA_TRUNCATED 2
@@ -563,6 +565,11 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 /* The adapter's front boundary as a post-pass over the rows of a detect call -- adp_adapter_front and adp_adapter_front_i16, an
  * extension --: a header of its own, with its prototype table in adapted_amd/lib.py, ADAPTER_FRONT_PROTOTYPES. */
 #include "adapted_hip_adapter_front.h"
+
+/* Validation from a given adapter start -- adp_validate_candidates_from -- and the front pass that validates its trimmed rows again
+ * -- adp_adapter_front_revalidate and adp_adapter_front_revalidate_i16, an extension --: a header of its own, with its prototype
+ * table in adapted_amd/lib.py, REVALIDATE_PROTOTYPES. */
+#include "adapted_hip_revalidate.h"
 
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */

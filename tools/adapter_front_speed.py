@@ -5,7 +5,10 @@ float32 pA and as raw int16.  The reads: the 64 synthetic reads of seed 11 with 
 the detector finds on most passing reads), repeated; minibatches of 1000.  Host clock around calls that end in a device
 synchronise, and per-kernel times from adp_kernel_times (HIP events on the handle's stream) in a call of their own.
 
-  python tools/adapter_front_speed.py [--reads N] [--reps R] [--out profiles/adapter_front_speed.json]
+  python tools/adapter_front_speed.py [--reads N] [--reps R] [--revalidate] [--out profiles/adapter_front_speed.json]
+
+--revalidate: also the re-validating forms (adp_adapter_front_revalidate / _i16: adapted_amd/csrc/adapter_front_revalidate.h) on
+host rows, beside the plain pass and the detect step (profiles/adapter_front_revalidate_speed.json).
 
 There is no gate: the figures say what the pass costs next to the detect call and next to that call's k_validate."""
 import argparse
@@ -37,7 +40,7 @@ def _timed(eng, fn, reps):
     return wall * 1e3, kt, res
 
 
-def measure(n, reps):
+def measure(n, reps, revalidate=False):
     from adapted_amd import lib, synth
     from adapted_amd.adapter_front import AdapterFrontParams
     from adapted_amd.config import get_chemistry_specific_config
@@ -65,11 +68,13 @@ def measure(n, reps):
         eng.h2d(d_raw, raw[idx])
         eng.h2d(d_len, lens)
         eng.h2d(d_cal, np.concatenate([scale[idx], offset[idx]]))
-        for name, detect, front in (
+        for name, detect, front, reval in (
                 ("float32", lambda: eng.detect_llr_rows(d_sig, d_len, n, mb, device_ptrs=True, tails_nan=True)[0],
-                 lambda rows: eng.adapter_front(d_sig, None, rows, args, n=n, m=m)),
+                 lambda rows: eng.adapter_front(d_sig, None, rows, args, n=n, m=m),
+                 lambda rows: eng.adapter_front_revalidate(d_sig, d_len, rows, args, n=n, m=m)),
                 ("int16", lambda: eng.detect_llr_rows_i16(d_raw, d_len, d_cal, d_cal + n * 4, n, mb)[0],
-                 lambda rows: eng.adapter_front_i16(d_raw, d_len, d_cal, d_cal + n * 4, rows, args, n=n, m=m))):
+                 lambda rows: eng.adapter_front_i16(d_raw, d_len, d_cal, d_cal + n * 4, rows, args, n=n, m=m),
+                 lambda rows: eng.adapter_front_revalidate_i16(d_raw, d_len, d_cal, d_cal + n * 4, rows, args, n=n, m=m))):
             d_wall, d_kt, rows = _timed(eng, detect, reps)
             # (every timed call starts from the detect call's rows: a patched row would be looked at from its new start)
             f_wall, f_kt, side = _timed(eng, lambda: front(rows.copy()), reps)
@@ -81,6 +86,13 @@ def measure(n, reps):
                              front_kernels_over_detect_kernels=front_ms / sum(d_kt.values()), front_wall_over_detect_wall=f_wall / d_wall,
                              front_kernels_over_k_validate=front_ms / validate_ms, passing=int((rows["success"] == 1).sum()),
                              patched=int(side[0][:, 3].sum()), value_error=int((side[0][:, 0] == 2).sum()))
+            if revalidate:
+                v_wall, v_kt, v_side = _timed(eng, lambda: reval(rows.copy()), reps)
+                v_ms = sum(v_kt.values())
+                out[name].update(revalidate_wall_ms_host_rows=v_wall, revalidate_kernel_ms=v_kt, revalidate_kernels_over_detect_kernels=v_ms / sum(d_kt.values()),
+                                 revalidate_wall_over_detect_wall=v_wall / d_wall, revalidate_wall_over_front_wall=v_wall / f_wall,
+                                 revalidate_kernels_over_k_validate=v_ms / validate_ms, kept=int((v_side[4][:, 0] == 1).sum()),
+                                 rejected=int((v_side[4][:, 0] == 0).sum()))
     finally:
         for p in (d_sig, d_raw, d_len, d_cal, d_rows):
             eng.dev_free(p)
@@ -92,9 +104,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=24000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--revalidate", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = measure(a.reads, a.reps)
+    res = measure(a.reads, a.reps, a.revalidate)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
