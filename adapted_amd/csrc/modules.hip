@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints and the adapter-front post-pass): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints, the template building and the adapter-front post-pass): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,7 @@
 #include "startmods_api.h"
 #include "events_api.h"
 #include "fingerprint_api.h"
+#include "dtw_align_api.h"
 #include "adapter_front.h"
 
 // ---- workspace, staging and per-read checks of the entry points
@@ -896,6 +897,141 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
     RCCHK(d2h(h, bestdist_out, dbd));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
+}
+
+} // extern "C"
+
+// ---- building barcode templates: the warping path of a DTW alignment and one DBA iteration (an extension; dtw_align_api.h)
+
+// what adp_dtw_align fills (host memory; lo, hi and sum may be null), or -- with t_new -- what adp_dba_step fills
+struct DaOut { double *dist; int32_t *status, *lo, *hi; double *sum; double *t_new; int32_t *members; double *inertia; };
+
+template <int C, bool G>
+static void da_launch(adp_handle *h, size_t nb, size_t lds, const double *dq, const int32_t *dqc, const int32_t *dwhich, int p0, int Eq,
+                      const double *dt, const int32_t *dtc, int Et, int band, int W, unsigned char *dcodes, double *ddist,
+                      int32_t *dstatus, int32_t *dlo, int32_t *dhi, double *dsum)
+{
+    hipLaunchKernelGGL((k_dtw_align<C, G>), dim3((unsigned)nb), dim3(64), lds, h->stream, dq, dqc, dwhich, p0, Eq, dt, dtc, Et, band, W,
+                       dcodes, ddist, dstatus, dlo, dhi, dsum);
+}
+
+// both calls: adp_dtw_assign's checks and which in [-1, nt); the queries in batches within the byte budget; per batch k_dtw_align
+// and either the copies of its path outputs or k_dba_reduce
+static int da_run(adp_handle *h, const double *q, const int32_t *q_count, const int32_t *which, int nq, int Eq, const double *t,
+                  const int32_t *t_count, int nt, int Et, int band, int flags, const DaOut &o)
+{
+    const bool dba = o.t_new != nullptr;
+    if (!h || !q || !q_count || !which || !t || !t_count || nq < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (Eq < 1 || Eq > FP_EMAX || Et < 1 || Et > FP_EMAX) { g_err = "Eq and Et must lie in [1, 512]"; return ADP_ERR_INVALID; }
+    if (nt < 1 || nt > DTW_NT_MAX) { g_err = "nt must lie in [1, 4096]"; return ADP_ERR_INVALID; }
+    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
+    int mmax = 1;
+    for (int k = 0; k < nt; k++) {
+        if (t_count[k] < 1 || t_count[k] > Et) { g_err = "need 1 <= t_count <= Et for every template"; return ADP_ERR_INVALID; }
+        for (int j = 0; j < t_count[k]; j++)
+            if (!std::isfinite(t[(size_t)k * Et + j])) { g_err = "template values inside their count must be finite"; return ADP_ERR_INVALID; }
+        if (t_count[k] > mmax) mmax = t_count[k];
+    }
+    if (!all_in<int32_t>(which, nq, -1, nt - 1)) { g_err = "need -1 <= which < nt for every query"; return ADP_ERR_INVALID; }
+    long long mib;
+    RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
+    // the direction codes: Eq rows of W units of C cells each (dtw_align_api.h), in LDS where they fit
+    const int C = (Et + 63) / 64 <= 1 ? 1 : (Et + 63) / 64 <= 2 ? 2 : (Et + 63) / 64 <= 4 ? 4 : 8;
+    const int W = (mmax + C - 1) / C;
+    const size_t nqs = nq, nts = nt, Ets = Et;
+    const size_t code_bytes = (size_t)Eq * W * (C == 8 ? 2 : 1);
+    const bool global_codes = code_bytes > DA_LDS_CODES;
+    const size_t per_query = Ets * 16 + (global_codes ? code_bytes : 0);
+    size_t rows = ((size_t)mib << 20) / per_query;
+    if (rows < 1) rows = 1;
+    if (rows > nqs) rows = nqs;
+    // the members of every template in ascending order (adp_dba_step)
+    std::vector<int32_t> offs, list;
+    if (dba) {
+        offs.assign(nts + 1, 0);
+        for (size_t p = 0; p < nqs; p++) if (which[p] >= 0) offs[which[p] + 1]++;
+        for (size_t k = 0; k < nts; k++) offs[k + 1] += offs[k];
+        list.resize(offs[nts] > 0 ? offs[nts] : 1);
+        std::vector<int32_t> at(offs.begin(), offs.end() - 1);
+        for (size_t p = 0; p < nqs; p++) if (which[p] >= 0) list[at[which[p]]++] = (int32_t)p;
+    }
+    RCCHK(begin_call(h));
+    Piece<double> s_q, dt, ddist, dsum, dT, dinert, dtnew; Piece<int32_t> s_qc, dwhich, dtc, dstatus, dlo, dhi, doffs, dlist, dmem;
+    Piece<long long> dN; Piece<unsigned char> dcodes;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_q = w.take<double>(nqs * Eq, !(flags & ADP_IN_DEVICE)); s_qc = w.take<int32_t>(nqs, !(flags & ADP_IN_DEVICE));
+        dwhich = w.take<int32_t>(nqs); dt = w.take<double>(nts * Ets); dtc = w.take<int32_t>(nts);
+        ddist = w.take<double>(nqs); dstatus = w.take<int32_t>(nqs);
+        dlo = w.take<int32_t>(rows * Ets); dhi = w.take<int32_t>(rows * Ets); dsum = w.take<double>(rows * Ets);
+        dcodes = w.take<unsigned char>(rows * code_bytes, global_codes);
+        doffs = w.take<int32_t>(nts + 1, dba); dlist = w.take<int32_t>(list.size(), dba);
+        dT = w.take<double>(nts * Ets, dba); dN = w.take<long long>(nts * Ets, dba); dmem = w.take<int32_t>(nts, dba);
+        dinert = w.take<double>(nts, dba); dtnew = w.take<double>(nts * Ets, dba);
+    }));
+    const double *dq; const int32_t *dqc;
+    RCCHK(stage_in(h, flags, q, s_q, &dq));
+    RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
+    RCCHK(h2d(h, dwhich, which));
+    RCCHK(h2d(h, dt, t));
+    RCCHK(h2d(h, dtc, t_count));
+    if (dba) {
+        RCCHK(h2d(h, doffs, offs.data()));
+        RCCHK(h2d(h, dlist, list.data()));
+        RCCHK(zero(h, dT)); RCCHK(zero(h, dN)); RCCHK(zero(h, dmem)); RCCHK(zero(h, dinert));
+    }
+    const size_t lds = global_codes ? 0 : (code_bytes + 15) & ~(size_t)15;
+    const unsigned cells = (unsigned)((nts * Ets + 63) / 64);
+    for (size_t p0 = 0; p0 < nqs; p0 += rows) {
+        const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
+        { Scope s(h, "k_dtw_align");
+#define DA_GO(C_, G_) da_launch<C_, G_>(h, nb, lds, dq, dqc, dwhich, (int)p0, Eq, dt, dtc, Et, band, W, dcodes, ddist, dstatus, dlo, dhi, dsum)
+          if (C == 1) { if (global_codes) DA_GO(1, true); else DA_GO(1, false); }
+          else if (C == 2) { if (global_codes) DA_GO(2, true); else DA_GO(2, false); }
+          else if (C == 4) { if (global_codes) DA_GO(4, true); else DA_GO(4, false); }
+          else { if (global_codes) DA_GO(8, true); else DA_GO(8, false); }
+#undef DA_GO
+        }
+        if (dba) {
+            Scope s(h, "k_dba_reduce");
+            hipLaunchKernelGGL(k_dba_reduce, dim3(cells), dim3(64), 0, h->stream, doffs, dlist, (int)p0, (int)nb, nt, Et, dtc, dstatus,
+                               ddist, dlo, dhi, dsum, dT, dN, dmem, dinert);
+        } else {
+            if (o.lo) RCCHK(d2h(h, o.lo + p0 * Ets, dlo, nb * Ets));
+            if (o.hi) RCCHK(d2h(h, o.hi + p0 * Ets, dhi, nb * Ets));
+            if (o.sum) RCCHK(d2h(h, o.sum + p0 * Ets, dsum, nb * Ets));
+        }
+    }
+    if (dba) {
+        { Scope s(h, "k_dba_finish");
+          hipLaunchKernelGGL(k_dba_finish, dim3(cells), dim3(64), 0, h->stream, dt, dtc, nt, Et, dT, dN, dmem, dtnew); }
+        RCCHK(d2h(h, o.t_new, dtnew));
+        RCCHK(d2h(h, o.members, dmem));
+        RCCHK(d2h(h, o.inertia, dinert));
+    }
+    HIPCHK(hipGetLastError());
+    if (o.dist) RCCHK(d2h(h, o.dist, ddist));
+    if (o.status) RCCHK(d2h(h, o.status, dstatus));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+extern "C" {
+
+int adp_dtw_align(adp_handle *h, const double *q, const int32_t *q_count, const int32_t *which, int nq, int Eq, const double *t,
+                  const int32_t *t_count, int nt, int Et, int band, int flags, double *dist_out, int32_t *status_out, int32_t *lo_out,
+                  int32_t *hi_out, double *sum_out)
+{
+    if (!dist_out || !status_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    return da_run(h, q, q_count, which, nq, Eq, t, t_count, nt, Et, band, flags, DaOut{dist_out, status_out, lo_out, hi_out, sum_out, nullptr, nullptr, nullptr});
+}
+
+int adp_dba_step(adp_handle *h, const double *q, const int32_t *q_count, const int32_t *which, int nq, int Eq, const double *t,
+                 const int32_t *t_count, int nt, int Et, int band, int flags, double *t_new_out, int32_t *members_out,
+                 double *inertia_out, double *dist_out)
+{
+    if (!t_new_out || !members_out || !inertia_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    return da_run(h, q, q_count, which, nq, Eq, t, t_count, nt, Et, band, flags,
+                  DaOut{dist_out, nullptr, nullptr, nullptr, nullptr, t_new_out, members_out, inertia_out});
 }
 
 } // extern "C"

@@ -269,7 +269,8 @@ def load():
     try:
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
-                            + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())):
+                            + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
+                            + list(TEMPLATE_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -499,6 +500,13 @@ REVALIDATE_PROTOTYPES = {
                                     "double* int32*",
     "adp_adapter_front_revalidate_i16": "int: adp_handle* int16* int32* float* float* int int adp_row* adp_adapter_front_args* int int32* "
                                         "int64* int64* double* int32*",
+}
+
+# include/adapted_hip_templates.h (the header adapted_hip.h includes for the warping path of a DTW alignment and the DBA iteration
+# that build barcode templates, an extension); tests/test_dtw_align_cpu.py holds this table against its header
+TEMPLATE_PROTOTYPES = {
+    "adp_dtw_align": "int: adp_handle* double* int32* int32* int int double* int32* int int int int double* int32* int32* int32* double*",
+    "adp_dba_step": "int: adp_handle* double* int32* int32* int int double* int32* int int int int double* int32* double* double*",
 }
 
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
@@ -1323,6 +1331,60 @@ class Engine:
             return dist, best, bestdist
         self._check(self.lib.adp_dtw_assign(self._h, q, q_count, nq, Eq, t, t_count, nt, Et, int(band), flags, dist, best, bestdist))
         return dist, best, bestdist
+
+    def _align_in(self, q, q_count, which, t, t_count, nq, Eq):
+        """the inputs adp_dtw_align and adp_dba_step share, as dtw_assign takes its own -> (q, q_count, which, nq, Eq, t, t_count, nt,
+        Et, flags)"""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError("templates: a float64 [nt, Et] array")
+        nt, Et = t.shape
+        t_count = self._per_read(t_count, nt, "t_count")
+        if isinstance(q, int):
+            if nq is None or Eq is None or not isinstance(q_count, int):
+                raise ValueError("device queries need a device pointer to their counts, nq and Eq")
+            _check_runtime_once_torch_is_here()
+            flags, nq, Eq = ADP_IN_DEVICE, int(nq), int(Eq)
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.ndim != 2:
+                raise ValueError("queries: a float64 [nq, Eq] array")
+            flags, (nq, Eq) = 0, q.shape
+            q_count = self._per_read(q_count, nq, "q_count")
+        return q, q_count, self._per_read(which, nq, "which"), nq, Eq, t, t_count, nt, Et, flags
+
+    def dtw_align(self, q, q_count, which, t, t_count, band: int = 0, nq: Optional[int] = None, Eq: Optional[int] = None,
+                  want_path: bool = True):
+        """adp_dtw_align: queries and templates as dtw_assign takes them, which int32 [nq] (host): every query's template, -1 to
+        skip it -> a dict: dist float64 [nq]; status int32 [nq] (0; 1 a count outside [1, Eq] or a value that is not finite; 2 a
+        distance that is not finite; 3 skipped); with ``want_path`` lo, hi int32 [nq, Et] (the first and the last query index of
+        every template position, -1 where there is none) and sum float64 [nq, Et] (the query summed over that run), else None"""
+        q, q_count, which, nq, Eq, t, t_count, nt, Et, flags = self._align_in(q, q_count, which, t, t_count, nq, Eq)
+        out = {"dist": np.full(nq, np.nan), "status": np.full(nq, 3, dtype=np.int32),
+               "lo": np.full((nq, Et), -1, dtype=np.int32) if want_path else None,
+               "hi": np.full((nq, Et), -1, dtype=np.int32) if want_path else None, "sum": np.full((nq, Et), np.nan) if want_path else None}
+        if nq == 0:  # (the library wants a query: an empty batch has an empty answer)
+            return out
+        self._check(self.lib.adp_dtw_align(self._h, q, q_count, which, nq, Eq, t, t_count, nt, Et, int(band), flags, out["dist"],
+                                           out["status"], out["lo"], out["hi"], out["sum"]))
+        return out
+
+    def dba_step(self, q, q_count, which, t, t_count, band: int = 0, nq: Optional[int] = None, Eq: Optional[int] = None,
+                 want_dist: bool = False):
+        """adp_dba_step: one iteration of DTW barycentre averaging over dtw_align's inputs (the queries may stay on the device
+        over the iterations: two device pointers with ``nq`` and ``Eq``) -> (t_new float64 [nt, Et]: per position the mean of the
+        query values aligned to it, NaN at and beyond the count, the old values of a template without a member; members int32 [nt];
+        inertia float64 [nt]: the members' distances added up; dist float64 [nq], or None without ``want_dist``)"""
+        q, q_count, which, nq, Eq, t, t_count, nt, Et, flags = self._align_in(q, q_count, which, t, t_count, nq, Eq)
+        t_new, members, inertia = np.full((nt, Et), np.nan), np.zeros(nt, dtype=np.int32), np.zeros(nt)
+        dist = np.full(nq, np.nan) if want_dist else None
+        if nq == 0:
+            for k in range(nt):
+                t_new[k, :t_count[k]] = t[k, :t_count[k]]
+            return t_new, members, inertia, dist
+        self._check(self.lib.adp_dba_step(self._h, q, q_count, which, nq, Eq, t, t_count, nt, Et, int(band), flags, t_new, members,
+                                          inertia, dist))
+        return t_new, members, inertia, dist
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

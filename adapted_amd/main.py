@@ -40,6 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     t = sub.add_parser("truncated", help="(extension) List the reads whose poly(A) was cut off by the preload window "
                                          "(runs made with --flag_truncated), for a rerun with a larger --max_obs_trace.")
     t.add_argument("directory", type=str, help="a run directory, or the directory that holds its detected_boundaries_*.csv files")
+    b = sub.add_parser("templates", help="(extension) Build barcode templates from the fingerprints of a run made with --fingerprints "
+                                         "and a CSV of labels, for detect --barcode_templates (on the GPU; untuned, nothing validated).")
+    from .barcode_templates import add_arguments
+
+    add_arguments(b)
     d.add_argument("-i", "--input", type=str, nargs="+", required=True, help="input files / directories (.pod5 or .npz bundles)")
     d.add_argument("-o", "--output", type=str, default=None)
     d.add_argument("--config", type=str, default=None, help="config TOML (overrides --chemistry)")
@@ -540,6 +545,11 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.mode == "truncated":
         list_truncated(args.directory)
+        return
+    if args.mode == "templates":
+        from .barcode_templates import templates_command
+
+        templates_command(args)
         return
     if args.mode == "continue":
         run_dir = args.continue_from

@@ -571,6 +571,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * table in adapted_amd/lib.py, REVALIDATE_PROTOTYPES. */
 #include "adapted_hip_revalidate.h"
 
+/* Building barcode templates: the warping path of a DTW alignment and one iteration of DTW barycentre averaging -- adp_dtw_align
+ * and adp_dba_step, an extension --: a header of its own, with its prototype table in adapted_amd/lib.py, TEMPLATE_PROTOTYPES. */
+#include "adapted_hip_templates.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
