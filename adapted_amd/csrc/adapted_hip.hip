@@ -629,6 +629,9 @@ static void launch_cumsum(adp_handle *h, int n)
                            h->nck, h->ck.as<double2>(), h->tail.as<double2>());
 }
 
+// k_gains' fast body for interior tiles (llr_stream.h; ADP_GAINS_TILE_FAST=0: every tile through the plain body, same results)
+static int gains_tile_fast() { return env_int("ADP_GAINS_TILE_FAST", 1) != 0; }
+
 // pkv: the maxima's heights as k_gains<2> listed them, or null.  ADP_PK_PREFIX=0: the whole list of maxima at once (peaks.h; same results)
 static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv)
 {
@@ -731,7 +734,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
             Scope s(h, "k_gains<1>");
             hipLaunchKernelGGL(k_gains<1>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
                                h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), minibatch, mbs,
-                               h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, h->oh1);
+                               h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, h->oh1, nullptr, gains_tile_fast());
         }
         if (upto >= 5) {
             Scope s(h, "k_adapter_peak");
@@ -746,7 +749,7 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
             Scope s(h, "k_gains<2>");
             hipLaunchKernelGGL(k_gains<2>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
                                h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), minibatch, mbs,
-                               h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, 5, pkvp);
+                               h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, 5, pkvp, gains_tile_fast());
         }
         if (upto >= 7) {
             Scope s(h, "k_polya_peak");
@@ -1767,7 +1770,7 @@ static int refine_chain(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int
       launch_cumsum(h, n);
       hipLaunchKernelGGL(k_gains<1>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
                          h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), 1, mbs, h->trace.as<double>(),
-                         h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 1, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, (double *)nullptr, n, 5); }
+                         h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 1, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, (double *)nullptr, n, 5, nullptr, gains_tile_fast()); }
     { Scope s(h, "k_polya_peak (refine)");
       launch_polya_peak(h, n, 1, nullptr); // (k_gains<1> lists no heights)
       hipLaunchKernelGGL(k_refine_out, dim3((n + 255) / 256), dim3(256), 0, st, mbs, h->nvalid.as<int32_t>(), h->polya_idx.as<int32_t>(),

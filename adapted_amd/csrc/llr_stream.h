@@ -22,6 +22,8 @@
 #include "log_cr.h"
 #include "wave_stats.h"
 
+extern __device__ unsigned long long g_dbg[ADP_NDBG]; // (debug tallies; 76 / 77: k_gains' tiles committed by the fast body / run again)
+
 // ---------------------------------------------------------------- D1
 #define NP_TILE 512
 // grid = n_reads blocks of 256 threads; dynamic LDS = NP_TILE * ds floats
@@ -406,6 +408,27 @@ static __device__ __forceinline__ double readlane_f64(double x, int lane)
 // index with a positive-or-NaN gain).  PASS 2: start = adapter candidate, offsets (1, 1).
 // Emits the trace (float64) and per-64-point summaries: PASS 1 of the raw trace (NaN => +inf max),
 // PASS 2 of the np.nan_to_num-sanitised trace that find_peaks sees in P4.
+//
+// THE FAST BODY OF AN INTERIOR TILE (tile_fast, ADP_GAINS_TILE_FAST=0 turns it off).  Per point the plain body decides three things
+// that hold for whole tiles of every ordinary read: that both variances are in log_cr_ok's range [2^-1022, inf), that the gain is
+// finite and not NaN, that the point lies inside the read.  The fast body decides them once per tile: it evaluates the 16 points of
+// a lane with the float64 operations of the plain body in their order and nothing else, and keeps a sticky flag per lane and
+// variance -- the unsigned maximum over the points of (high word of the variance) - 0x00100000.  log_cr_ok is
+// ix - 0x0010000000000000 < 0x7FE0000000000000 (unsigned, 64 bits): the subtrahend's low word is zero, so the subtraction never
+// borrows from the high word and leaves the low word as it is, and the bound's low word is zero, so (h, l) < (0x7FE00000, 0) exactly
+// when h < 0x7FE00000 -- the high word decides, with the accept set unchanged.  One wave vote after the 16 points: no lane flagged,
+// and the tile is COMMITTED; otherwise the plain body runs the tile again from the checkpoint and everything it writes (the staged
+// gains, the summaries, the accumulators) replaces the fast body's.  The fast body accumulates into copies that start from the
+// read's accumulators and are assigned back on commit only (the sum itself: set aside and put back when the tile is redone), so a redone tile leaves nothing behind and the additions a lane commits
+// are the plain body's in the plain body's order.
+// Why a committed tile has the plain body's bits: the read's precondition (wave-uniform) is that vs is finite and not -0; both
+// variances of every point are in [2^-1022, inf), so both logarithms are finite, their products with lengths below 2^31 are finite,
+// and gi = vs - (h + tl) is finite and not NaN -- every select the fast body drops would have taken its first arm (log_cr_ok: no
+// library log; finite: the plain max / min; gi == gi: the sums, no NaN count; sanitising: the identity; i < n: true in an interior
+// tile), and the float64 operations and their order are untouched.  Max and min are v_max_f64 / v_min_f64 there: for operands that
+// are not NaN these return the bits of `x > m ? x : m` / `x < m ? x : m` unless the operands are zeros of different sign, and gi is
+// never -0: a difference x - y rounds to -0 only for x = -0, y = +0, and x = vs is not -0 (mx / mn start from infinities and then
+// hold gains only).
 #ifndef GAINS_UNROLL
 #define GAINS_UNROLL 1
 #endif
@@ -426,7 +449,7 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
                                               double *__restrict__ bmax, double *__restrict__ bmin, int nsum,
                                               int2 *__restrict__ t1, int sanitize, int32_t *__restrict__ pk_all,
                                               int32_t *__restrict__ npk_all, int pk_stride, double *__restrict__ gstat, int n_reads, int oh1,
-                                              double *__restrict__ pkv_all = nullptr)
+                                              double *__restrict__ pkv_all = nullptr, int tile_fast = 0)
 {
     // GAINS_WPB waves (reads) per block share log_cr's table; everything else is private to a wave, so the only
     // block-wide barrier is the one after the table copy
@@ -469,6 +492,9 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
         double v = (start == E) ? 0.0 : var_seg(te.y, c2s, te.x, cs, (double)(E - start));
         vs = (double)(E - start) * flog(v);
     }
+    // the fast body's precondition on the read: vs finite and not -0 (the same value in every lane: a vote makes it the wave's)
+    const bool fast_read = tile_fast && __all(__builtin_fabs(vs) < __builtin_inf() && __builtin_bit_cast(uint64_t, vs) != 0x8000000000000000ULL);
+    int n_fast = 0, n_redo = 0; // tiles committed by the fast body / run again by the plain one (g_dbg[76], g_dbg[77])
     int first_pos = 0x7fffffff, last_pos = -1;
     double st_s1 = 0.0, st_s2 = 0.0; // PASS 1: sum and sum of squares of the non-NaN trace values (for np.nanstd in P1)
     int st_nan = 0;
@@ -542,7 +568,60 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
             sg[ln * (CK + 1) + t] = gi;
         };
         const bool interior = tb >= start + oh && tb + TRACE_TILE <= E - ot; // (then also tb + TRACE_TILE <= n)
-        if (interior) {
+        bool committed = false; // wave-uniform
+        if (__builtin_amdgcn_readfirstlane((int)(interior && fast_read))) {
+            uint32_t fh = 0u, ft = 0u; // sticky: max over the lane's points of hi(variance) - 0x00100000 (head / tail segment)
+            int f_first = first_pos, f_last = last_pos;
+            double f_s2 = st_s2;
+            if (PASS == 1) sg[ln * (CK + 1) + CK] = st_s1; // (the sum's value before the tile waits in the lane's padding word of the staging tile: registers)
+#pragma unroll GAINS_UNROLL
+            for (int tq = 0; tq < CK / 4; tq++) {
+                const float4 q4 = s4[tq];
+                const float qv[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int t = tq * 4 + u, i = i0 + t;
+                    const double lh_len = dlh, lt_len = dlt;
+                    dlh += 1.0; dlt -= 1.0;
+                    const double vh = var_seg(b, c2s, a, cs, lh_len);
+                    const double vt = var_seg(te.y, b, te.x, a, lt_len);
+                    fh = max(fh, (uint32_t)(__builtin_bit_cast(uint64_t, vh) >> 32) - 0x00100000u);
+                    ft = max(ft, (uint32_t)(__builtin_bit_cast(uint64_t, vt) >> 32) - 0x00100000u);
+#ifdef ADP_GAINS_LOG_CR
+                    const double lh = log_cr_fast(vh, lt), ll = log_cr_fast(vt, lt);
+#else
+                    const double lh = log_1ulp_fast(vh, lt), ll = log_1ulp_fast(vt, lt);
+#endif
+                    const double h = lh_len * lh;
+                    const double tl = lt_len * ll;
+                    const double gi = vs - (h + tl);
+                    if (PASS == 1) {
+                        if (!(gi <= 0.0)) { f_first = min(f_first, i); f_last = i; }
+                        st_s1 += gi; f_s2 += gi * gi;
+                    }
+                    mx = __builtin_fmax(gi, mx);
+                    mn = __builtin_fmin(gi, mn);
+                    const double v = (double)qv[u];
+                    a += v;
+                    b += v * v;
+                    sg[ln * (CK + 1) + t] = gi;
+                }
+            }
+            committed = !__any(max(fh, ft) >= 0x7FE00000u);
+            if (committed) {
+                n_fast++;
+                if (PASS == 1) { first_pos = f_first; last_pos = f_last; st_s2 = f_s2; }
+            } else { // the plain body, from the tile's start
+                n_redo++;
+                if (PASS == 1) st_s1 = sg[ln * (CK + 1) + CK];
+                const double2 p = c[i0 / CK];
+                a = p.x; b = p.y;
+                mx = -__builtin_inf(); mn = __builtin_inf();
+                dlh = (double)(i0 - start); dlt = (double)(E - i0);
+            }
+        }
+        if (committed) {
+        } else if (interior) {
 #pragma unroll GAINS_UNROLL
             for (int tq = 0; tq < CK / 4; tq++) {
                 const float4 q4 = s4[tq];
@@ -579,13 +658,44 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
             return x;
         };
         auto sval = [&](int e) { return sanit(sg[(e / CK) * (CK + 1) + (e % CK)]); }; // sanitised value at tile offset e (e >= 0)
+        // (a committed tile lies inside the read and holds finite gains: `i < n` and sanit() are identities there, and its candidates
+        // j = i - 1 >= tb - 1 >= 1023 lie before E - ot)
         if (!emit) {
+            if (committed) {
 #pragma unroll GAINS_SU
-            for (int k = 0; k < CK; k++) {
-                int e = k * 64 + ln;
-                int i = tb + e;
-                if (i < n) g[i] = sg[(e / CK) * (CK + 1) + (e % CK)];
+                for (int k = 0; k < CK; k++) {
+                    const int e = k * 64 + ln;
+                    g[tb + e] = sg[(e / CK) * (CK + 1) + (e % CK)];
+                }
+            } else {
+#pragma unroll GAINS_SU
+                for (int k = 0; k < CK; k++) {
+                    int e = k * 64 + ln;
+                    int i = tb + e;
+                    if (i < n) g[i] = sg[(e / CK) * (CK + 1) + (e % CK)];
+                }
             }
+        } else if (committed) {
+            double p1 = carry1, p2 = carry2;
+#pragma unroll GAINS_EU
+            for (int k = 0; k < CK; k++) {
+                const int e = k * 64 + ln;
+                const int j = tb + e - 1;
+                const double xn = sg[(e / CK) * (CK + 1) + (e % CK)];
+                g[tb + e] = xn;
+                const double xj = wave_shr1_f64(xn, p1);
+                const double xp = wave_shr1_f64(xj, p2);
+                p1 = readlane_f64(xn, 63); p2 = readlane_f64(xn, 62);
+                bool pkf = false;
+                if (xp < xj) {
+                    if (xn < xj) pkf = true;
+                    else if (xn == xj) plateau = true;
+                }
+                unsigned long long mk = __ballot(pkf);
+                if (pkf) { const int at = npk + __popcll(mk & ((1ull << ln) - 1ull)); pk[at] = j; if (pkv) pkv[at] = xj; }
+                npk += __popcll(mk);
+            }
+            carry1 = sg[63 * (CK + 1) + CK - 1]; carry2 = sg[63 * (CK + 1) + CK - 2]; // tile offsets 1023, 1022
         } else {
             // ONE read of the staging tile serves both the trace's write-out and the pick-up of local maxima: the element a lane
             // stores is its "next" value, the two in front of it are its neighbours' -- a wave shift (v_mov_dpp wave_shr:1, lane 0
@@ -623,6 +733,8 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
         plateau = __any(plateau);
         if (ln == 0) npk_all[r] = plateau ? -1 : npk;
     }
+    if (ln == 0 && n_fast) atomicAdd(&g_dbg[76], (unsigned long long)n_fast);
+    if (ln == 0 && n_redo) atomicAdd(&g_dbg[77], (unsigned long long)n_redo); // (next to never)
     if (PASS == 1) {
         first_pos = wave_min(first_pos);
         last_pos = wave_max(last_pos);
