@@ -112,6 +112,8 @@ static int alloc_all(adp_handle *h, int reads, bool llr)
     bad |= h->pk.ensure(R * (Lp / 2 + 1) * 4);   // per-read peak lists (k_gains -> k_polya_peak)
     if (env_int("ADP_PK_VALUES", 1)) bad |= h->pkv.ensure(R * (Lp / 2 + 1) * 8);  // ... and the maxima's heights (twice the list's size: only when they are used)
     bad |= h->npk.ensure(R * 4);
+    bad |= h->wend.ensure(R * 4);          // how far pass 2 computed each read's trace (k_gains<2> -> k_polya_peak)
+    bad |= h->redo.ensure((R + 1) * 4);    // the windowed pass 2's redo list: count, then reads
     bad |= h->mk.ensure((size_t)h->pslots * (Lp / 2 + 1) * 4);
     }
     ALLOCCHK(bad);
@@ -632,13 +634,34 @@ static void launch_cumsum(adp_handle *h, int n)
 // k_gains' fast body for interior tiles (llr_stream.h; ADP_GAINS_TILE_FAST=0: every tile through the plain body, same results)
 static int gains_tile_fast() { return env_int("ADP_GAINS_TILE_FAST", 1) != 0; }
 
+// The window of pass 2 in pooled points behind the adapter candidate (llr_stream.h, peaks.h; 0: the whole trace).  ADP_G2_WINDOW, read
+// per call: unset -> the default for a full detect call and the whole trace for a staged debug call (whose callers fetch whole
+// buffers behind stages 6 and 7); set -> that value for both.  Same results either way.
+#define G2_WINDOW_DEFAULT 1024
+static int g2_window(int upto)
+{
+    const char *e = getenv("ADP_G2_WINDOW");
+    if (!e || !*e) return upto >= 8 ? G2_WINDOW_DEFAULT : 0;
+    const int w = env_int("ADP_G2_WINDOW", G2_WINDOW_DEFAULT);
+    return w < 0 ? 0 : (w > (1 << 28) ? (1 << 28) : w);
+}
+static void launch_gains2(adp_handle *h, int n, int mbsize, double *pkv, int win, const int32_t *redo)
+{
+    hipLaunchKernelGGL(k_gains<2>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, h->stream, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
+                       h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), mbsize, h->mbs.as<MbState>(),
+                       h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, 5, pkv, gains_tile_fast(),
+                       win, h->wend.as<int32_t>(), redo);
+}
+
 // pkv: the maxima's heights as k_gains<2> listed them, or null.  ADP_PK_PREFIX=0: the whole list of maxima at once (peaks.h; same results)
-static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv)
+// windowed: pass 2 left wend[r] and the reads it cannot decide go to the redo list; redo_pass: over that list, on whole traces
+static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv, bool windowed = false, bool redo_pass = false)
 {
     const int grid = n < h->pslots ? n : h->pslots;
     hipLaunchKernelGGL(k_polya_peak, dim3(grid), dim3(64), (size_t)(((h->Lp / 2 + 1) + 8) / 16 + 2) * 4, h->stream, h->trace.as<double>(), h->nvalid.as<int32_t>(), h->Lp,
                        h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, mbsize, h->mbs.as<MbState>(),
-                       h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>(), pkv, env_int("ADP_PK_PREFIX", PK_PREFIX));
+                       h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>(), pkv, env_int("ADP_PK_PREFIX", PK_PREFIX),
+                       (windowed || redo_pass) ? h->wend.as<int32_t>() : (const int32_t *)nullptr, (windowed || redo_pass) ? h->redo.as<int32_t>() : (int32_t *)nullptr, redo_pass ? 1 : 0);
 }
 
 template <class SIG>
@@ -745,15 +768,26 @@ static int llr_enqueue(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         }
         // (ADP_PK_VALUES=0: k_polya_peak gathers the heights from the trace, as before round 4; a handle made without the buffer keeps doing so)
         double *pkvp = (env_int("ADP_PK_VALUES", 1) && h->pkv.cap >= (size_t)n * (h->Lp / 2 + 1) * 8) ? h->pkv.as<double>() : nullptr;
+        // pass 2 over a window behind the adapter candidate; the reads the window does not settle are listed on the device and
+        // both kernels run again over the list with the whole trace -- no count comes back to the host, the launches cover the
+        // worst case and leave at once where the list ends
+        int win = g2_window(upto);
+        // (a window whose first tiles already hold the longest trace is the whole trace for every read: no list, no second launches)
+        if (win > 0 && (win + 1 + TRACE_TILE - 1) / TRACE_TILE * TRACE_TILE >= h->L) win = 0;
         if (upto >= 6) {
+            if (win > 0) HIPCHK(hipMemsetAsync(h->redo.p, 0, 4, st));
             Scope s(h, "k_gains<2>");
-            hipLaunchKernelGGL(k_gains<2>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, st, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
-                               h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), minibatch, mbs,
-                               h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, 5, pkvp, gains_tile_fast());
+            launch_gains2(h, n, minibatch, pkvp, win, nullptr);
         }
         if (upto >= 7) {
-            Scope s(h, "k_polya_peak");
-            launch_polya_peak(h, n, minibatch, pkvp);
+            { Scope s(h, "k_polya_peak");
+              launch_polya_peak(h, n, minibatch, pkvp, win > 0); }
+            if (win > 0) {
+                { Scope s(h, "k_gains<2> redo");
+                  launch_gains2(h, n, minibatch, pkvp, 0, h->redo.as<int32_t>()); }
+                { Scope s(h, "k_polya_peak redo");
+                  launch_polya_peak(h, n, minibatch, pkvp, false, true); }
+            }
         }
         if (ps && ps->done[1]) HIPCHK(hipEventRecord(ps->done[1], st));
     }
@@ -2334,6 +2368,8 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
     case 20: // (a handle made with ADP_PK_VALUES=0 has no such buffer)
         if (!h->pkv.p) { g_err = "this handle keeps no heights beside its maxima lists (ADP_PK_VALUES=0)"; return ADP_ERR_INVALID; }
         src = h->pkv.p; if (bytes > h->pkv.cap) return ADP_ERR_INVALID; break;
+    case 22: src = h->wend.p; if (bytes > h->wend.cap) return ADP_ERR_INVALID; break; // how far pass 2 computed each read's trace
+    case 23: src = h->redo.p; if (bytes > h->redo.cap) return ADP_ERR_INVALID; break; // the windowed pass 2's redo list: count, reads
     case 21: { // the minibatches' status words (ADP_MB_*), as the kernels of the last plain call left them
         if (h->last_grouped || !h->mbs.p || h->last_nmb < 1 || bytes > (uint64_t)h->last_nmb * 4 || h->gbelow.cap < (size_t)h->last_nmb * 4) return ADP_ERR_INVALID;
         hipLaunchKernelGGL(k_mb_status_out, dim3((h->last_nmb + 255) / 256), dim3(256), 0, h->stream, h->mbs.as<MbState>(), h->last_nmb, h->gbelow.as<int32_t>());

@@ -154,8 +154,10 @@ static __device__ int coop_find_up(const TV &t, int start, int limit, double xp,
 // is xp - max(left_min, right_min) <= xp - either minimum, in floating point too, so whatever the other side holds the test
 // pmin <= prominence fails -- the noise maxima of a rising or falling stretch, whose walk on the far side would run on to the end of
 // the trace, leave here), or PB_LEFT / PB_RIGHT bits: that side's walk was cut short by the budget (its minimum so far is not final).
-enum { PB_DONE = 0, PB_LEFT = 1, PB_RIGHT = 2, PB_REJECT = 4 };
-template <class TV>
+// WIN (a trace known on [lo, hi] only, the windowed pass 2: wave_peak_ok_win below): PB_OPEN says that the right walk reached hi
+// without meeting a higher sample -- its minimum is an upper bound of the side's true one, and shows nothing about the prominence.
+enum { PB_DONE = 0, PB_LEFT = 1, PB_RIGHT = 2, PB_REJECT = 4, PB_OPEN = 8 };
+template <bool WIN = false, class TV>
 static __device__ int tv_prominence_budget(const TV &t, int p, int budget, double pmin, double &prom, double &lmin_out, double &rmin_out)
 {
     const double xp = tv_get(t, p);
@@ -177,6 +179,7 @@ static __device__ int tv_prominence_budget(const TV &t, int p, int budget, doubl
     }
     if (!(more & PB_LEFT) && !(pmin <= xp - left_min)) return PB_REJECT;
     stopped = false;
+    bool higher = false; // (WIN) the right walk ended at a higher sample
     for (int i0 = p, steps = 0; !stopped && i0 <= t.hi; i0 += WALK_CHUNK, steps += WALK_CHUNK) {
         if (steps >= budget) { more |= PB_RIGHT; break; }
         double v[WALK_CHUNK];
@@ -185,17 +188,19 @@ static __device__ int tv_prominence_budget(const TV &t, int p, int budget, doubl
 #pragma unroll
         for (int u = 0; u < WALK_CHUNK; u++) {
             if (!stopped) {
-                if (i0 + u > t.hi || !(v[u] <= xp)) stopped = true;
+                if (i0 + u > t.hi || !(v[u] <= xp)) { stopped = true; if (WIN && i0 + u <= t.hi) higher = true; }
                 else if (v[u] < right_min) right_min = v[u];
             }
         }
     }
-    if (!(more & PB_RIGHT) && !(pmin <= xp - right_min)) return PB_REJECT;
+    if (WIN && !(more & PB_RIGHT) && !higher) more |= PB_OPEN;
+    if (!(more & (WIN ? PB_RIGHT | PB_OPEN : PB_RIGHT)) && !(pmin <= xp - right_min)) return PB_REJECT;
     prom = xp - (left_min > right_min ? left_min : right_min);
     lmin_out = left_min; rmin_out = right_min;
     return more;
 }
-template <class TV>
+// WIN: a right walk that ends at hi without a sample at or below the height leaves width = NaN (the crossing lies behind the window)
+template <bool WIN = false, class TV>
 static __device__ bool tv_width_budget(const TV &t, int p, double prom, double rel, int budget, double &width, double lmin, double rmin)
 {
     const double xp = tv_get(t, p);
@@ -219,6 +224,7 @@ static __device__ bool tv_width_budget(const TV &t, int p, double prom, double r
         }
     }
     int ir = t.hi;
+    bool crossed = false; // (WIN)
     {
         bool stopped = false;
         for (int i0 = p, steps = 0; !stopped && i0 < t.hi; i0 += WALK_CHUNK, steps += WALK_CHUNK) {
@@ -230,7 +236,7 @@ static __device__ bool tv_width_budget(const TV &t, int p, double prom, double r
             for (int u = 0; u < WALK_CHUNK; u++) {
                 if (!stopped) {
                     if (i0 + u >= t.hi) { stopped = true; ir = t.hi; }
-                    else if (!(height < v[u]) || v[u] == rmin) { stopped = true; ir = i0 + u; }
+                    else if (!(height < v[u]) || v[u] == rmin) { stopped = true; ir = i0 + u; crossed = true; }
                 }
             }
         }
@@ -239,6 +245,7 @@ static __device__ bool tv_width_budget(const TV &t, int p, double prom, double r
     { double xi = tv_get(t, il); if (xi < height) left_ip += (height - xi) / (tv_get(t, il + 1) - xi); }
     { double xi = tv_get(t, ir); if (xi < height) right_ip -= (height - xi) / (tv_get(t, ir - 1) - xi); }
     width = right_ip - left_ip;
+    if (WIN && !crossed) width = __builtin_nan("");
     return true;
 }
 
@@ -295,6 +302,117 @@ static __device__ bool wave_peak_ok(const TV &t, int p, double pmin, double wmin
         if (ln == src) width = right_ip - left_ip;
     }
     return cand && (wmin <= width);
+}
+
+// ---- a trace known on a window only ------------------------------------------------------------------------
+// The windowed pass 2 (llr_stream.h) computes x[0 .. wend) of a longer trace: t.lo = 0 is the trace's true start, t.hi = wend - 1
+// the last KNOWN sample, and what lies behind it is unknown.  wave_peak_ok's question then has three answers per maximum:
+// PK3_FAIL / PK3_PASS are what the whole trace would say, PK3_UNKNOWN is everything that cannot be shown from the window (the
+// caller computes the whole trace for that read, so an unknown costs time and never a wrong answer).  With h = x[p], lmin the left
+// walk's minimum (always exact: the trace is known back to its start) and rp the right walk's minimum:
+//   * the right walk met a higher sample inside the window: both minima are exact, and so is everything below.
+//   * it reached the window's end (PB_OPEN); the true right minimum is <= rp.
+//       rp <= lmin: the prominence is h - max(lmin, true right minimum) = h - lmin, exactly.  The evaluation height h - prom rel
+//         must lie above rp (else: unknown); then the right crossing comes no later than the sample that attains rp, inside the
+//         window, and a right base stop `v == true minimum` could only fire on a sample <= rp, which is below the height and stops
+//         the walk anyway -- the width is exact.
+//       rp > lmin: the prominence lies in [h - rp, h - lmin]; h - lmin < pmin was rejected when the left side completed.
+//         The width is non-decreasing in the prominence: a lower evaluation height moves the left crossing left and the right one
+//         right, whole samples first and within a sample by the interpolation, whose pieces -- h - prom rel, (height - xi) /
+//         (x[il+1] - xi), index +- quotient -- are each monotone under rounding.  Lower bound h - rp: its height lies above rp
+//         (else: unknown), so the right crossing is inside the window, and both base stops are idle (lmin < rp < height);
+//         pmin <= h - rp and wmin <= width(h - rp): PASS.  Upper bound h - lmin, walked with the known left base and NO right
+//         base stop (the walk without one goes at least as far): both crossings inside the window and width(h - lmin) < wmin: FAIL.
+//         Anything else: unknown.
+//   * a width walk that reaches the window's end without a crossing: unknown, whatever the prominence.
+enum { PK3_FAIL = 0, PK3_PASS = 1, PK3_UNKNOWN = 2 };
+
+// width at `height` of the maximum pp, cooperatively (uniform call); sl / sr: the base stops (-inf: none).  crossed: the right
+// crossing was found in front of t.hi
+template <class TV>
+static __device__ double coop_width(const TV &t, int pp, double xp, double height, double sl, double sr, bool &crossed)
+{
+    double dummy;
+    int il = coop_find_down<WALK_WIDTH>(t, pp, t.lo + 1, xp, height, dummy, sl);
+    if (il < t.lo + 1) il = t.lo;
+    int ir = coop_find_up<WALK_WIDTH>(t, pp, t.hi - 1, xp, height, dummy, sr);
+    crossed = ir <= t.hi - 1;
+    if (!crossed) ir = t.hi;
+    double left_ip = (double)il, right_ip = (double)ir;
+    { double xi = tv_get(t, il); if (xi < height) left_ip += (height - xi) / (tv_get(t, il + 1) - xi); }
+    { double xi = tv_get(t, ir); if (xi < height) right_ip -= (height - xi) / (tv_get(t, ir - 1) - xi); }
+    return right_ip - left_ip;
+}
+
+// Per lane: PK3_* for the local maximum p (or -1: none, PK3_FAIL).  Uniform call; p + 10 <= t.hi + 1 is the caller's distance rule.
+template <class TV>
+static __device__ int wave_peak_ok_win(const TV &t, int p, double pmin, double wmin, double rel)
+{
+    const int ln = lane_id();
+    double prom = 0.0, lmn = 0.0, rmn = 0.0;
+    bool have = p >= 0;
+    int pb = PB_DONE;
+    if (have) pb = tv_prominence_budget<true>(t, p, WALK_BUDGET, pmin, prom, lmn, rmn);
+    if (pb == PB_REJECT) { have = false; pb = PB_DONE; }
+    unsigned long long todo = __ballot(have && (pb & (PB_LEFT | PB_RIGHT)));
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int pp = __shfl(p, src), sides = __shfl(pb, src);
+        const double xp = tv_get(t, pp);
+        double lmin = __shfl(lmn, src), rmin = __shfl(rmn, src);
+        bool rej = false;
+        int open = sides & PB_OPEN;
+        if (sides & PB_LEFT) { coop_find_down<WALK_PROM>(t, pp, t.lo, xp, 0.0, lmin); rej = !(pmin <= xp - lmin); }
+        if (!rej && (sides & PB_RIGHT)) { if (coop_find_up<WALK_PROM>(t, pp, t.hi, xp, 0.0, rmin) > t.hi) open = PB_OPEN; }
+        if (ln == src) { if (rej) have = false; else { lmn = lmin; rmn = rmin; pb = open; } }
+    }
+    const double xpl = have ? tv_get(t, p) : 0.0;
+    const bool bounds = have && (pb & PB_OPEN) && rmn > lmn; // the prominence is known as an interval only
+    prom = xpl - (lmn > rmn ? lmn : rmn);
+    const bool cand = have && !bounds && (pmin <= prom);
+    int res = PK3_FAIL;
+    double width = 0.0;
+    bool done = true;
+    if (cand) done = tv_width_budget<true>(t, p, prom, rel, WALK_BUDGET, width, lmn, rmn);
+    todo = __ballot(cand && !done);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int pp = __shfl(p, src);
+        const double pr = __shfl(prom, src);
+        const double sl = __shfl(lmn, src), sr = __shfl(rmn, src);
+        const double xp = tv_get(t, pp);
+        bool crossed;
+        const double w = coop_width(t, pp, xp, xp - pr * rel, sl, sr, crossed);
+        if (ln == src) width = crossed ? w : __builtin_nan("");
+    }
+    if (cand) {
+        const double height = xpl - prom * rel;
+        if (width != width || ((pb & PB_OPEN) && !(rmn < height))) res = PK3_UNKNOWN;
+        else res = (wmin <= width) ? PK3_PASS : PK3_FAIL;
+    }
+    todo = __ballot(bounds);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int pp = __shfl(p, src);
+        const double sl = __shfl(lmn, src), sr = __shfl(rmn, src);
+        const double xp = tv_get(t, pp);
+        int rs = PK3_UNKNOWN;
+        bool crossed;
+        const double plo = xp - sr, phi = xp - sl;
+        if (pmin <= plo) {
+            const double hlo = xp - plo * rel;
+            if (sr < hlo) { const double w = coop_width(t, pp, xp, hlo, sl, sr, crossed); if (crossed && wmin <= w) rs = PK3_PASS; }
+        }
+        if (rs == PK3_UNKNOWN) {
+            const double w = coop_width(t, pp, xp, xp - phi * rel, sl, -__builtin_inf(), crossed);
+            if (crossed && w < wmin) rs = PK3_FAIL;
+        }
+        if (ln == src) res = rs;
+    }
+    return res;
 }
 
 // First peak (lowest index) of find_peaks(x[lo..hi], prominence=pmin, width=wmin, rel_height=rel),

@@ -64,7 +64,7 @@ struct adp_handle {
     // geometry of the LLR path
     int T = 0, off = 0, ds = 1, L = 0, Lp = 0, nck = 0, nsum = 0;
     DevBuf mbs, ghist, gbelow, gcnt, cbuf, fz, fcnt, n1heavy, ct_pk, ct_pv, ct_out, gstat, down, nvalid, ck, tail, trace, bmax, bmin, t1, adapter_idx, polya_idx;
-    DevBuf bounds, topk_none, rows, preq, series, have_series, vscratch, pk, pkv, npk, mk, st, sp, any_none, sig_stage, len_stage, bounds_stage;
+    DevBuf bounds, topk_none, rows, preq, series, have_series, vscratch, pk, pkv, npk, wend, redo, mk, st, sp, any_none, sig_stage, len_stage, bounds_stage;
     int vslots = 0, vstride = 0, pslots = 0;
     bool profiling = false;
     std::vector<ProfEntry> prof;

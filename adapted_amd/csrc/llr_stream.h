@@ -408,6 +408,9 @@ static __device__ __forceinline__ double readlane_f64(double x, int lane)
 // index with a positive-or-NaN gain).  PASS 2: start = adapter candidate, offsets (1, 1).
 // Emits the trace (float64) and per-64-point summaries: PASS 1 of the raw trace (NaN => +inf max),
 // PASS 2 of the np.nan_to_num-sanitised trace that find_peaks sees in P4.
+// PASS 2 only: win > 0 computes the tiles that hold the first win points behind the candidate and no more (the comment at the tile
+// loop); win <= 0 is the whole trace.  wend_all[r] takes how far the read's trace was computed.  redo != nullptr: the launch runs
+// over the reads listed in redo[1 .. 1 + redo[0]) instead of over all n_reads (the fallback behind the windowed k_polya_peak).
 //
 // THE FAST BODY OF AN INTERIOR TILE (tile_fast, ADP_GAINS_TILE_FAST=0 turns it off).  Per point the plain body decides three things
 // that hold for whole tiles of every ordinary read: that both variances are in log_cr_ok's range [2^-1022, inf), that the gain is
@@ -449,17 +452,21 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
                                               double *__restrict__ bmax, double *__restrict__ bmin, int nsum,
                                               int2 *__restrict__ t1, int sanitize, int32_t *__restrict__ pk_all,
                                               int32_t *__restrict__ npk_all, int pk_stride, double *__restrict__ gstat, int n_reads, int oh1,
-                                              double *__restrict__ pkv_all = nullptr, int tile_fast = 0)
+                                              double *__restrict__ pkv_all = nullptr, int tile_fast = 0, int win = 0,
+                                              int32_t *__restrict__ wend_all = nullptr, const int32_t *__restrict__ redo = nullptr)
 {
     // GAINS_WPB waves (reads) per block share log_cr's table; everything else is private to a wave, so the only
     // block-wide barrier is the one after the table copy
     __shared__ __attribute__((aligned(16))) double sg_[GAINS_WPB][64 * (CK + 1)];
     __shared__ __attribute__((aligned(16))) double lt_[3 * LOGCR_N]; // log_cr's table
     LDS double *sg = (LDS double *)sg_[threadIdx.x >> 6];
-    const int r = blockIdx.x * GAINS_WPB + (threadIdx.x >> 6);
+    int r = blockIdx.x * GAINS_WPB + (threadIdx.x >> 6);
     const int ln = lane_id();
+    // (the fallback of the windowed pass: wave w takes read redo[1 + w] of the redo[0] listed; a block behind the list leaves at once)
+    if (PASS == 2 && redo && (int)(blockIdx.x * GAINS_WPB) >= redo[0]) return;
     for (int i = threadIdx.x; i < 3 * LOGCR_N; i += 64 * GAINS_WPB) lt_[i] = g_logcr_table[i];
     __syncthreads();
+    if (PASS == 2 && redo) { if (r >= redo[0]) return; r = redo[1 + r]; }
     if (r >= n_reads) return;
     const LDS double *lt = (const LDS double *)lt_;
     auto flog = [&](double v) { return log_cr_impl(v, lt, [](double u) { return gains_log_slow(u); }); };
@@ -507,7 +514,18 @@ __global__ void __launch_bounds__(64 * GAINS_WPB, 4) k_gains(const float *__rest
     int npk = 0;
     bool plateau = false;
     double carry1 = 0.0, carry2 = 0.0; // sanitised x[tb-1], x[tb-2]
-    for (int tb = 0; tb < n; tb += TRACE_TILE) {
+    // THE WINDOW OF PASS 2 (win > 0): only the tiles that hold x[0 .. start + 1 + win) are computed -- every point depends on the
+    // checkpoints, tail[r] and start alone, so what is written on [0, wend) is what the whole-trace run writes there, bit for bit:
+    // the trace, the summaries, and the maxima up to wend - 2 (the window's last point has no known successor: it is never listed,
+    // and a plateau that reaches it is flagged where it starts, as any plateau).  Behind wend the buffers keep what was there.
+    // wend_all[r] = wend tells k_polya_peak how far the trace is known (peaks.h); n for a whole-trace read.
+    int wend = n;
+    if (PASS == 2 && win > 0) {
+        const int we = (start + 1 + win + TRACE_TILE - 1) / TRACE_TILE * TRACE_TILE;
+        wend = we < n ? we : n;
+    }
+    if (PASS == 2 && wend_all && ln == 0) wend_all[r] = wend;
+    for (int tb = 0; tb < wend; tb += TRACE_TILE) {
         // each lane walks CK = 16 consecutive pooled samples: four float4 loads (rows start 256-byte aligned and
         // are padded to Lp, so the loads stay inside the row; samples at or beyond n are not used)
         ws_sync();

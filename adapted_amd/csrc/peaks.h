@@ -135,21 +135,40 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                                                    const int32_t *__restrict__ adapter_idx, int n_reads, int mbsize,
                                                    const MbState *__restrict__ mbs, int32_t *__restrict__ pk_all,
                                                    uint32_t *__restrict__ mk_all, int32_t *__restrict__ polya_idx,
-                                                   const int32_t *__restrict__ npk_all, const double *__restrict__ pkv_all, int prefix)
+                                                   const int32_t *__restrict__ npk_all, const double *__restrict__ pkv_all, int prefix,
+                                                   const int32_t *__restrict__ wend_all = nullptr, int32_t *__restrict__ redo = nullptr,
+                                                   int redo_pass = 0)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t stw_raw[];
     LDS uint32_t *stw = (LDS uint32_t *)stw_raw; // ordinal k is slot k + 4 (slots 0..3 stay PST_NONE)
     const int ln = lane_id();
     const int half = Lp / 2 + 1;
     uint32_t *mk = mk_all + (size_t)blockIdx.x * half;
-    for (int r = blockIdx.x; r < n_reads; r += gridDim.x) {
+    // THE WINDOWED PASS 2 (wend_all != nullptr, redo_pass = 0): read r's trace, summaries and maxima are known on [0, wend_all[r])
+    // only.  wend == n: the whole-trace code, untouched.  wend < n: t.hi = wend - 1 is the last KNOWN sample, and every step answers "unknown" where
+    // the window does not show what the whole trace would say --
+    //   distance rule: a maximum at p >= wend - 10 may have an unseen neighbour within 9 samples; it stays undecided for good (not on
+    //     the work list), and the prefix machinery does the rest: what depends on it stays undecided, what is decided is final,
+    //     survivors are taken in front of the first undecided maximum only;
+    //   prominence and width: wave_peak_ok_win (find_peaks.h), three-valued;
+    //   the read: an unknown maximum met before the second survivor, fewer than two survivors, or (recount) a plateau that reaches the
+    //     window's end leave the read UNDECIDED -- nothing is written for it, its index goes to the redo list (redo[0]: count, zeroed
+    //     by the host; redo[1 ..]: reads), and k_gains<2> / this kernel run again over the list with the whole trace (redo_pass = 1).
+    //   A decided read's p0 < p1 and g[p0 .. p1] lie inside the window: step 5 is the whole trace's.
+    int n_decided = 0, n_listed = 0; // (g_dbg[78] / g_dbg[79]: windowed reads decided in the window / sent to the redo list)
+    const int n_work = redo_pass ? redo[0] : n_reads;
+    for (int wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
+        const int r = redo_pass ? redo[1 + wi] : wi;
         int32_t *pk = pk_all + (size_t)r * half; // per-read list, pre-filled by k_gains
         int result = 0;
         const int n = nvalid[r];
         const bool active = mbs[r / mbsize].status == ADP_MB_OK && adapter_idx[r] >= 0 && n >= 3;
+        bool undecided = false;
         if (active) {
             const double *g = trace + (size_t)r * Lp;
-            TraceView tv{g, bmax + (size_t)r * nsum, bmin + (size_t)r * nsum, 0, n - 1, 1};
+            const int wend = (wend_all && !redo_pass) ? min(wend_all[r], n) : n; // the trace is known on [0, wend)
+            const bool win = wend < n;
+            TraceView tv{g, bmax + (size_t)r * nsum, bmin + (size_t)r * nsum, 0, wend - 1, 1};
             // 1. all local maxima, in index order: normally found by k_gains while the trace tile was in LDS;
             //    recounted here (one load per lane, neighbours by shuffle) when a plateau was met
             int npk = npk_all[r];
@@ -159,18 +178,18 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
             if (recount) npk = 0;
             double carry = 0.0; // value at base - 1
             __syncthreads();
-            for (int base0 = 0; recount && base0 < n; base0 += 256) {
+            for (int base0 = 0; recount && base0 < wend; base0 += 256) {
                 double vv[4], ee[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) { // four tiles in flight
                     const int i = base0 + u * 64 + ln;
-                    vv[u] = (i < n) ? tv_get(tv, i) : 0.0;
-                    ee[u] = (ln == 63 && i + 1 < n) ? tv_get(tv, i + 1) : 0.0;
+                    vv[u] = (i < wend) ? tv_get(tv, i) : 0.0;
+                    ee[u] = (ln == 63 && i + 1 < wend) ? tv_get(tv, i + 1) : 0.0;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int base = base0 + u * 64;
-                    if (base >= n) break;
+                    if (base >= wend) break;
                     const int i = base + ln;
                     const double v = vv[u];
                     double prev = __shfl_up(v, 1);
@@ -179,12 +198,13 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                     if (ln == 63) next = ee[u];
                     carry = __shfl(v, 63);
                     int p = -1;
-                    if (i > 0 && i < n - 1 && prev < v) {
+                    if (i > 0 && i < wend - 1 && prev < v) {
                         if (next < v) p = i;
                         else if (next == v) { // plateau: walk to its end (rare on float64 traces)
                             int j = i + 1;
-                            while (j < n - 1 && tv_get(tv, j) == v) j++;
+                            while (j < wend - 1 && tv_get(tv, j) == v) j++;
                             if (tv_get(tv, j) < v) p = (i + j - 1) / 2;
+                            else if (win && tv_get(tv, j) == v) undecided = true; // (it reaches the window's end: its midpoint is unknown)
                         }
                     }
                     unsigned long long m = __ballot(p >= 0);
@@ -192,6 +212,7 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                     npk += __popcll(m);
                 }
             }
+            undecided = __any(undecided);
             if (ABLATED(256)) npk = 0;
             // Only the first two survivors in index order are wanted, and they lie near the front of almost every trace: steps 2-4 run
             // on a PREFIX of the list first (the first wn maxima; the maxima behind it read as undecided, so a state that depends on
@@ -262,12 +283,13 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                         if (lb >> (j - 1) & 1u) mask |= 1u << (4 + j - 1); // k-j is within 9 and k is lower than it
                     }
                     const bool out = valid && ln >= 4 && ln < 60 && k < wn;
+                    const bool late = win && p >= wend - 10; // (a neighbour within 9 samples may lie behind the window)
                     if (out) {
                         const uint32_t sl = (uint32_t)(k + 4);
-                        __hip_atomic_fetch_or(&stw[sl >> 4], (mask ? PST_UNDECIDED : PST_KEPT) << ((sl & 15u) * 2u), __ATOMIC_RELAXED,
+                        __hip_atomic_fetch_or(&stw[sl >> 4], ((mask || late) ? PST_UNDECIDED : PST_KEPT) << ((sl & 15u) * 2u), __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
-                    const bool und = out && mask;
+                    const bool und = out && mask && !late;
                     const unsigned long long m = __ballot(und);
                     if (und) mk[nund + __popcll(m & ((1ull << ln) - 1ull))] = ((uint32_t)k << 8) | mask;
                     nund += __popcll(m);
@@ -350,22 +372,30 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
             p0 = -1; p1 = -1;
             // (16 candidates per step: the second survivor is among the first 32 kept maxima of almost every read, and
             // every candidate with a long walk costs the whole wave a cooperative scan)
-            for (int base = 0; base < nkept && p1 < 0 && !ABLATED(1024); base += PK_STEP) {
+            for (int base = 0; base < nkept && p1 < 0 && !undecided && !ABLATED(1024); base += PK_STEP) {
                 int k = base + ln;
                 int i = (ln < PK_STEP && k < nkept) ? kl[k] : -1;
-                const bool ok = wave_peak_ok(tv, i, 1.0, 10.0, 0.5);
-                unsigned long long m = __ballot(ok);
+                int ok3;
+                if (win) ok3 = wave_peak_ok_win(tv, i, 1.0, 10.0, 0.5);
+                else ok3 = wave_peak_ok(tv, i, 1.0, 10.0, 0.5) ? PK3_PASS : PK3_FAIL;
+                unsigned long long m = __ballot(ok3 != PK3_FAIL);
+                const unsigned long long unk = __ballot(ok3 == PK3_UNKNOWN);
                 while (m && p1 < 0) {
                     int f = __ffsll((long long)m) - 1;
                     m &= m - 1;
+                    if (unk >> f & 1ull) { undecided = true; break; } // (in index order: an unknown in front of the second survivor)
                     int pi = __shfl(i, f);
                     if (p0 < 0) p0 = pi; else p1 = pi;
                 }
             }
-            if (p1 >= 0 || first_und >= npk) break; // (else: the prefix did not settle it)
+            if (p1 >= 0 || first_und >= npk || undecided) break; // (else: the prefix did not settle it)
             }
+            if (win && p1 < 0) undecided = true; // (a survivor may lie behind the window)
             // 5. spike heuristics on the UN-sanitised trace
-            if (p0 >= 0 && p1 < 0) result = p0;
+            if (undecided) {
+                n_listed++;
+                if (ln == 0) redo[1 + atomicAdd(&redo[0], 1)] = r;
+            } else if (p0 >= 0 && p1 < 0) result = p0;
             else if (p0 >= 0) {
                 double h0 = g[p0], h1 = g[p1];
                 if (h1 > h0) result = p1;
@@ -404,8 +434,11 @@ __global__ void __launch_bounds__(64, 8) k_polya_peak(const double *__restrict__
                     result = (rr * rr >= 0.99) ? p1 : 0;
                 }
             }
+            if (win && !undecided) n_decided++;
             __syncthreads();
         }
-        if (ln == 0) polya_idx[r] = result;
+        if (ln == 0 && !undecided) polya_idx[r] = result;
     }
+    if (ln == 0 && n_decided) atomicAdd(&g_dbg[78], (unsigned long long)n_decided);
+    if (ln == 0 && n_listed) atomicAdd(&g_dbg[79], (unsigned long long)n_listed);
 }

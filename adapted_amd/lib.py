@@ -1495,7 +1495,8 @@ class Engine:
                   5: ((n,), np.int32), 7: ((n, 2), np.int32), 9: ((n,), np.int8),
                   13: ((n, Lp // 16, 2), np.float64), 14: ((n, 2), np.float64), 15: ((n, Lp // 64), np.float64),
                   16: ((n, Lp // 64), np.float64), 17: ((n, 3), np.float64), 18: ((n,), np.int32),
-                  19: ((n, Lp // 2 + 1), np.int32), 20: ((n, Lp // 2 + 1), np.float64), 21: ((n,), np.int32)}
+                  19: ((n, Lp // 2 + 1), np.int32), 20: ((n, Lp // 2 + 1), np.float64), 21: ((n,), np.int32),
+                  22: ((n,), np.int32), 23: ((n + 1,), np.int32)}
         if what == 0:
             raise ValueError("use debug_norm_params")
         shp, dt = shapes[what]

@@ -602,7 +602,10 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *       18 npk int32[n]: strict local maxima of pass 2's sanitised trace, -1: a plateau was met (k_polya_peak recounts);
  *       19 pk int32[n*(Lp/2+1)]: their positions; 20 pkv float64[n*(Lp/2+1)]: their heights (ADP_ERR_INVALID on a handle made
  *       with ADP_PK_VALUES=0); 21 int32[n_minibatch]: the minibatches' status words.  Reads of a dropped minibatch and reads
- *       whose pass did not run (no adapter candidate: pass 2) keep what an earlier call left. */
+ *       whose pass did not run (no adapter candidate: pass 2) keep what an earlier call left.
+ *       22 wend int32[n]: pass 2 computed the read's trace, summaries and maxima on [0, wend) (ADP_G2_WINDOW; n_valid: all of it;
+ *       a read of the redo list ends with n_valid); 23 int32[n+1]: the windowed pass 2's redo list of the last call, count then reads
+ *       (in no order).  Tallies 78 / 79 of selector 8: windowed reads decided inside the window / sent to the redo list. */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,
