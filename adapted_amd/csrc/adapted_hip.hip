@@ -209,7 +209,6 @@ int adp_destroy(adp_handle *h)
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipStreamDestroy(h->stream3); }
     for (int i = 0; i < 16; i++) if (h->ev_copy[i]) (void)hipEventDestroy(h->ev_copy[i]);
-    for (int i = 0; i < 3; i++) if (h->ev_conv[i]) (void)hipEventDestroy(h->ev_conv[i]);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1443,8 +1442,7 @@ int adp_cnn_prepare(adp_handle *h, const float *signals, int n_reads, int m, int
 #define CNN_B2 (CNN_W2 + CNN_C * CNN_C * CNN_K)
 #define CNN_W3 (CNN_B2 + CNN_C)
 #define CNN_B3 (CNN_W3 + CNN_C * 2 * CNN_K)
-#define CNN_W3S (CNN_B3 + 2)                 // layer 3's weights times 1 / CNS_ASCALE (exact: a power of two) for the split stack's last layer
-#define CNN_WTOTAL (CNN_W3S + CNN_C * 2 * CNN_K)
+#define CNN_WTOTAL (CNN_B3 + 2)
 
 int adp_cnn_set_weights(adp_handle *h, const float *w0, const float *b0, const float *w1, const float *b1, const float *w2,
                         const float *b2, const float *w3, const float *b3)
@@ -1457,7 +1455,6 @@ int adp_cnn_set_weights(adp_handle *h, const float *w0, const float *b0, const f
     memcpy(&all[CNN_W1], w1, sizeof(float) * CNN_C * CNN_C * CNN_K); memcpy(&all[CNN_B1], b1, sizeof(float) * CNN_C);
     memcpy(&all[CNN_W2], w2, sizeof(float) * CNN_C * CNN_C * CNN_K); memcpy(&all[CNN_B2], b2, sizeof(float) * CNN_C);
     memcpy(&all[CNN_W3], w3, sizeof(float) * CNN_C * 2 * CNN_K); memcpy(&all[CNN_B3], b3, sizeof(float) * 2);
-    for (int i = 0; i < CNN_C * 2 * CNN_K; i++) all[CNN_W3S + i] = w3[i] * (1.0f / CNS_ASCALE);
     HIPCHK(hipMemcpyAsync(h->cnn_w.p, all.data(), (size_t)CNN_WTOTAL * 4, hipMemcpyHostToDevice, h->stream));
     // the 64 -> 64 layers once more as split float16 B fragments (cnn_conv_split.h), scaled by a power of two per layer so that the
     // largest weight lands in [2^13, 2^14)
@@ -1533,6 +1530,55 @@ static int launch_conv64s(adp_handle *h, const _Float16 *in, _Float16 *out, cons
                        w3sp, b3, inv_s3, scores, Lo, first);
     return 0;
 }
+// The split stack's kernels over the n reads of a chunk, each launcher with the arguments of its role (wh: the handle that owns the weights).
+// Layers 0 + 1: the prepared signal x in, layer 1's rows out; tiles that advance by 64 NT - 6 positions
+template <int NT>
+static int launch_conv_first(adp_handle *h, adp_handle *wh, const float *x, int Lc, _Float16 *rows, int n, int L1, int Lrows, int32_t *flag)
+{
+    Scope s(h, "k_cnn_conv64 (layer 1)");
+    const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
+    const float *W = wh->cnn_w.as<float>();
+    const CnsFirst first{x, Lc, wsp + (size_t)2 * CNS_WSP_LAYER + CNS_W3SP, W + CNN_B0, wh->cnn_sw[3]};
+    return launch_conv64s<NT, false, true>(h, nullptr, rows, wsp, W + CNN_B1, wh->cnn_sw[0], n, L1, Lrows, (L1 + 64 * NT - 7) / (64 * NT - 6), flag,
+                                           nullptr, nullptr, 0.f, nullptr, 0, first);
+}
+// Layers 2 + 3: layer 1's rows in, the scores out (`dump`: one row for the stores that have no output); tiles that advance by 64 NT - 2
+template <int NT>
+static int launch_conv_last(adp_handle *h, adp_handle *wh, const _Float16 *rows, _Float16 *dump, float *scores, int Lo, int n, int L1, int Lrows,
+                            int32_t *flag)
+{
+    Scope s(h, "k_cnn_conv64 (layer 2)");
+    const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
+    const float *W = wh->cnn_w.as<float>();
+    return launch_conv64s<NT, true>(h, rows, dump, wsp + CNS_WSP_LAYER, W + CNN_B2, wh->cnn_sw[1], n, L1, Lrows, (L1 + 64 * NT - 3) / (64 * NT - 2), flag,
+                                    wsp + (size_t)2 * CNS_WSP_LAYER, W + CNN_B3, 1.0f / (wh->cnn_sw[2] * CNS_ASCALE), scores, Lo);
+}
+// ADP_CNN_FUSE_IN=0, FIRST's A/B partner: layer 0 as a kernel of its own, its rows through HBM (rows0) into layer 1 in the kernel's plain form
+template <int NT>
+static int launch_conv_first_apart(adp_handle *h, adp_handle *wh, const float *x, int Lc, _Float16 *rows0, _Float16 *rows, int n, int L1, int Lrows,
+                                   int32_t *flag)
+{
+    const float *W = wh->cnn_w.as<float>();
+    { Scope s(h, "k_cnn_conv_in");
+      hipLaunchKernelGGL(k_cnn_conv_in_s, dim3((L1 + CNS_IN_P * CNS_IN_T - 1) / (CNS_IN_P * CNS_IN_T), n), dim3(256), 0, h->stream, x, Lc, L1, Lrows,
+                         W + CNN_W0, W + CNN_B0, rows0, flag); }
+    Scope s(h, "k_cnn_conv64 (layer 1)");
+    return launch_conv64s<NT, false>(h, rows0, rows, wh->cnn_wsp.as<_Float16>(), W + CNN_B1, wh->cnn_sw[0], n, L1, Lrows, (L1 + 64 * NT - 1) / (64 * NT), flag);
+}
+// the chunks of a call: layers 0 + 1, then layers 2 + 3
+template <int NT>
+static int conv_split_chunks(adp_handle *h, adp_handle *wh, const float *prepared, int n_reads, int C, int Lc, int L1, int Lo, int Lrows,
+                             _Float16 *rows0, _Float16 *rows, _Float16 *dump, int32_t *flag, float *scores_out)
+{
+    for (int s0 = 0; s0 < n_reads; s0 += C) {
+        const int n = n_reads - s0 < C ? n_reads - s0 : C;
+        const float *x = prepared + (size_t)s0 * Lc;
+        if (rows0) RCCHK(launch_conv_first_apart<NT>(h, wh, x, Lc, rows0, rows, n, L1, Lrows, flag));
+        else RCCHK(launch_conv_first<NT>(h, wh, x, Lc, rows, n, L1, Lrows, flag));
+        RCCHK(launch_conv_last<NT>(h, wh, rows, dump, scores_out + (size_t)s0 * 2 * Lo, Lo, n, L1, Lrows, flag));
+    }
+    return 0;
+}
 } // extern "C++"
 
 // the conv stack on split float16 operands (cnn_conv_split.h); the out-of-range flag is the second word of the call's arena counter
@@ -1540,89 +1586,30 @@ static int cnn_forward_split(adp_handle *h, adp_handle *wh, const float *prepare
 {
     const int PB = 64 * NT, tiles = (L1 + PB - 1) / PB, Lrows = CNS_FRONT + tiles * PB + 4;
     const size_t per_read = (size_t)Lrows * CNS_ROWB;
-    size_t cap_reads = ((size_t)4 << 30) / per_read; // two activation buffers of at most 4 GiB each
+    size_t cap_reads = ((size_t)4 << 30) / per_read; // an activation buffer of at most 4 GiB
     if (cap_reads < 1) cap_reads = 1;
-    if (cap_reads > 65535) cap_reads = 65535;        // (the first / last layer's kernels take the chunk's reads as grid.y)
+    if (cap_reads > 65535) cap_reads = 65535;        // (k_cnn_conv_in_s takes the chunk's reads as grid.y)
     int C = (int)((size_t)n_reads < cap_reads ? (size_t)n_reads : cap_reads);
-    if (h->cnn_Lpad != Lrows || h->cnn_L1 != L1 || h->cnn_chunk < C) {
-        for (int k = 0; k < 2; k++) {
-            ALLOCCHK(h->cnn_act[k].ensure((size_t)C * per_read + CNS_SLACK)); // (+ what the tile DMAs read past the last read's rows)
+    // cnn_act[0]: layer 1's rows, the only activations in HBM; cnn_act[1]: layer 0's, under ADP_CNN_FUSE_IN=0 alone
+    const int nbuf = env_int("ADP_CNN_FUSE_IN", 1) != 0 ? 1 : 2;
+    if (h->cnn_Lpad != Lrows || h->cnn_L1 != L1 || h->cnn_chunk < C || h->cnn_nbuf < nbuf) {
+        size_t bytes = (size_t)C * per_read + CNS_SLACK; // (+ what the tile DMAs read past the last read's rows)
+        for (int k = 0; k < nbuf; k++) {
+            if (bytes < h->cnn_act[0].cap) bytes = h->cnn_act[0].cap; // (cnn_chunk comes from cnn_act[0]: the other is never smaller)
+            ALLOCCHK(h->cnn_act[k].ensure(bytes));
             HIPCHK(hipMemsetAsync(h->cnn_act[k].p, 0, h->cnn_act[k].cap, h->stream)); // the padding rows are never written again
         }
+        h->cnn_nbuf = nbuf; // (the buffers laid down for this geometry)
         h->cnn_Lpad = Lrows; h->cnn_L1 = L1; h->cnn_chunk = (int)((h->cnn_act[0].cap - CNS_SLACK) / per_read); if (h->cnn_chunk > 65535) h->cnn_chunk = 65535;
     }
     C = h->cnn_chunk < n_reads ? h->cnn_chunk : n_reads;
+    ALLOCCHK(h->cnn_dump.ensure(CNS_ROWB)); // written by the LAST kernel's stores without an output, never read: no clearing
     ALLOCCHK(wh->op_used.ensure(16));
     int32_t *flag = wh->op_used.as<int32_t>() + 1;
-    const float *W = wh->cnn_w.as<float>();
-    const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
-    _Float16 *bufs[2] = {h->cnn_act[0].as<_Float16>(), h->cnn_act[1].as<_Float16>()};
-    // The chunks' LAST layer runs on the side stream beside the NEXT chunk's first layer (round 4): layer 3 only reads split rows (4.4 TB/s),
-    // layer 0 only writes them (3.5 TB/s), neither touches the matrix cores -- together they move more bytes per second than in turn.  The
-    // two activation buffers swap roles from chunk to chunk (X: layer 0's output and layer 2's; Y: layer 1's), so layer 0 of chunk c + 1
-    // writes what layer 2 of chunk c has just finished READING while layer 3 of chunk c reads the other buffer; layer 1 of chunk c + 1 waits
-    // for that layer 3 (it overwrites its input).  ADP_CNN_OVERLAP=0: everything in turn on one stream, as before.
-    // ADP_CNN_FOLD=1 (round 5): layer 3 in layer 2's epilogue (k_cnn_conv64s<NT, true>): no rows of layer 2 in HBM, no k_cnn_conv_out_s, nothing
-    // left to run beside the next chunk's first layer -- one stream, the buffers keep their roles
-    const bool fold = env_int("ADP_CNN_FOLD", 1) != 0;
-    // ADP_CNN_FUSE_IN=1 (round 5): layer 0 in layer 1's prologue, on the matrix cores (k_cnn_conv64s<NT, false, true>): no k_cnn_conv_in_s, no
-    // rows of layer 0 in HBM
-    const bool fuse_in = env_int("ADP_CNN_FUSE_IN", 1) != 0;
-    const int tiles_last = (L1 + PB - 3) / (PB - 2); // tiles of the folded layer: they advance by PB - 2 positions
-    const int tiles_first = (L1 + PB - 7) / (PB - 6); // ... of the layer that makes its input rows: by PB - 6
-    const bool overlap = env_int("ADP_CNN_OVERLAP", 1) != 0 && !fold && !fuse_in;
-    if (overlap && !h->ev_conv[0]) {
-        for (int i = 0; i < 3; i++) if (hipEventCreateWithFlags(&h->ev_conv[i], hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; return ADP_ERR_HIP; }
-    }
-    int chunk = 0;
-    bool out_pending = false; // a layer 3 on the side stream that the main stream has not waited for yet
-    // an error return from inside the chunk loop must not leave that layer 3 running: the caller's repeat (or its float32 fallback)
-    // reuses the activation buffers and the scores on the main stream
-    struct SideJoin { hipStream_t side; bool *pending; ~SideJoin() { if (*pending) (void)hipStreamSynchronize(side); } } side_join{h->stream2, &out_pending};
-    for (int s0 = 0; s0 < n_reads; s0 += C, chunk++) {
-        const int n = n_reads - s0 < C ? n_reads - s0 : C;
-        const float *x = prepared + (size_t)s0 * Lc;
-        float *sc = scores_out + (size_t)s0 * 2 * Lo;
-        _Float16 *A = bufs[overlap ? (chunk & 1) : 0], *B = bufs[overlap ? 1 - (chunk & 1) : 1];
-        if (!fuse_in) {
-            Scope s(h, "k_cnn_conv_in");
-            hipLaunchKernelGGL(k_cnn_conv_in_s, dim3((L1 + CNS_IN_P * CNS_IN_T - 1) / (CNS_IN_P * CNS_IN_T), n), dim3(256), 0, h->stream, x, Lc, L1, Lrows, W + CNN_W0, W + CNN_B0, A, flag);
-        }
-        if (out_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_conv[1 + ((chunk - 1) & 1)], 0)); out_pending = false; } // (layer 1 overwrites what that layer 3 reads)
-        for (int layer = 0; layer < 2; layer++) {
-            Scope s(h, layer ? "k_cnn_conv64 (layer 2)" : "k_cnn_conv64 (layer 1)");
-            const _Float16 *in = layer ? B : A; _Float16 *out = layer ? A : B;
-            const _Float16 *w = wsp + (size_t)layer * CNS_WSP_LAYER;
-            const float *b = W + (layer ? CNN_B2 : CNN_B1);
-            const float sw = wh->cnn_sw[layer];
-            int rc;
-            if (layer == 1 && fold) {
-                const _Float16 *w3sp = wsp + (size_t)2 * CNS_WSP_LAYER;
-                const float inv_s3 = 1.0f / (wh->cnn_sw[2] * CNS_ASCALE);
-                rc = NT == 4 ? launch_conv64s<4, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_last, flag, w3sp, W + CNN_B3, inv_s3, sc, Lo)
-                   : NT == 3 ? launch_conv64s<3, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_last, flag, w3sp, W + CNN_B3, inv_s3, sc, Lo)
-                             : launch_conv64s<2, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_last, flag, w3sp, W + CNN_B3, inv_s3, sc, Lo);
-            } else if (layer == 0 && fuse_in) {
-                const CnsFirst first{x, Lc, wsp + (size_t)2 * CNS_WSP_LAYER + CNS_W3SP, W + CNN_B0, wh->cnn_sw[3]};
-                rc = NT == 4 ? launch_conv64s<4, false, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_first, flag, nullptr, nullptr, 0.f, nullptr, 0, first)
-                   : NT == 3 ? launch_conv64s<3, false, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_first, flag, nullptr, nullptr, 0.f, nullptr, 0, first)
-                             : launch_conv64s<2, false, true>(h, in, out, w, b, sw, n, L1, Lrows, tiles_first, flag, nullptr, nullptr, 0.f, nullptr, 0, first);
-            } else
-                rc = NT == 4 ? launch_conv64s<4, false>(h, in, out, w, b, sw, n, L1, Lrows, tiles, flag)
-                   : NT == 3 ? launch_conv64s<3, false>(h, in, out, w, b, sw, n, L1, Lrows, tiles, flag)
-                             : launch_conv64s<2, false>(h, in, out, w, b, sw, n, L1, Lrows, tiles, flag);
-            if (rc) return rc;
-        }
-        if (fold) continue;
-        const bool last = s0 + C >= n_reads;
-        hipStream_t so = (overlap && !last) ? h->stream2 : h->stream; // (the last chunk's layer 3 has nothing to run beside)
-        if (so != h->stream) { HIPCHK(hipEventRecord(h->ev_conv[0], h->stream)); HIPCHK(hipStreamWaitEvent(so, h->ev_conv[0], 0)); }
-        { Scope s(h, "k_cnn_conv_out", so);
-          hipLaunchKernelGGL(k_cnn_conv_out_s, dim3((L1 + CNS_OUT_P - 1) / CNS_OUT_P, n), dim3(CNS_OUT_P), 0, so, A, L1, Lrows, Lo, W + CNN_W3S, W + CNN_B3, sc); }
-        if (so != h->stream) { HIPCHK(hipEventRecord(h->ev_conv[1 + (chunk & 1)], so)); out_pending = true; }
-    }
-    if (out_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_conv[1 + ((chunk - 1) & 1)], 0)); out_pending = false; }
-    return 0;
+    _Float16 *rows0 = nbuf == 2 ? h->cnn_act[1].as<_Float16>() : nullptr, *rows = h->cnn_act[0].as<_Float16>(), *dump = h->cnn_dump.as<_Float16>();
+    return NT == 4 ? conv_split_chunks<4>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out)
+         : NT == 3 ? conv_split_chunks<3>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out)
+                   : conv_split_chunks<2>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out);
 }
 
 // the conv stack over device buffers, asynchronous on the handle's stream

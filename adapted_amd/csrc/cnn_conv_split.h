@@ -56,12 +56,15 @@ static __device__ __forceinline__ void cns_static_for(F &&f)
 #define CNS_LIMIT 32768.0f   // a STORED activation at or beyond it (or non-finite) repeats the call on the float32 kernels ...
 #define CNS_ASCALE 0.0625f   // ... and activations are stored times 2^-4: real values up to 5.2e5 stay in range (exact scaling; it
                              // rides through the 64 -> 64 layers with the bias and leaves in layer 3)
-#define CNS_SLACK 131072     // bytes behind the last read's rows that a tile DMA may read (k_cnn_conv_out_s: up to 130 rows from a row below L1;
-                             // the overlapping tiles of the folded last layer: up to 64 NT rows)
+#define CNS_SLACK 131072     // bytes behind the last read's rows that a tile DMA may read.  The LAST kernel's tiles advance by PB - 2 positions: a read's
+                             // last tile starts at row CNS_FRONT - 4 + L1 - 1 at the latest and its DMA is PB + 6 rows rounded up to whole KBs; with
+                             // Lrows >= CNS_FRONT + L1 + 4 that ends at most PB - 3 rows + 1023 bytes behind the read's rows: 69 839 bytes at NT = 4
+                             // (the plain form's tiles advance by PB and end inside the rows or less than 1 KB behind them)
 #define CNS_WSP_LAYER (2 * CNS_KSTEPS * 2 * 64 * 8) // float16 per layer in the split-weight buffer
 // Row 0 of a read's front padding is the DUMP row: the epilogues store the pieces of rows at or beyond L1 there so that every store is issued
-// and the counted s_waitcnt stays exact.  Nothing may read it: a tile's DMA starts at row CNS_FRONT - 3, layer 3's block at CNS_FRONT - 1.
-static_assert(CNS_FRONT >= 4, "the dump row (row 0) must lie in front of every row a tile DMA or the last layer reads");
+// and the counted s_waitcnt stays exact.  No result may depend on it: the LAST kernel's first tile starts there (row CNS_FRONT - 4), but only
+// position -1 is computed from it, and that one is replaced by layer 3's zero padding; every other tile DMA starts behind it.
+static_assert(CNS_FRONT >= 4, "the dump row (row 0) must lie in front of every row that a kept position is computed from");
 
 static __device__ __forceinline__ void cns_split(float y, _Float16 &hi, _Float16 &lo)
 {
@@ -217,7 +220,8 @@ __global__ void __launch_bounds__(256) k_cnn_conv_in_s(const float *__restrict__
 // they are the B operand of one more GEMM (k_cns_split_w3's A fragments: 12 MFMAs per 32 positions); the partial sums of a position's
 // seven taps go to LDS, and output 3 j + d of channel o is b + P[j - 1][6] + P[j][3] + P[j + 1][0] (d = 0), P[j][3 + d] + P[j + 1][d]
 // (d = 1, 2).  A tile's first and last position only lend their partial sums: tiles advance by PB - 2 positions and start at -1.
-// No rows of layer 2 in HBM (1.8 MB per read written and read back) and no k_cnn_conv_out_s.
+// No rows of layer 2 in HBM (1.8 MB per read written and read back) and no kernel for layer 3; `out` is only the 256-byte dump target.
+// Layer 2 always runs in this form.
 // FIRST (round 5): layer 0 -- Conv1d(1 -> 64, k 7, stride 3, pad 3) + ReLU -- in this kernel's prologue.  No input rows in HBM: the
 // tile's input rows are made in LDS from the prepared signal by 3 MFMAs per 32 rows and channel half (k_cns_split_w0's A fragments;
 // the samples of a row are its B fragment, loaded a tile ahead), converted like an epilogue's results; rows outside [0, L1) are the
@@ -599,63 +603,7 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
 // the next tile's MFMAs -- k_cnn_conv64p, slower; layer 0 computed inside layer 1's kernel as float32 fmaf chains -- no gain (round 5's
 // FIRST does it on the matrix cores).  Sources and records: tools/experiments/r05_pruned_variants.patch,
 // profiles/r04_tried_and_dropped.txt.)
-
-// ---------------------------------------------------------------- layer 3: ConvTranspose1d(64 -> 2, k 7, stride 3, pad 3) from split rows
-// the arithmetic of k_cnn_conv_out on a = hi + lo 2^-11; thread j makes the outputs 3 j, 3 j + 1, 3 j + 2 of both channels.
-// grid = (ceil(L1 / 128), n); block = 128: the 130 rows of the block are one contiguous range, brought into LDS by LDS-DMA
-// (coalesced) and read from there row by row (272-byte pitch: conflict-free 16-byte reads).
-#define CNS_OUT_P 128
-#define CNS_OUT_LDS (((CNS_OUT_P + 2) * CNS_ROWB + 1023) / 1024 * 1024)
-__global__ void __launch_bounds__(CNS_OUT_P) k_cnn_conv_out_s(const _Float16 *__restrict__ h, int L1, int Lrows, int Lo,
-                                                               const float *__restrict__ w /* [64][2][7] times 1 / CNS_ASCALE */, const float *__restrict__ b,
-                                                               float *__restrict__ scores /* [n][2][Lo] */)
-{
-    __shared__ __attribute__((aligned(16))) char rows_[CNS_OUT_LDS];
-    LDS char *rows = (LDS char *)rows_;
-    const int n = blockIdx.y;
-    const int j0 = blockIdx.x * CNS_OUT_P;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    {
-        const GLB char *src = (const GLB char *)h + ((size_t)n * Lrows + CNS_FRONT + j0 - 1) * CNS_ROWB + lane * 16;
-        for (int inst = wave; inst < CNS_OUT_LDS / 1024; inst += CNS_OUT_P / 64)
-            __builtin_amdgcn_global_load_lds((const GLB float *)(src + inst * 1024), (LDS float *)(rows + inst * 1024), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int j = j0 + threadIdx.x;
-    if (j >= L1) return;
-    const LDS char *hr = rows + (threadIdx.x + 1) * CNS_ROWB;
-    float y[2][3];
-#pragma unroll
-    for (int o = 0; o < 2; o++) { y[o][0] = b[o]; y[o][1] = b[o]; y[o][2] = b[o]; }
-#pragma unroll 2
-    for (int c8 = 0; c8 < CNN_C / 8; c8++) {
-        const cnn_h8 mh_ = *reinterpret_cast<const LDS cnn_h8 *>(hr - CNS_ROWB + c8 * 16), ml_ = *reinterpret_cast<const LDS cnn_h8 *>(hr - CNS_ROWB + 128 + c8 * 16);
-        const cnn_h8 zh_ = *reinterpret_cast<const LDS cnn_h8 *>(hr + c8 * 16), zl_ = *reinterpret_cast<const LDS cnn_h8 *>(hr + 128 + c8 * 16);
-        const cnn_h8 ph_ = *reinterpret_cast<const LDS cnn_h8 *>(hr + CNS_ROWB + c8 * 16), pl_ = *reinterpret_cast<const LDS cnn_h8 *>(hr + CNS_ROWB + 128 + c8 * 16);
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            // (the activations carry CNS_ASCALE; its inverse sits in the weights -- w holds w3 / CNS_ASCALE: a power of two moved from one
-            // factor of every product to the other, the same real products and so the same fmaf results, three multiplies per channel fewer)
-            const float hm = cns_join(mh_[e], ml_[e]), h0 = cns_join(zh_[e], zl_[e]), hp = cns_join(ph_[e], pl_[e]);
-            const float *wc = w + (c8 * 8 + e) * 2 * CNN_K;
-#pragma unroll
-            for (int o = 0; o < 2; o++) {
-                const float *wo = wc + o * CNN_K;
-                y[o][0] = __builtin_fmaf(hm, wo[6], y[o][0]);
-                y[o][0] = __builtin_fmaf(h0, wo[3], y[o][0]);
-                y[o][0] = __builtin_fmaf(hp, wo[0], y[o][0]);
-                y[o][1] = __builtin_fmaf(h0, wo[4], y[o][1]);
-                y[o][1] = __builtin_fmaf(hp, wo[1], y[o][1]);
-                y[o][2] = __builtin_fmaf(h0, wo[5], y[o][2]);
-                y[o][2] = __builtin_fmaf(hp, wo[2], y[o][2]);
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < 2; o++) {
-        float *so = scores + ((size_t)n * 2 + o) * Lo + 3 * j;
-#pragma unroll
-        for (int d = 0; d < 3; d++) if (3 * j + d < Lo) so[d] = y[o][d];
-    }
-}
+// (Round 5's layer 3 as a kernel of its own from split rows -- k_cnn_conv_out_s, LAST's A/B partner -- left in a prune of its own with the
+// switches ADP_CNN_FOLD and ADP_CNN_OVERLAP; its scores differed from LAST's in the last place.  Sources:
+// tools/experiments/cnn_split_layer3_apart.patch; records: profiles/r05_tried_and_dropped.txt, profiles/cnn_split_prune_isa.txt.
+// FIRST's partner -- k_cnn_conv_in_s and the plain form of this kernel as layer 1, ADP_CNN_FUSE_IN=0 -- is still here.)

@@ -278,25 +278,22 @@ def test_device_topk_behind_given_argmaxes():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("conv", ["split", "split_unfolded", "split_layer0apart", "f32"])
+@pytest.mark.parametrize("conv", ["split", "split_layer0apart", "f32"])
 @pytest.mark.parametrize("Lc,n", [(1650, 37), (20050, 9), (1651, 5), (1652, 5), (100, 3), (7, 2), (193 * 3, 4), (256 * 3 + 1, 4), (190 * 3, 3), (191 * 3 + 2, 3), (380 * 3 + 1, 3),
                                   (186 * 3, 3), (186 * 3 + 1, 3), (372 * 3 + 1, 3), (123 * 3, 3), (251 * 3, 3),
                                   (512 * 3, 3), (1024 * 3, 2)])  # (the last two: several tiles of the 256-position shape, NT = 4)
 def test_hip_conv_stack_equals_torch(Lc, n, conv, monkeypatch):
     """C2: the hand-written conv stacks (adp_cnn_forward) against torch's float32 conv1d / conv_transpose1d on the same device
     with the shipped weights -- "split": the default, float16 matrix cores on split operands (cnn_conv_split.h), layer 3 folded into
-    layer 2's kernel (round 5: tiles that advance by 64 NT - 2 positions -- lengths around multiples of 190 sit on their seams);
-    and layer 0 made in layer 1's prologue (tiles that advance by 64 NT - 6 positions, their 64 NT input rows made from 192 NT + 4 samples:
-    lengths around multiples of 186 / 122 / 250 sit on their seams, 7 and 100 are shorter than one subtile);
-    "split_unfolded": the same stack with layer 3 as a kernel of its own (ADP_CNN_FOLD=0); "split_layer0apart": with layer 0 as a
-    kernel of its own (ADP_CNN_FUSE_IN=0); "f32": the exact
-    float32 matrix-core kernels (cnn_conv.h, ADP_CNN_CONV=f32).  The float32 stack and torch are float32 sums of the same 448
+    layer 2's kernel (tiles that advance by 64 NT - 2 positions -- lengths around multiples of 190 sit on their seams) and layer 0
+    made in layer 1's prologue (tiles that advance by 64 NT - 6 positions, their 64 NT input rows made from 192 NT + 4 samples:
+    lengths around multiples of 186 / 122 / 250 sit on their seams, 7 and 100 are shorter than one subtile); "split_layer0apart":
+    the same stack with layer 0 as a kernel of its own (ADP_CNN_FUSE_IN=0); "f32": the exact float32 matrix-core kernels (cnn_conv.h, ADP_CNN_CONV=f32).  The float32 stack and torch are float32 sums of the same 448
     products per output in different orders, the split stack carries 22 bits per operand: tolerance 2e-5 relative to the score
     scale for both (the golden test pins the scores themselves)."""
     import torch
 
     monkeypatch.setenv("ADP_CNN_CONV", conv.split("_")[0])
-    monkeypatch.setenv("ADP_CNN_FOLD", "0" if conv.endswith("unfolded") else "1")
     monkeypatch.setenv("ADP_CNN_FUSE_IN", "0" if conv.endswith("layer0apart") else "1")
 
     from adapted_amd import lib
@@ -329,6 +326,50 @@ def test_hip_conv_stack_equals_torch(Lc, n, conv, monkeypatch):
     eng.cnn_forward(xt.data_ptr(), n, Lc, got2.data_ptr())
     assert torch.equal(got, got2)
     eng.close()
+
+
+@pytest.mark.gpu
+def test_split_conv_stack_after_a_change_of_row_geometry_equals_a_fresh_engine():
+    """The split stack keeps ONE buffer of rows (layer 1's) whose padding rows are laid down once per row geometry.  Calls of
+    changing geometry on a live handle -- longer, shorter (the buffer is larger than the call needs), shorter than a subtile, another
+    tile shape -- must each give the bits a fresh engine gives for the same input: no padding row may hold what an earlier
+    geometry's rows left there."""
+    import torch
+
+    from adapted_amd import lib
+    from adapted_amd.detect import cnn
+    from golden_cases import CASES
+    from util import make_spc
+
+    torch.cuda.init()
+    spc = make_spc(CASES["rna004_cnn_default"])
+    weights = {k: v for k, v in cnn.load_cnn_model(spc.cnn_boundaries.model_name, device=0).state_dict().items()}
+
+    def engine():
+        eng = lib.Engine(spc, 8, spc.sig_preload_size, device=0)
+        eng.cnn_set_weights(weights)
+        return eng
+
+    def forward(eng, xt, n, Lc):
+        Lo = ((Lc + 6 - 7) // 3 + 1 - 1) * 3 - 6 + 7
+        got = torch.full((n, 2, Lo), float("nan"), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        eng.cnn_forward(xt.data_ptr(), n, Lc, got.data_ptr())
+        return got
+
+    live = engine()
+    for Lc, n in [(100, 3), (1650, 37), (100, 3), (7, 2), (193 * 3, 4)]:
+        rng = np.random.default_rng(Lc)
+        x = rng.normal(0.0, 1.5, (n, 1, Lc)).astype(np.float32)
+        x[0, 0, Lc // 2:] = -5.0  # a padded tail, as prepare_data makes it
+        xt = torch.from_numpy(x).cuda()
+        got = forward(live, xt, n, Lc)
+        fresh = engine()
+        want = forward(fresh, xt, n, Lc)
+        fresh.close()
+        assert not torch.isnan(want).any()
+        assert torch.equal(got, want), (Lc, n)
+    live.close()
 
 
 def _conv_engine(monkeypatch, conv, spc, n, m):
