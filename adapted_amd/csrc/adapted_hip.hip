@@ -524,6 +524,7 @@ static int launch_n1(adp_handle *h, SIG dsig, int n, int m, int T, int minibatch
                      const int32_t *tails = nullptr) // tails: full_len when ADP_TAILS_NAN holds
 {
     hipStream_t st = h->stream;
+    h->n1_fused_nmb = 0;
     MbState *mbs = h->mbs.as<MbState>();
     uint32_t *gh = h->ghist.as<uint32_t>(), *gb = h->gbelow.as<uint32_t>();
     unsigned long long *gc = h->gcnt.as<unsigned long long>();
@@ -550,6 +551,7 @@ static int launch_n1(adp_handle *h, SIG dsig, int n, int m, int T, int minibatch
         ALLOCCHK(h->cbuf.ensure((size_t)n_mb * N1_CB_CAP * 4) || h->fz.ensure((size_t)n_mb * sizeof(N1Fused)) ||
                  h->fcnt.ensure((size_t)n_mb * 8 * N1F_NCNT) || h->n1heavy.ensure((size_t)n_mb * N1H_WORDS * 4));
         cb = h->cbuf.as<uint32_t>();
+        h->n1_fused_nmb = n_mb; // (adp_debug_fetch 24)
         N1Fused *fz = h->fz.as<N1Fused>();
         unsigned long long *fc = h->fcnt.as<unsigned long long>();
         HIPCHK(hipMemsetAsync(fc, 0, (size_t)n_mb * 8 * N1F_NCNT, st));
@@ -2361,6 +2363,30 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         if (h->last_grouped || !h->mbs.p || h->last_nmb < 1 || bytes > (uint64_t)h->last_nmb * 4 || h->gbelow.cap < (size_t)h->last_nmb * 4) return ADP_ERR_INVALID;
         hipLaunchKernelGGL(k_mb_status_out, dim3((h->last_nmb + 255) / 256), dim3(256), 0, h->stream, h->mbs.as<MbState>(), h->last_nmb, h->gbelow.as<int32_t>());
         src = h->gbelow.p; break; }
+    case 24: { // the fused N1 state of the last plain call, N1F_DEBUG_WORDS 32-bit words per minibatch: plain copies of fz, mbs, n1heavy
+        const int n_mb = h->last_nmb;
+        if (h->last_grouped || n_mb < 1 || h->n1_fused_nmb != n_mb || !h->fz.p || !h->mbs.p || !h->n1heavy.p) {
+            g_err = "the last call on this handle did not take the single-pass N1 route"; return ADP_ERR_INVALID;
+        }
+        if (bytes != (uint64_t)n_mb * N1F_DEBUG_WORDS * 4) return ADP_ERR_INVALID;
+        static_assert(sizeof(N1Fused) == 40 && 12 + 2 + 2 * N1H_MAX == N1F_DEBUG_WORDS, "layout of adp_debug_fetch(24)");
+        std::vector<N1Fused> f((size_t)n_mb);
+        std::vector<MbState> s((size_t)n_mb);
+        std::vector<uint32_t> hv((size_t)n_mb * N1H_WORDS);
+        HIPCHK(hipMemcpyAsync(f.data(), h->fz.p, f.size() * sizeof(N1Fused), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(s.data(), h->mbs.p, s.size() * sizeof(MbState), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(hv.data(), h->n1heavy.p, hv.size() * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        uint32_t *o = (uint32_t *)host_out;
+        for (int mb = 0; mb < n_mb; mb++, o += N1F_DEBUG_WORDS) {
+            memcpy(o, &f[mb], 40);
+            o[10] = (uint32_t)s[mb].fused; o[11] = (uint32_t)s[mb].status;
+            const uint32_t *g = hv.data() + (size_t)mb * N1H_WORDS;
+            o[12] = g[N1H_NH]; o[13] = g[N1H_NH + 1];
+            memcpy(o + 14, g + N1H_KEYS, N1H_MAX * 4);
+            memcpy(o + 14 + N1H_MAX, g + N1H_CNTS, N1H_MAX * 4);
+        }
+        return ADP_OK; }
     case 8: { if (bytes < 64 || bytes > sizeof(unsigned long long) * ADP_NDBG) return ADP_ERR_INVALID;
               HIPCHK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg), bytes, 0, hipMemcpyDeviceToHost));
               static unsigned long long tally[ADP_NTALLY][8];

@@ -70,6 +70,7 @@ struct adp_handle {
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
     int last_n = 0, last_nmb = 0;
+    int n1_fused_nmb = 0; // minibatches of the last launch_n1 if it took the single-pass route (n1_fused.h), else 0
     int layout = 0;   // ADP_LAYOUT_*: 1 = the single-read API (pooled from sample 0)
     int oh1 = 5;      // head offset of the first gains pass
     int pos_off = 0;  // added to pooled indices * ds for sample positions

@@ -51,6 +51,7 @@ struct N1Fused {
 #define N1H_NH 512
 #define N1H_KEYS 514
 #define N1H_CNTS 546
+#define N1F_DEBUG_WORDS 78 // adp_debug_fetch(24), per minibatch: N1Fused (10 words), fused, status, hv[N1H_NH], hv[N1H_NH + 1], keys, counts
 
 static __device__ __forceinline__ bool n1h_insert(uint32_t *tab, uint32_t key, uint32_t cnt)
 {
@@ -547,6 +548,8 @@ __global__ void __launch_bounds__(1024) k_n1_fused_finish(MbState *__restrict__ 
 #ifdef N1F_DEBUG_PRINT
     if (tid == 0 && mb < 6) printf("mb %d nvalid %llu below %llu inner %llu n_cm %llu n_cb %llu ovf %llu med_s %.6f A0 %.6f A1 %.6f D0 %.6f D1 %.6f eps %.6f nh %d\n", mb, n_valid, n_below, n_inner, n_cm, n_cb, ovf, f.med_s, f.A0, f.A1, f.D0, f.D1, f.eps, nh);
 #endif
+    // (slots 17..19 are shared with k_partition_stats' tallies, block_stats.h: they are N1's own only while nothing behind N1 runs,
+    // as in a call staged to stop after N1)
     if (tid == 0) { atomicAdd(&g_dbg[5], 1ull); atomicAdd(&g_dbg[22], (unsigned long long)nh); atomicAdd(&g_dbg[23], (unsigned long long)hsum_[0] + hsum_[1]);
                     if (ovf) atomicAdd(&g_dbg[19], 1ull); if (n_cm > N1F_MCAP) atomicAdd(&g_dbg[18], 1ull); if (n_cb > N1F_BCAP) atomicAdd(&g_dbg[17], 1ull); }
     if (ovf || n_cm > N1F_MCAP || n_cb > N1F_BCAP || n_valid < 4) { if (tid == 0) atomicAdd(&g_dbg[6], 1ull); return; }

@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(256) k_n1_pick(MbState *__restrict__ mbs, uint
     const unsigned long long before = s_before;
     if (bin < 0) miss = true;
     if (PASS == 1 && KIND == N1_SAMPLE) {
-        // bracket: the buckets holding the sample ranks krem -/+ D, D = 8 standard deviations of the rank of the
+        // bracket: the buckets holding the sample ranks krem -/+ D, D = N1_BRACKET_SIGMAS (6) standard deviations of the rank of the
         // true median inside an independent sample of M_s (binomial) -- reads differ, so the sample is clustered
         // and the bracket is only a good bet; whether it held is verified exactly after pass 1
         const unsigned long long tot = s_total;

@@ -1529,6 +1529,23 @@ class Engine:
         self._check(self.lib.adp_debug_fetch(self._h, 8, a, 8 * n))
         return a
 
+    def debug_n1_fused(self, n_mb: int):
+        """what the single-pass N1 of the last plain call left per minibatch (adp_debug_fetch 24; an error when the call did not
+        take that route): a list of dicts -- the brackets as float32 (med_s, A0, A1, D0, D1, eps, D0w, D1w) with ok / wide_ok,
+        fused, status, nh, sample_in (sample points inside the brackets), keys uint32[nh] and counts uint32[nh]"""
+        W = 78
+        a = np.zeros((n_mb, W), dtype=np.uint32)
+        self._check(self.lib.adp_debug_fetch(self._h, 24, a, a.nbytes))
+        out = []
+        for w in a:
+            f = w[:10].view(np.float32)
+            nh = int(w[12])
+            d = {k: f[i] for i, k in ((0, "med_s"), (1, "A0"), (2, "A1"), (3, "D0"), (4, "D1"), (5, "eps"), (8, "D0w"), (9, "D1w"))}
+            d.update(ok=int(w[6]), wide_ok=int(w[7]), fused=int(w[10]), status=int(w[11].view(np.int32)), nh=nh, sample_in=int(w[13]),
+                     keys=w[14:14 + 32].copy(), counts=w[46:46 + 32].copy())
+            out.append(d)
+        return out
+
     def debug_norm_params(self, n_mb: int):
         a = np.zeros((n_mb, 4), dtype=np.float64)
         self._check(self.lib.adp_debug_fetch(self._h, 0, a, a.nbytes))

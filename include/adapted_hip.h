@@ -605,7 +605,14 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *       whose pass did not run (no adapter candidate: pass 2) keep what an earlier call left.
  *       22 wend int32[n]: pass 2 computed the read's trace, summaries and maxima on [0, wend) (ADP_G2_WINDOW; n_valid: all of it;
  *       a read of the redo list ends with n_valid); 23 int32[n+1]: the windowed pass 2's redo list of the last call, count then reads
- *       (in no order).  Tallies 78 / 79 of selector 8: windowed reads decided inside the window / sent to the redo list. */
+ *       (in no order).  Tallies 78 / 79 of selector 8: windowed reads decided inside the window / sent to the redo list.
+ *       24 uint32[n_minibatch * 78]: what the single-pass N1 (n1_fused.h) of the last plain call left behind, per
+ *       minibatch: words 0-9 the brackets as float bits and flags (med_s, A0, A1, D0, D1, eps, ok, wide_ok, D0w, D1w; D0 / D1 are
+ *       the band the pass used), 10 whether the pass settled the minibatch, 11 its status word, 12 the number of heavy keys,
+ *       13 the sample points inside the brackets, 14-45 the heavy keys (ascending, order-preserving uint32 keys of the float32
+ *       values), 46-77 the samples the pass counted on each.  bytes must be exactly that; ADP_ERR_INVALID when the last call did
+ *       not take the single-pass route (or was grouped).  Tallies 17 / 18 / 19 of selector 8 count the minibatches whose band
+ *       list / median list / LDS staging overflowed (shared with k_partition_stats' own tallies in those slots). */
 int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes);
 /* Run the LLR pipeline only up to a stage (1 N1, 2 pool, 3 cumsum, 4 gains1, 5 adapter, 6 gains2, 7 polya) */
 int adp_debug_llr_upto(adp_handle *h, const float *signals, const int32_t *full_len, int n_reads, int m,

@@ -196,10 +196,24 @@ def test_n1_fused_single_pass_is_exact_or_falls_back(hip, oracle_mod, kind, monk
     eng.debug_llr_upto(sig, lens, n, n, 1)
     got = eng.debug_norm_params(1)[0]
     after = eng.debug_counters()
+    st = eng.debug_n1_fused(1)[0]
     rc, want = oracle_mod.norm_params(sig, spc.core.max_obs_trace, spc.core.sig_norm_outlier_thresh)
     assert list(got) == list(want), (kind, got, want)
     print(kind, "fused attempts/median misses/MAD misses:", (after - before)[5:8])
-    # (small batches are clustered samples: the brackets may well miss, or not be set up at all)
+    # (small batches are clustered samples: the brackets may well miss, or not be set up at all -- which of the two, and whether
+    # the pass then settles, is what tests/n1_fused_cases.py predicts from the device's heavy keys and band)
+    import n1_fused_cases as N
+
+    T = min(spc.core.max_obs_trace, m)
+    Te, vec = np.full(n, T), m % 4 == 0
+    fs = N.brackets(sig, Te, T, n, vec)
+    wide = bool(st["nh"] > 0 and fs["wide_ok"] and st["D0"] == fs["D0w"])
+    p = N.predict(sig, Te, T, n, st["keys"][:st["nh"]], wide, f=fs, vec=vec, thresh=spc.core.sig_norm_outlier_thresh)
+    print(kind, "predicted", p["outcome"], p["why"])
+    assert [int(v) for v in (after - before)[5:8]] == [p["counters"][k] for k in (5, 6, 7)], (kind, p["outcome"], p["why"])
+    assert st["fused"] == int(p["outcome"] == "settled")
+    if p["outcome"] == "settled":
+        assert [float(p[k]) for k in ("med", "mad", "lo", "hi")] == list(want)
     eng.close()
 
 
