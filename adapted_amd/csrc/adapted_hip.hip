@@ -32,6 +32,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "cnn_second_opinion.h"
 #include "polya_truncated.h"
 #include "adapter_front_revalidate.h"
+#include "llr_resegment.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -339,11 +340,13 @@ static int env_int(const char *name, int dflt)
 // arena_begin: allocated, counter zeroed (on the handle's stream, ahead of every kernel of the call).  arena_end (the call's
 // stream(s) drained): how much the call wanted; > capacity = lists were dropped: grow and tell the caller to run again.
 // op_used: [0] arena words wanted, [1] the split conv stack's out-of-range flag, [2] reads selected for the CNN path's short-read
-// fallback, [3] reads selected for its LLR second opinion, [4] reads whose tail window passed the truncation look's T1 -- zeroed by
-// arena_begin, read by arena_end.  Behind them the phases' counts for adp_debug_fetch (10 / 11 / 12), zeroed by the phase that runs:
+// fallback, [3] reads selected for its LLR second opinion, [4] reads whose tail window passed the truncation look's T1, or -- the two
+// flags exclude each other -- reads selected for the LLR re-segmentation -- zeroed by arena_begin, read by arena_end.  Behind them the
+// phases' counts for adp_debug_fetch (10 / 11 / 12 / 25), zeroed by the phase that runs:
 // the fallback's [0] exception rows made, [1] rows re-validated; the second opinion's [0] rows replaced, [1] re-validated and still
-// failing, [2] minibatches without one; the truncation look's [0] eligible reads, [1] T1 passed, [2] rows replaced
-enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_END = 13 };
+// failing, [2] minibatches without one; the truncation look's [0] eligible reads, [1] T1 passed, [2] rows replaced; the
+// re-segmentation's [0] eligible reads, [1] reads with a second poly(A) end, [2] rows replaced
+enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_RS = 13, OPW_END = 16 };
 static unsigned int *phase_counts(adp_handle *h, int opw) { return h->op_used.as<unsigned int>() + opw; }
 static int arena_begin(adp_handle *h)
 {
@@ -354,7 +357,7 @@ static int arena_begin(adp_handle *h)
 // -> 0 done, 1 run the call again (arena grown), < 0 error
 // (cnn: the call ran the conv stack -- its out-of-range flag is read with the counter; set = repeat the call on the float32 kernels)
 // (n_sel: the call ran k_cnn_fb_select -- its count comes with the same copy; left 0 when the call is to be repeated)
-// (n_so: the same for k_cnn_so_select; n_pt: for k_pt_select)
+// (n_so: the same for k_cnn_so_select; n_pt: for k_pt_select, or k_rs_select)
 static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr, unsigned int *n_pt = nullptr)
 {
     const bool conv_flag = cnn && h->cnn_mode == 1 && !h->cnn_redo_f32;
@@ -646,21 +649,22 @@ static int g2_window(int upto)
     const int w = env_int("ADP_G2_WINDOW", G2_WINDOW_DEFAULT);
     return w < 0 ? 0 : (w > (1 << 28) ? (1 << 28) : w);
 }
-static void launch_gains2(adp_handle *h, int n, int mbsize, double *pkv, int win, const int32_t *redo)
+// (mbs: the minibatch states to read instead of the handle's -- the re-segmentation's per-read copies, with mbsize = 1)
+static void launch_gains2(adp_handle *h, int n, int mbsize, double *pkv, int win, const int32_t *redo, const MbState *mbs = nullptr)
 {
     hipLaunchKernelGGL(k_gains<2>, dim3((n + GAINS_WPB - 1) / GAINS_WPB), dim3(64 * GAINS_WPB), 0, h->stream, h->down.as<float>(), h->nvalid.as<int32_t>(), h->Lp, h->nck,
-                       h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), mbsize, h->mbs.as<MbState>(),
+                       h->ck.as<double2>(), h->tail.as<double2>(), h->adapter_idx.as<int32_t>(), mbsize, mbs ? mbs : h->mbs.as<MbState>(),
                        h->trace.as<double>(), h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->t1.as<int2>(), 0, h->pk.as<int32_t>(), h->npk.as<int32_t>(), h->Lp / 2 + 1, h->gstat.as<double>(), n, 5, pkv, gains_tile_fast(),
                        win, h->wend.as<int32_t>(), redo);
 }
 
 // pkv: the maxima's heights as k_gains<2> listed them, or null.  ADP_PK_PREFIX=0: the whole list of maxima at once (peaks.h; same results)
 // windowed: pass 2 left wend[r] and the reads it cannot decide go to the redo list; redo_pass: over that list, on whole traces
-static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv, bool windowed = false, bool redo_pass = false)
+static void launch_polya_peak(adp_handle *h, int n, int mbsize, const double *pkv, bool windowed = false, bool redo_pass = false, const MbState *mbs = nullptr)
 {
     const int grid = n < h->pslots ? n : h->pslots;
     hipLaunchKernelGGL(k_polya_peak, dim3(grid), dim3(64), (size_t)(((h->Lp / 2 + 1) + 8) / 16 + 2) * 4, h->stream, h->trace.as<double>(), h->nvalid.as<int32_t>(), h->Lp,
-                       h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, mbsize, h->mbs.as<MbState>(),
+                       h->bmax.as<double>(), h->bmin.as<double>(), h->nsum, h->adapter_idx.as<int32_t>(), n, mbsize, mbs ? mbs : h->mbs.as<MbState>(),
                        h->pk.as<int32_t>(), h->mk.as<uint32_t>(), h->polya_idx.as<int32_t>(), h->npk.as<int32_t>(), pkv, env_int("ADP_PK_PREFIX", PK_PREFIX),
                        (windowed || redo_pass) ? h->wend.as<int32_t>() : (const int32_t *)nullptr, (windowed || redo_pass) ? h->redo.as<int32_t>() : (int32_t *)nullptr, redo_pass ? 1 : 0);
 }
@@ -889,13 +893,95 @@ static int trunc_finish(adp_handle *h, const float *dsig, const int32_t *dlen, i
     HIPCHK(hipStreamSynchronize(h->stream));
     return arena_end(h);
 }
-// What the LLR path does behind llr_enqueue's last group, in both execution forms: the arena counter and, with look, the truncation
-// look on the rows (float32 signals only: adp_detect_llr_i16 refuses the flag) -> as arena_end
-static int llr_after_first_pass(adp_handle *h, SigF32 dsig, const int32_t *dlen, int n, int m, adp_row *rows, bool look)
+// ---- the re-segmentation of failed reads (ADP_LLR_RESEGMENT, llr_resegment.h) ---------------------------------------------------
+static bool reseg_wanted(int flags, const adp_row *rows) { return (flags & ADP_LLR_RESEGMENT) && rows; }
+// what the flag cannot go with, said before anything is launched
+static int reseg_supported(const adp_handle *h, int flags)
 {
+    if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_LLR_RESEGMENT does not go with ADP_FLAG_TRUNCATED (the truncation look validates from start 0)"; return ADP_ERR_UNSUPPORTED; }
+    if (h->cfg.mvs_detect_overwrite) { g_err = "ADP_LLR_RESEGMENT does not go with mvs_detect_overwrite"; return ADP_ERR_UNSUPPORTED; }
+    if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "ADP_LLR_RESEGMENT does not go with the single-read layout"; return ADP_ERR_UNSUPPORTED; }
+    return 0;
+}
+// The second segmentation, its validation and the merge for the n_rs selected reads, enqueued on the handle's stream.  The first
+// pass has drained: its stage buffers on this handle are spent (a grouped call's owner has none yet) and take the subset's trace
+// phase, read j of the subset at position j.  The second rows have a buffer of their own (the handle's may be the call's); their
+// open-pore lists append to the call's arena: the caller looks at its counter once more.
+// mbs: the call's minibatch states (the handle's own, or the copies a grouped call's lanes left in rs_mbs)
+static int reseg_run(adp_handle *h, const float *dsig, const int32_t *dlen, int m, int minibatch, int flags, adp_row *rows, const MbState *mbs, int n_rs)
+{
+    hipStream_t st = h->stream;
+    RCCHK(alloc_all(h, n_rs, true));
+    const size_t N = (size_t)n_rs;
+    Piece<int64_t> b2, starts; Piece<int32_t> dlen_sub; Piece<int8_t> tsub; Piece<MbState> mbs_sub; Piece<adp_row> rows2;
+    RCCHK(sub_carve(h, [&](Carve &c) {
+        b2 = c.take<int64_t>(2 * N); starts = c.take<int64_t>(N); dlen_sub = c.take<int32_t>(N); tsub = c.take<int8_t>(N);
+        mbs_sub = c.take<MbState>(N); rows2 = c.take<adp_row>(N);
+    }));
+    const int32_t *sel = h->rs_sel.as<int32_t>();
+    unsigned int *counts = phase_counts(h, OPW_RS);
+    { Scope s(h, "k_rs_gather");
+      hipLaunchKernelGGL(k_rs_gather, dim3((n_rs + 255) / 256), dim3(256), 0, st, sel, n_rs, minibatch, mbs, dlen, (const adp_row *)rows, h->ds, h->pos_off,
+                         dlen_sub.p, starts.p, b2.p, tsub.p, h->adapter_idx.as<int32_t>(), mbs_sub.p); }
+    // the trace phase as llr_enqueue runs it (an eligible read has a poly(A) end: h->L > 0), every read its own "minibatch"
+    { Scope s(h, "k_norm_pool (resegment)");
+      hipLaunchKernelGGL((k_norm_pool<SigIdx>), dim3(n_rs), dim3(256), (size_t)NP_TILE * h->ds * 4, st, SigIdx{dsig, sel}, m, h->T, h->off, h->ds, h->L, h->Lp, 1,
+                         (const MbState *)mbs_sub.p, h->down.as<float>(), h->nvalid.as<int32_t>(), (const int64_t *)nullptr, (const int32_t *)dlen_sub.p,
+                         (flags & ADP_TAILS_NAN) ? 1 : 0); }
+    { Scope s(h, "k_cumsum (resegment)");
+      launch_cumsum(h, n_rs); }
+    double *pkvp = (env_int("ADP_PK_VALUES", 1) && h->pkv.cap >= N * (h->Lp / 2 + 1) * 8) ? h->pkv.as<double>() : nullptr;
+    int win = g2_window(8);
+    if (win > 0 && (win + 1 + TRACE_TILE - 1) / TRACE_TILE * TRACE_TILE >= h->L) win = 0;
+    if (win > 0) HIPCHK(hipMemsetAsync(h->redo.p, 0, 4, st));
+    { Scope s(h, "k_gains<2> (resegment)");
+      launch_gains2(h, n_rs, 1, pkvp, win, nullptr, mbs_sub.p); }
+    { Scope s(h, "k_polya_peak (resegment)");
+      launch_polya_peak(h, n_rs, 1, pkvp, win > 0, false, mbs_sub.p); }
+    if (win > 0) {
+        Scope s(h, "k_gains<2> / k_polya_peak redo (resegment)");
+        launch_gains2(h, n_rs, 1, pkvp, 0, h->redo.as<int32_t>(), mbs_sub.p);
+        launch_polya_peak(h, n_rs, 1, pkvp, false, true, mbs_sub.p);
+    }
+    { Scope s(h, "k_rs_bounds");
+      hipLaunchKernelGGL(k_rs_bounds, dim3((n_rs + 255) / 256), dim3(256), 0, st, (const int32_t *)h->polya_idx.as<int32_t>(), n_rs, h->ds, h->pos_off, b2.p, tsub.p, counts); }
+    const ValBufs vb{b2.p, tsub.p, rows2.p};
+    RCCHK(launch_validate_t<true>(h, SigIdx{dsig, sel}, dlen_sub.p, n_rs, m, 1, n_rs, false, &vb, false, starts.p));
+    { Scope s(h, "k_rs_merge");
+      hipLaunchKernelGGL(k_rs_merge, dim3(n_rs), dim3(64), 0, st, sel, n_rs, (const adp_row *)rows2.p, rows, counts); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// The phase behind a call whose first rows are all in `rows` (device) and whose lanes, if any, have drained: the selection in front
+// of the arena counter, which brings its count, then the rest where a read was selected -> 0 done, 1 run the call again (arena
+// grown), < 0 error
+static int reseg_finish(adp_handle *h, const float *dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, const MbState *mbs)
+{
+    ALLOCCHK(h->rs_sel.ensure((size_t)n * 4));
+    unsigned int *counts = phase_counts(h, OPW_RS);
+    h->rs_ran = true;
+    HIPCHK(hipMemsetAsync(counts, 0, 12, h->stream));
+    { Scope s(h, "k_rs_select");
+      hipLaunchKernelGGL(k_rs_select, dim3(1), dim3(SEL_THREADS), 0, h->stream, (const adp_row *)rows, n, minibatch, mbs, h->rs_sel.as<int32_t>(),
+                         h->op_used.as<unsigned int>() + 4, counts); }
+    unsigned int n_rs = 0;
+    const int rc = arena_end(h, false, nullptr, nullptr, &n_rs); // (with the count it copies the counter and waits for the stream)
+    if (rc || !n_rs) return rc;
+    if (n_rs > (unsigned int)n) { g_err = "ADP_LLR_RESEGMENT: selection count out of range"; return ADP_ERR_HIP; }
+    RCCHK(reseg_run(h, dsig, dlen, m, minibatch, flags, rows, mbs, (int)n_rs));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return arena_end(h);
+}
+// What the LLR path does behind llr_enqueue's last group, in both execution forms: the arena counter and, with look, the truncation
+// look on the rows, or, with reseg, the re-segmentation (float32 signals only: adp_detect_llr_i16 refuses both flags; they exclude
+// each other) -> as arena_end.  mbs: the call's minibatch states, for the re-segmentation
+static int llr_after_first_pass(adp_handle *h, SigF32 dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, bool look, bool reseg,
+                                const MbState *mbs)
+{
+    if (reseg) return reseg_finish(h, dsig.base, dlen, n, m, minibatch, flags, rows, mbs);
     return look ? trunc_finish(h, dsig.base, dlen, n, m, rows) : arena_end(h);
 }
-static int llr_after_first_pass(adp_handle *h, SigI16, const int32_t *, int, int, adp_row *, bool) { return arena_end(h); }
+static int llr_after_first_pass(adp_handle *h, SigI16, const int32_t *, int, int, int, int, adp_row *, bool, bool, const MbState *) { return arena_end(h); }
 
 // how a call's minibatches are cut into groups: ADP_GROUPS (unset / 1: one group = the plain serial pipeline, 0: automatic = three
 // groups per lane, k: aim at k groups); ADP_LANES (streams the groups rotate over, default 2); ADP_STAGGER (bit p set: phase p of
@@ -939,6 +1025,8 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         drop_profile(lanes[i]);
     }
     adp_row *rows_dev = rows_out ? (out_dev ? rows_out : h->rows.as<adp_row>()) : nullptr;
+    const bool reseg = reseg_wanted(flags, rows_dev);
+    ALLOCCHK(reseg && h->rs_mbs.ensure((size_t)n_mb * sizeof(MbState)));
     RCCHK(call_attempts(h, lanes, n_lanes, [&]() -> int {
         HIPCHK(hipEventRecord(h->ev_start, h->stream));      // (inputs staged on this stream, arena counter zeroed)
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamWaitEvent(lanes[i]->stream, h->ev_start, 0));
@@ -954,9 +1042,12 @@ static int llr_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
             const int rc = llr_enqueue(l, sig_from(dsig, (size_t)r0, m), dlen + r0, ng, m, minibatch, flags, rows_dev ? rows_dev + r0 : nullptr,
                                        hipMemcpyDeviceToDevice, h->mbstat.as<int32_t>() + mb0, h->mbparams.as<double>() + 4 * (size_t)mb0, 8, &ps);
             if (rc) { for (int i = 0; i < n_lanes; i++) (void)hipStreamSynchronize(lanes[i]->stream); return rc; }
+            // (the lane's states are zeroed for its next group: the re-segmentation reads the call's from the owner's copy)
+            if (reseg) HIPCHK(hipMemcpyAsync(h->rs_mbs.as<MbState>() + mb0, l->mbs.p, (size_t)((ng + minibatch - 1) / minibatch) * sizeof(MbState),
+                                             hipMemcpyDeviceToDevice, l->stream));
         }
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
-        return llr_after_first_pass(h, dsig, dlen, n, m, rows_dev, trunc_wanted(flags, rows_dev));
+        return llr_after_first_pass(h, dsig, dlen, n, m, minibatch, flags, rows_dev, trunc_wanted(flags, rows_dev), reseg, h->rs_mbs.as<MbState>());
     }));
     if (rows_out && !out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
     if (mb_status) HIPCHK(hipMemcpyAsync(mb_status, h->mbstat.p, (size_t)n_mb * 4, hipMemcpyDeviceToHost, h->stream));
@@ -987,7 +1078,9 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
     h->last_grouped = false;
     // ADP_FLAG_TRUNCATED: the look rides behind the validation on the device rows (the caller's, or the handle's -- host rows are
     // then delivered once, behind it); its T1 count comes back with the arena counter
-    const bool pt = upto >= 8 && trunc_wanted(flags, rows_out), out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    // ADP_LLR_RESEGMENT: the same arrangement (the two flags exclude each other; `pt` below stands for either)
+    const bool look = upto >= 8 && trunc_wanted(flags, rows_out), reseg = upto >= 8 && reseg_wanted(flags, rows_out);
+    const bool pt = look || reseg, out_dev = (flags & ADP_OUT_DEVICE) != 0;
     return call_attempts(h, nullptr, 0, [&]() -> int {
         RCCHK(llr_enqueue(h, dsig, dlen, n, m, minibatch, flags, upto >= 8 && !(pt && !out_dev) ? rows_out : nullptr,
                           out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, nullptr, nullptr, upto, nullptr));
@@ -999,7 +1092,7 @@ static int llr_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
         if (upto < 8) return 0;
-        const int rc = llr_after_first_pass(h, dsig, dlen, n, m, out_dev ? rows_out : h->rows.as<adp_row>(), pt);
+        const int rc = llr_after_first_pass(h, dsig, dlen, n, m, minibatch, flags, out_dev ? rows_out : h->rows.as<adp_row>(), look, reseg, h->mbs.as<MbState>());
         if (rc == 0 && pt && !out_dev) {
             HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -1014,7 +1107,8 @@ static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full
     if (!h || !signals || !full_len || n < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ && minibatch != 1) { g_err = "the single-read layout normalises every read on its own: minibatch must be 1"; return ADP_ERR_INVALID; }
-    h->pt_looked = false;
+    h->pt_looked = false; h->rs_ran = false;
+    if (reseg_wanted(flags, rows_out)) RCCHK(reseg_supported(h, flags));
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
@@ -1051,6 +1145,8 @@ int adp_detect_llr_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "the single-read layout takes float32 input"; return ADP_ERR_UNSUPPORTED; }
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_llr)"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT takes float32 input (adp_calibrate_i16 + adp_detect_llr)"; return ADP_ERR_UNSUPPORTED; }
+    h->rs_ran = false;
     RCCHK(begin_call(h));
     // (samples at or beyond min(full_len, m) read as NaN: the padding is implied, so the passes always stop at a read's end)
     return llr_pipeline_t(h, SigI16{raw, scale, offset, full_len}, full_len, n_reads, m, minibatch, flags | ADP_TAILS_NAN, rows_out, mb_status, 8);
@@ -1121,6 +1217,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED goes with adp_detect_llr and adp_detect_cnn"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr"; return ADP_ERR_UNSUPPORTED; }
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
@@ -2080,6 +2177,7 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
 {
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
+    if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr (the LLR primary)"; return ADP_ERR_UNSUPPORTED; }
     h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
@@ -2101,6 +2199,7 @@ int adp_detect_cnn_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "the single-read layout takes float32 input"; return ADP_ERR_UNSUPPORTED; }
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_cnn)"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr (the LLR primary)"; return ADP_ERR_UNSUPPORTED; }
     h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
     RCCHK(begin_call(h));
     RCCHK(cnn_ready(h, m));
@@ -2344,6 +2443,11 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         if (bytes < 12) return ADP_ERR_INVALID;
         int32_t c[3] = {0, 0, 0};
         if (h->pt_looked) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_PT), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        memcpy(host_out, c, 12); return ADP_OK; }
+    case 25: { // the re-segmentation of the last adp_detect_llr call: eligible reads, reads with a second poly(A) end, rows replaced
+        if (bytes < 12) return ADP_ERR_INVALID;
+        int32_t c[3] = {0, 0, 0};
+        if (h->rs_ran) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_RS), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     // what the kernels of phase C hand to each other (llr_stream.h, peaks.h), each copy bounded by its buffer

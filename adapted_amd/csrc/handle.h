@@ -89,6 +89,11 @@ struct adp_handle {
     // detect call looked for truncated tails
     unsigned int fb_n_sel = 0, so_n_sel = 0;
     bool pt_looked = false;
+    // the re-segmentation of adp_detect_llr (ADP_LLR_RESEGMENT, llr_resegment.h): the reads it selected [reads of the call], the
+    // minibatch states of a GROUPED call (the lanes recycle theirs from group to group: every group leaves a copy here), and
+    // whether the last detect call ran the phase (adp_debug_fetch 25)
+    DevBuf rs_sel, rs_mbs;
+    bool rs_ran = false;
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, cnn_nbuf = 0, n_cu = 256;

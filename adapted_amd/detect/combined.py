@@ -63,12 +63,16 @@ def combined_detect_llr2(batch_of_signals: np.ndarray, full_signal_lens: np.ndar
     """flag_truncated (an extension, off by default; the reference never sets ``polya_truncated``): reads whose poly(A) runs into
     the end of the preloaded window come back with ``polya_truncated=True``, ``polya_end`` at the window's end and no RNA
     partition; every other passing read with ``polya_truncated=False`` (include/adapted_hip.h, ADP_FLAG_TRUNCATED)."""
+    return _detect_llr2(batch_of_signals, full_signal_lens, spc, device, with_start_peak=with_start_peak, flag_truncated=flag_truncated)
+
+
+def _detect_llr2(batch_of_signals, full_signal_lens, spc, device, **options) -> List[DetectResults]:
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
     n, m = sig.shape
     if n == 0:
         return []
     eng = get_engine(spc, n, m, device)
-    rows, mbs = eng.detect_llr_rows(sig, lens, n, n, with_start_peak=with_start_peak, flag_truncated=flag_truncated)
+    rows, mbs = eng.detect_llr_rows(sig, lens, n, n, **options)
     if mbs[0] == lib.MB_MAD_ZERO:
         msg = "MAD normalization failed: scale is 0"
         logging.error(msg)
@@ -123,6 +127,16 @@ def combined_detect_start_peak(batch_of_signals: np.ndarray, full_signal_lens: n
     rows = eng.detect_start_peak_rows(sig, lens, n, n)
     res = lib.rows_to_results(rows, "start_peak", consume=True)
     return lib.open_pore_float_column(res)
+
+
+def combined_detect_llr2_resegment(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, spc, device: int = 0) -> List[DetectResults]:
+    """combined_detect_llr2 with one more segmentation step for the reads it fails (an extension, off everywhere by default, UNTUNED:
+    nothing validated on real data; include/adapted_hip_resegment.h, ADP_LLR_RESEGMENT).  A read whose first row fails with an
+    adapter end a1 > 0 and a poly(A) end p1 > a1 -- the pattern of a stall, a level step or a long start peak in front of the
+    adapter: the first change point is the end of that stretch, the "poly(A) end" the true adapter end -- is segmented again from
+    p1 and validated with Boundaries(adapter_start=a1, adapter_end=p1, polya_end=p2).  Where that passes, the read comes back with
+    those boundaries and ``llr_detect_log = "resegmented: first pass failed (<reason>)"``; every other read is combined_detect_llr2's."""
+    return _detect_llr2(batch_of_signals, full_signal_lens, spc, device, resegment=True)
 
 
 def validate_boundaries(signal: np.ndarray, boundaries: Boundaries, spc, full_signal_len: int,

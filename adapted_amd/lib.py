@@ -28,11 +28,14 @@ ADP_CNN_FALLBACK = 1 << 17  # adp_detect_cnn: the short-read LLR fallback inside
 ADP_CNN_SECOND_LLR = 1 << 18  # adp_detect_cnn: reads that fail get the LLR path's row where that one passes (row["reserved_"] bit 0)
 ADP_FLAG_TRUNCATED = 1 << 19  # adp_detect_llr / adp_detect_cnn: flag poly(A) tails cut off by the preload window (row["reserved_"] bits 1, 2)
 ADP_POLYA_TRUNCATED = 1 << 20  # adp_validate_candidates: Boundaries.polya_truncated is True -- no RNA partition
+ADP_LLR_RESEGMENT = 1 << 21  # adp_detect_llr: re-segment failed reads behind their first change point (row["reserved_"] bits 5-9)
 ROW_FROM_SECOND_LLR = 1  # bits of row["reserved_"]
 ROW_POLYA_TRUNCATED = 2  # the poly(A) runs into the end of the preloaded window
 ROW_TRUNC_LOOKED = 4  # the call looked for that (every row of a call made with ADP_FLAG_TRUNCATED)
 ROW_ADAPTER_FRONT = 8  # adp_adapter_front moved adapter_start: adapter_start / _len / _mean / _std / _med / _mad are the trimmed adapter's
 ROW_REVALIDATED = 16  # adp_adapter_front_revalidate replaced the row by the validation from the trimmed start (beside ROW_ADAPTER_FRONT)
+ROW_RESEGMENTED = 32  # the row is the validation of the second segmentation (ADP_LLR_RESEGMENT, include/adapted_hip_resegment.h)
+ROW_FIRST_FAIL_SHIFT, ROW_FIRST_FAIL_MASK = 6, 15 << 6  # ... and bits 6-9 hold the fail_code of the row it replaced
 ADP_ERR_UNSUPPORTED = -4
 MB_OK, MB_MAD_ZERO, MB_EMPTY_TRACE = 0, 1, 2
 
@@ -270,7 +273,7 @@ def load():
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
-                            + list(TEMPLATE_PROTOTYPES.items())):
+                            + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -509,6 +512,11 @@ TEMPLATE_PROTOTYPES = {
     "adp_dba_step": "int: adp_handle* double* int32* int32* int int double* int32* int int int int double* int32* double* double*",
 }
 
+# include/adapted_hip_resegment.h (the header adapted_hip.h includes for the re-segmentation of reads the LLR primary fails, an
+# extension): a flag of adp_detect_llr, row bits and a selector of adp_debug_fetch -- it declares no entry point;
+# tests/test_resegment_cpu.py holds this table against its header
+RESEGMENT_PROTOTYPES: dict = {}
+
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
 _RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
 _SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
@@ -554,7 +562,7 @@ def _argtype(kind):
 
 # a detect call's options -> their bits of its flag word (include/adapted_hip.h)
 _OPTION_FLAGS = {"with_start_peak": ADP_WITH_START_PEAK, "tails_nan": ADP_TAILS_NAN, "flag_truncated": ADP_FLAG_TRUNCATED,
-                 "fallback": ADP_CNN_FALLBACK, "second_opinion": ADP_CNN_SECOND_LLR}
+                 "fallback": ADP_CNN_FALLBACK, "second_opinion": ADP_CNN_SECOND_LLR, "resegment": ADP_LLR_RESEGMENT}
 
 
 def _flag_word(**options) -> int:
@@ -638,6 +646,32 @@ def truncation_unsupported(spc) -> Optional[str]:
     return None
 
 
+def resegment_unsupported(spc, flag_truncated: bool = False) -> Optional[str]:
+    """why the re-segmentation (ADP_LLR_RESEGMENT) does not go with this configuration, or None (what the library refuses with
+    ADP_ERR_UNSUPPORTED, said without a GPU)"""
+    if spc.primary_method != "llr":
+        return "it belongs to the LLR primary (the configuration selects %s)" % spc.primary_method
+    if flag_truncated:
+        return "it does not go with the truncation look (which validates from start 0)"
+    if spc.mvs_polya.mvs_detect_overwrite:
+        return "it does not go with mvs_polya.mvs_detect_overwrite"
+    return None
+
+
+def first_fail_text(code: int) -> str:
+    """the fail_reason text of a first row's fail_code as a re-segmented row keeps it (the MVS check's names are not kept)"""
+    return FAIL_REASONS[int(code)].rstrip(": ")
+
+
+def resegment_log(reserved: np.ndarray) -> str:
+    """the log line of a run: how many rows the re-segmentation kept, by the first row's fail_reason (reserved: the rows' ``reserved_``)"""
+    reserved = np.asarray(reserved, dtype=np.int64)
+    kept = reserved[(reserved & ROW_RESEGMENTED) != 0]
+    codes = (kept & ROW_FIRST_FAIL_MASK) >> ROW_FIRST_FAIL_SHIFT
+    by = ", ".join("%s: %d" % (first_fail_text(c), int((codes == c).sum())) for c in np.unique(codes))
+    return "LLR re-segmentation: %d reads kept%s" % (kept.size, " (first failure: %s)" % by if kept.size else "")
+
+
 def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> List[DetectResults]:
     """adp_row[] -> DetectResults, value for value what the reference's validate_boundaries
     returns (types: python int / float, np.float32 where the reference keeps numpy scalars).
@@ -645,7 +679,9 @@ def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> Li
     every row exactly once: adapted_amd/main.py).
     A row made by the CNN path's LLR second opinion (``reserved_`` bit 0) is named as the LLR path names it, whatever ``primary``.
     ``polya_truncated`` (an extension: the reference never sets it): True for a row the truncation look replaced (bit 1; its six
-    ``rna_preloaded_*`` fields are None), False for a passing row of a call that looked (bit 2), None otherwise."""
+    ``rna_preloaded_*`` fields are None), False for a passing row of a call that looked (bit 2), None otherwise.
+    A row the re-segmentation made (bit 5) says so in ``llr_detect_log``, the reference's column for the LLR detector's messages:
+    "resegmented: first pass failed (<the fail_reason text of the first row's code>)"; every other LLR row keeps ""."""
     out = []
     names_of = {primary: [c.format(primary=primary) for c in COLS]}
     if rows.size and (rows["reserved_"] & ROW_FROM_SECOND_LLR).any():
@@ -701,6 +737,8 @@ def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> Li
                 fr = fr + "+" + spt
         else:
             d.llr_detect_log = "" if primary == "llr" else None
+            if res & ROW_RESEGMENTED:
+                d.llr_detect_log = "resegmented: first pass failed (%s)" % first_fail_text((res & ROW_FIRST_FAIL_MASK) >> ROW_FIRST_FAIL_SHIFT)
         d.fail_reason = fr
         out.append(d)
     return out
@@ -880,15 +918,19 @@ class Engine:
         return self.attach_open_pores(rows), mbs
 
     def detect_llr_rows(self, signals, full_lens, n: int, minibatch: int, with_start_peak: bool = False,
-                        device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False, flag_truncated: bool = False):
+                        device_ptrs: bool = False, rows_dev: Optional[int] = None, tails_nan: bool = False, flag_truncated: bool = False,
+                        resegment: bool = False):
         """-> (rows ndarray[ROW_DTYPE] or None when rows_dev is given, mb_status int32[n_mb]).
         tails_nan: the caller guarantees that every row is NaN from min(full_len, m) on (the reference's own padding,
         adapted/file_proc.py:170-174); the streaming passes then skip the padding (ADP_TAILS_NAN).
         flag_truncated: the call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension): a read whose poly(A) runs into
         the end of the preloaded window gets the row of the validation with (adapter end, window end) and polya_truncated
-        (reserved_ bit 1); every row carries reserved_ bit 2."""
+        (reserved_ bit 1); every row carries reserved_ bit 2.
+        resegment: reads whose first row fails behind a first change point are segmented once more from their "poly(A) end" and
+        validated from the first adapter end (ADP_LLR_RESEGMENT, an extension, untuned; include/adapted_hip_resegment.h): a
+        validation that passes replaces the row (reserved_ bit 5, the first fail_code in bits 6-9)."""
         sig, lens, flags = self._in(signals, full_lens, n, device_ptrs)
-        flags |= _flag_word(with_start_peak=with_start_peak, tails_nan=tails_nan, flag_truncated=flag_truncated)
+        flags |= _flag_word(with_start_peak=with_start_peak, tails_nan=tails_nan, flag_truncated=flag_truncated, resegment=resegment)
         return self._detect_llr(self.lib.adp_detect_llr, (sig, lens), n, minibatch, flags, rows_dev)
 
     def detect_llr_rows_i16(self, raw_dev: int, len_dev: int, scale_dev: int, offset_dev: int, n: int, minibatch: int,
@@ -1522,6 +1564,13 @@ class Engine:
         whose tail window passed T1, rows replaced)"""
         a = np.zeros(3, dtype=np.int32)
         self._check(self.lib.adp_debug_fetch(self._h, 12, a, a.nbytes))
+        return tuple(int(v) for v in a)
+
+    def debug_resegment(self):
+        """the re-segmentation of the last detect_llr_rows call: (eligible reads, reads whose second segmentation found a poly(A)
+        end, rows replaced); (0, 0, 0) behind a call without ``resegment``"""
+        a = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.adp_debug_fetch(self._h, 25, a, a.nbytes))
         return tuple(int(v) for v in a)
 
     def debug_counters(self, n: int = 8):

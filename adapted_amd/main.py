@@ -61,6 +61,11 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("--flag_truncated", action="store_true",
                    help="(extension) fill the polya_truncated column: True where the poly(A) runs into the end of the preloaded "
                         "signal (rerun those reads with a larger --max_obs_trace: `adapted truncated`), False on every other passing read")
+    d.add_argument("--llr_resegment", action="store_true",
+                   help="(extension) LLR primary: a read whose first boundaries fail validation behind a first change point (a stall, a "
+                        "level step or a long start peak in front of the adapter) is segmented once more from its first poly(A) end and "
+                        "validated from its first adapter end; boundaries that pass replace the failed row, whose llr_detect_log says so "
+                        "(untuned, nothing validated on real data).  Not with --flag_truncated or mvs_detect_overwrite")
     d.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     d.add_argument("--int16_ingest", action="store_true",
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
@@ -263,6 +268,14 @@ def _check_flag_truncated(args):
             raise SystemExit("--flag_truncated does not go with this configuration: %s." % why)
 
 
+def _check_llr_resegment(args):
+    """--llr_resegment and what it does not go with: said before a GPU is touched"""
+    if getattr(args, "llr_resegment", False) and (args.config or args.chemistry):
+        why = lib.resegment_unsupported(_load_spc(args), bool(getattr(args, "flag_truncated", False)))
+        if why:
+            raise SystemExit("--llr_resegment does not go with this run: %s." % why)
+
+
 def _check_adapter_front(args):
     """--adapter_front and what it does not go with: said before a GPU is touched.  -> its AdapterFrontParams (min_adapter_len left
     to run_detect, which knows the configuration), or None"""
@@ -399,9 +412,10 @@ def list_truncated(directory: str) -> int:
 
 
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, adapter_front=None,
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, llr_resegment=False, adapter_front=None,
                fingerprints=None, polya_length=None, adapter_nt=None, event_params=None):
-    """adapter_front: None, or an adapter_front.AdapterFrontParams (--adapter_front: the adapter's front trimmed on the final rows of
+    """llr_resegment: --llr_resegment (the LLR primary's detect calls re-segment the reads they fail; everything below sees the final rows);
+    adapter_front: None, or an adapter_front.AdapterFrontParams (--adapter_front: the adapter's front trimmed on the final rows of
     every detect call, ahead of the two below; its min_adapter_len is set here to core.min_obs_adapter);
     fingerprints: None, or (E, templates or None, band) (--fingerprints: fingerprints/fingerprints_<k>.npz and, with templates,
     fingerprints/barcodes_<k>.csv beside boundaries/; the events' parameters are event_params);
@@ -438,7 +452,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     GROUP = 4  # minibatches per staging slot and detect call (normalisation stays per minibatch)
     pipe = HostPipeline(spc, minibatch, m, device=device, primary=primary, with_start_peak=start_peak,
                         model=model, int16_input="native" if int16_ingest else False, group=GROUP, ragged=True, second_opinion=second_opinion,
-                        flag_truncated=flag_truncated)
+                        flag_truncated=flag_truncated, resegment=llr_resegment)
     if adapter_front is not None:
         import dataclasses
 
@@ -457,6 +471,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
     n_trunc = [0]  # rows the truncation look replaced (reserved_ bit 1)
     n_front = [0]  # rows whose adapter_start the adapter-front pass moved (reserved_ bit 3)
     n_reval = [0]  # ... that are the validation from the trimmed start (reserved_ bit 4: --adapter_front_revalidate)
+    reseg_marks = []  # reserved_ of the rows the re-segmentation made (bit 5; bits 6-9: the first row's fail_code)
     n_rejected = [0]  # trims that validation rejected (the pipeline counts them: such a row says nothing)
     sharder = GroupSharder(ws, rank, m) if multi else None
     ordinals: List[int] = []  # stream index of the first read of every group this rank yields
@@ -482,6 +497,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_trunc[0] += int(((rows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             n_front[0] += int(((rows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
             n_reval[0] += int(((rows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
+            reseg_marks.append(rows["reserved_"][(rows["reserved_"] & lib.ROW_RESEGMENTED) != 0])
             res = lib.rows_to_results(rows, primary, consume=True)
             out = [ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                    for rid, r in zip(tagged[:, 0], res)]
@@ -515,6 +531,7 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_trunc[0] += int(((allrows["reserved_"] & lib.ROW_POLYA_TRUNCATED) != 0).sum())
             n_front[0] += int(((allrows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
             n_reval[0] += int(((allrows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
+            reseg_marks.append(allrows["reserved_"][(allrows["reserved_"] & lib.ROW_RESEGMENTED) != 0])
             n_rejected[0] += sum(int(part[2]) for part in lists if len(part) > 2)
             res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
             writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
@@ -536,6 +553,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
                 if not multi:
                     n_rejected[0] = int(getattr(pipe, "front_rejected", 0))
                 logging.info("Adapter front re-validated: %d kept, %d trims rejected by validation", n_reval[0], n_rejected[0])
+        if llr_resegment:
+            logging.info(lib.resegment_log(np.concatenate(reseg_marks) if reseg_marks else np.zeros(0, dtype=np.int32)))
     if multi:
         dist.barrier()
         logging.info("process group: backend %s, %d rank(s); HIP runtimes mapped: %s", dist.get_backend(), ws, ", ".join(lib.hip_runtimes()))
@@ -564,6 +583,7 @@ def main(argv=None):
                 setattr(args, k, v)
         _check_second_opinion(args)
         _check_flag_truncated(args)
+        _check_llr_resegment(args)
         _check_polya_length(args)
         front = _check_adapter_front(args)
         templates = _check_fingerprints(args)
@@ -572,6 +592,7 @@ def main(argv=None):
         run_dir = os.path.join(args.output, "adapted_" + __version__.replace(".", "_") + "_" + str(uuid.uuid4())[:8])
         _check_second_opinion(args)
         _check_flag_truncated(args)
+        _check_llr_resegment(args)
         _check_polya_length(args)
         front = _check_adapter_front(args)
         templates = _check_fingerprints(args)
@@ -612,7 +633,7 @@ def main(argv=None):
     run_detect(files, set(read_ids), excl, spc, run_dir, args.minibatch_size, args.batch_size, args.device,
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
                int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
-               flag_truncated=getattr(args, "flag_truncated", False), adapter_front=front,
+               flag_truncated=getattr(args, "flag_truncated", False), adapter_front=front, llr_resegment=getattr(args, "llr_resegment", False),
                fingerprints=(args.fingerprints, templates, getattr(args, "dtw_band", None)) if getattr(args, "fingerprints", None) is not None else None,
                polya_length=getattr(args, "polya_length", None),
                adapter_nt=getattr(args, "adapter_nt", None), event_params=getattr(args, "event_params", None))

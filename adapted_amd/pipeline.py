@@ -30,8 +30,8 @@ from . import lib
 def native_int16_plan(primary: str, int16_input, m: int, flag_truncated: bool) -> bool:
     """Do the detect kernels read the raw int16 rows themselves (no float32 matrix on the device)?  int16_input: False, True
     (the LLR primary natively, the CNN primary through the calibrated float32 matrix) or "native" (the CNN primary natively as
-    well: adp_detect_cnn_i16).  Never for rows that are not 8-byte aligned (m % 4), with the truncation look (a float32-row
-    phase) or for the start-peak primary."""
+    well: adp_detect_cnn_i16).  Never for rows that are not 8-byte aligned (m % 4), with the truncation look or the LLR
+    re-segmentation (float32-row phases: callers pass ``flag_truncated or resegment``) or for the start-peak primary."""
     if not int16_input or m % 4 != 0 or flag_truncated:
         return False
     if primary == "llr":
@@ -71,13 +71,15 @@ class AdapterFingerprints:
 class HostPipeline:
     def __init__(self, spc, minibatch: int, m: int, device: int = 0, n_slots: int = 3, primary: str = "llr",
                  with_start_peak: bool = False, model=None, int16_input: bool = False, group: int = 1, ragged: bool = False,
-                 flag_truncated: bool = False, second_opinion: Optional[str] = None):
+                 flag_truncated: bool = False, resegment: bool = False, second_opinion: Optional[str] = None):
         """with_start_peak: the start-peak columns on every row of the LLR and CNN primaries (an extension; the start-peak primary
         fills them anyway).
         second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
         minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py).
         flag_truncated: every detect call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension; LLR and CNN
         primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one.
+        resegment: every LLR detect call re-segments the reads its first pass fails behind a first change point (ADP_LLR_RESEGMENT,
+        an extension, untuned; LLR primary only, not with flag_truncated).  Like the truncation look it reads float32 rows.
         int16_input: the staging slots hold raw ADC samples (int16) plus per-read (scale, offset); they are calibrated
         to float32 pA on the device (adp_calibrate_i16), so only 2 bytes per sample cross PCIe.  get_buffers() then hands
         out (raw, lengths, scale, offset) instead of (signals, lengths).  True: the LLR primary reads the raw rows itself, the
@@ -106,11 +108,18 @@ class HostPipeline:
             why = lib.truncation_unsupported(spc)
             if why:
                 raise ValueError("flag_truncated: " + why)
+        self.resegment = bool(resegment)
+        if self.resegment:
+            if primary != "llr":
+                raise ValueError("resegment goes with the LLR primary")
+            why = lib.resegment_unsupported(spc, self.flag_truncated)
+            if why:
+                raise ValueError("resegment: " + why)
         self.eng = lib.Engine(spc, self.N, self.m, device=self.device)
         self.slots = []
         # int16 input + LLR primary (or the CNN primary with "native"): the kernels read the raw samples themselves
         # (adp_detect_llr_i16, adp_detect_cnn_i16) -- no float32 matrix is made
-        self.native_i16 = native_int16_plan(primary, int16_input, self.m, self.flag_truncated)
+        self.native_i16 = native_int16_plan(primary, int16_input, self.m, self.flag_truncated or self.resegment)
         # the float32 minibatch made on the device (calibrated and / or laid out from packed reads); one: detect is serial
         # (native int16 + packed reads: the raw int16 matrix instead)
         self.dsig16 = None
@@ -354,7 +363,7 @@ class HostPipeline:
         if self.primary == "llr":
             # (the staging slots are NaN padded by the reader / the on-device calibration: the passes may stop at each read's end)
             rows, mbs = self.eng.detect_llr_rows(dsig, dlen, n, self.mb, with_start_peak=self.with_start_peak, device_ptrs=True,
-                                                 tails_nan=True, flag_truncated=self.flag_truncated)
+                                                 tails_nan=True, flag_truncated=self.flag_truncated, resegment=getattr(self, "resegment", False))
             return rows, mbs
         if self.primary == "start_peak":
             return self.eng.detect_start_peak_rows(dsig, dlen, n, self.mb, device_ptrs=True), None

@@ -79,6 +79,7 @@ extern "C" {
                                       see adp_detect_llr; adp_row.reserved_ bits 1 and 2) */
 #define ADP_POLYA_TRUNCATED (1 << 20) /* adp_validate_candidates: Boundaries.polya_truncated is True for every read -- the RNA partition
                                       is all None (adapted/partition/signal_partitions.py:74-77) */
+/* (1 << 21 is ADP_LLR_RESEGMENT, a flag of adp_detect_llr with a header of its own: adapted_hip_resegment.h, included below) */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -166,7 +167,9 @@ typedef struct adp_row {
                                   the row's adapter_start (adapted_hip_adapter_front.h): adapter_start, adapter_len and the four adapter
                                   statistics are the trimmed adapter's, everything else the first validation's.  bit 4 (beside bit 3):
                                   adp_adapter_front_revalidate replaced the row by the validation from the trimmed start
-                                  (adapted_hip_revalidate.h).  0 in every other row */
+                                  (adapted_hip_revalidate.h).  bit 5: the row is the validation of the second segmentation of
+                                  ADP_LLR_RESEGMENT, bits 6-9 the fail_code of the row it replaced (adapted_hip_resegment.h).  0 in
+                                  every other row */
 } adp_row;
 #define ADP_ROW_FROM_SECOND_LLR 1
 #define ADP_ROW_POLYA_TRUNCATED 2
@@ -575,6 +578,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * and adp_dba_step, an extension --: a header of its own, with its prototype table in adapted_amd/lib.py, TEMPLATE_PROTOTYPES. */
 #include "adapted_hip_templates.h"
 
+/* Re-segmentation of reads the LLR primary fails -- ADP_LLR_RESEGMENT, a flag of adp_detect_llr, an extension --: its rule, its row
+ * bits and its counters in a header of its own; it declares no entry point (adapted_amd/lib.py, RESEGMENT_PROTOTYPES, is empty). */
+#include "adapted_hip_resegment.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
@@ -593,6 +600,8 @@ int adp_kernel_times(adp_handle *h, const char **names_out, float *ms_out, int c
  *          still failing, minibatches (with a selected read) that gave none
  *       12 int32[3], the truncation look of the last adp_detect_llr / adp_detect_cnn call made with ADP_FLAG_TRUNCATED: eligible
  *          reads, reads whose tail window looks like poly(A) (T1), rows replaced
+ *       25 int32[3], the re-segmentation of the last adp_detect_llr call (ADP_LLR_RESEGMENT, adapted_hip_resegment.h): eligible
+ *          reads, reads whose second segmentation found a poly(A) end, rows replaced
  *       9 int8[n], 1: the read's moving-window series were prepared by a series kernel
  *       What phase C's kernels hand to each other (nck = Lp / 16, nsum = Lp / 64; a copy beyond the buffer is ADP_ERR_INVALID):
  *       13 ck float64[n*nck*2]: (c, c2) in front of pooled sample 16 q, written for q < ceil(n_valid / 16);
