@@ -1614,18 +1614,20 @@ static int launch_conv64(adp_handle *h, const float *in, float *out, const float
 } // extern "C++"
 
 extern "C++" {
-template <int NT, bool LAST, bool FIRST = false>
+// k_cnn_conv64s in one of its two roles: the LDS size and the persistent grid they share.  The arguments behind `flag` are LAST's (layer 3's
+// fragments, bias and scale, the scores), `first` is FIRST's; each launcher below passes nothing for the other role's.
+template <int NT, bool LAST>
 static int launch_conv64s(adp_handle *h, const _Float16 *in, _Float16 *out, const _Float16 *wsp, const float *b, float sw, int n, int L1,
-                          int Lrows, int tiles, int32_t *flag, const _Float16 *w3sp = nullptr, const float *b3 = nullptr, float inv_s3 = 0.f,
-                          float *scores = nullptr, int Lo = 0, CnsFirst first = CnsFirst{})
+                          int Lrows, int tiles, int32_t *flag, const _Float16 *w3sp, const float *b3, float inv_s3, float *scores, int Lo,
+                          CnsFirst first)
 {
     // (LAST: layer 3 in the epilogue -- tiles that advance by 64 NT - 2 positions, the taps' partial sums of a tile in LDS behind the two tile buffers)
     const size_t lds = (size_t)2 * (((size_t)(64 * NT + 6) * CNS_ROWB + 1023) / 1024 * 1024) + (LAST ? (size_t)2 * CNN_K * 64 * NT * 4 : 0);
-    RCCHK(lds_attr_once(h, (const void *)k_cnn_conv64s<NT, LAST, FIRST>, lds));
+    RCCHK(lds_attr_once(h, (const void *)k_cnn_conv64s<NT, LAST>, lds));
     long long total = (long long)n * tiles;
     if (total >= (1ll << 31)) { g_err = "too many tiles for one launch of k_cnn_conv64s"; return ADP_ERR_UNSUPPORTED; }
     int grid = (int)(total < h->n_cu ? total : h->n_cu);
-    hipLaunchKernelGGL((k_cnn_conv64s<NT, LAST, FIRST>), dim3(grid), dim3(256), lds, h->stream, in, out, wsp, b, sw, 1.0f / sw, n, L1, Lrows, tiles, flag,
+    hipLaunchKernelGGL((k_cnn_conv64s<NT, LAST>), dim3(grid), dim3(256), lds, h->stream, in, out, wsp, b, sw, 1.0f / sw, n, L1, Lrows, tiles, flag,
                        w3sp, b3, inv_s3, scores, Lo, first);
     return 0;
 }
@@ -1638,8 +1640,8 @@ static int launch_conv_first(adp_handle *h, adp_handle *wh, const float *x, int 
     const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
     const float *W = wh->cnn_w.as<float>();
     const CnsFirst first{x, Lc, wsp + (size_t)2 * CNS_WSP_LAYER + CNS_W3SP, W + CNN_B0, wh->cnn_sw[3]};
-    return launch_conv64s<NT, false, true>(h, nullptr, rows, wsp, W + CNN_B1, wh->cnn_sw[0], n, L1, Lrows, (L1 + 64 * NT - 7) / (64 * NT - 6), flag,
-                                           nullptr, nullptr, 0.f, nullptr, 0, first);
+    return launch_conv64s<NT, false>(h, nullptr, rows, wsp, W + CNN_B1, wh->cnn_sw[0], n, L1, Lrows, (L1 + 64 * NT - 7) / (64 * NT - 6), flag,
+                                     nullptr, nullptr, 0.f, nullptr, 0, first);
 }
 // Layers 2 + 3: layer 1's rows in, the scores out (`dump`: one row for the stores that have no output); tiles that advance by 64 NT - 2
 template <int NT>
@@ -1650,30 +1652,16 @@ static int launch_conv_last(adp_handle *h, adp_handle *wh, const _Float16 *rows,
     const _Float16 *wsp = wh->cnn_wsp.as<_Float16>();
     const float *W = wh->cnn_w.as<float>();
     return launch_conv64s<NT, true>(h, rows, dump, wsp + CNS_WSP_LAYER, W + CNN_B2, wh->cnn_sw[1], n, L1, Lrows, (L1 + 64 * NT - 3) / (64 * NT - 2), flag,
-                                    wsp + (size_t)2 * CNS_WSP_LAYER, W + CNN_B3, 1.0f / (wh->cnn_sw[2] * CNS_ASCALE), scores, Lo);
-}
-// ADP_CNN_FUSE_IN=0, FIRST's A/B partner: layer 0 as a kernel of its own, its rows through HBM (rows0) into layer 1 in the kernel's plain form
-template <int NT>
-static int launch_conv_first_apart(adp_handle *h, adp_handle *wh, const float *x, int Lc, _Float16 *rows0, _Float16 *rows, int n, int L1, int Lrows,
-                                   int32_t *flag)
-{
-    const float *W = wh->cnn_w.as<float>();
-    { Scope s(h, "k_cnn_conv_in");
-      hipLaunchKernelGGL(k_cnn_conv_in_s, dim3((L1 + CNS_IN_P * CNS_IN_T - 1) / (CNS_IN_P * CNS_IN_T), n), dim3(256), 0, h->stream, x, Lc, L1, Lrows,
-                         W + CNN_W0, W + CNN_B0, rows0, flag); }
-    Scope s(h, "k_cnn_conv64 (layer 1)");
-    return launch_conv64s<NT, false>(h, rows0, rows, wh->cnn_wsp.as<_Float16>(), W + CNN_B1, wh->cnn_sw[0], n, L1, Lrows, (L1 + 64 * NT - 1) / (64 * NT), flag);
+                                    wsp + (size_t)2 * CNS_WSP_LAYER, W + CNN_B3, 1.0f / (wh->cnn_sw[2] * CNS_ASCALE), scores, Lo, CnsFirst{});
 }
 // the chunks of a call: layers 0 + 1, then layers 2 + 3
 template <int NT>
 static int conv_split_chunks(adp_handle *h, adp_handle *wh, const float *prepared, int n_reads, int C, int Lc, int L1, int Lo, int Lrows,
-                             _Float16 *rows0, _Float16 *rows, _Float16 *dump, int32_t *flag, float *scores_out)
+                             _Float16 *rows, _Float16 *dump, int32_t *flag, float *scores_out)
 {
     for (int s0 = 0; s0 < n_reads; s0 += C) {
         const int n = n_reads - s0 < C ? n_reads - s0 : C;
-        const float *x = prepared + (size_t)s0 * Lc;
-        if (rows0) RCCHK(launch_conv_first_apart<NT>(h, wh, x, Lc, rows0, rows, n, L1, Lrows, flag));
-        else RCCHK(launch_conv_first<NT>(h, wh, x, Lc, rows, n, L1, Lrows, flag));
+        RCCHK(launch_conv_first<NT>(h, wh, prepared + (size_t)s0 * Lc, Lc, rows, n, L1, Lrows, flag));
         RCCHK(launch_conv_last<NT>(h, wh, rows, dump, scores_out + (size_t)s0 * 2 * Lo, Lo, n, L1, Lrows, flag));
     }
     return 0;
@@ -1687,28 +1675,22 @@ static int cnn_forward_split(adp_handle *h, adp_handle *wh, const float *prepare
     const size_t per_read = (size_t)Lrows * CNS_ROWB;
     size_t cap_reads = ((size_t)4 << 30) / per_read; // an activation buffer of at most 4 GiB
     if (cap_reads < 1) cap_reads = 1;
-    if (cap_reads > 65535) cap_reads = 65535;        // (k_cnn_conv_in_s takes the chunk's reads as grid.y)
+    if (cap_reads > 65535) cap_reads = 65535;        // (the grid.y limit of layer 0's retired kernel, here and below; kept so that the chunks keep the shapes they had)
     int C = (int)((size_t)n_reads < cap_reads ? (size_t)n_reads : cap_reads);
-    // cnn_act[0]: layer 1's rows, the only activations in HBM; cnn_act[1]: layer 0's, under ADP_CNN_FUSE_IN=0 alone
-    const int nbuf = env_int("ADP_CNN_FUSE_IN", 1) != 0 ? 1 : 2;
-    if (h->cnn_Lpad != Lrows || h->cnn_L1 != L1 || h->cnn_chunk < C || h->cnn_nbuf < nbuf) {
-        size_t bytes = (size_t)C * per_read + CNS_SLACK; // (+ what the tile DMAs read past the last read's rows)
-        for (int k = 0; k < nbuf; k++) {
-            if (bytes < h->cnn_act[0].cap) bytes = h->cnn_act[0].cap; // (cnn_chunk comes from cnn_act[0]: the other is never smaller)
-            ALLOCCHK(h->cnn_act[k].ensure(bytes));
-            HIPCHK(hipMemsetAsync(h->cnn_act[k].p, 0, h->cnn_act[k].cap, h->stream)); // the padding rows are never written again
-        }
-        h->cnn_nbuf = nbuf; // (the buffers laid down for this geometry)
-        h->cnn_Lpad = Lrows; h->cnn_L1 = L1; h->cnn_chunk = (int)((h->cnn_act[0].cap - CNS_SLACK) / per_read); if (h->cnn_chunk > 65535) h->cnn_chunk = 65535;
+    // cnn_rows: layer 1's rows, the only activations in HBM
+    if (h->cnn_Lpad != Lrows || h->cnn_L1 != L1 || h->cnn_chunk < C) {
+        ALLOCCHK(h->cnn_rows.ensure((size_t)C * per_read + CNS_SLACK)); // (+ what the tile DMAs read past the last read's rows)
+        HIPCHK(hipMemsetAsync(h->cnn_rows.p, 0, h->cnn_rows.cap, h->stream)); // the padding rows are never written again
+        h->cnn_Lpad = Lrows; h->cnn_L1 = L1; h->cnn_chunk = (int)((h->cnn_rows.cap - CNS_SLACK) / per_read); if (h->cnn_chunk > 65535) h->cnn_chunk = 65535;
     }
     C = h->cnn_chunk < n_reads ? h->cnn_chunk : n_reads;
     ALLOCCHK(h->cnn_dump.ensure(CNS_ROWB)); // written by the LAST kernel's stores without an output, never read: no clearing
     ALLOCCHK(wh->op_used.ensure(16));
     int32_t *flag = wh->op_used.as<int32_t>() + 1;
-    _Float16 *rows0 = nbuf == 2 ? h->cnn_act[1].as<_Float16>() : nullptr, *rows = h->cnn_act[0].as<_Float16>(), *dump = h->cnn_dump.as<_Float16>();
-    return NT == 4 ? conv_split_chunks<4>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out)
-         : NT == 3 ? conv_split_chunks<3>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out)
-                   : conv_split_chunks<2>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows0, rows, dump, flag, scores_out);
+    _Float16 *rows = h->cnn_rows.as<_Float16>(), *dump = h->cnn_dump.as<_Float16>();
+    return NT == 4 ? conv_split_chunks<4>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows, dump, flag, scores_out)
+         : NT == 3 ? conv_split_chunks<3>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows, dump, flag, scores_out)
+                   : conv_split_chunks<2>(h, wh, prepared, n_reads, C, Lc, L1, Lo, Lrows, rows, dump, flag, scores_out);
 }
 
 // the conv stack over device buffers, asynchronous on the handle's stream

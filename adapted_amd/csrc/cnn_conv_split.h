@@ -59,7 +59,7 @@ static __device__ __forceinline__ void cns_static_for(F &&f)
 #define CNS_SLACK 131072     // bytes behind the last read's rows that a tile DMA may read.  The LAST kernel's tiles advance by PB - 2 positions: a read's
                              // last tile starts at row CNS_FRONT - 4 + L1 - 1 at the latest and its DMA is PB + 6 rows rounded up to whole KBs; with
                              // Lrows >= CNS_FRONT + L1 + 4 that ends at most PB - 3 rows + 1023 bytes behind the read's rows: 69 839 bytes at NT = 4
-                             // (the plain form's tiles advance by PB and end inside the rows or less than 1 KB behind them)
+                             // (the FIRST kernel reads no rows)
 #define CNS_WSP_LAYER (2 * CNS_KSTEPS * 2 * 64 * 8) // float16 per layer in the split-weight buffer
 // Row 0 of a read's front padding is the DUMP row: the epilogues store the pieces of rows at or beyond L1 there so that every store is issued
 // and the counted s_waitcnt stays exact.  No result may depend on it: the LAST kernel's first tile starts there (row CNS_FRONT - 4), but only
@@ -135,78 +135,6 @@ __global__ void k_cns_split_w0(const float *__restrict__ w0 /* [64][1][7] */, fl
 }
 struct CnsFirst { const float *x; int Lc; const _Float16 *w0sp; const float *b0; float s0; }; // the prepared signal [n][Lc], layer 0's fragments, bias, scale
 
-// ---------------------------------------------------------------- layer 0: Conv1d(1 -> 64, k 7, stride 3, pad 3) + ReLU, split rows out
-// grid = (ceil(L1 / 64), n); block = 256: 64 positions, wave q makes channels 16 q .. 16 q + 15 of all of them (weights wave-uniform:
-// scalar operands; the float32 fmaf chain of k_cnn_conv_in, two channels per v_pk_fma_f32).  The rows are put together in LDS
-// (272-byte pitch: conflict-free 16-byte writes) and leave as one contiguous, fully coalesced copy -- written from the threads
-// directly, a wave's store would touch 64 different rows.  17 KB of LDS and 256 threads per block: eight blocks per CU, the
-// copies of some behind the arithmetic of others.
-#define CNS_IN_P 64
-#define CNS_IN_T 4 // position tiles per block (the weights are fetched once per block: as scalar operands they were a chain of
-                   // dependent scalar-cache round trips in front of every tile's arithmetic)
-__global__ void __launch_bounds__(256) k_cnn_conv_in_s(const float *__restrict__ x, int Lc, int L1, int Lrows,
-                                                        const float *__restrict__ w /* [64][1][7] */, const float *__restrict__ b,
-                                                        _Float16 *__restrict__ out, int32_t *__restrict__ flag)
-{
-    __shared__ __attribute__((aligned(16))) _Float16 rows_[CNS_IN_P * CNS_ROW];
-    LDS _Float16 *rows = (LDS _Float16 *)rows_;
-    const int n = blockIdx.y;
-    const int pl = threadIdx.x & (CNS_IN_P - 1), qw = threadIdx.x >> 6;
-    const float *row = x + (size_t)n * Lc;
-    // the wave's 16 channels as 8 pairs: weights and biases in vector registers (every lane the same values, all loads in flight at once)
-    cnn_f2 wp[8][CNN_K], bp[8];
-    {
-        const float *wq = w + 16 * qw * CNN_K, *bq = b + 16 * qw;
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            bp[e] = (cnn_f2){bq[2 * e], bq[2 * e + 1]};
-#pragma unroll
-            for (int t = 0; t < CNN_K; t++) wp[e][t] = (cnn_f2){wq[(2 * e) * CNN_K + t], wq[(2 * e + 1) * CNN_K + t]};
-        }
-    }
-    cnn_us2 hmax = {0, 0};
-    LDS _Float16 *o = rows + pl * CNS_ROW + 16 * qw;
-    for (int tile = 0; tile < CNS_IN_T; tile++) {
-        const int p0 = (blockIdx.x * CNS_IN_T + tile) * CNS_IN_P;
-        if (p0 >= L1) break;
-        const int p = p0 + pl;
-        float v[CNN_K];
-#pragma unroll
-        for (int t = 0; t < CNN_K; t++) { const int i = 3 * p + t - 3; v[t] = (i >= 0 && i < Lc) ? row[i] : 0.f; }
-#pragma unroll
-        for (int c8 = 0; c8 < 2; c8++) {
-            cnn_h2 hq[4], lq[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                cnn_f2 acc = bp[c8 * 4 + e];
-#pragma unroll
-                for (int t = 0; t < CNN_K; t++) acc = __builtin_elementwise_fma(wp[c8 * 4 + e][t], (cnn_f2){v[t], v[t]}, acc);
-                acc = __builtin_elementwise_max(acc, (cnn_f2){0.f, 0.f}) * CNS_ASCALE; // (a NaN becomes 0, as `acc > 0 ? acc : 0` makes it in k_cnn_conv_in)
-                const cnn_h2 hi = __builtin_convertvector(acc, cnn_h2);
-                const cnn_f2 rs = (acc - __builtin_convertvector(hi, cnn_f2)) * 2048.0f;
-                hq[e] = hi; lq[e] = __builtin_convertvector(rs, cnn_h2);
-                hmax = __builtin_elementwise_max(hmax, __builtin_bit_cast(cnn_us2, hi));
-            }
-            const cnn_h8 hh = {hq[0][0], hq[0][1], hq[1][0], hq[1][1], hq[2][0], hq[2][1], hq[3][0], hq[3][1]};
-            const cnn_h8 ll = {lq[0][0], lq[0][1], lq[1][0], lq[1][1], lq[2][0], lq[2][1], lq[3][0], lq[3][1]};
-            *reinterpret_cast<LDS cnn_h8 *>(o + c8 * 8) = hh;
-            *reinterpret_cast<LDS cnn_h8 *>(o + 64 + c8 * 8) = ll;
-        }
-        __syncthreads();
-        // 17 16-byte pieces per row (the last one is the row's padding: stays as it is), rows at or beyond L1 stay zero
-        const int nrows = L1 - p0 < CNS_IN_P ? L1 - p0 : CNS_IN_P;
-        cnn_h8 *dst = reinterpret_cast<cnn_h8 *>(out + ((size_t)n * Lrows + CNS_FRONT + p0) * CNS_ROW);
-        const LDS cnn_h8 *src = reinterpret_cast<const LDS cnn_h8 *>(rows);
-        for (int i = threadIdx.x; i < nrows * 17; i += 256)
-            dst[i] = src[i]; // (the 17th piece of a row, its padding, goes along: a hole per row would make every line a partial write)
-        __syncthreads();
-    }
-    // out of range: a hi part of 32768 or more, or infinite (the values are non-negative: bit patterns order like values); rows at
-    // or beyond L1 see zeros or real samples like their neighbours -- a needless flag only costs the float32 repeat
-    const bool bad = hmax[0] >= 0x7800 || hmax[1] >= 0x7800;
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
 // ---------------------------------------------------------------- layers 1, 2: Conv1d(64 -> 64, k 7, pad 3) + ReLU, split float16 MFMA
 // grid = persistent (one workgroup per CU); block = 256 = 4 waves = 2 channel halves (mh) x 2 position halves (ph);
 // dynamic LDS = 2 tiles of (64 NT + 6) rows, each rounded up to whole 1 KB DMA instructions.
@@ -215,6 +143,8 @@ __global__ void __launch_bounds__(256) k_cnn_conv_in_s(const float *__restrict__
 // Synchronisation per step: the tile's DMA is the OLDEST of the wave's outstanding vector-memory operations (it was issued before
 // the previous step's stores), so a counted s_waitcnt leaves those stores in flight; every store of the epilogue is issued
 // unconditionally (rows at or beyond L1 go to the read's row 0, which nothing reads) to keep that count exact.
+// The kernel has TWO roles: layer 1 runs as FIRST (= !LAST) and layer 2 as LAST.  (The third, plain one -- rows in, rows out -- is in
+// tools/experiments/cnn_split_layer0_apart.patch: see the end of this file.)
 // LAST (round 5): layer 3 -- ConvTranspose1d(64 -> 2, k 7, stride 3, pad 3) -- in this kernel's epilogue.  The tile's output rows are
 // laid down in LDS as before (with the rows outside [0, L1) zeroed: layer 3 reads them as its padding), but instead of leaving for HBM
 // they are the B operand of one more GEMM (k_cns_split_w3's A fragments: 12 MFMAs per 32 positions); the partial sums of a position's
@@ -226,8 +156,9 @@ __global__ void __launch_bounds__(256) k_cnn_conv_in_s(const float *__restrict__
 // tile's input rows are made in LDS from the prepared signal by 3 MFMAs per 32 rows and channel half (k_cns_split_w0's A fragments;
 // the samples of a row are its B fragment, loaded a tile ahead), converted like an epilogue's results; rows outside [0, L1) are the
 // zero padding.  Tiles advance by PB - 6 positions: the PB rows made are what PB - 6 positions need.  (Round 3 made these rows with float32 fmaf chains in the one wave per SIMD: no gain; on the matrix cores they cost
-// 11 MFMAs per wave and tile.)  No k_cnn_conv_in_s, 1.8 MB per read not written and not read back.
-template <int NT, bool LAST = false, bool FIRST = false>
+// 11 MFMAs per wave and tile.)  No kernel for layer 0, 1.8 MB per read not written and not read back; `in` is not read.
+// Layer 1 always runs in this form.
+template <int NT, bool LAST>
 __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restrict__ in, _Float16 *__restrict__ out,
                                                         const _Float16 *__restrict__ wsp, const float *__restrict__ bias, float sw,
                                                         float inv_sw, int n_reads, int L1, int Lrows, int tiles_per_read,
@@ -235,12 +166,12 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
                                                         const float *__restrict__ b3 = nullptr, float inv_s3 = 0.f,
                                                         float *__restrict__ scores = nullptr, int Lo = 0, CnsFirst F = CnsFirst{})
 {
-    static_assert(!(FIRST && LAST), "layer 1 takes layer 0 in, layer 2 takes layer 3 in");
+    constexpr bool FIRST = !LAST; // layer 1 takes layer 0 in, layer 2 takes layer 3 in
     constexpr int PB = 64 * NT, R = PB + 6, TILE_B = (R * CNS_ROWB + 1023) / 1024 * 1024, NDMA = TILE_B / 1024;
     // positions a tile advances by.  FIRST: PB - 6, so that the rows a tile needs (PBS + 6) are exactly its 2 NT subtiles of 32 -- a seventh
     // subtile for six rows cost a quarter of the prologue at NT = 3; the tile's last six positions are computed from rows nobody made and
     // are dropped (zeroed before the range check, not stored): 3 % more tiles
-    constexpr int PBS = LAST ? PB - 2 : FIRST ? PB - 6 : PB;
+    constexpr int PBS = LAST ? PB - 2 : PB - 6;
     constexpr int NSTORE = (PB * 17 + 255) / 256; // vector-memory instructions of one epilogue: 16-byte pieces of PB rows over 256 threads
     static_assert(NSTORE * 256 >= PB * 17 && (NSTORE - 1) * 256 < PB * 17, "the epilogue issues exactly NSTORE stores per thread: the s_waitcnt below counts them");
     extern __shared__ __attribute__((aligned(16))) float cns_lds_raw[];
@@ -268,11 +199,11 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
     constexpr bool BS_LDS = FIRST && NT == 4;
     const cnn_f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int total = n_reads * tiles_per_read; // (the host keeps it below 2^31)
-    auto dma = [&](int tix, int b) {
+    auto dma = [&](int tix, int b) { // (LAST alone: FIRST makes its rows)
         const int n = tix / tiles_per_read, tile = tix - n * tiles_per_read;
-        // rows (position tile * PB - 3) ... of read n: one contiguous range (the instructions of the last KB read a little past it,
+        // rows (position tile * PBS - 4) ... of read n: one contiguous range (the instructions of the last KB read a little past it,
         // into the next rows or the buffer's slack)
-        const GLB char *src = (const GLB char *)in + ((size_t)n * Lrows + CNS_FRONT - 3 - (LAST ? 1 : 0) + (size_t)tile * PBS) * CNS_ROWB + lane * 16;
+        const GLB char *src = (const GLB char *)in + ((size_t)n * Lrows + CNS_FRONT - 4 + (size_t)tile * PBS) * CNS_ROWB + lane * 16;
         for (int inst = wave; inst < NDMA; inst += 4)
             __builtin_amdgcn_global_load_lds((const GLB float *)(src + inst * 1024), (LDS float *)(lds + b * TILE_B + inst * 1024), 16, 0, 0);
     };
@@ -420,12 +351,12 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
         // (NT = 4 sits at the register limit -- 512 with the accumulators of four tiles: there the pieces stay a burst at the step's top)
         CNS_PH(0);
         constexpr bool INLOOP = NT < 4;
-        if (!FIRST && !INLOOP && it + gridDim.x < total) dma(it + gridDim.x, buf ^ 1);
-        const bool more = !FIRST && INLOOP && it + gridDim.x < total;
+        if (LAST && !INLOOP && it + gridDim.x < total) dma(it + gridDim.x, buf ^ 1);
+        const bool more = LAST && INLOOP && it + gridDim.x < total;
         const GLB char *nsrc = nullptr;
         if (more) {
             const int tix = it + gridDim.x, nn = tix / tiles_per_read, tile2 = tix - nn * tiles_per_read;
-            nsrc = (const GLB char *)in + ((size_t)nn * Lrows + CNS_FRONT - 3 - (LAST ? 1 : 0) + (size_t)tile2 * PBS) * CNS_ROWB + lane * 16;
+            nsrc = (const GLB char *)in + ((size_t)nn * Lrows + CNS_FRONT - 4 + (size_t)tile2 * PBS) * CNS_ROWB + lane * 16;
         }
         LDS char *ndst = lds + (buf ^ 1) * TILE_B;
         static_assert((NDMA + 3) / 4 <= CNS_KSTEPS, "one DMA piece per k-step and wave");
@@ -480,7 +411,7 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
             // LAST: a row outside the read is layer 3's zero padding (its activation of the padded input is not zero)
             const int pos_ = tile * PBS - 1 + ph * (NT * 32) + 32 * j + l31;
             // (a select, not a factor: position -1 is computed from the dump row in front of the read; FIRST: the last six positions from rows nobody made)
-            const bool keep_ = LAST ? (pos_ >= 0 && pos_ < L1) : FIRST ? (ph * (NT * 32) + 32 * j + l31 < PBS) : true;
+            const bool keep_ = LAST ? (pos_ >= 0 && pos_ < L1) : (ph * (NT * 32) + 32 * j + l31 < PBS);
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 // two values per instruction where the hardware has a packed form (v_pk_mul / v_pk_fma / v_cvt_pk_f16_f32 / v_pk_add):
@@ -491,7 +422,7 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
                     const cnn_f2 a2 = {am[j][4 * g + 2 * q], am[j][4 * g + 2 * q + 1]}, x2 = {ax[j][4 * g + 2 * q], ax[j][4 * g + 2 * q + 1]};
                     cnn_f2 v = __builtin_elementwise_fma(x2, (cnn_f2){cx, cx}, a2 * inv_sw);
                     v = __builtin_elementwise_max(v, (cnn_f2){0.f, 0.f}); // (a NaN becomes 0, as `v > 0 ? v : 0` makes it in k_cnn_conv64)
-                    if ((LAST || FIRST) && !keep_) v = (cnn_f2){0.f, 0.f};
+                    if (!keep_) v = (cnn_f2){0.f, 0.f};
                     const cnn_h2 hi = __builtin_convertvector(v, cnn_h2);
                     const cnn_f2 rs = (v - __builtin_convertvector(hi, cnn_f2)) * 2048.0f;
                     hq[q] = hi; lq[q] = __builtin_convertvector(rs, cnn_h2);
@@ -557,7 +488,7 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NIT) : "memory");
         } else {
         {
-            // rows tile * PB .. of read n; pieces of rows at or beyond L1 go to the read's row 0 (which nothing reads), so that
+            // FIRST: rows tile * PBS .. of read n leave for HBM; pieces of rows at or beyond L1 go to the read's row 0 (which nothing reads), so that
             // every store is issued and the count below stays exact
             const int nvalid = (L1 - tile * PBS < PBS ? L1 - tile * PBS : PBS) * 17;
             char *rbase = reinterpret_cast<char *>(out) + (size_t)n * Lrows * CNS_ROWB;
@@ -581,7 +512,7 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
         // the DMA issued at the top of this step is older than these NSTORE stores
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE) : "memory");
         }
-        if (!FIRST) buf ^= 1;
+        if (LAST) buf ^= 1; // (FIRST has one tile buffer)
         CNS_PH(3);
 #ifdef ADP_PHASE_TIMING
         nst_++;
@@ -605,5 +536,8 @@ __global__ void __launch_bounds__(256, 1) k_cnn_conv64s(const _Float16 *__restri
 // profiles/r04_tried_and_dropped.txt.)
 // (Round 5's layer 3 as a kernel of its own from split rows -- k_cnn_conv_out_s, LAST's A/B partner -- left in a prune of its own with the
 // switches ADP_CNN_FOLD and ADP_CNN_OVERLAP; its scores differed from LAST's in the last place.  Sources:
-// tools/experiments/cnn_split_layer3_apart.patch; records: profiles/r05_tried_and_dropped.txt, profiles/cnn_split_prune_isa.txt.
-// FIRST's partner -- k_cnn_conv_in_s and the plain form of this kernel as layer 1, ADP_CNN_FUSE_IN=0 -- is still here.)
+// tools/experiments/cnn_split_layer3_apart.patch; records: profiles/r05_tried_and_dropped.txt, profiles/cnn_split_prune_isa.txt.)
+// (FIRST's A/B partner -- layer 0 as a kernel of its own (a float32 fmaf chain that wrote split rows to a second buffer in HBM) and a
+// third, plain role of k_cnn_conv64s as layer 1 behind it -- left in the prune after that one with its switch; its scores, too, differed
+// from the default's in the last place.  The kernel has had the two roles FIRST and LAST since.  Sources:
+// tools/experiments/cnn_split_layer0_apart.patch; records: profiles/r05_ab_layer0_in_layer1_*.txt, profiles/cnn_split_layer0_isa.txt.)

@@ -75,10 +75,10 @@ struct adp_handle {
     int oh1 = 5;      // head offset of the first gains pass
     int pos_off = 0;  // added to pooled indices * ds for sample positions
     DevBuf rng0;      // per-read [0, T) ranges of the single-read layout
-    // CNN head: weights of the four layers; the split stack's activations (cnn_conv_split.h): rows [chunk][Lrows][272 B] of layer 1 and,
-    // under ADP_CNN_FUSE_IN=0, of layer 0 (cnn_nbuf of them hold the current geometry's padding), and the one row that takes the last
+    // CNN head: weights of the four layers; the split stack's activations (cnn_conv_split.h): rows [chunk][Lrows][272 B] of layer 1, the
+    // only ones in HBM (their padding is laid down per geometry: cnn_Lpad, cnn_L1, cnn_chunk), and the one row that takes the last
     // kernel's stores without an output
-    DevBuf cnn_w, cnn_act[2], cnn_dump, cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
+    DevBuf cnn_w, cnn_rows, cnn_dump, cnn_x, cnn_sc, ct_st, ct_lnz, ct_ap, cstat, op_arena, op_used, series_plan;
     DevBuf ws;              // the module entry points (modules.hip): one call's staging and scratch (ws_carve)
     // the phases behind a detect call's first pass (cnn_fallback.h, cnn_second_opinion.h, polya_truncated.h): the reads each one
     // selected [reads of the call] -- fb_sel and so_sel are both live between the first pass and the counter read -- and the
@@ -96,11 +96,11 @@ struct adp_handle {
     bool rs_ran = false;
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
-    int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, cnn_nbuf = 0, n_cu = 256;
+    int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;
     // conv stack: 1 = split float16 MFMA (cnn_conv_split.h, the default), 0 = exact float32 MFMA (cnn_conv.h; ADP_CNN_CONV=f32).
     // cnn_redo_f32: the split kernels met an activation outside the float16 range in this call -- it is being repeated in float32
     int cnn_mode = 1;
-    DevBuf cnn_actf[2];                                  // the exact-float32 stack's activations [chunk][64][Lpad] (cnn_act: the split rows)
+    DevBuf cnn_actf[2];                                  // the exact-float32 stack's activations [chunk][64][Lpad] (cnn_rows: the split rows)
     int cnn_f_Lpad = 0, cnn_f_L1 = 0, cnn_f_chunk = 0;
     bool cnn_redo_f32 = false;
     DevBuf cnn_wsp;          // split B fragments of layers 1 and 2

@@ -278,7 +278,7 @@ def test_device_topk_behind_given_argmaxes():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("conv", ["split", "split_layer0apart", "f32"])
+@pytest.mark.parametrize("conv", ["split", "f32"])
 @pytest.mark.parametrize("Lc,n", [(1650, 37), (20050, 9), (1651, 5), (1652, 5), (100, 3), (7, 2), (193 * 3, 4), (256 * 3 + 1, 4), (190 * 3, 3), (191 * 3 + 2, 3), (380 * 3 + 1, 3),
                                   (186 * 3, 3), (186 * 3 + 1, 3), (372 * 3 + 1, 3), (123 * 3, 3), (251 * 3, 3),
                                   (512 * 3, 3), (1024 * 3, 2)])  # (the last two: several tiles of the 256-position shape, NT = 4)
@@ -287,14 +287,12 @@ def test_hip_conv_stack_equals_torch(Lc, n, conv, monkeypatch):
     with the shipped weights -- "split": the default, float16 matrix cores on split operands (cnn_conv_split.h), layer 3 folded into
     layer 2's kernel (tiles that advance by 64 NT - 2 positions -- lengths around multiples of 190 sit on their seams) and layer 0
     made in layer 1's prologue (tiles that advance by 64 NT - 6 positions, their 64 NT input rows made from 192 NT + 4 samples:
-    lengths around multiples of 186 / 122 / 250 sit on their seams, 7 and 100 are shorter than one subtile); "split_layer0apart":
-    the same stack with layer 0 as a kernel of its own (ADP_CNN_FUSE_IN=0); "f32": the exact float32 matrix-core kernels (cnn_conv.h, ADP_CNN_CONV=f32).  The float32 stack and torch are float32 sums of the same 448
+    lengths around multiples of 186 / 122 / 250 sit on their seams, 7 and 100 are shorter than one subtile); "f32": the exact float32 matrix-core kernels (cnn_conv.h, ADP_CNN_CONV=f32).  The float32 stack and torch are float32 sums of the same 448
     products per output in different orders, the split stack carries 22 bits per operand: tolerance 2e-5 relative to the score
     scale for both (the golden test pins the scores themselves)."""
     import torch
 
-    monkeypatch.setenv("ADP_CNN_CONV", conv.split("_")[0])
-    monkeypatch.setenv("ADP_CNN_FUSE_IN", "0" if conv.endswith("layer0apart") else "1")
+    monkeypatch.setenv("ADP_CNN_CONV", conv)
 
     from adapted_amd import lib
     from adapted_amd.detect import cnn

@@ -1,10 +1,10 @@
 """The kernels that stay in the tree beside the defaults must keep giving the same BYTES: every switch below selects another
 implementation of the same reference rows -- one wave per moving-window recurrence (`ADP_SERIES_PIPE=0`) against the pipeline of
-waves (series_pipe.h), layer 0 of the conv stack as a kernel of its own (`ADP_CNN_FUSE_IN=0`) against layer 0 in layer 1's prologue, every
-sampled row in the first level of N1's sample (`ADP_N1_S0=1`), the lane-per-read series kernel on the LLR
+waves (series_pipe.h), every sampled row in the first level of N1's sample (`ADP_N1_S0=1`), the lane-per-read series kernel on the LLR
 path (`ADP_SERIES_PIPE_LLR=0`).  (The variants that lost their A/B in rounds 2-4 left the product in round 5:
 tools/experiments/r05_pruned_variants.patch; layer 3 of the conv stack as a kernel of its own -- `ADP_CNN_FOLD`, `ADP_CNN_OVERLAP` --
-after it: tools/experiments/cnn_split_layer3_apart.patch.)  Reference rows: V1-V4 adapted/detect/combined.py:358-631, mvs.py:45-158; C2
+after it: tools/experiments/cnn_split_layer3_apart.patch; then layer 0 as a kernel of its own:
+tools/experiments/cnn_split_layer0_apart.patch.)  Reference rows: V1-V4 adapted/detect/combined.py:358-631, mvs.py:45-158; C2
 adapted/detect/cnn.py:16-52.
 `ADP_ABLATE` is no such switch: it belongs to a `-DADP_ABLATE` build of the library (timing experiments, wrong rows) and the product
 ignores it."""
@@ -16,7 +16,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("ADP_SERIES_PIPE", "ADP_N1_S0", "ADP_SERIES_PIPE_LLR", "ADP_CNN_FUSE_IN", "ADP_CUMSUM_GATHER", "ADP_PK_PREFIX", "ADP_ABLATE")
+SWITCHES = ("ADP_SERIES_PIPE", "ADP_N1_S0", "ADP_SERIES_PIPE_LLR", "ADP_CUMSUM_GATHER", "ADP_PK_PREFIX", "ADP_ABLATE")
 
 
 def _with_env(env, fn):
@@ -95,9 +95,7 @@ def test_cnn_path_variants_give_the_same_rows(window, k, quantise, windows):
     spc, sig, lens, nan_reads = _cnn_batch(window, k, quantise, windows)
     n, m = sig.shape
     ref = None
-    # (ADP_CNN_FUSE_IN=0: layer 0 as a kernel of its own is a float32 fmaf chain, in layer 1's prologue it is a split-operand product: scores
-    # differ in their last bits, which flips a near-tied candidate on about one read in 10^4: not on these)
-    for env in ({}, {"ADP_SERIES_PIPE": "0"}, {"ADP_CNN_FUSE_IN": "0"}):
+    for env in ({}, {"ADP_SERIES_PIPE": "0"}):
         def run():
             eng = lib.Engine(spc, n, m, device=0)
             try:
