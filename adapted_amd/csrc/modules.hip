@@ -1,9 +1,10 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints, the template building and the adapter-front post-pass): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints, the template building, the adapter-front post-pass and the CSV text of a file's rows): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <type_traits>
@@ -20,6 +21,7 @@
 #include "fingerprint_api.h"
 #include "dtw_align_api.h"
 #include "adapter_front.h"
+#include "csv_api.h"
 
 // ---- workspace, staging and per-read checks of the entry points
 
@@ -1146,6 +1148,94 @@ int adp_adapter_front_i16(adp_handle *h, const int16_t *raw, const int32_t *full
     AfBufs b;
     RCCHK(ws_carve(h, [&](Carve &w) { af_pieces(w, b, n_reads, m, (flags & ADP_OUT_DEVICE) != 0); }));
     return af_run(h, SigI16{raw, scale, offset, full_len}, n_reads, m, rows, args, flags, b, info_out, shift_out, cand_out, diff_out);
+}
+
+} // extern "C"
+
+// ---- the rows of one output file to that file's CSV text (an extension; csv_api.h)
+
+static bool csv_offsets_ok(const int64_t *off, int n)
+{
+    if (off[0] != 0) return false;
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+extern "C" {
+
+int adp_format_rows(adp_handle *h, const adp_row *rows, int n, int fail, int primary, const void *ids, const int64_t *id_off,
+                    const int64_t *more, const int64_t *more_off, const void *strings, const int32_t *str_off, int n_str,
+                    void *text_out, uint64_t text_cap, uint64_t *len_out, int32_t *n_fallback_out)
+{
+    if (!h || n < 0 || !len_out || !n_fallback_out || (!text_out && text_cap) || primary < 0 || primary > 2) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    *n_fallback_out = 0;
+    if (n == 0) { // (no rows, no columns: the frame's text is a line break)
+        *len_out = 1;
+        if (text_cap >= 1) *(char *)text_out = '\n';
+        return ADP_OK;
+    }
+    if (!rows || !ids || !id_off || !more_off || !strings || !str_off) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (n_str != CSV_N_STR || str_off[0] != 0) { g_err = "the string table must hold 69 entries from offset 0"; return ADP_ERR_INVALID; }
+    for (int k = 0; k < n_str; k++) if (str_off[k + 1] < str_off[k]) { g_err = "the string table's offsets must ascend"; return ADP_ERR_INVALID; }
+    if (!csv_offsets_ok(id_off, n) || !csv_offsets_ok(more_off, n)) { g_err = "offsets must ascend from 0"; return ADP_ERR_INVALID; }
+    if (more_off[n] && !more) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    for (int i = 0; i < n; i++) {
+        const adp_row &r = rows[i];
+        if (r.fail_code < 0 || r.fail_code > 15 || r.start_peak_type < 0 || r.start_peak_type > 2) { g_err = "a row's fail_code or start_peak_type names no text"; return ADP_ERR_INVALID; }
+        if (r.n_cand < -1 || r.n_cand > ADP_MAX_CAND || r.n_open_pores < -1) { g_err = "a row's list counts are out of range"; return ADP_ERR_INVALID; }
+        const bool whole = r.n_open_pores > ADP_MAX_OPEN_PORES && !ADP_F_IS_EXCEPTION(r.fail_code); // (an exception row prints no list)
+        if (more_off[i + 1] - more_off[i] != (whole ? r.n_open_pores : 0)) {
+            g_err = "a row with more open pores than it holds needs its whole list, every other row none";
+            return ADP_ERR_INVALID;
+        }
+    }
+    const size_t ns = n, head = (size_t)(str_off[CSV_S_HEAD + (fail ? 1 : 0) + 1] - str_off[CSV_S_HEAD + (fail ? 1 : 0)]);
+    const size_t body_cap = text_cap > head ? text_cap - head : 0;
+    RCCHK(begin_call(h));
+    Piece<adp_row> drows; Piece<unsigned char> dids, dstr, dtext; Piece<int64_t> did_off, dmore, dmore_off; Piece<int32_t> dstr_off;
+    Piece<unsigned long long> dstate; Piece<unsigned int> dbad; Piece<uint32_t> dlen; Piece<uint64_t> doff;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        drows = w.take<adp_row>(ns); dids = w.take<unsigned char>((size_t)id_off[n] + 1); did_off = w.take<int64_t>(ns + 1);
+        dmore = w.take<int64_t>((size_t)more_off[n] + 1); dmore_off = w.take<int64_t>(ns + 1);
+        dstr = w.take<unsigned char>((size_t)str_off[n_str] + 1); dstr_off = w.take<int32_t>((size_t)n_str + 1);
+        dstate = w.take<unsigned long long>(1); dbad = w.take<unsigned int>(1); dlen = w.take<uint32_t>(ns); doff = w.take<uint64_t>(ns + 1);
+        dtext = w.take<unsigned char>(body_cap + 1);
+    }));
+    RCCHK(h2d(h, drows, rows));
+    if (id_off[n]) RCCHK(h2d(h, dids, ids, (size_t)id_off[n]));
+    RCCHK(h2d(h, did_off, id_off));
+    if (more_off[n]) RCCHK(h2d(h, dmore, more, (size_t)more_off[n]));
+    RCCHK(h2d(h, dmore_off, more_off));
+    if (str_off[n_str]) RCCHK(h2d(h, dstr, strings, (size_t)str_off[n_str]));
+    RCCHK(h2d(h, dstr_off, str_off));
+    RCCHK(zero(h, dstate));
+    RCCHK(zero(h, dbad));
+    const CsvIn in{drows, n, fail ? 1 : 0, primary, dids, did_off, dmore, dmore_off, dstr, dstr_off};
+    const unsigned nb = (unsigned)((ns + 255) / 256);
+    { Scope s(h, "k_csv_state");
+      hipLaunchKernelGGL(k_csv_state, dim3(nb), dim3(256), 0, h->stream, in, dstate.p); }
+    { Scope s(h, "k_csv_rows");
+      hipLaunchKernelGGL(k_csv_rows<false>, dim3(nb), dim3(256), 0, h->stream, in, (const unsigned long long *)dstate.p, dlen.p, dbad.p,
+                         (const uint64_t *)nullptr, (unsigned char *)nullptr, (uint64_t)0); }
+    { Scope s(h, "k_csv_scan");
+      hipLaunchKernelGGL(k_csv_scan, dim3(1), dim3(256), 0, h->stream, (const uint32_t *)dlen.p, n, doff.p); }
+    HIPCHK(hipGetLastError());
+    uint64_t body = 0;
+    unsigned int bad = 0;
+    RCCHK(d2h(h, &body, Piece<uint64_t>{doff.p + ns, 1})); // (the sum behind the offsets)
+    RCCHK(d2h(h, &bad, dbad));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *len_out = head + body;
+    *n_fallback_out = (int32_t)bad;
+    if (head + body > text_cap) return ADP_OK; // (nothing written: the caller comes again with that many bytes)
+    { Scope s(h, "k_csv_rows");
+      hipLaunchKernelGGL(k_csv_rows<true>, dim3(nb), dim3(256), 0, h->stream, in, (const unsigned long long *)dstate.p, dlen.p, dbad.p,
+                         (const uint64_t *)doff.p, dtext.p, (uint64_t)body_cap); }
+    HIPCHK(hipGetLastError());
+    memcpy(text_out, (const char *)strings + str_off[CSV_S_HEAD + (fail ? 1 : 0)], head);
+    if (body) RCCHK(d2h(h, (char *)text_out + head, dtext, (size_t)body));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
 }
 
 } // extern "C"

@@ -273,7 +273,7 @@ def load():
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
-                            + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items())):
+                            + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -517,6 +517,12 @@ TEMPLATE_PROTOTYPES = {
 # tests/test_resegment_cpu.py holds this table against its header
 RESEGMENT_PROTOTYPES: dict = {}
 
+# include/adapted_hip_csv.h (the header adapted_hip.h includes for the CSV text of one output file's rows, an extension);
+# tests/test_native_csv_cpu.py holds this table against its header
+CSV_PROTOTYPES = {
+    "adp_format_rows": "int: adp_handle* adp_row* int int int void* int64* int64* int64* void* int32* int void* uint64 uint64* int32*",
+}
+
 _VoidP = C.c_void_p  # a handle, and what an adp_handle ** / void ** out-parameter points to
 _RETURNS = {"int": C.c_int, "char*": C.c_char_p, "void*": _VoidP}
 _SCALARS = {"int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double}
@@ -663,6 +669,53 @@ def first_fail_text(code: int) -> str:
     return FAIL_REASONS[int(code)].rstrip(": ")
 
 
+def resegmented_row_log(code: int) -> str:
+    """the llr_detect_log of a row the re-segmentation made, by the fail_code of the row it replaced"""
+    return "resegmented: first pass failed (%s)" % first_fail_text(code)
+
+
+# the magnitudes below which Engine.format_csv's text is known to be pandas' (CSV_F64_BOUND, CSV_F32_BOUND of
+# adapted_amd/csrc/csv_api.h; tests/test_native_csv_cpu.py holds them against that header and against pandas)
+CSV_F64_BOUND = 2.0 ** 43
+CSV_F32_BOUND = 2.0 ** 14
+_CSV_STRINGS = None
+
+
+def csv_string_table():
+    """the texts adp_format_rows prints for a row's codes, packed (include/adapted_hip_csv.h: 69 entries) -> (uint8 bytes, int32
+    offsets [70]).  They are stated here and nowhere else: FAIL_REASONS, START_PEAK_TYPES, resegmented_row_log, the MVS check's
+    names as fail_reason_of joins them, and the two header lines from output.CSV_COLUMNS."""
+    global _CSV_STRINGS
+    if _CSV_STRINGS is None:
+        from .output import CSV_COLUMNS
+
+        texts = [FAIL_REASONS[c] or "" for c in range(16)] + [START_PEAK_TYPES[c] or "" for c in range(3)]
+        texts += [resegmented_row_log(c) if FAIL_REASONS[c] else "" for c in range(16)]
+        texts += [" ".join(n for b, n in enumerate(_MVS_NAMES) if mask >> b & 1) for mask in range(32)]
+        assert not any(ch in name for name in CSV_COLUMNS for ch in ',"\r\n')  # (a header cell that would need quotes)
+        texts += [",".join(CSV_COLUMNS) + "\n", ",".join(CSV_COLUMNS + ["fail_reason"]) + "\n"]
+        raw = [t.encode() for t in texts]
+        off = np.zeros(len(raw) + 1, dtype=np.int32)
+        np.cumsum([len(b) for b in raw], out=off[1:])
+        _CSV_STRINGS = (np.frombuffer(b"".join(raw), dtype=np.uint8), off)
+    return _CSV_STRINGS
+
+
+def rows_csv_text(rows: np.ndarray, read_ids, primary: str, fail: bool = False, consume: bool = False) -> bytes:
+    """the text of one output file as the pandas writer makes it (output.save_detected_boundaries on rows_to_results of the rows):
+    the specification of Engine.format_csv, and what it returns for a file with a value outside its bounds"""
+    import io
+
+    from .container_types import ReadResult
+    from .output import save_detected_boundaries
+
+    res = rows_to_results(rows, primary, consume=consume)
+    buf = io.StringIO()
+    save_detected_boundaries([ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
+                              for rid, r in zip(read_ids, res)], buf, save_fail_reasons=fail)
+    return buf.getvalue().encode()
+
+
 def resegment_log(reserved: np.ndarray) -> str:
     """the log line of a run: how many rows the re-segmentation kept, by the first row's fail_reason (reserved: the rows' ``reserved_``)"""
     reserved = np.asarray(reserved, dtype=np.int64)
@@ -738,7 +791,7 @@ def rows_to_results(rows: np.ndarray, primary: str, consume: bool = False) -> Li
         else:
             d.llr_detect_log = "" if primary == "llr" else None
             if res & ROW_RESEGMENTED:
-                d.llr_detect_log = "resegmented: first pass failed (%s)" % first_fail_text((res & ROW_FIRST_FAIL_MASK) >> ROW_FIRST_FAIL_SHIFT)
+                d.llr_detect_log = resegmented_row_log((res & ROW_FIRST_FAIL_MASK) >> ROW_FIRST_FAIL_SHIFT)
         d.fail_reason = fr
         out.append(d)
     return out
@@ -1427,6 +1480,70 @@ class Engine:
         self._check(self.lib.adp_dba_step(self._h, q, q_count, which, nq, Eq, t, t_count, nt, Et, int(band), flags, t_new, members,
                                           inertia, dist))
         return t_new, members, inertia, dist
+
+    # the files Engine.format_csv made, and those among them that went through the pandas writer (a value outside the bounds)
+    csv_files = 0
+    csv_fallback_files = 0
+
+    @staticmethod
+    def _overflow_open_pores(rows, pop: bool = False):
+        """the rows whose open_pores list lies in the registry (more entries than a row holds; an exception row prints none) and
+        those lists, as rows_to_results finds them"""
+        exc = (rows["fail_code"] >= 9) & (rows["fail_code"] <= 14)
+        big = np.flatnonzero((rows["n_open_pores"] > MAX_OPEN_PORES) & ~exc)
+        lists = []
+        for i in big:
+            more = (_OPEN_PORES_MORE.pop if pop else _OPEN_PORES_MORE.get)(int(rows["open_pores_more"][i]), None)
+            if more is None or more.size != int(rows["n_open_pores"][i]):
+                raise HipLibraryError("a row with %d open pores lost its overflow list (rows from a device buffer? fetch them "
+                                      "through Engine.attach_open_pores)" % int(rows["n_open_pores"][i]))
+            lists.append(more)
+        return big, lists
+
+    def format_csv_native(self, rows, read_ids, primary: str, fail: bool = False):
+        """adp_format_rows (include/adapted_hip_csv.h): the rows of ONE output file (host, ROW_DTYPE, in file order) and their read
+        ids -> (the file's text as the GPU printed it, the number of rows with a value outside the bounds within which that text
+        is the pandas writer's).  With a count other than 0 the text is not the file's: format_csv is the call that always is."""
+        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        n = int(rows.shape[0])
+        ids = [str(x).encode() for x in read_ids]
+        if rows.ndim != 1 or len(ids) != n:
+            raise ValueError("one read id per row")
+        id_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.fromiter(map(len, ids), dtype=np.int64, count=n), out=id_off[1:])
+        blob = np.frombuffer(b"".join(ids) or b"\0", dtype=np.uint8)
+        more_off, more = np.zeros(n + 1, dtype=np.int64), None
+        big, lists = self._overflow_open_pores(rows)
+        if big.size:
+            count = np.zeros(n, dtype=np.int64)
+            count[big] = [a.size for a in lists]
+            np.cumsum(count, out=more_off[1:])
+            more = np.ascontiguousarray(np.concatenate(lists), dtype=np.int64)
+        strings, str_off = csv_string_table()
+        text = np.empty(int(id_off[n]) + 640 * n + 2048, dtype=np.uint8)
+        size, bad = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.int32)
+        for _ in range(2):  # (a text longer than the first guess: once more with the length the first call reported)
+            self._check(self.lib.adp_format_rows(self._h, rows, n, int(bool(fail)), PRIMARY_CODE[primary], blob, id_off, more, more_off,
+                                                 strings, str_off, str_off.size - 1, text, text.size, size, bad))
+            if int(size[0]) <= text.size:
+                break
+            text = np.empty(int(size[0]), dtype=np.uint8)
+        return text[:int(size[0])].tobytes(), int(bad[0])
+
+    def format_csv(self, rows, read_ids, primary: str, fail: bool = False, consume: bool = False) -> bytes:
+        """the text of detected_boundaries_<k>.csv (``fail``: of failed_reads_<k>.csv) for the rows of that ONE file, byte for byte
+        what output.save_detected_boundaries writes for rows_to_results of them -- printed on the GPU, without a DetectResults or a
+        DataFrame.  A file that holds a value outside the printer's verified bounds (CSV_F64_BOUND, CSV_F32_BOUND) is not
+        approximated: it goes through that pandas writer (csv_fallback_files counts such files, csv_files all).
+        consume: as in rows_to_results"""
+        text, bad = self.format_csv_native(rows, read_ids, primary, fail)
+        self.csv_files += 1
+        if bad:
+            self.csv_fallback_files += 1
+            return rows_csv_text(rows, read_ids, primary, fail, consume=consume)
+        if consume:
+            self._overflow_open_pores(rows, pop=True)
+        return text
 
     def cnn_topk(self, scores_ptr: int, adapter_pos_ptr: int, polya_pos_ptr: int, n: int, Lo: int, k: int):
         """the k > 1 part of C3 behind given arg-maxes (tests): (cand int32 [n, k], n_peaks int32 [n]); device pointers in"""

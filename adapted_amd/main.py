@@ -66,6 +66,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "level step or a long start peak in front of the adapter) is segmented once more from its first poly(A) end and "
                         "validated from its first adapter end; boundaries that pass replace the failed row, whose llr_detect_log says so "
                         "(untuned, nothing validated on real data).  Not with --flag_truncated or mvs_detect_overwrite")
+    d.add_argument("--native_csv", action="store_true",
+                   help="(extension) print detected_boundaries_<k>.csv and failed_reads_<k>.csv on the GPU from the result rows, without "
+                        "pandas: the same bytes (a file that holds a value the GPU printer is not verified for goes through pandas, "
+                        "and the log says how many did).  Every primary, every other option, several ranks")
     d.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK or 0)")
     d.add_argument("--int16_ingest", action="store_true",
                    help="(extension) move raw int16 ADC samples + calibration to the GPU and compute pA there "
@@ -174,6 +178,7 @@ class _Writer:
         self.batch = batch
         self.n = {True: 0, False: 0}
         self.fp_dir, self.fp_width, self.barcodes = None, 0, False
+        self.csv_engine, self.csv_primary = None, None
 
     def enable_fingerprints(self, run_dir: str, width: int, barcodes: bool = False):
         """every detected_boundaries_<k>.csv gets a fingerprints/fingerprints_<k>.npz beside it (read_id, count, status, lengths,
@@ -181,6 +186,36 @@ class _Writer:
         the `fingerprint` record its ReadResult carries (fingerprint_records).  Distances are written in full precision."""
         self.fp_dir, self.fp_width, self.barcodes = os.path.join(run_dir, "fingerprints"), int(width), bool(barcodes)
         os.makedirs(self.fp_dir, exist_ok=True)
+
+    def enable_native_csv(self, engine, primary: str):
+        """detected_boundaries_<k>.csv and failed_reads_<k>.csv are printed on the GPU from the rows themselves
+        (engine.format_csv: the same bytes, no DetectResults, ReadResult or DataFrame): the writer takes `add_rows` instead of
+        `add` and keeps pending rows as ROW_DTYPE arrays -- a file's text depends on ALL its rows (pandas picks a column's type
+        from the whole file) and a file's rows can come from two detect calls, so a file is formatted when it is flushed.
+        engine: an Engine of the writer's own (the writer runs beside the detect calls, and a handle serves one thread at a time)"""
+        self.csv_engine, self.csv_primary = engine, primary
+        self.pending = {True: ([], [], []), False: ([], [], [])}  # per kind: row arrays, read ids, extension records
+
+    def add_rows(self, rows: np.ndarray, read_ids, extras=None):
+        """the rows of a detect call (with enable_native_csv).  extras: None, or per read an object that carries the `polya_length`
+        / `fingerprint` record of the extension files, as a ReadResult does in `add`"""
+        passed = (rows["success"] != 0) & ~((rows["fail_code"] >= 9) & (rows["fail_code"] <= 14))  # ReadResult.success of rows_to_results
+        for ok in (True, False):
+            idx = np.flatnonzero(passed == ok)
+            chunks, ids, ext = self.pending[ok]
+            chunks.append(rows[idx])
+            ids.extend(str(read_ids[i]) for i in idx)
+            ext.extend(extras[i] if extras is not None else None for i in idx)
+            while len(ids) >= self.batch:
+                held = np.concatenate(chunks)
+                self._flush_rows(ok, held[: self.batch], ids[: self.batch], ext[: self.batch])
+                chunks[:] = [held[self.batch:]]
+                del ids[: self.batch], ext[: self.batch]
+
+    def _flush_rows(self, ok: bool, rows: np.ndarray, ids, ext):
+        with open(os.path.join(self.dirs[ok], "%s_%d.csv" % (self.names[ok], self.bidx[ok])), "wb") as fh:
+            fh.write(self.csv_engine.format_csv(rows, ids, self.csv_primary, fail=not ok, consume=True))
+        self._flush_extensions(ok, ext)
 
     def add(self, results: List[ReadResult]):
         for r in results:
@@ -193,6 +228,10 @@ class _Writer:
     def _flush(self, ok: bool, items: List[ReadResult]):
         fn = os.path.join(self.dirs[ok], "%s_%d.csv" % (self.names[ok], self.bidx[ok]))
         save_detected_boundaries(items, fn, save_fail_reasons=not ok)
+        self._flush_extensions(ok, items)
+
+    def _flush_extensions(self, ok: bool, items):
+        """the extension files beside a flushed CSV file, from the records its reads carry; then the file counts"""
         if ok and self.polya_dir:
             pd.DataFrame([r.polya_length for r in items], columns=POLYA_LENGTH_COLUMNS).round(3).to_csv(
                 os.path.join(self.polya_dir, "polya_length_%d.csv" % self.bidx[ok]), index=False)
@@ -212,7 +251,12 @@ class _Writer:
 
     def close(self):
         for ok in (True, False):
-            if self.pending[ok]:
+            if self.csv_engine is not None:
+                chunks, ids, ext = self.pending[ok]
+                if ids:
+                    self._flush_rows(ok, np.concatenate(chunks), ids, ext)
+                self.pending[ok] = ([], [], [])
+            elif self.pending[ok]:
                 self._flush(ok, self.pending[ok])
                 self.pending[ok] = []
 
@@ -412,9 +456,10 @@ def list_truncated(directory: str) -> int:
 
 
 def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, batch_out, device, start_peak=False,
-               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, llr_resegment=False, adapter_front=None,
-               fingerprints=None, polya_length=None, adapter_nt=None, event_params=None):
-    """llr_resegment: --llr_resegment (the LLR primary's detect calls re-segment the reads they fail; everything below sees the final rows);
+               bidx_pass=0, bidx_fail=0, int16_ingest=False, second_opinion=None, flag_truncated=False, llr_resegment=False, native_csv=False,
+               adapter_front=None, fingerprints=None, polya_length=None, adapter_nt=None, event_params=None):
+    """native_csv: --native_csv (rank 0 prints the two reference files on the GPU from the rows: _Writer.enable_native_csv);
+    llr_resegment: --llr_resegment (the LLR primary's detect calls re-segment the reads they fail; everything below sees the final rows);
     adapter_front: None, or an adapter_front.AdapterFrontParams (--adapter_front: the adapter's front trimmed on the final rows of
     every detect call, ahead of the two below; its min_adapter_len is set here to core.min_obs_adapter);
     fingerprints: None, or (E, templates or None, band) (--fingerprints: fingerprints/fingerprints_<k>.npz and, with templates,
@@ -439,6 +484,10 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
               else _Writer(run_dir, batch_out, bidx_pass, bidx_fail)) if rank == 0 else None
     if fingerprints and writer is not None:
         writer.enable_fingerprints(run_dir, fingerprints[0], barcodes=fingerprints[1] is not None)
+    csv_engine = None
+    if native_csv and writer is not None:  # (an engine of the writer's own: it formats beside the detect calls)
+        csv_engine = lib.Engine(spc, 1, m, device=device)
+        writer.enable_native_csv(csv_engine, primary)
     t0 = time.time()
     my_rows, my_ids, my_ord = [], [], []
     dropped_text = {1: "MAD normalization failed: scale is 0", 2: "a read has no signal after min_obs_adapter"}
@@ -498,6 +547,20 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_front[0] += int(((rows["reserved_"] & lib.ROW_ADAPTER_FRONT) != 0).sum())
             n_reval[0] += int(((rows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
             reseg_marks.append(rows["reserved_"][(rows["reserved_"] & lib.ROW_RESEGMENTED) != 0])
+            if csv_engine is not None:
+                extras = None
+                if events is not None or fp is not None:  # the extension files' records travel beside the rows
+                    import types
+
+                    extras = [types.SimpleNamespace() for _ in range(len(rows))]
+                    if events is not None:
+                        for x, rec in zip(extras, polya_length_records(tagged[:, 0], lib.rows_to_results(rows, primary), events, polya_length, adapter_nt)):
+                            x.polya_length = rec
+                    if fp is not None:
+                        for x, rec in zip(extras, fingerprint_records(tagged[:, 0], fp, fingerprints[1].names if fingerprints[1] is not None else None)):
+                            x.fingerprint = rec
+                writer.add_rows(rows, tagged[:, 0], extras)
+                return
             res = lib.rows_to_results(rows, primary, consume=True)
             out = [ReadResult(read_id=str(rid), success=r.success, fail_reason=r.fail_reason, detect_results=r)
                    for rid, r in zip(tagged[:, 0], res)]
@@ -533,11 +596,18 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             n_reval[0] += int(((allrows["reserved_"] & lib.ROW_REVALIDATED) != 0).sum())
             reseg_marks.append(allrows["reserved_"][(allrows["reserved_"] & lib.ROW_RESEGMENTED) != 0])
             n_rejected[0] += sum(int(part[2]) for part in lists if len(part) > 2)
-            res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
-            writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
-                        for i, r in zip(order, res)])
+            if csv_engine is not None:
+                writer.add_rows(allrows[order], [ids[i] for i in order])
+            else:
+                res = lib.rows_to_results(allrows[order], primary, consume=True)  # stream order: the files read like a one-GPU run's
+                writer.add([ReadResult(read_id=str(ids[i]), success=r.success, fail_reason=r.fail_reason, detect_results=r)
+                            for i, r in zip(order, res)])
     if writer is not None:
-        writer.close()
+        try:
+            writer.close()
+        finally:
+            if csv_engine is not None:
+                csv_engine.close()
         tot = writer.n[True] + writer.n[False]
         logging.info("Processed %d reads in %.2f s (%.0f reads/s on %d GPU(s))", tot, time.time() - t0,
                      tot / max(time.time() - t0, 1e-9), ws)
@@ -553,6 +623,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
                 if not multi:
                     n_rejected[0] = int(getattr(pipe, "front_rejected", 0))
                 logging.info("Adapter front re-validated: %d kept, %d trims rejected by validation", n_reval[0], n_rejected[0])
+        if csv_engine is not None:
+            logging.info("native CSV: %d files, %d through pandas", csv_engine.csv_files, csv_engine.csv_fallback_files)
         if llr_resegment:
             logging.info(lib.resegment_log(np.concatenate(reseg_marks) if reseg_marks else np.zeros(0, dtype=np.int32)))
     if multi:
@@ -634,6 +706,7 @@ def main(argv=None):
                start_peak=getattr(args, "start_peak", False), bidx_pass=bp, bidx_fail=bf,
                int16_ingest=getattr(args, "int16_ingest", False), second_opinion=getattr(args, "second_opinion", None),
                flag_truncated=getattr(args, "flag_truncated", False), adapter_front=front, llr_resegment=getattr(args, "llr_resegment", False),
+               native_csv=getattr(args, "native_csv", False),
                fingerprints=(args.fingerprints, templates, getattr(args, "dtw_band", None)) if getattr(args, "fingerprints", None) is not None else None,
                polya_length=getattr(args, "polya_length", None),
                adapter_nt=getattr(args, "adapter_nt", None), event_params=getattr(args, "event_params", None))

@@ -582,6 +582,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * bits and its counters in a header of its own; it declares no entry point (adapted_amd/lib.py, RESEGMENT_PROTOTYPES, is empty). */
 #include "adapted_hip_resegment.h"
 
+/* The rows of one output file to that file's CSV text on the GPU -- adp_format_rows, an extension --: a header of its own, with its
+ * prototype table in adapted_amd/lib.py, CSV_PROTOTYPES. */
+#include "adapted_hip_csv.h"
+
 /* Per-kernel timing of the LAST detect call, measured with HIP events on the handle's stream.
  * Enable with adp_set_profiling(h, 1).  names_out: up to cap pointers to static strings. */
 int adp_set_profiling(adp_handle *h, int on);
