@@ -196,6 +196,21 @@ def _fingerprint_files(paths):
     return out
 
 
+def _fingerprint_file(f, width=None):
+    """one fingerprints_<k>.npz, checked -> (read ids, fingerprints float64 [n, E], counts int32 [n]); ``width``: the E of the files
+    before it.  ValueError: not such a file, or another width"""
+    try:
+        with np.load(f, allow_pickle=False) as z:
+            ids, fp, c = [str(s) for s in z["read_id"]], np.asarray(z["fingerprints"], dtype=np.float64), np.asarray(z["count"], dtype=np.int32)
+    except (OSError, KeyError, ValueError, EOFError) as e:
+        raise ValueError("not a fingerprint file (%s): %s" % (f, e)) from e
+    if fp.ndim != 2 or c.shape != (fp.shape[0],) or len(ids) != fp.shape[0]:
+        raise ValueError("not a fingerprint file (%s): read_id [n], count [n] and fingerprints [n, E] are needed" % f)
+    if width is not None and fp.shape[1] != width:
+        raise ValueError("fingerprint files of different widths (%d, %d in %s)" % (width, fp.shape[1], f))
+    return ids, fp, c
+
+
 def read_labels(labels_csv, read_id_col: str = "read_id", label_col: str = "barcode") -> dict:
     """read id -> label from a CSV with a header; rows with an empty label are left out.  ValueError: a file that cannot be read,
     a column that is not there"""
@@ -222,15 +237,7 @@ def labelled_fingerprints(paths, labels_csv, read_id_col: str = "read_id", label
     label_of = read_labels(labels_csv, read_id_col, label_col)
     fps, cnts, labs, seen, total = [], [], [], set(), 0
     for f in _fingerprint_files(paths):
-        try:
-            with np.load(f, allow_pickle=False) as z:
-                ids, fp, c = [str(s) for s in z["read_id"]], np.asarray(z["fingerprints"], dtype=np.float64), np.asarray(z["count"], dtype=np.int32)
-        except (OSError, KeyError, ValueError, EOFError) as e:
-            raise ValueError("not a fingerprint file (%s): %s" % (f, e)) from e
-        if fp.ndim != 2 or c.shape != (fp.shape[0],) or len(ids) != fp.shape[0]:
-            raise ValueError("not a fingerprint file (%s): read_id [n], count [n] and fingerprints [n, E] are needed" % f)
-        if fps and fp.shape[1] != fps[0].shape[1]:
-            raise ValueError("fingerprint files of different widths (%d, %d in %s)" % (fps[0].shape[1], fp.shape[1], f))
+        ids, fp, c = _fingerprint_file(f, fps[0].shape[1] if fps else None)
         keep = [i for i, rid in enumerate(ids) if rid in label_of]
         total += len(ids)
         seen.update(ids[i] for i in keep)

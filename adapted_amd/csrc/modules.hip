@@ -1,4 +1,4 @@
-// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints, the template building, the adapter-front post-pass and the CSV text of a file's rows): their kernels and entry points, a
+// modules.hip -- the reference-module drop-ins (adp_c_llr_*, adp_llr_*, adp_mvs_*, the signal statistics, the start peak, the adapter start, the event segmentation, the event fingerprints, the template building, the clustering of fingerprints, the adapter-front post-pass and the CSV text of a file's rows): their kernels and entry points, a
 // translation unit of their own, so that nothing here can move the code the compiler makes for the detect path's kernels.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,7 @@
 #include "events_api.h"
 #include "fingerprint_api.h"
 #include "dtw_align_api.h"
+#include "dtw_cluster_api.h"
 #include "adapter_front.h"
 #include "csv_api.h"
 
@@ -1034,6 +1035,190 @@ int adp_dba_step(adp_handle *h, const double *q, const int32_t *q_count, const i
     if (!t_new_out || !members_out || !inertia_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     return da_run(h, q, q_count, which, nq, Eq, t, t_count, nt, Et, band, flags,
                   DaOut{dist_out, nullptr, nullptr, nullptr, nullptr, t_new_out, members_out, inertia_out});
+}
+
+} // extern "C"
+
+// ---- clustering fingerprints without labels: the all-pairs DTW matrix, BUILD, k-medoids, the silhouette (an extension;
+// dtw_cluster_api.h)
+
+// a [n, n] matrix that is device memory with ADP_IN_DEVICE, else staged into `piece`; refused where an entry is NaN, negative or
+// infinite (k_cl_check: on the device, before anything else; the handle stays usable)
+static int cl_matrix_in(adp_handle *h, int flags, const double *dist, size_t n, Piece<double> piece, Piece<int32_t> dflag, const double **dev)
+{
+    RCCHK(stage_in(h, flags, dist, piece, dev));
+    RCCHK(zero(h, dflag));
+    const size_t count = n * n, blocks = (count + 255) / 256;
+    { Scope s(h, "k_cl_check");
+      hipLaunchKernelGGL(k_cl_check, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, h->stream, *dev, count, dflag.p); }
+    HIPCHK(hipGetLastError());
+    int32_t flag = 0;
+    RCCHK(d2h(h, &flag, dflag));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (flag) { g_err = "the distance matrix holds a NaN, a negative value or an infinity"; return ADP_ERR_INVALID; }
+    return ADP_OK;
+}
+
+static bool cl_sizes_ok(int n, int k) { return n >= 1 && n <= CL_NMAX && k >= 1 && k <= CL_KMAX && k <= n; }
+
+extern "C" {
+
+int adp_dtw_pairwise(adp_handle *h, const double *q, const int32_t *q_count, int n, int E, int band, int flags, double *dist_out)
+{
+    if (!h || !q || !q_count || !dist_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (E < 1 || E > FP_EMAX) { g_err = "E must lie in [1, 512]"; return ADP_ERR_INVALID; }
+    if (n < 1 || n > CL_NMAX) { g_err = "n must lie in [1, 16384]"; return ADP_ERR_INVALID; }
+    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
+    long long mib;
+    RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
+    // scratch is needed for a host matrix only: the whole matrix where it fits the budget (every pair once, both entries written),
+    // else bands of its rows (a pair once per band its rows lie in: the same bits, the recurrence being symmetric)
+    const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
+    const size_t ns = n;
+    size_t rows = ((size_t)mib << 20) / (ns * 8);
+    if (rows < 1) rows = 1;
+    const bool whole = out_dev || rows >= ns;
+    if (whole) rows = ns;
+    RCCHK(begin_call(h));
+    Piece<double> s_q, dmat; Piece<int32_t> s_qc;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_q = w.take<double>(ns * E, !(flags & ADP_IN_DEVICE)); s_qc = w.take<int32_t>(ns, !(flags & ADP_IN_DEVICE));
+        dmat = w.take<double>(rows * ns, !out_dev);
+    }));
+    const double *dq; const int32_t *dqc;
+    RCCHK(stage_in(h, flags, q, s_q, &dq));
+    RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
+    double *dout = out_dev ? dist_out : dmat.p;
+    const int C = (E + 63) / 64;
+    const int partners = whole ? n / 2 : n - 1;
+    const int nchunks = partners < 1 ? 1 : (partners + CL_STRIP - 1) / CL_STRIP;
+    for (size_t r0 = 0; r0 < ns; r0 += rows) {
+        const size_t nb = ns - r0 < rows ? ns - r0 : rows;
+        const dim3 grid((unsigned)(nb * nchunks)), block(64);
+        { Scope s(h, "k_dtw_pairs");
+          if (C <= 1) hipLaunchKernelGGL(k_dtw_pairs<1>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
+          else if (C <= 2) hipLaunchKernelGGL(k_dtw_pairs<2>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
+          else if (C <= 4) hipLaunchKernelGGL(k_dtw_pairs<4>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
+          else hipLaunchKernelGGL(k_dtw_pairs<8>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout); }
+        if (!out_dev) RCCHK(d2h(h, dist_out + r0 * ns, dmat, nb * ns));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_kmedoids_build(adp_handle *h, const double *dist, int n, int kmax, int flags, int32_t *medoids_out, double *gain_out)
+{
+    if (!h || !dist || !medoids_out || !gain_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!cl_sizes_ok(n, kmax)) { g_err = "need 1 <= n <= 16384 and 1 <= kmax <= min(n, 4096)"; return ADP_ERR_INVALID; }
+    const size_t ns = n, ks = kmax;
+    RCCHK(begin_call(h));
+    Piece<double> s_d, dvals, ddmin, dgain; Piece<int32_t> dflag, dismed, dmed;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_d = w.take<double>(ns * ns, !(flags & ADP_IN_DEVICE)); dflag = w.take<int32_t>(1);
+        dvals = w.take<double>(ns); ddmin = w.take<double>(ns); dismed = w.take<int32_t>(ns);
+        dmed = w.take<int32_t>(ks); dgain = w.take<double>(ks);
+    }));
+    const double *dd;
+    RCCHK(cl_matrix_in(h, flags, dist, ns, s_d, dflag, &dd));
+    RCCHK(zero(h, dismed));
+    for (int c = 0; c < kmax; c++) {
+        { Scope s(h, "k_cl_rowsum");
+          if (c == 0) hipLaunchKernelGGL(k_cl_rowsum<false>, dim3((unsigned)n), dim3(64), 0, h->stream, dd, n, ddmin.p, dvals.p);
+          else hipLaunchKernelGGL(k_cl_rowsum<true>, dim3((unsigned)n), dim3(64), 0, h->stream, dd, n, ddmin.p, dvals.p); }
+        { Scope s(h, "k_cl_pick");
+          hipLaunchKernelGGL(k_cl_pick, dim3(1), dim3(256), 0, h->stream, dd, n, c, dvals.p, dismed.p, dmed.p, dgain.p, ddmin.p); }
+    }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, medoids_out, dmed));
+    RCCHK(d2h(h, gain_out, dgain));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+int adp_kmedoids(adp_handle *h, const double *dist, int n, int k, int max_iter, int flags, int32_t *medoids_io, int32_t *assign_out,
+                 double *sums_out, double *cost_out, int32_t *iters_out)
+{
+    if (!h || !dist || !medoids_io || !assign_out || !cost_out || !iters_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!cl_sizes_ok(n, k)) { g_err = "need 1 <= n <= 16384 and 1 <= k <= min(n, 4096)"; return ADP_ERR_INVALID; }
+    if (max_iter < 0 || max_iter > (1 << 20)) { g_err = "max_iter must lie in [0, 2^20]"; return ADP_ERR_INVALID; }
+    {
+        std::vector<char> seen(n, 0);
+        for (int c = 0; c < k; c++) {
+            const int m = medoids_io[c];
+            if (m < 0 || m >= n || seen[m]) { g_err = "the medoids must be k different rows"; return ADP_ERR_INVALID; }
+            seen[m] = 1;
+        }
+    }
+    const size_t ns = n, ks = k;
+    RCCHK(begin_call(h));
+    Piece<double> s_d, dnear, dsums, dcost; Piece<int32_t> dflag, dmed, dnew, dassign, dchanged;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_d = w.take<double>(ns * ns, !(flags & ADP_IN_DEVICE)); dflag = w.take<int32_t>(1);
+        dmed = w.take<int32_t>(ks); dnew = w.take<int32_t>(ks); dassign = w.take<int32_t>(ns); dnear = w.take<double>(ns);
+        dsums = w.take<double>(ns * ks); dcost = w.take<double>((size_t)max_iter + 1); dchanged = w.take<int32_t>(1);
+    }));
+    const double *dd;
+    RCCHK(cl_matrix_in(h, flags, dist, ns, s_d, dflag, &dd));
+    RCCHK(h2d(h, dmed, medoids_io));
+    int it = 0;
+    for (;;) {
+        { Scope s(h, "k_cl_assign");
+          hipLaunchKernelGGL(k_cl_assign, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, dd, n, dmed.p, k, dassign.p, dnear.p); }
+        { Scope s(h, "k_cl_total");
+          hipLaunchKernelGGL(k_cl_total, dim3(1), dim3(64), 0, h->stream, dnear.p, n, dcost.p + it); }
+        if (it == max_iter && !sums_out) break;
+        { Scope s(h, "k_cl_sums");
+          hipLaunchKernelGGL(k_cl_sums, dim3((unsigned)n), dim3(64), 0, h->stream, dd, n, dassign.p, k, dsums.p); }
+        if (it == max_iter) break;
+        RCCHK(zero(h, dchanged));
+        { Scope s(h, "k_cl_update");
+          hipLaunchKernelGGL(k_cl_update, dim3((unsigned)k), dim3(256), 0, h->stream, dsums.p, n, k, dassign.p, dmed.p, dnew.p, dchanged.p); }
+        HIPCHK(hipGetLastError());
+        int32_t changed = 0;
+        RCCHK(d2h(h, &changed, dchanged));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (!changed) break;
+        std::swap(dmed, dnew);
+        it++;
+    }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, medoids_io, dmed));
+    RCCHK(d2h(h, assign_out, dassign));
+    if (sums_out) RCCHK(d2h(h, sums_out, dsums));
+    RCCHK(d2h(h, cost_out, dcost, (size_t)it + 1));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *iters_out = it;
+    return ADP_OK;
+}
+
+int adp_silhouette(adp_handle *h, const double *dist, int n, const int32_t *assign, int k, int flags, double *sil_out)
+{
+    if (!h || !dist || !assign || !sil_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!cl_sizes_ok(n, k)) { g_err = "need 1 <= n <= 16384 and 1 <= k <= min(n, 4096)"; return ADP_ERR_INVALID; }
+    if (!all_in<int32_t>(assign, n, 0, k - 1)) { g_err = "need 0 <= assign < k for every row"; return ADP_ERR_INVALID; }
+    std::vector<int32_t> size(k, 0);
+    for (int i = 0; i < n; i++) size[assign[i]]++;
+    for (int c = 0; c < k; c++) if (!size[c]) { g_err = "a cluster without a member"; return ADP_ERR_INVALID; }
+    const size_t ns = n, ks = k;
+    RCCHK(begin_call(h));
+    Piece<double> s_d, dsums, dsil; Piece<int32_t> dflag, dassign, dsize;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_d = w.take<double>(ns * ns, !(flags & ADP_IN_DEVICE)); dflag = w.take<int32_t>(1);
+        dassign = w.take<int32_t>(ns); dsize = w.take<int32_t>(ks); dsums = w.take<double>(ns * ks); dsil = w.take<double>(ns);
+    }));
+    const double *dd;
+    RCCHK(cl_matrix_in(h, flags, dist, ns, s_d, dflag, &dd));
+    RCCHK(h2d(h, dassign, assign));
+    RCCHK(h2d(h, dsize, size.data()));
+    { Scope s(h, "k_cl_sums");
+      hipLaunchKernelGGL(k_cl_sums, dim3((unsigned)n), dim3(64), 0, h->stream, dd, n, dassign.p, k, dsums.p); }
+    { Scope s(h, "k_cl_sil");
+      hipLaunchKernelGGL(k_cl_sil, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, dsums.p, n, k, dassign.p, dsize.p, dsil.p); }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, sil_out, dsil));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
 }
 
 } // extern "C"

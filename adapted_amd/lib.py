@@ -273,7 +273,8 @@ def load():
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
-                            + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())):
+                            + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())
+                            + list(CLUSTER_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -511,6 +512,18 @@ TEMPLATE_PROTOTYPES = {
     "adp_dtw_align": "int: adp_handle* double* int32* int32* int int double* int32* int int int int double* int32* int32* int32* double*",
     "adp_dba_step": "int: adp_handle* double* int32* int32* int int double* int32* int int int int double* int32* double* double*",
 }
+
+# include/adapted_hip_clusters.h (the header adapted_hip.h includes for the clustering of fingerprints without labels -- the
+# all-pairs DTW matrix, PAM's BUILD, alternating k-medoids, the silhouette --, an extension); tests/test_clusters_cpu.py holds this
+# table against its header
+CLUSTER_PROTOTYPES = {
+    "adp_dtw_pairwise": "int: adp_handle* double* int32* int int int int double*",
+    "adp_kmedoids_build": "int: adp_handle* double* int int int int32* double*",
+    "adp_kmedoids": "int: adp_handle* double* int int int int int32* int32* double* double* int32*",
+    "adp_silhouette": "int: adp_handle* double* int int32* int int double*",
+}
+CLUSTER_MAX_ROWS = 16384  # CL_NMAX of adapted_amd/csrc/dtw_cluster_api.h
+CLUSTER_MAX_K = 4096  # CL_KMAX
 
 # include/adapted_hip_resegment.h (the header adapted_hip.h includes for the re-segmentation of reads the LLR primary fails, an
 # extension): a flag of adp_detect_llr, row bits and a selector of adp_debug_fetch -- it declares no entry point;
@@ -1480,6 +1493,69 @@ class Engine:
         self._check(self.lib.adp_dba_step(self._h, q, q_count, which, nq, Eq, t, t_count, nt, Et, int(band), flags, t_new, members,
                                           inertia, dist))
         return t_new, members, inertia, dist
+
+    def dtw_pairwise(self, q, q_count, band: int = 0, n: Optional[int] = None, E: Optional[int] = None, out_ptr: Optional[int] = None):
+        """adp_dtw_pairwise: fingerprints float64 [n, E] with their counts (host arrays, or two device pointers with ``n`` and
+        ``E``) -> the symmetric DTW matrix float64 [n, n]; with ``out_ptr`` (device memory of n * n doubles) it is written there
+        and None is returned"""
+        if isinstance(q, int):
+            if n is None or E is None or not isinstance(q_count, int):
+                raise ValueError("device fingerprints need a device pointer to their counts, n and E")
+            _check_runtime_once_torch_is_here()
+            flags, n, E = ADP_IN_DEVICE, int(n), int(E)
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.ndim != 2:
+                raise ValueError("fingerprints: a float64 [n, E] array")
+            flags, (n, E) = 0, q.shape
+            q_count = self._per_read(q_count, n, "q_count")
+        if n == 0:
+            raise ValueError("no fingerprints")
+        out = np.zeros((n, n)) if out_ptr is None else None
+        self._check(self.lib.adp_dtw_pairwise(self._h, q, q_count, n, E, int(band), flags | (0 if out_ptr is None else ADP_OUT_DEVICE),
+                                              out if out_ptr is None else int(out_ptr)))
+        return out
+
+    @staticmethod
+    def _matrix_in(dist, n):
+        """a distance matrix: a float64 [n, n] host array, or a device pointer with ``n`` -> (dist, n, flags)"""
+        if isinstance(dist, int):
+            if n is None:
+                raise ValueError("a device matrix needs n")
+            _check_runtime_once_torch_is_here()
+            return dist, int(n), ADP_IN_DEVICE
+        dist = np.ascontiguousarray(dist, dtype=np.float64)
+        if dist.ndim != 2 or dist.shape[0] != dist.shape[1] or dist.shape[0] == 0:
+            raise ValueError("distances: a float64 [n, n] array")
+        return dist, dist.shape[0], 0
+
+    def kmedoids_build(self, dist, kmax: int, n: Optional[int] = None):
+        """adp_kmedoids_build: PAM's BUILD on a distance matrix (host [n, n], or a device pointer with ``n``) -> (medoids int32
+        [kmax]: the first K are BUILD's answer for every K <= kmax; gain float64 [kmax])"""
+        dist, n, flags = self._matrix_in(dist, n)
+        kmax = int(kmax)
+        medoids, gain = np.zeros(max(kmax, 0), dtype=np.int32), np.zeros(max(kmax, 0))
+        self._check(self.lib.adp_kmedoids_build(self._h, dist, n, kmax, flags, medoids, gain))
+        return medoids, gain
+
+    def kmedoids(self, dist, medoids, max_iter: int = 50, n: Optional[int] = None, want_sums: bool = False):
+        """adp_kmedoids: alternating k-medoids from ``medoids`` int32 [k] -> a dict: medoids int32 [k], assign int32 [n], sums
+        float64 [n, k] (None without ``want_sums``), cost float64 [iters + 1], iters"""
+        dist, n, flags = self._matrix_in(dist, n)
+        med = np.array(medoids, dtype=np.int32).reshape(-1)
+        k, max_iter = med.size, int(max_iter)
+        assign, sums = np.zeros(n, dtype=np.int32), (np.zeros((n, k)) if want_sums else None)
+        cost, iters = np.zeros(max(max_iter, 0) + 1), np.zeros(1, dtype=np.int32)
+        self._check(self.lib.adp_kmedoids(self._h, dist, n, k, max_iter, flags, med, assign, sums, cost, iters))
+        return {"medoids": med, "assign": assign, "sums": sums, "cost": cost[:int(iters[0]) + 1].copy(), "iters": int(iters[0])}
+
+    def silhouette(self, dist, assign, k: int, n: Optional[int] = None):
+        """adp_silhouette: the silhouette float64 [n] of every row under ``assign`` int32 [n] with values in [0, k)"""
+        dist, n, flags = self._matrix_in(dist, n)
+        assign = self._per_read(assign, n, "assign")
+        sil = np.zeros(n)
+        self._check(self.lib.adp_silhouette(self._h, dist, n, assign, int(k), flags, sil))
+        return sil
 
     # the files Engine.format_csv made, and those among them that went through the pandas writer (a value outside the bounds)
     csv_files = 0

@@ -45,6 +45,12 @@ def build_parser() -> argparse.ArgumentParser:
     from .barcode_templates import add_arguments
 
     add_arguments(b)
+    k = sub.add_parser("clusters", help="(extension) Find barcode clusters in the fingerprints of a run made with --fingerprints, without "
+                                        "labels: pairwise DTW, k-medoids and the silhouette on the GPU; writes templates for detect "
+                                        "--barcode_templates (untuned, nothing validated on real data).")
+    from .clusters import add_arguments as add_cluster_arguments
+
+    add_cluster_arguments(k)
     d.add_argument("-i", "--input", type=str, nargs="+", required=True, help="input files / directories (.pod5 or .npz bundles)")
     d.add_argument("-o", "--output", type=str, default=None)
     d.add_argument("--config", type=str, default=None, help="config TOML (overrides --chemistry)")
@@ -641,6 +647,11 @@ def main(argv=None):
         from .barcode_templates import templates_command
 
         templates_command(args)
+        return
+    if args.mode == "clusters":
+        from .clusters import clusters_command
+
+        clusters_command(args)
         return
     if args.mode == "continue":
         run_dir = args.continue_from

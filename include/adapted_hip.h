@@ -578,6 +578,11 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * and adp_dba_step, an extension --: a header of its own, with its prototype table in adapted_amd/lib.py, TEMPLATE_PROTOTYPES. */
 #include "adapted_hip_templates.h"
 
+/* Clustering fingerprints without labels -- the all-pairs DTW matrix, PAM's BUILD, alternating k-medoids and the silhouette, on a
+ * matrix that stays on the device; an extension --: a header of its own, with its prototype table in adapted_amd/lib.py,
+ * CLUSTER_PROTOTYPES. */
+#include "adapted_hip_clusters.h"
+
 /* Re-segmentation of reads the LLR primary fails -- ADP_LLR_RESEGMENT, a flag of adp_detect_llr, an extension --: its rule, its row
  * bits and its counters in a header of its own; it declares no entry point (adapted_amd/lib.py, RESEGMENT_PROTOTYPES, is empty). */
 #include "adapted_hip_resegment.h"
