@@ -21,6 +21,7 @@
 #include "fingerprint_api.h"
 #include "dtw_align_api.h"
 #include "dtw_cluster_api.h"
+#include "dtw_knn_api.h"
 #include "adapter_front.h"
 #include "csv_api.h"
 
@@ -1217,6 +1218,92 @@ int adp_silhouette(adp_handle *h, const double *dist, int n, const int32_t *assi
       hipLaunchKernelGGL(k_cl_sil, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, dsums.p, n, k, dassign.p, dsize.p, dsil.p); }
     HIPCHK(hipGetLastError());
     RCCHK(d2h(h, sil_out, dsil));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return ADP_OK;
+}
+
+} // extern "C"
+
+// ---- the k nearest labelled fingerprints of every query under DTW, pairs abandoned behind a lower bound (an extension;
+// dtw_knn_api.h)
+
+// a number the environment may hold under `name` (`value`: its getenv, read per call): `dflt` without it, else within [lo, hi]
+static int knn_env(const char *name, const char *value, long long dflt, long long lo, long long hi, bool pow2, long long *out)
+{
+    *out = value ? atoll(value) : dflt;
+    if (value && (*out < lo || *out > hi || (pow2 && (*out & (*out - 1))))) {
+        g_err = std::string(name) + " must " + (pow2 ? "be a power of two and " : "") + "lie in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
+        return ADP_ERR_INVALID;
+    }
+    return ADP_OK;
+}
+
+extern "C" {
+
+int adp_dtw_knn(adp_handle *h, const double *q, const int32_t *q_count, int nq, int Eq, const double *r, const int32_t *r_count, int nr,
+                int Er, int k, int band, int flags, const int32_t *exclude, int32_t *idx_out, double *dist_out, int64_t *work_out)
+{
+    if (!h || !q || !q_count || !r || !r_count || !idx_out || !dist_out || nq < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (Eq < 1 || Eq > FP_EMAX || Er < 1 || Er > FP_EMAX) { g_err = "Eq and Er must lie in [1, 512]"; return ADP_ERR_INVALID; }
+    if (k < 1 || k > KNN_KMAX) { g_err = "k must lie in [1, 32]"; return ADP_ERR_INVALID; }
+    if (nr < 1 || nr > KNN_NR_MAX) { g_err = "nr must lie in [1, 262144]"; return ADP_ERR_INVALID; }
+    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
+    for (int j = 0; j < nr; j++) {
+        if (r_count[j] < 1 || r_count[j] > Er) { g_err = "need 1 <= r_count <= Er for every reference"; return ADP_ERR_INVALID; }
+        for (int e = 0; e < r_count[j]; e++)
+            if (!std::isfinite(r[(size_t)j * Er + e])) { g_err = "reference values inside their count must be finite"; return ADP_ERR_INVALID; }
+    }
+    if (exclude && !all_in<int32_t>(exclude, nq, -1, nr - 1)) { g_err = "every exclude must lie in [-1, nr)"; return ADP_ERR_INVALID; }
+    long long mib, seg_env, period;
+    RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
+    RCCHK(knn_env("ADP_KNN_SEGMENT_REFS", getenv("ADP_KNN_SEGMENT_REFS"), 0, 1, KNN_NR_MAX, false, &seg_env));
+    RCCHK(knn_env("ADP_KNN_CHECK_PERIOD", getenv("ADP_KNN_CHECK_PERIOD"), KNN_CHECK_PERIOD, 1, 64, true, &period));
+    // the segments of a query's references, a workgroup each: as many as make KNN_TARGET_WGS workgroups of all queries, of at least
+    // KNN_SEG_MIN references (the fewer the segments, the more of a query's pairs tighten one threshold)
+    int seg_refs = (int)seg_env;
+    if (!seg_refs) {
+        const int want = (KNN_TARGET_WGS + nq - 1) / nq;
+        seg_refs = (nr + want - 1) / want;
+        if (seg_refs < KNN_SEG_MIN) seg_refs = KNN_SEG_MIN;
+    }
+    if (seg_refs > nr) seg_refs = nr;
+    const int nseg = (nr + seg_refs - 1) / seg_refs;
+    // the segments' lists of a batch of queries within the byte budget
+    const size_t nqs = nq, nrs = nr, ks = k, per_query = (size_t)nseg * (ks * 12 + 24);
+    size_t rows = ((size_t)mib << 20) / per_query;
+    if (rows < 1) rows = 1;
+    if (rows > nqs) rows = nqs;
+    if (rows > (size_t)0x7fffffff / nseg) rows = (size_t)0x7fffffff / nseg; // (a workgroup per segment of the batch)
+    RCCHK(begin_call(h));
+    Piece<double> s_q, dr, dsd, ddist; Piece<int32_t> s_qc, drc, dex, dsi, didx; Piece<long long> dsw, dwork;
+    RCCHK(ws_carve(h, [&](Carve &w) {
+        s_q = w.take<double>(nqs * Eq, !(flags & ADP_IN_DEVICE)); s_qc = w.take<int32_t>(nqs, !(flags & ADP_IN_DEVICE));
+        dr = w.take<double>(nrs * Er); drc = w.take<int32_t>(nrs); dex = w.take<int32_t>(nqs, exclude != nullptr);
+        dsd = w.take<double>(rows * nseg * ks); dsi = w.take<int32_t>(rows * nseg * ks); dsw = w.take<long long>(rows * nseg * 3);
+        didx = w.take<int32_t>(nqs * ks); ddist = w.take<double>(nqs * ks); dwork = w.take<long long>(nqs * 3, work_out != nullptr);
+    }));
+    const double *dq; const int32_t *dqc;
+    RCCHK(stage_in(h, flags, q, s_q, &dq));
+    RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
+    RCCHK(h2d(h, dr, r));
+    RCCHK(h2d(h, drc, r_count));
+    if (exclude) RCCHK(h2d(h, dex, exclude));
+    const int C = (Er + 63) / 64, pmask = (int)period - 1, prune = (flags & ADP_KNN_NO_PRUNE) ? 0 : 1;
+    for (size_t p0 = 0; p0 < nqs; p0 += rows) {
+        const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
+        const dim3 grid((unsigned)(nb * nseg)), block(64 * KNN_WAVES);
+        { Scope s(h, "k_dtw_knn");
+          if (C <= 1) hipLaunchKernelGGL(k_dtw_knn<1>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
+          else if (C <= 2) hipLaunchKernelGGL(k_dtw_knn<2>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
+          else if (C <= 4) hipLaunchKernelGGL(k_dtw_knn<4>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
+          else hipLaunchKernelGGL(k_dtw_knn<8>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p); }
+        { Scope s(h, "k_knn_merge");
+          hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)nb), dim3(64), 0, h->stream, dsd.p, dsi.p, dsw.p, nseg, k, (int)p0, didx.p, ddist.p, dwork.p); }
+    }
+    HIPCHK(hipGetLastError());
+    RCCHK(d2h(h, idx_out, didx));
+    RCCHK(d2h(h, dist_out, ddist));
+    if (work_out) RCCHK(d2h(h, work_out, dwork));
     HIPCHK(hipStreamSynchronize(h->stream));
     return ADP_OK;
 }

@@ -274,7 +274,7 @@ def load():
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
                             + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())
-                            + list(CLUSTER_PROTOTYPES.items())):
+                            + list(CLUSTER_PROTOTYPES.items()) + list(KNN_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -524,6 +524,15 @@ CLUSTER_PROTOTYPES = {
 }
 CLUSTER_MAX_ROWS = 16384  # CL_NMAX of adapted_amd/csrc/dtw_cluster_api.h
 CLUSTER_MAX_K = 4096  # CL_KMAX
+
+# include/adapted_hip_knn.h (the header adapted_hip.h includes for the k nearest labelled fingerprints of every query under DTW, an
+# extension); tests/test_knn_cpu.py holds this table and the three constants against its header
+KNN_PROTOTYPES = {
+    "adp_dtw_knn": "int: adp_handle* double* int32* int int double* int32* int int int int int int32* int32* double* int64*",
+}
+ADP_KNN_NO_PRUNE = 1 << 22  # adp_dtw_knn: every pair runs to the end
+KNN_KMAX = 32
+KNN_NR_MAX = 262144
 
 # include/adapted_hip_resegment.h (the header adapted_hip.h includes for the re-segmentation of reads the LLR primary fails, an
 # extension): a flag of adp_detect_llr, row bits and a selector of adp_debug_fetch -- it declares no entry point;
@@ -1556,6 +1565,40 @@ class Engine:
         sil = np.zeros(n)
         self._check(self.lib.adp_silhouette(self._h, dist, n, assign, int(k), flags, sil))
         return sil
+
+    def dtw_knn(self, q, q_count, r, r_count, k: int, band: int = 0, exclude=None, prune: bool = True, n: Optional[int] = None,
+                E: Optional[int] = None, want_work: bool = False):
+        """adp_dtw_knn: queries float64 [nq, Eq] with their counts (host arrays, or two device pointers with ``n`` and ``E``),
+        references float64 [nr, Er] with their counts (host), ``exclude`` int32 [nq] (the reference that does not count for a query,
+        -1 for none) or None -> (idx int32 [nq, k]: the k nearest references in the order (distance, index), -1 where there is none;
+        dist float64 [nq, k], NaN where -1; with ``want_work`` work int64 [nq, 3]: pairs finished, pairs abandoned, DP steps).
+        ``prune=False``: every pair runs to the end (the same idx and dist)"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.ndim != 2:
+            raise ValueError("references: a float64 [nr, Er] array")
+        nr, Er = r.shape
+        r_count = self._per_read(r_count, nr, "r_count")
+        if isinstance(q, int):
+            if n is None or E is None or not isinstance(q_count, int):
+                raise ValueError("device queries need a device pointer to their counts, n and E")
+            _check_runtime_once_torch_is_here()
+            flags, nq, Eq = ADP_IN_DEVICE, int(n), int(E)
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.ndim != 2:
+                raise ValueError("queries: a float64 [nq, Eq] array")
+            flags, (nq, Eq) = 0, q.shape
+            q_count = self._per_read(q_count, nq, "q_count")
+        k = int(k)
+        if exclude is not None:
+            exclude = self._per_read(exclude, nq, "exclude")
+        idx = np.full((nq, max(k, 0)), -1, dtype=np.int32)
+        dist = np.full((nq, max(k, 0)), np.nan)
+        work = np.zeros((nq, 3), dtype=np.int64) if want_work else None
+        if nq > 0:  # (the library wants a query: an empty batch has an empty answer)
+            self._check(self.lib.adp_dtw_knn(self._h, q, q_count, nq, Eq, r, r_count, nr, Er, k, int(band),
+                                             flags | (0 if prune else ADP_KNN_NO_PRUNE), exclude, idx, dist, work))
+        return (idx, dist, work) if want_work else (idx, dist)
 
     # the files Engine.format_csv made, and those among them that went through the pandas writer (a value outside the bounds)
     csv_files = 0

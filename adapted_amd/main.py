@@ -51,6 +51,11 @@ def build_parser() -> argparse.ArgumentParser:
     from .clusters import add_arguments as add_cluster_arguments
 
     add_cluster_arguments(k)
+    n = sub.add_parser("knn", help="(extension) Assign barcodes by the k nearest labelled fingerprints of a run made with --fingerprints "
+                                   "(pruned DTW on the GPU), and measure leave-one-out accuracy (untuned, nothing validated on real data).")
+    from .knn import add_arguments as add_knn_arguments
+
+    add_knn_arguments(n)
     d.add_argument("-i", "--input", type=str, nargs="+", required=True, help="input files / directories (.pod5 or .npz bundles)")
     d.add_argument("-o", "--output", type=str, default=None)
     d.add_argument("--config", type=str, default=None, help="config TOML (overrides --chemistry)")
@@ -652,6 +657,11 @@ def main(argv=None):
         from .clusters import clusters_command
 
         clusters_command(args)
+        return
+    if args.mode == "knn":
+        from .knn import knn_command
+
+        knn_command(args)
         return
     if args.mode == "continue":
         run_dir = args.continue_from

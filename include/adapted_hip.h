@@ -583,6 +583,10 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
  * CLUSTER_PROTOTYPES. */
 #include "adapted_hip_clusters.h"
 
+/* The k nearest labelled fingerprints of every query under DTW, pairs abandoned behind a lower bound -- adp_dtw_knn, an extension --:
+ * a header of its own, with its prototype table in adapted_amd/lib.py, KNN_PROTOTYPES. */
+#include "adapted_hip_knn.h"
+
 /* Re-segmentation of reads the LLR primary fails -- ADP_LLR_RESEGMENT, a flag of adp_detect_llr, an extension --: its rule, its row
  * bits and its counters in a header of its own; it declares no entry point (adapted_amd/lib.py, RESEGMENT_PROTOTYPES, is empty). */
 #include "adapted_hip_resegment.h"
