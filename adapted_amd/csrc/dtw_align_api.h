@@ -2,8 +2,8 @@
 // templates (an extension, as fingerprint_api.h is, whose k_dtw this continues).  Compiled in modules.hip only.  Everything is
 // float64 in a fixed order of operations, so that a numpy restatement is the exact oracle (tests/dtw_align_oracle.py).  Three kernels:
 //
-//   k_dtw_align   one wave per query and ITS template (which[p]).  The forward pass is k_dtw's: lane l owns C = ceil(Et / 64)
-//                 template columns in registers and works on query row s - l at step s, so the distance has k_dtw's bits.  Every
+//   k_dtw_align   one wave per query and ITS template (which[p]).  The forward pass is dtw_wave.h's wavefront, which is k_dtw's
+//                 (C = ceil(Et / 64) template columns per lane), so the distance has k_dtw's bits.  With its switch on, every
 //                 cell also leaves the 2-bit code of the predecessor it took (0 diagonal, 1 up, 2 left: the least value, the
 //                 diagonal first on equal values, then up): the C codes of a lane's cells of one row are one unit (a byte; 16 bits
 //                 with C = 8), W = ceil(longest template of the call / C) units per row, Eq rows.  The units live in LDS where
@@ -52,24 +52,13 @@ __global__ void __launch_bounds__(64) k_dtw_align(const double *__restrict__ q, 
     const double inf = __builtin_inf(), nan = __builtin_nan("");
     int st = 0;
     if (k < 0) st = 3;
-    else {
-        bool bad = n < 1 || n > Eq;
-        if (!bad) {
-            for (int i = ln; i < n; i += 64) {
-                const double v = q[(size_t)p * Eq + i];
-                qa[i] = v;
-                bad |= !__builtin_isfinite(v);
-            }
-        }
-        if (__any(bad)) st = 1;
-    }
+    else if (__any(dtw_stage(q + (size_t)p * Eq, n, Eq, qa, ln, 64))) st = 1;
     __syncthreads();
     double res = nan;
     int m = 0;
     if (st == 0) {
         m = tc[k];
-        int R = 1 << 30;
-        if (band > 0) { const int dm = n > m ? n - m : m - n; R = band > dm ? band : dm; }
+        const int R = dtw_radius(band, n, m);
         double c[C], P[C]; // this lane's template values and D[row before][its columns]
 #pragma unroll
         for (int jj = 0; jj < C; jj++) {
@@ -80,37 +69,14 @@ __global__ void __launch_bounds__(64) k_dtw_align(const double *__restrict__ q, 
         double plold = inf; // D[two rows before the next][its last column]
         const int steps = n + (m - 1) / C;
         for (int s = 1; s <= steps; s++) {
-            const int i = s - ln;
-            const double left_in = __shfl_up(P[C - 1], 1), diag_in = __shfl_up(plold, 1);
-            if (i >= 1 && i <= n) {
-                const double a = qa[i - 1];
-                double left = ln == 0 ? inf : left_in;
-                double diag = ln == 0 ? (i == 1 ? 0.0 : inf) : diag_in;
-                plold = P[C - 1];
-                unsigned code = 0;
-#pragma unroll
-                for (int jj = 0; jj < C; jj++) {
-                    const int dj = i - (ln * C + jj + 1);
-                    const double up = P[jj];
-                    const double d = a - c[jj];
-                    const unsigned dir = (diag <= up && diag <= left) ? 0u : (up <= left ? 1u : 2u);
-                    double v = d * d + fmin(fmin(up, left), diag);
-                    if (dj > R || -dj > R) v = inf;
-                    code |= dir << (2 * jj);
-                    diag = up;
-                    left = v;
-                    P[jj] = v;
-                }
+            dtw_step<C, true>(s, ln, n, R, qa, c, P, plold, [&](int i, unsigned code) {
                 if (ln < W) { // (i - 1 < n <= Eq: inside the Eq * W units)
                     if (G) gc[(size_t)(i - 1) * W + ln] = (U)code;
                     else lcodes[(i - 1) * W + ln] = (U)code;
                 }
-            }
+            });
         }
-        double mine = inf;
-#pragma unroll
-        for (int jj = 0; jj < C; jj++) if (jj == (m - 1) % C) mine = P[jj];
-        res = __shfl(mine, (m - 1) / C);
+        res = __shfl(dtw_corner<C>(P, m), dtw_corner_lane<C>(m));
         if (!__builtin_isfinite(res)) st = 2;
     }
     __syncthreads(); // (the codes, of other lanes: LDS, or global memory inside the workgroup)

@@ -4,7 +4,7 @@
 // the exact oracle (tests/dtw_cluster_oracle.py).  No float atomics: nothing depends on scheduling.  The kernels:
 //
 //   k_dtw_pairs    one wave per row i and a strip of CL_STRIP partners j.  Row i is staged once in LDS and checked once; per partner
-//                  the body is k_dtw's (lane l owns C = ceil(E / 64) of the partner's columns in registers), so a pair has k_dtw's
+//                  dtw_wave.h's wavefront, which is k_dtw's (C = ceil(E / 64) of the partner's columns per lane), so a pair has k_dtw's
 //                  bits, and -- the recurrence being symmetric in its operands to the bit -- the bits of either order.  mirror: the
 //                  partners of row i are (i + d) % n for d = 1 .. (n - 1) / 2 (and d = n / 2 for i < n / 2 with an even n): every
 //                  unordered pair once, the same number of pairs for every row (no long and short rows), and both entries written.
@@ -50,15 +50,7 @@ __global__ void __launch_bounds__(64) k_dtw_pairs(const double *__restrict__ q, 
     const int il = (int)(blockIdx.x / (unsigned)nchunks), chunk = (int)(blockIdx.x % (unsigned)nchunks), i = r0 + il;
     const int na = qc[i];
     const double inf = __builtin_inf(), nan = __builtin_nan("");
-    bool bad_i = na < 1 || na > E;
-    if (!bad_i) {
-        for (int e = ln; e < na; e += 64) {
-            const double v = q[(size_t)i * E + e];
-            qa[e] = v;
-            bad_i |= !__builtin_isfinite(v);
-        }
-    }
-    bad_i = __any(bad_i);
+    const bool bad_i = __any(dtw_stage(q + (size_t)i * E, na, E, qa, ln, 64));
     __syncthreads();
     double *orow = out + (size_t)il * n;
     if (chunk == 0 && ln == 0) orow[i] = bad_i ? nan : 0.0;
@@ -82,35 +74,12 @@ __global__ void __launch_bounds__(64) k_dtw_pairs(const double *__restrict__ q, 
         double res = nan;
         int last = 0;
         if (!bad) {
-            int R = 1 << 30;
-            if (band > 0) { const int dm = na > m ? na - m : m - na; R = band > dm ? band : dm; }
+            const int R = dtw_radius(band, na, m);
             double plold = inf; // D[two rows before the next][its last column]
             const int steps = na + (m - 1) / C;
-            for (int s = 1; s <= steps; s++) {
-                const int r = s - ln;
-                const double left_in = __shfl_up(P[C - 1], 1), diag_in = __shfl_up(plold, 1);
-                if (r >= 1 && r <= na) {
-                    const double a = qa[r - 1];
-                    double left = ln == 0 ? inf : left_in;
-                    double diag = ln == 0 ? (r == 1 ? 0.0 : inf) : diag_in;
-                    plold = P[C - 1];
-#pragma unroll
-                    for (int jj = 0; jj < C; jj++) {
-                        const int dj = r - (ln * C + jj + 1);
-                        const double up = P[jj];
-                        const double d = a - c[jj];
-                        double v = d * d + fmin(fmin(up, left), diag);
-                        if (dj > R || -dj > R) v = inf;
-                        diag = up;
-                        left = v;
-                        P[jj] = v;
-                    }
-                }
-            }
-            res = inf;
-#pragma unroll
-            for (int jj = 0; jj < C; jj++) if (jj == (m - 1) % C) res = P[jj];
-            last = (m - 1) / C;
+            for (int s = 1; s <= steps; s++) dtw_step<C>(s, ln, na, R, qa, c, P, plold);
+            res = dtw_corner<C>(P, m);
+            last = dtw_corner_lane<C>(m);
         }
         if (ln == last) {
             orow[j] = res;

@@ -1,7 +1,7 @@
 // dtw_knn_api.h -- the k nearest labelled fingerprints of every query under DTW, without the distance matrix (an extension, as
 // dtw_cluster_api.h is, whose pair kernel this one continues).  Compiled in modules.hip only.  The distance of a pair is k_dtw's to
-// the bit (fingerprint_api.h: the same body, lane l owns C = ceil(Er / 64) reference columns in registers, the query staged once in
-// LDS); what is new is that a pair is ABANDONED as soon as a lower bound of its distance is strictly greater than a distance that
+// the bit (dtw_wave.h: the one wavefront of both, lane l owns C = ceil(Er / 64) reference columns in registers, the query staged once
+// in LDS); what is new is that a pair is ABANDONED as soon as a lower bound of its distance is strictly greater than a distance that
 // is known to be >= the query's final k-th least -- which no result can see (include/adapted_hip_knn.h).  No data passes between
 // workgroups inside a launch, no float atomics, nothing depends on scheduling.  Two kernels:
 //
@@ -95,15 +95,7 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
     double *od = seg_dist + at * k;
     int32_t *oi = seg_idx + at * k;
     long long *ow = seg_work + at * 3;
-    bool bad = n < 1 || n > Eq;
-    if (!bad) {
-        for (int i = threadIdx.x; i < n; i += 64 * KNN_WAVES) {
-            const double v = q[(size_t)p * Eq + i];
-            qa[i] = v;
-            bad |= !__builtin_isfinite(v);
-        }
-    }
-    bad = __any(bad);
+    bool bad = __any(dtw_stage(q + (size_t)p * Eq, n, Eq, qa, (int)threadIdx.x, 64 * KNN_WAVES));
     if (ln == 0) badw[w] = bad ? 1 : 0;
     if (threadIdx.x < KNN_WAVES) slot[threadIdx.x] = inf;
     __syncthreads();
@@ -133,7 +125,7 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
             c[jj] = c0 < m ? r[(size_t)j * Er + c0] : 0.0;
             P[jj] = inf;
         }
-        const int last = (m - 1) / C;
+        const int last = dtw_corner_lane<C>(m);
         bool gone = false;
         if (prune && (n > 1 || m > 1)) {
             // THE ENDPOINT BOUND.  Every warping path starts in cell (1, 1) and ends in (n, m), two cells unless n == m == 1, both
@@ -141,7 +133,8 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
             // predecessors from (n, m) back to (1, 1) the values never decrease in floating point -- D[cell] = fl(cost + D[pred])
             // with cost >= 0, and fl(x + c) >= x for c >= 0 (rounding is monotone and x is representable) --, so the predecessor
             // of (n, m) has a value >= fl(d1 * d1), and by the monotonicity of a rounded sum in its operand
-            // D[n][m] = fl(fl(dn * dn) + D[pred]) >= fl(fl(dn * dn) + fl(d1 * d1)): the value computed here, in these operations.
+            // D[n][m] = fl(fl(dn * dn) + D[pred]) >= fl(fl(dn * dn) + fl(d1 * d1)): the value computed here, in these operations
+            // (D is dtw_step's, dtw_wave.h: fl(fl(d * d) + the least predecessor), nothing contracted).
             double cl = 0.0;
 #pragma unroll
             for (int jj = 0; jj < C; jj++) if (jj == (m - 1) % C) cl = c[jj];
@@ -154,32 +147,11 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
         }
         int ran = 0; // the steps made
         if (!gone) {
-            int R = 1 << 30;
-            if (band > 0) { const int dm = n > m ? n - m : m - n; R = band > dm ? band : dm; }
+            const int R = dtw_radius(band, n, m);
             double plold = inf; // D[two rows before the next][its last column]
             const int steps = n + (m - 1) / C;
-            // one step of k_dtw's wavefront: lane ln computes row s - ln of its columns
-            auto step = [&](int s) __attribute__((always_inline)) {
-                const int i = s - ln;
-                const double left_in = __shfl_up(P[C - 1], 1), diag_in = __shfl_up(plold, 1);
-                if (i >= 1 && i <= n) {
-                    const double a = qa[i - 1];
-                    double left = ln == 0 ? inf : left_in;
-                    double diag = ln == 0 ? (i == 1 ? 0.0 : inf) : diag_in;
-                    plold = P[C - 1];
-#pragma unroll
-                    for (int jj = 0; jj < C; jj++) {
-                        const int dj = i - (ln * C + jj + 1);
-                        const double up = P[jj];
-                        const double d = a - c[jj];
-                        double v = d * d + fmin(fmin(up, left), diag);
-                        if (dj > R || -dj > R) v = inf;
-                        diag = up;
-                        left = v;
-                        P[jj] = v;
-                    }
-                }
-            };
+            // dtw_wave.h's step under a local name (its two sites calling it directly cost a register: profiles/dtw_wave_isa.txt)
+            auto step = [&](int s) __attribute__((always_inline)) { dtw_step<C>(s, ln, n, R, qa, c, P, plold); };
             // plain steps up to the next multiple b of the period, then step b with the abandon test around it
             int s = 1;
             for (;;) {
@@ -188,7 +160,8 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
                 for (; s < stop; s++) step(s);
                 if (b > steps) break;
                 // THE FRONTIER BOUND.  Call the TIME of cell (i, j) i + (j - 1) / C: the step at which lane (j - 1) / C computes
-                // it.  A path starts at time 1, in (1, 1), ends at time `steps`, in (n, m), and one warping step -- (i + 1, j),
+                // it (dtw_step, dtw_wave.h: this bound relies on its layout of P and on its +inf outside the band).  A path
+                // starts at time 1, in (1, 1), ends at time `steps`, in (n, m), and one warping step -- (i + 1, j),
                 // (i, j + 1) or (i + 1, j + 1) -- raises the time by 0, 1 or 2.  So for every 1 <= b <= steps every path holds a
                 // cell of time b or b - 1, and so does the chain of arg-min predecessors of (n, m), along which the values never
                 // decrease in floating point (above): the least D over the cells of the times b - 1 and b is <= D[n][m].  ONE
@@ -212,10 +185,7 @@ __global__ void __launch_bounds__(64 * KNN_WAVES) k_dtw_knn(const double *__rest
         n_steps += ran;
         if (gone) { n_ab++; continue; }
         n_fin++;
-        double res = inf;
-#pragma unroll
-        for (int jj = 0; jj < C; jj++) if (jj == (m - 1) % C) res = P[jj];
-        const double D = __shfl(res, last);
+        const double D = __shfl(dtw_corner<C>(P, m), last);
         // into the list: behind the entries that are before (D, j)
         const bool have = ln < cnt;
         const int pos = __popcll(__ballot(have && knn_before(myd, myi, D, j)));

@@ -10,13 +10,12 @@
 //                 of the equal ones, the latest.  The level of an event is np.mean of its widened samples: np_sum.h's order, a lane
 //                 per event of at most 128 samples (one leaf of numpy's tree), the whole wave on a longer one.  np.median of the
 //                 levels and of their absolute deviations by counting ranks in LDS (at most 512 values: exact, no sort).
-//   k_dtw         one wave per (query, template) pair.  Lane l owns C = ceil(Et / 64) template columns in registers and works on
-//                 query row s - l at step s; its left neighbour's last column of this row and of the row before arrive through a
-//                 lane shift.  A cell's value does not depend on the order of the visits, so the anti-diagonal order gives what the
-//                 row order gives.  The query is staged once in LDS.
+//   k_dtw         one wave per (query, template) pair: dtw_wave.h's wavefront and nothing else, with C = ceil(Et / 64) template
+//                 columns per lane.  The query is staged once in LDS.
 //   k_dtw_best    the least and the second least distance of every query, a thread per query.
 #pragma once
 #include "common.h"
+#include "dtw_wave.h"
 #include "events_api.h"
 #include "np_sum.h"
 
@@ -203,22 +202,13 @@ __global__ void __launch_bounds__(64) k_dtw(const double *__restrict__ q, const 
     const int n = qc[p], m = tc[k];
     double *o = dist + (size_t)pl * nt + k;
     const double inf = __builtin_inf();
-    bool bad = n < 1 || n > Eq;
-    if (!bad) {
-        for (int i = ln; i < n; i += 64) {
-            const double v = q[(size_t)p * Eq + i];
-            qa[i] = v;
-            bad |= !__builtin_isfinite(v);
-        }
-    }
-    bad = __any(bad);
+    const bool bad = __any(dtw_stage(q + (size_t)p * Eq, n, Eq, qa, ln, 64));
     __syncthreads();
     if (bad) {
         if (ln == 0) *o = __builtin_nan("");
         return;
     }
-    int R = 1 << 30;
-    if (band > 0) { const int dm = n > m ? n - m : m - n; R = band > dm ? band : dm; }
+    const int R = dtw_radius(band, n, m);
     double c[C], P[C]; // this lane's template values and D[row before][its columns]
 #pragma unroll
     for (int jj = 0; jj < C; jj++) {
@@ -228,31 +218,9 @@ __global__ void __launch_bounds__(64) k_dtw(const double *__restrict__ q, const 
     }
     double plold = inf; // D[two rows before the next][its last column]
     const int steps = n + (m - 1) / C;
-    for (int s = 1; s <= steps; s++) {
-        const int i = s - ln;
-        const double left_in = __shfl_up(P[C - 1], 1), diag_in = __shfl_up(plold, 1);
-        if (i >= 1 && i <= n) {
-            const double a = qa[i - 1];
-            double left = ln == 0 ? inf : left_in;
-            double diag = ln == 0 ? (i == 1 ? 0.0 : inf) : diag_in;
-            plold = P[C - 1];
-#pragma unroll
-            for (int jj = 0; jj < C; jj++) {
-                const int dj = i - (ln * C + jj + 1);
-                const double up = P[jj];
-                const double d = a - c[jj];
-                double v = d * d + fmin(fmin(up, left), diag);
-                if (dj > R || -dj > R) v = inf;
-                diag = up;
-                left = v;
-                P[jj] = v;
-            }
-        }
-    }
-    double res = inf;
-#pragma unroll
-    for (int jj = 0; jj < C; jj++) if (jj == (m - 1) % C) res = P[jj];
-    if (ln == (m - 1) / C) *o = res;
+    for (int s = 1; s <= steps; s++) dtw_step<C>(s, ln, n, R, qa, c, P, plold);
+    const double res = dtw_corner<C>(P, m);
+    if (ln == dtw_corner_lane<C>(m)) *o = res;
 }
 
 // block = 64, a thread per query of the batch.  best [.., 2]: the template of the least distance (the lowest index on ties) and of

@@ -66,6 +66,57 @@ static int scratch_mib(const char *name, const char *value, long long dflt, long
     return ADP_OK;
 }
 
+// the DTW kernels' register tile for rows of up to E <= FP_EMAX values: fn(C as an integral_constant), the least C of 1, 2, 4, 8
+// with C * 64 >= E; dtw_width: that C as a number
+template <class F> static auto by_width(int E, F &&fn)
+{
+    const int C = (E + 63) / 64;
+    if (C <= 1) return fn(std::integral_constant<int, 1>());
+    if (C <= 2) return fn(std::integral_constant<int, 2>());
+    if (C <= 4) return fn(std::integral_constant<int, 4>());
+    return fn(std::integral_constant<int, 8>());
+}
+static int dtw_width(int E) { return by_width(E, [](auto c) { return (int)decltype(c)::value; }); }
+
+// a host table t [rows, E] with its counts, as the DTW calls take their templates / references: 1 <= count <= E and finite values
+// inside the count, refused in the caller's nouns; -> the greatest count (cmax may be null)
+static int table_check(const double *t, const int32_t *count, int rows, int E, const char *count_name, const char *E_name,
+                       const char *noun, int *cmax)
+{
+    int most = 1;
+    for (int k = 0; k < rows; k++) {
+        if (count[k] < 1 || count[k] > E) {
+            g_err = std::string("need 1 <= ") + count_name + " <= " + E_name + " for every " + noun;
+            return ADP_ERR_INVALID;
+        }
+        for (int j = 0; j < count[k]; j++)
+            if (!std::isfinite(t[(size_t)k * E + j])) { g_err = std::string(noun) + " values inside their count must be finite"; return ADP_ERR_INVALID; }
+        if (count[k] > most) most = count[k];
+    }
+    if (cmax) *cmax = most;
+    return ADP_OK;
+}
+
+// what adp_dtw_assign, adp_dtw_align and adp_dba_step check of their sizes and templates; -> the longest template
+static int dtw_templates_check(int Eq, const double *t, const int32_t *t_count, int nt, int Et, int band, int *mmax)
+{
+    if (Eq < 1 || Eq > FP_EMAX || Et < 1 || Et > FP_EMAX) { g_err = "Eq and Et must lie in [1, 512]"; return ADP_ERR_INVALID; }
+    if (nt < 1 || nt > DTW_NT_MAX) { g_err = "nt must lie in [1, 4096]"; return ADP_ERR_INVALID; }
+    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
+    return table_check(t, t_count, nt, Et, "t_count", "Et", "template", mmax);
+}
+
+// the rows of one batch of `n` rows of `row_bytes` each within a budget of `mib` MiB: at least one; with wgs_per_row > 0 no more
+// than keep a grid of that many workgroups per row within 0x7fffffff
+static size_t batch_rows(long long mib, size_t row_bytes, size_t n, size_t wgs_per_row)
+{
+    size_t rows = ((size_t)mib << 20) / row_bytes;
+    if (rows < 1) rows = 1;
+    if (rows > n) rows = n;
+    if (wgs_per_row && rows > (size_t)0x7fffffff / wgs_per_row) rows = (size_t)0x7fffffff / wgs_per_row;
+    return rows;
+}
+
 // the per-read checks (host arrays of n entries): lo <= a <= hi; 0 <= len <= L; 0 <= start <= end <= len; positions in [0, 2^40]
 template <class T> static bool all_in(const T *a, int n, T lo, T hi)
 {
@@ -854,23 +905,13 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
                    int nt, int Et, int band, int flags, double *dist_out, int32_t *best_out, double *bestdist_out)
 {
     if (!h || !q || !q_count || !t || !t_count || !best_out || !bestdist_out || nq < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    if (Eq < 1 || Eq > FP_EMAX || Et < 1 || Et > FP_EMAX) { g_err = "Eq and Et must lie in [1, 512]"; return ADP_ERR_INVALID; }
-    if (nt < 1 || nt > DTW_NT_MAX) { g_err = "nt must lie in [1, 4096]"; return ADP_ERR_INVALID; }
-    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
-    for (int k = 0; k < nt; k++) {
-        if (t_count[k] < 1 || t_count[k] > Et) { g_err = "need 1 <= t_count <= Et for every template"; return ADP_ERR_INVALID; }
-        for (int j = 0; j < t_count[k]; j++)
-            if (!std::isfinite(t[(size_t)k * Et + j])) { g_err = "template values inside their count must be finite"; return ADP_ERR_INVALID; }
-    }
+    RCCHK(dtw_templates_check(Eq, t, t_count, nt, Et, band, nullptr));
     // the distance matrix of a batch of queries within a byte budget: DTW_SCRATCH_MIB, or ADP_DTW_SCRATCH_MIB from the environment,
     // read per call
     long long mib;
     RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
     const size_t nqs = nq, nts = nt;
-    size_t rows = ((size_t)mib << 20) / (nts * 8);
-    if (rows < 1) rows = 1;
-    if (rows > nqs) rows = nqs;
-    if (rows > (size_t)0x7fffffff / nts) rows = (size_t)0x7fffffff / nts; // (a workgroup per pair of the batch)
+    const size_t rows = batch_rows(mib, nts * 8, nqs, nts); // (a workgroup per pair of the batch)
     RCCHK(begin_call(h));
     Piece<double> s_q, dt, ddist, dbd; Piece<int32_t> s_qc, dtc, dbest;
     RCCHK(ws_carve(h, [&](Carve &w) {
@@ -883,15 +924,11 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
     RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
     RCCHK(h2d(h, dt, t));
     RCCHK(h2d(h, dtc, t_count));
-    const int C = (Et + 63) / 64;
     for (size_t p0 = 0; p0 < nqs; p0 += rows) {
         const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
         const dim3 grid((unsigned)(nb * nts)), block(64);
         { Scope s(h, "k_dtw");
-          if (C <= 1) hipLaunchKernelGGL(k_dtw<1>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
-          else if (C <= 2) hipLaunchKernelGGL(k_dtw<2>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
-          else if (C <= 4) hipLaunchKernelGGL(k_dtw<4>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist);
-          else hipLaunchKernelGGL(k_dtw<8>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist); }
+          by_width(Et, [&](auto c) { hipLaunchKernelGGL(k_dtw<decltype(c)::value>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dt, dtc, nt, Et, band, ddist); }); }
         { Scope s(h, "k_dtw_best");
           hipLaunchKernelGGL(k_dtw_best, dim3((unsigned)((nb + 63) / 64)), block, 0, h->stream, ddist, (int)nb, nt, dbest + p0 * 2, dbd + p0 * 2); }
         if (dist_out) RCCHK(d2h(h, dist_out + p0 * nts, ddist, nb * nts));
@@ -910,15 +947,6 @@ int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int n
 // what adp_dtw_align fills (host memory; lo, hi and sum may be null), or -- with t_new -- what adp_dba_step fills
 struct DaOut { double *dist; int32_t *status, *lo, *hi; double *sum; double *t_new; int32_t *members; double *inertia; };
 
-template <int C, bool G>
-static void da_launch(adp_handle *h, size_t nb, size_t lds, const double *dq, const int32_t *dqc, const int32_t *dwhich, int p0, int Eq,
-                      const double *dt, const int32_t *dtc, int Et, int band, int W, unsigned char *dcodes, double *ddist,
-                      int32_t *dstatus, int32_t *dlo, int32_t *dhi, double *dsum)
-{
-    hipLaunchKernelGGL((k_dtw_align<C, G>), dim3((unsigned)nb), dim3(64), lds, h->stream, dq, dqc, dwhich, p0, Eq, dt, dtc, Et, band, W,
-                       dcodes, ddist, dstatus, dlo, dhi, dsum);
-}
-
 // both calls: adp_dtw_assign's checks and which in [-1, nt); the queries in batches within the byte budget; per batch k_dtw_align
 // and either the copies of its path outputs or k_dba_reduce
 static int da_run(adp_handle *h, const double *q, const int32_t *q_count, const int32_t *which, int nq, int Eq, const double *t,
@@ -926,29 +954,18 @@ static int da_run(adp_handle *h, const double *q, const int32_t *q_count, const 
 {
     const bool dba = o.t_new != nullptr;
     if (!h || !q || !q_count || !which || !t || !t_count || nq < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    if (Eq < 1 || Eq > FP_EMAX || Et < 1 || Et > FP_EMAX) { g_err = "Eq and Et must lie in [1, 512]"; return ADP_ERR_INVALID; }
-    if (nt < 1 || nt > DTW_NT_MAX) { g_err = "nt must lie in [1, 4096]"; return ADP_ERR_INVALID; }
-    if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
-    int mmax = 1;
-    for (int k = 0; k < nt; k++) {
-        if (t_count[k] < 1 || t_count[k] > Et) { g_err = "need 1 <= t_count <= Et for every template"; return ADP_ERR_INVALID; }
-        for (int j = 0; j < t_count[k]; j++)
-            if (!std::isfinite(t[(size_t)k * Et + j])) { g_err = "template values inside their count must be finite"; return ADP_ERR_INVALID; }
-        if (t_count[k] > mmax) mmax = t_count[k];
-    }
+    int mmax;
+    RCCHK(dtw_templates_check(Eq, t, t_count, nt, Et, band, &mmax));
     if (!all_in<int32_t>(which, nq, -1, nt - 1)) { g_err = "need -1 <= which < nt for every query"; return ADP_ERR_INVALID; }
     long long mib;
     RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
     // the direction codes: Eq rows of W units of C cells each (dtw_align_api.h), in LDS where they fit
-    const int C = (Et + 63) / 64 <= 1 ? 1 : (Et + 63) / 64 <= 2 ? 2 : (Et + 63) / 64 <= 4 ? 4 : 8;
+    const int C = dtw_width(Et);
     const int W = (mmax + C - 1) / C;
     const size_t nqs = nq, nts = nt, Ets = Et;
     const size_t code_bytes = (size_t)Eq * W * (C == 8 ? 2 : 1);
     const bool global_codes = code_bytes > DA_LDS_CODES;
-    const size_t per_query = Ets * 16 + (global_codes ? code_bytes : 0);
-    size_t rows = ((size_t)mib << 20) / per_query;
-    if (rows < 1) rows = 1;
-    if (rows > nqs) rows = nqs;
+    const size_t rows = batch_rows(mib, Ets * 16 + (global_codes ? code_bytes : 0), nqs, 0);
     // the members of every template in ascending order (adp_dba_step)
     std::vector<int32_t> offs, list;
     if (dba) {
@@ -988,13 +1005,13 @@ static int da_run(adp_handle *h, const double *q, const int32_t *q_count, const 
     for (size_t p0 = 0; p0 < nqs; p0 += rows) {
         const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
         { Scope s(h, "k_dtw_align");
-#define DA_GO(C_, G_) da_launch<C_, G_>(h, nb, lds, dq, dqc, dwhich, (int)p0, Eq, dt, dtc, Et, band, W, dcodes, ddist, dstatus, dlo, dhi, dsum)
-          if (C == 1) { if (global_codes) DA_GO(1, true); else DA_GO(1, false); }
-          else if (C == 2) { if (global_codes) DA_GO(2, true); else DA_GO(2, false); }
-          else if (C == 4) { if (global_codes) DA_GO(4, true); else DA_GO(4, false); }
-          else { if (global_codes) DA_GO(8, true); else DA_GO(8, false); }
-#undef DA_GO
-        }
+          by_width(Et, [&](auto c) {
+              auto go = [&](auto g) {
+                  hipLaunchKernelGGL((k_dtw_align<decltype(c)::value, decltype(g)::value>), dim3((unsigned)nb), dim3(64), lds, h->stream, dq, dqc,
+                                     dwhich.p, (int)p0, Eq, dt, dtc.p, Et, band, W, dcodes.p, ddist.p, dstatus.p, dlo.p, dhi.p, dsum.p);
+              };
+              if (global_codes) go(std::true_type()); else go(std::false_type());
+          }); }
         if (dba) {
             Scope s(h, "k_dba_reduce");
             hipLaunchKernelGGL(k_dba_reduce, dim3(cells), dim3(64), 0, h->stream, doffs, dlist, (int)p0, (int)nb, nt, Et, dtc, dstatus,
@@ -1076,9 +1093,8 @@ int adp_dtw_pairwise(adp_handle *h, const double *q, const int32_t *q_count, int
     // else bands of its rows (a pair once per band its rows lie in: the same bits, the recurrence being symmetric)
     const bool out_dev = (flags & ADP_OUT_DEVICE) != 0;
     const size_t ns = n;
-    size_t rows = ((size_t)mib << 20) / (ns * 8);
-    if (rows < 1) rows = 1;
-    const bool whole = out_dev || rows >= ns;
+    size_t rows = batch_rows(mib, ns * 8, ns, 0);
+    const bool whole = out_dev || rows == ns;
     if (whole) rows = ns;
     RCCHK(begin_call(h));
     Piece<double> s_q, dmat; Piece<int32_t> s_qc;
@@ -1090,17 +1106,13 @@ int adp_dtw_pairwise(adp_handle *h, const double *q, const int32_t *q_count, int
     RCCHK(stage_in(h, flags, q, s_q, &dq));
     RCCHK(stage_in(h, flags, q_count, s_qc, &dqc));
     double *dout = out_dev ? dist_out : dmat.p;
-    const int C = (E + 63) / 64;
     const int partners = whole ? n / 2 : n - 1;
     const int nchunks = partners < 1 ? 1 : (partners + CL_STRIP - 1) / CL_STRIP;
     for (size_t r0 = 0; r0 < ns; r0 += rows) {
         const size_t nb = ns - r0 < rows ? ns - r0 : rows;
         const dim3 grid((unsigned)(nb * nchunks)), block(64);
         { Scope s(h, "k_dtw_pairs");
-          if (C <= 1) hipLaunchKernelGGL(k_dtw_pairs<1>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
-          else if (C <= 2) hipLaunchKernelGGL(k_dtw_pairs<2>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
-          else if (C <= 4) hipLaunchKernelGGL(k_dtw_pairs<4>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout);
-          else hipLaunchKernelGGL(k_dtw_pairs<8>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout); }
+          by_width(E, [&](auto c) { hipLaunchKernelGGL(k_dtw_pairs<decltype(c)::value>, grid, block, 0, h->stream, dq, dqc, n, E, band, (int)r0, nchunks, whole ? 1 : 0, dout); }); }
         if (!out_dev) RCCHK(d2h(h, dist_out + r0 * ns, dmat, nb * ns));
     }
     HIPCHK(hipGetLastError());
@@ -1248,11 +1260,7 @@ int adp_dtw_knn(adp_handle *h, const double *q, const int32_t *q_count, int nq, 
     if (k < 1 || k > KNN_KMAX) { g_err = "k must lie in [1, 32]"; return ADP_ERR_INVALID; }
     if (nr < 1 || nr > KNN_NR_MAX) { g_err = "nr must lie in [1, 262144]"; return ADP_ERR_INVALID; }
     if (band < 0) { g_err = "band must be >= 0"; return ADP_ERR_INVALID; }
-    for (int j = 0; j < nr; j++) {
-        if (r_count[j] < 1 || r_count[j] > Er) { g_err = "need 1 <= r_count <= Er for every reference"; return ADP_ERR_INVALID; }
-        for (int e = 0; e < r_count[j]; e++)
-            if (!std::isfinite(r[(size_t)j * Er + e])) { g_err = "reference values inside their count must be finite"; return ADP_ERR_INVALID; }
-    }
+    RCCHK(table_check(r, r_count, nr, Er, "r_count", "Er", "reference", nullptr));
     if (exclude && !all_in<int32_t>(exclude, nq, -1, nr - 1)) { g_err = "every exclude must lie in [-1, nr)"; return ADP_ERR_INVALID; }
     long long mib, seg_env, period;
     RCCHK(scratch_mib("ADP_DTW_SCRATCH_MIB", getenv("ADP_DTW_SCRATCH_MIB"), DTW_SCRATCH_MIB, &mib));
@@ -1270,10 +1278,7 @@ int adp_dtw_knn(adp_handle *h, const double *q, const int32_t *q_count, int nq, 
     const int nseg = (nr + seg_refs - 1) / seg_refs;
     // the segments' lists of a batch of queries within the byte budget
     const size_t nqs = nq, nrs = nr, ks = k, per_query = (size_t)nseg * (ks * 12 + 24);
-    size_t rows = ((size_t)mib << 20) / per_query;
-    if (rows < 1) rows = 1;
-    if (rows > nqs) rows = nqs;
-    if (rows > (size_t)0x7fffffff / nseg) rows = (size_t)0x7fffffff / nseg; // (a workgroup per segment of the batch)
+    const size_t rows = batch_rows(mib, per_query, nqs, (size_t)nseg); // (a workgroup per segment of the batch)
     RCCHK(begin_call(h));
     Piece<double> s_q, dr, dsd, ddist; Piece<int32_t> s_qc, drc, dex, dsi, didx; Piece<long long> dsw, dwork;
     RCCHK(ws_carve(h, [&](Carve &w) {
@@ -1288,15 +1293,12 @@ int adp_dtw_knn(adp_handle *h, const double *q, const int32_t *q_count, int nq, 
     RCCHK(h2d(h, dr, r));
     RCCHK(h2d(h, drc, r_count));
     if (exclude) RCCHK(h2d(h, dex, exclude));
-    const int C = (Er + 63) / 64, pmask = (int)period - 1, prune = (flags & ADP_KNN_NO_PRUNE) ? 0 : 1;
+    const int pmask = (int)period - 1, prune = (flags & ADP_KNN_NO_PRUNE) ? 0 : 1;
     for (size_t p0 = 0; p0 < nqs; p0 += rows) {
         const size_t nb = nqs - p0 < rows ? nqs - p0 : rows;
         const dim3 grid((unsigned)(nb * nseg)), block(64 * KNN_WAVES);
         { Scope s(h, "k_dtw_knn");
-          if (C <= 1) hipLaunchKernelGGL(k_dtw_knn<1>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
-          else if (C <= 2) hipLaunchKernelGGL(k_dtw_knn<2>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
-          else if (C <= 4) hipLaunchKernelGGL(k_dtw_knn<4>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p);
-          else hipLaunchKernelGGL(k_dtw_knn<8>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p); }
+          by_width(Er, [&](auto c) { hipLaunchKernelGGL(k_dtw_knn<decltype(c)::value>, grid, block, 0, h->stream, dq, dqc, (int)p0, Eq, dr.p, drc.p, nr, Er, band, k, seg_refs, nseg, pmask, prune, dex.p, dsd.p, dsi.p, dsw.p); }); }
         { Scope s(h, "k_knn_merge");
           hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)nb), dim3(64), 0, h->stream, dsd.p, dsi.p, dsw.p, nseg, k, (int)p0, didx.p, ddist.p, dwork.p); }
     }

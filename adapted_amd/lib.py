@@ -1419,28 +1419,35 @@ class Engine:
                                               out["lengths"], out["levels"], int(fp_ptr) if on_dev else out["fingerprints"], out["norm"]))
         return out
 
+    def _fp_rows(self, q, q_count, n, E, noun: str, sizes: str, shape: Optional[str] = None):
+        """fingerprint rows with their counts: a float64 [n, E] host array and a count per row, or two device pointers with ``n``
+        and ``E`` (the refusals call those arguments ``sizes`` and the array's shape ``shape``) -> (q, q_count, n, E, flags)"""
+        if isinstance(q, int):
+            if n is None or E is None or not isinstance(q_count, int):
+                raise ValueError("device %s need a device pointer to their counts, %s" % (noun, sizes))
+            _check_runtime_once_torch_is_here()
+            return q, q_count, int(n), int(E), ADP_IN_DEVICE
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.ndim != 2:
+            raise ValueError("%s: a float64 [%s] array" % (noun, shape or sizes.replace(" and ", ", ")))
+        n, E = q.shape
+        return q, self._per_read(q_count, n, "q_count"), n, E, 0
+
+    def _fp_table(self, t, t_count, noun: str, sizes: str, count_name: str):
+        """a host table with its counts: float64 [rows, E] and a count per row -> (t, t_count, rows, E)"""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError("%s: a float64 [%s] array" % (noun, sizes))
+        return t, self._per_read(t_count, t.shape[0], count_name), t.shape[0], t.shape[1]
+
     def dtw_assign(self, q, q_count, t, t_count, band: int = 0, nq: Optional[int] = None, Eq: Optional[int] = None,
                    want_dist: bool = True):
         """adp_dtw_assign: queries float64 [nq, Eq] with their counts (host arrays, or two device pointers with ``nq`` and ``Eq``:
         event_levels' fp_ptr and count_ptr), templates float64 [nt, Et] with their counts (host) -> (dist float64 [nq, nt], or
         None without ``want_dist``; best int32 [nq, 2]: the nearest and the second nearest template, -1 where there is none;
         bestdist float64 [nq, 2], NaN where -1)"""
-        t = np.ascontiguousarray(t, dtype=np.float64)
-        if t.ndim != 2:
-            raise ValueError("templates: a float64 [nt, Et] array")
-        nt, Et = t.shape
-        t_count = self._per_read(t_count, nt, "t_count")
-        if isinstance(q, int):
-            if nq is None or Eq is None or not isinstance(q_count, int):
-                raise ValueError("device queries need a device pointer to their counts, nq and Eq")
-            _check_runtime_once_torch_is_here()
-            flags, nq, Eq = ADP_IN_DEVICE, int(nq), int(Eq)
-        else:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.ndim != 2:
-                raise ValueError("queries: a float64 [nq, Eq] array")
-            flags, (nq, Eq) = 0, q.shape
-            q_count = self._per_read(q_count, nq, "q_count")
+        t, t_count, nt, Et = self._fp_table(t, t_count, "templates", "nt, Et", "t_count")
+        q, q_count, nq, Eq, flags = self._fp_rows(q, q_count, nq, Eq, "queries", "nq and Eq")
         dist = np.zeros((nq, nt)) if want_dist else None
         best = np.full((nq, 2), -1, dtype=np.int32)
         bestdist = np.full((nq, 2), np.nan)
@@ -1450,24 +1457,10 @@ class Engine:
         return dist, best, bestdist
 
     def _align_in(self, q, q_count, which, t, t_count, nq, Eq):
-        """the inputs adp_dtw_align and adp_dba_step share, as dtw_assign takes its own -> (q, q_count, which, nq, Eq, t, t_count, nt,
+        """the inputs adp_dtw_align and adp_dba_step share: dtw_assign's and ``which`` -> (q, q_count, which, nq, Eq, t, t_count, nt,
         Et, flags)"""
-        t = np.ascontiguousarray(t, dtype=np.float64)
-        if t.ndim != 2:
-            raise ValueError("templates: a float64 [nt, Et] array")
-        nt, Et = t.shape
-        t_count = self._per_read(t_count, nt, "t_count")
-        if isinstance(q, int):
-            if nq is None or Eq is None or not isinstance(q_count, int):
-                raise ValueError("device queries need a device pointer to their counts, nq and Eq")
-            _check_runtime_once_torch_is_here()
-            flags, nq, Eq = ADP_IN_DEVICE, int(nq), int(Eq)
-        else:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.ndim != 2:
-                raise ValueError("queries: a float64 [nq, Eq] array")
-            flags, (nq, Eq) = 0, q.shape
-            q_count = self._per_read(q_count, nq, "q_count")
+        t, t_count, nt, Et = self._fp_table(t, t_count, "templates", "nt, Et", "t_count")
+        q, q_count, nq, Eq, flags = self._fp_rows(q, q_count, nq, Eq, "queries", "nq and Eq")
         return q, q_count, self._per_read(which, nq, "which"), nq, Eq, t, t_count, nt, Et, flags
 
     def dtw_align(self, q, q_count, which, t, t_count, band: int = 0, nq: Optional[int] = None, Eq: Optional[int] = None,
@@ -1507,17 +1500,7 @@ class Engine:
         """adp_dtw_pairwise: fingerprints float64 [n, E] with their counts (host arrays, or two device pointers with ``n`` and
         ``E``) -> the symmetric DTW matrix float64 [n, n]; with ``out_ptr`` (device memory of n * n doubles) it is written there
         and None is returned"""
-        if isinstance(q, int):
-            if n is None or E is None or not isinstance(q_count, int):
-                raise ValueError("device fingerprints need a device pointer to their counts, n and E")
-            _check_runtime_once_torch_is_here()
-            flags, n, E = ADP_IN_DEVICE, int(n), int(E)
-        else:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.ndim != 2:
-                raise ValueError("fingerprints: a float64 [n, E] array")
-            flags, (n, E) = 0, q.shape
-            q_count = self._per_read(q_count, n, "q_count")
+        q, q_count, n, E, flags = self._fp_rows(q, q_count, n, E, "fingerprints", "n and E")
         if n == 0:
             raise ValueError("no fingerprints")
         out = np.zeros((n, n)) if out_ptr is None else None
@@ -1573,22 +1556,8 @@ class Engine:
         -1 for none) or None -> (idx int32 [nq, k]: the k nearest references in the order (distance, index), -1 where there is none;
         dist float64 [nq, k], NaN where -1; with ``want_work`` work int64 [nq, 3]: pairs finished, pairs abandoned, DP steps).
         ``prune=False``: every pair runs to the end (the same idx and dist)"""
-        r = np.ascontiguousarray(r, dtype=np.float64)
-        if r.ndim != 2:
-            raise ValueError("references: a float64 [nr, Er] array")
-        nr, Er = r.shape
-        r_count = self._per_read(r_count, nr, "r_count")
-        if isinstance(q, int):
-            if n is None or E is None or not isinstance(q_count, int):
-                raise ValueError("device queries need a device pointer to their counts, n and E")
-            _check_runtime_once_torch_is_here()
-            flags, nq, Eq = ADP_IN_DEVICE, int(n), int(E)
-        else:
-            q = np.ascontiguousarray(q, dtype=np.float64)
-            if q.ndim != 2:
-                raise ValueError("queries: a float64 [nq, Eq] array")
-            flags, (nq, Eq) = 0, q.shape
-            q_count = self._per_read(q_count, nq, "q_count")
+        r, r_count, nr, Er = self._fp_table(r, r_count, "references", "nr, Er", "r_count")
+        q, q_count, nq, Eq, flags = self._fp_rows(q, q_count, n, E, "queries", "n and E", shape="nq, Eq")
         k = int(k)
         if exclude is not None:
             exclude = self._per_read(exclude, nq, "exclude")

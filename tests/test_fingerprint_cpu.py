@@ -62,7 +62,9 @@ def test_the_new_header_defines_no_numeric_macro_and_lib_restates_the_kernels_co
     assert int(re.search(r"#define DTW_SCRATCH_MIB (\d+)", text).group(1)) == lib.DTW_SCRATCH_MIB == 512
     with open(os.path.join(ROOT, "adapted_amd", "csrc", "modules.hip")) as fh:
         entry = fh.read()
-    assert 'getenv("ADP_DTW_SCRATCH_MIB")' in entry and "((size_t)mib << 20) / (nts * 8)" in entry
+    # (the budget over the bytes of a row of the distance matrix: batch_rows states the division, adp_dtw_assign the row)
+    assert 'getenv("ADP_DTW_SCRATCH_MIB")' in entry and "batch_rows(mib, nts * 8, nqs, nts)" in entry
+    assert "size_t rows = ((size_t)mib << 20) / row_bytes;" in entry
 
 
 def test_null_handle_is_refused_and_wrong_types_never_enter_the_library():
