@@ -33,6 +33,7 @@ __device__ unsigned long long g_bs_tally[ADP_NTALLY][8] = {{0}};
 #include "polya_truncated.h"
 #include "adapter_front_revalidate.h"
 #include "llr_resegment.h"
+#include "cnn_second_resegment.h"
 #include "wave_stats.h"
 
 thread_local std::string g_err;
@@ -345,8 +346,9 @@ static int env_int(const char *name, int dflt)
 // phases' counts for adp_debug_fetch (10 / 11 / 12 / 25), zeroed by the phase that runs:
 // the fallback's [0] exception rows made, [1] rows re-validated; the second opinion's [0] rows replaced, [1] re-validated and still
 // failing, [2] minibatches without one; the truncation look's [0] eligible reads, [1] T1 passed, [2] rows replaced; the
-// re-segmentation's [0] eligible reads, [1] reads with a second poly(A) end, [2] rows replaced
-enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_RS = 13, OPW_END = 16 };
+// re-segmentation's [0] eligible reads, [1] reads with a second poly(A) end, [2] rows replaced; the same three of the re-segmentation
+// behind the second opinion (what = 26) and, as [3], the reads that one selected -- zeroed with its counts and read by arena_end
+enum { OPW_FB = 5, OPW_SO = 7, OPW_PT = 10, OPW_RS = 13, OPW_SR = 16, OPW_END = 20 };
 static unsigned int *phase_counts(adp_handle *h, int opw) { return h->op_used.as<unsigned int>() + opw; }
 static int arena_begin(adp_handle *h)
 {
@@ -357,22 +359,25 @@ static int arena_begin(adp_handle *h)
 // -> 0 done, 1 run the call again (arena grown), < 0 error
 // (cnn: the call ran the conv stack -- its out-of-range flag is read with the counter; set = repeat the call on the float32 kernels)
 // (n_sel: the call ran k_cnn_fb_select -- its count comes with the same copy; left 0 when the call is to be repeated)
-// (n_so: the same for k_cnn_so_select; n_pt: for k_pt_select, or k_rs_select)
-static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr, unsigned int *n_pt = nullptr)
+// (n_so: the same for k_cnn_so_select; n_pt: for k_pt_select, or k_rs_select; n_sr: for k_csr_select, whose word lies behind the counts)
+static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = nullptr, unsigned int *n_so = nullptr, unsigned int *n_pt = nullptr,
+                     unsigned int *n_sr = nullptr)
 {
     const bool conv_flag = cnn && h->cnn_mode == 1 && !h->cnn_redo_f32;
     if (n_sel) *n_sel = 0;
     if (n_so) *n_so = 0;
     if (n_pt) *n_pt = 0;
-    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel && !n_so && !n_pt) { h->op_last_used = 0; return 0; }
-    unsigned int w[5] = {0, 0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(w, h->op_used.p, n_pt ? 20 : 16, hipMemcpyDeviceToHost, h->stream));
+    if (n_sr) *n_sr = 0;
+    if (!h->cfg.detect_open_pores && !conv_flag && !n_sel && !n_so && !n_pt && !n_sr) { h->op_last_used = 0; return 0; }
+    unsigned int w[OPW_END] = {0};
+    HIPCHK(hipMemcpyAsync(w, h->op_used.p, n_sr ? OPW_END * 4 : (n_pt ? 20 : 16), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (conv_flag && w[1]) { h->cnn_redo_f32 = true; return 1; }
     const bool arena_ok = !h->cfg.detect_open_pores || (size_t)w[0] * 4 <= h->op_arena.cap;
     if (n_sel && arena_ok) *n_sel = w[2];
     if (n_so && arena_ok) *n_so = w[3];
     if (n_pt && arena_ok) *n_pt = w[4];
+    if (n_sr && arena_ok) *n_sr = w[OPW_SR + 3];
     if (!h->cfg.detect_open_pores) { h->op_last_used = 0; return 0; }
     const unsigned int used = w[0];
     h->op_last_used = used;
@@ -383,10 +388,11 @@ static int arena_end(adp_handle *h, bool cnn = false, unsigned int *n_sel = null
 
 // A call's attempts on the arena: attempt() runs behind arena_begin -> 0 done, 1 run the call again (arena_end grew the arena, or
 // the conv stack goes to float32), < 0 error.  A repeat drops what the attempt recorded in the handle's profile and its lanes'.
+// max_attempts: three, or what the call's phases need (cnn_after_first_pass)
 template <class F>
-static int call_attempts(adp_handle *h, adp_handle *const *lanes, int n_lanes, F &&attempt)
+static int call_attempts(adp_handle *h, adp_handle *const *lanes, int n_lanes, F &&attempt, int max_attempts = 3)
 {
-    for (int a = 0; a < 3; a++) {
+    for (int a = 0; a < max_attempts; a++) {
         RCCHK(arena_begin(h));
         const int rc = attempt();
         if (rc <= 0) return rc;
@@ -903,31 +909,32 @@ static int reseg_supported(const adp_handle *h, int flags)
     if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "ADP_LLR_RESEGMENT does not go with the single-read layout"; return ADP_ERR_UNSUPPORTED; }
     return 0;
 }
-// The second segmentation, its validation and the merge for the n_rs selected reads, enqueued on the handle's stream.  The first
-// pass has drained: its stage buffers on this handle are spent (a grouped call's owner has none yet) and take the subset's trace
-// phase, read j of the subset at position j.  The second rows have a buffer of their own (the handle's may be the call's); their
-// open-pore lists append to the call's arena: the caller looks at its counter once more.
-// mbs: the call's minibatch states (the handle's own, or the copies a grouped call's lanes left in rs_mbs)
-static int reseg_run(adp_handle *h, const float *dsig, const int32_t *dlen, int m, int minibatch, int flags, adp_row *rows, const MbState *mbs, int n_rs)
-{
-    hipStream_t st = h->stream;
-    RCCHK(alloc_all(h, n_rs, true));
-    const size_t N = (size_t)n_rs;
+// the per-subset arrays of a re-segmentation over (up to) N reads: the bounds and adapter starts of its validation, full_len,
+// polya_end_topk's None-ness, each read's own minibatch state, the rows of the validation
+struct RsPieces {
     Piece<int64_t> b2, starts; Piece<int32_t> dlen_sub; Piece<int8_t> tsub; Piece<MbState> mbs_sub; Piece<adp_row> rows2;
-    RCCHK(sub_carve(h, [&](Carve &c) {
+    void take(Carve &c, size_t N)
+    {
         b2 = c.take<int64_t>(2 * N); starts = c.take<int64_t>(N); dlen_sub = c.take<int32_t>(N); tsub = c.take<int8_t>(N);
         mbs_sub = c.take<MbState>(N); rows2 = c.take<adp_row>(N);
-    }));
-    const int32_t *sel = h->rs_sel.as<int32_t>();
-    unsigned int *counts = phase_counts(h, OPW_RS);
-    { Scope s(h, "k_rs_gather");
-      hipLaunchKernelGGL(k_rs_gather, dim3((n_rs + 255) / 256), dim3(256), 0, st, sel, n_rs, minibatch, mbs, dlen, (const adp_row *)rows, h->ds, h->pos_off,
-                         dlen_sub.p, starts.p, b2.p, tsub.p, h->adapter_idx.as<int32_t>(), mbs_sub.p); }
+    }
+};
+// What lies between a re-segmentation's gather and its merge (the LLR primary's, reseg_run; the one behind the CNN primary's second
+// opinion, cnn_sr_run): the second segmentation of the n_rs gathered reads -- sig: the subset's rows read where they lie; the
+// gather left pass 2's starts in h->adapter_idx -- p2 into the bounds with counts[1], and the validation from the reads' adapter
+// starts into p.rows2.  tails_nan: the pooling pass stops at a read's end (ADP_TAILS_NAN, or int16 rows)
+template <class SUB>
+static int reseg_trace_validate(adp_handle *h, SUB sig, const RsPieces &p, int m, bool tails_nan, int n_rs, unsigned int *counts)
+{
+    hipStream_t st = h->stream;
+    const size_t N = (size_t)n_rs;
+    const Piece<int64_t> &b2 = p.b2, &starts = p.starts; const Piece<int32_t> &dlen_sub = p.dlen_sub; const Piece<int8_t> &tsub = p.tsub;
+    const Piece<MbState> &mbs_sub = p.mbs_sub; const Piece<adp_row> &rows2 = p.rows2;
     // the trace phase as llr_enqueue runs it (an eligible read has a poly(A) end: h->L > 0), every read its own "minibatch"
     { Scope s(h, "k_norm_pool (resegment)");
-      hipLaunchKernelGGL((k_norm_pool<SigIdx>), dim3(n_rs), dim3(256), (size_t)NP_TILE * h->ds * 4, st, SigIdx{dsig, sel}, m, h->T, h->off, h->ds, h->L, h->Lp, 1,
+      hipLaunchKernelGGL((k_norm_pool<SUB>), dim3(n_rs), dim3(256), (size_t)NP_TILE * h->ds * 4, st, sig, m, h->T, h->off, h->ds, h->L, h->Lp, 1,
                          (const MbState *)mbs_sub.p, h->down.as<float>(), h->nvalid.as<int32_t>(), (const int64_t *)nullptr, (const int32_t *)dlen_sub.p,
-                         (flags & ADP_TAILS_NAN) ? 1 : 0); }
+                         tails_nan ? 1 : 0); }
     { Scope s(h, "k_cumsum (resegment)");
       launch_cumsum(h, n_rs); }
     double *pkvp = (env_int("ADP_PK_VALUES", 1) && h->pkv.cap >= N * (h->Lp / 2 + 1) * 8) ? h->pkv.as<double>() : nullptr;
@@ -946,9 +953,27 @@ static int reseg_run(adp_handle *h, const float *dsig, const int32_t *dlen, int 
     { Scope s(h, "k_rs_bounds");
       hipLaunchKernelGGL(k_rs_bounds, dim3((n_rs + 255) / 256), dim3(256), 0, st, (const int32_t *)h->polya_idx.as<int32_t>(), n_rs, h->ds, h->pos_off, b2.p, tsub.p, counts); }
     const ValBufs vb{b2.p, tsub.p, rows2.p};
-    RCCHK(launch_validate_t<true>(h, SigIdx{dsig, sel}, dlen_sub.p, n_rs, m, 1, n_rs, false, &vb, false, starts.p));
+    return launch_validate_t<true>(h, sig, dlen_sub.p, n_rs, m, 1, n_rs, false, &vb, false, starts.p);
+}
+// The second segmentation, its validation and the merge for the n_rs selected reads, enqueued on the handle's stream.  The first
+// pass has drained: its stage buffers on this handle are spent (a grouped call's owner has none yet) and take the subset's trace
+// phase, read j of the subset at position j.  The second rows have a buffer of their own (the handle's may be the call's); their
+// open-pore lists append to the call's arena: the caller looks at its counter once more.
+// mbs: the call's minibatch states (the handle's own, or the copies a grouped call's lanes left in rs_mbs)
+static int reseg_run(adp_handle *h, const float *dsig, const int32_t *dlen, int m, int minibatch, int flags, adp_row *rows, const MbState *mbs, int n_rs)
+{
+    hipStream_t st = h->stream;
+    RCCHK(alloc_all(h, n_rs, true));
+    RsPieces p;
+    RCCHK(sub_carve(h, [&](Carve &c) { p.take(c, (size_t)n_rs); }));
+    const int32_t *sel = h->rs_sel.as<int32_t>();
+    unsigned int *counts = phase_counts(h, OPW_RS);
+    { Scope s(h, "k_rs_gather");
+      hipLaunchKernelGGL(k_rs_gather, dim3((n_rs + 255) / 256), dim3(256), 0, st, sel, n_rs, minibatch, mbs, dlen, (const adp_row *)rows, h->ds, h->pos_off,
+                         p.dlen_sub.p, p.starts.p, p.b2.p, p.tsub.p, h->adapter_idx.as<int32_t>(), p.mbs_sub.p); }
+    RCCHK(reseg_trace_validate(h, SigIdx{dsig, sel}, p, m, (flags & ADP_TAILS_NAN) != 0, n_rs, counts));
     { Scope s(h, "k_rs_merge");
-      hipLaunchKernelGGL(k_rs_merge, dim3(n_rs), dim3(64), 0, st, sel, n_rs, (const adp_row *)rows2.p, rows, counts); }
+      hipLaunchKernelGGL(k_rs_merge, dim3(n_rs), dim3(64), 0, st, sel, n_rs, (const adp_row *)p.rows2.p, rows, counts); }
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1107,6 +1132,7 @@ static int llr_pipeline(adp_handle *h, const float *signals, const int32_t *full
     if (!h || !signals || !full_len || n < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (h->layout == ADP_LAYOUT_SINGLE_READ && minibatch != 1) { g_err = "the single-read layout normalises every read on its own: minibatch must be 1"; return ADP_ERR_INVALID; }
+    if (flags & ADP_CNN_SECOND_RESEGMENT) { g_err = "ADP_CNN_SECOND_RESEGMENT goes with adp_detect_cnn and ADP_CNN_SECOND_LLR (the CNN primary)"; return ADP_ERR_UNSUPPORTED; }
     h->pt_looked = false; h->rs_ran = false;
     if (reseg_wanted(flags, rows_out)) RCCHK(reseg_supported(h, flags));
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
@@ -1146,6 +1172,7 @@ int adp_detect_llr_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_llr)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT takes float32 input (adp_calibrate_i16 + adp_detect_llr)"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_CNN_SECOND_RESEGMENT) { g_err = "ADP_CNN_SECOND_RESEGMENT goes with adp_detect_cnn and ADP_CNN_SECOND_LLR (the CNN primary)"; return ADP_ERR_UNSUPPORTED; }
     h->rs_ran = false;
     RCCHK(begin_call(h));
     // (samples at or beyond min(full_len, m) read as NaN: the padding is implied, so the passes always stop at a read's end)
@@ -1218,6 +1245,7 @@ int adp_detect_start_peak(adp_handle *h, const float *signals, const int32_t *fu
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED goes with adp_detect_llr and adp_detect_cnn"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr"; return ADP_ERR_UNSUPPORTED; }
+    if (flags & ADP_CNN_SECOND_RESEGMENT) { g_err = "ADP_CNN_SECOND_RESEGMENT goes with adp_detect_cnn and ADP_CNN_SECOND_LLR (the CNN primary)"; return ADP_ERR_UNSUPPORTED; }
     RCCHK(begin_call(h));
     const float *dsig; const int32_t *dlen;
     int rc = stage_inputs(h, signals, full_len, n_reads, m, flags, &dsig, &dlen);
@@ -1954,12 +1982,21 @@ static int cnn_second_select(adp_handle *h, int n, const adp_row *rows)
 // adp_detect_llr computes -- with its boundaries in a buffer of this phase (the handle's bounds / topk_none / rows hold the CNN
 // path's).  The validation (k = 1) reads the selected rows in place and leaves its rows in the phase's own; the merge copies those
 // that passed into `rows`.  Open-pore lists of the second rows append to the call's arena: the caller looks at its counter once more.
+//
+// sr (ADP_CNN_SECOND_RESEGMENT, else null; cnn_second_resegment.h): the re-segmentation of the reads whose second row fails too.  Its
+// arrays -- sized for the whole subset, which bounds its selection -- are pieces of the SAME carve, so that the second rows it reads
+// stay where they are until its merge has run; its selection is enqueued here, behind the merge, and its count comes back with
+// the arena counter the caller reads next.
+struct SrPieces { RsPieces rs; Piece<int32_t> sel_j, sel_r; const adp_row *rows2_so = nullptr; };
+static bool cnn_sr_wanted(int flags, const adp_row *rows) { return (flags & ADP_CNN_SECOND_RESEGMENT) && (flags & ADP_CNN_SECOND_LLR) && rows; }
+static int cnn_tails(int flags, SigF32) { return flags & ADP_TAILS_NAN; }
+// (int16 rows: the padding is implied, so the passes always stop at a read's end -- as adp_detect_llr_i16 runs them)
+static int cnn_tails(int, SigI16) { return ADP_TAILS_NAN; }
 template <class SIG>
-static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so)
+static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows, int n_so, SrPieces *sr)
 {
     hipStream_t st = h->stream;
-    // (int16 rows: the padding is implied, so the passes always stop at a read's end -- as adp_detect_llr_i16 runs them)
-    const int tails = std::is_same<SIG, SigF32>::value ? (flags & ADP_TAILS_NAN) : ADP_TAILS_NAN;
+    const int tails = cnn_tails(flags, dsig);
     int rc = llr_enqueue(h, dsig, dlen, n, m, minibatch, tails, nullptr, 0, nullptr, nullptr, 7, nullptr);
     if (rc) return rc;
     const size_t R = (size_t)n, N = (size_t)n_so;
@@ -1967,6 +2004,7 @@ static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
     RCCHK(sub_carve(h, [&](Carve &c) { // LLR bounds and topk_none of all reads; of the subset: bounds of the validation, full_len, topk_none, rows
         ball = c.take<int64_t>(2 * R); tall = c.take<int8_t>(R);
         b2 = c.take<int64_t>(2 * N); dlen_sub = c.take<int32_t>(N); tsub = c.take<int8_t>(N); rows2 = c.take<adp_row>(N);
+        if (sr) { sr->rs.take(c, N); sr->sel_j = c.take<int32_t>(N); sr->sel_r = c.take<int32_t>(N); }
     }));
     unsigned int *counts = phase_counts(h, OPW_SO);
     const int32_t *sel = h->so_sel.as<int32_t>();
@@ -1983,6 +2021,49 @@ static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
     if (rc) return rc;
     { Scope s(h, "k_cnn_so_merge");
       hipLaunchKernelGGL(k_cnn_so_merge, dim3(n_so), dim3(64), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)rows2, rows, counts); }
+    if (sr) {
+        unsigned int *sr_counts = phase_counts(h, OPW_SR);
+        sr->rows2_so = rows2;
+        h->sr_ran = true;
+        HIPCHK(hipMemsetAsync(sr_counts, 0, 16, st)); // (the three counts and the selection's)
+        Scope s(h, "k_csr_select");
+        hipLaunchKernelGGL(k_csr_select, dim3(1), dim3(SEL_THREADS), 0, st, sel, n_so, minibatch, mbs, (const adp_row *)rows2, sr->sel_j.p, sr->sel_r.p,
+                           sr_counts + 3, sr_counts);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- the re-segmentation behind the second opinion (ADP_CNN_SECOND_RESEGMENT, cnn_second_resegment.h) -----------------------------------
+// what the flag cannot go with, said before anything is launched
+static int cnn_sr_supported(const adp_handle *h, int flags, const adp_row *rows)
+{
+    if (!(flags & ADP_CNN_SECOND_LLR) || !rows) { g_err = "ADP_CNN_SECOND_RESEGMENT needs ADP_CNN_SECOND_LLR and rows_out"; return ADP_ERR_INVALID; }
+    if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_CNN_SECOND_RESEGMENT does not go with ADP_FLAG_TRUNCATED (the truncation look validates from start 0)"; return ADP_ERR_UNSUPPORTED; }
+    if (h->cfg.mvs_detect_overwrite) { g_err = "ADP_CNN_SECOND_RESEGMENT does not go with mvs_detect_overwrite"; return ADP_ERR_UNSUPPORTED; }
+    if (h->layout == ADP_LAYOUT_SINGLE_READ) { g_err = "ADP_CNN_SECOND_RESEGMENT does not go with the single-read layout"; return ADP_ERR_UNSUPPORTED; }
+    return 0;
+}
+// The second segmentation, its validation and the merge for the n_sr reads k_csr_select listed, enqueued on the handle's stream
+// behind cnn_second_run, whose carve `sr` is a part of.  The stage buffers llr_enqueue filled over all reads of the call on THIS
+// handle (pooled signal, cumulative sums, trace, peak lists) were last read by k_llr_bounds, which ran in front of the second
+// opinion's validation on the same stream: they are spent and take the subset's trace phase, read i of the subset at position i
+// (alloc_all over n reads covers n_sr <= n).  The minibatch states stay: llr_enqueue ran over all reads, so h->mbs is the call's.
+// The new rows' open-pore lists append to the call's arena: the caller looks at its counter once more.
+template <class SIG>
+static int cnn_sr_run(adp_handle *h, SIG dsig, const int32_t *dlen, int m, int minibatch, int flags, adp_row *rows, const SrPieces &sr, int n_sr)
+{
+    hipStream_t st = h->stream;
+    unsigned int *counts = phase_counts(h, OPW_SR);
+    const RsPieces &p = sr.rs;
+    { Scope s(h, "k_csr_gather");
+      hipLaunchKernelGGL(k_csr_gather, dim3((n_sr + 255) / 256), dim3(256), 0, st, (const int32_t *)sr.sel_j.p, (const int32_t *)sr.sel_r.p, n_sr, minibatch,
+                         (const MbState *)h->mbs.as<MbState>(), dlen, sr.rows2_so, h->ds, h->pos_off, p.dlen_sub.p, p.starts.p, p.b2.p, p.tsub.p,
+                         h->adapter_idx.as<int32_t>(), p.mbs_sub.p); }
+    RCCHK(reseg_trace_validate(h, sig_subset(dsig, sr.sel_r.p), p, m, cnn_tails(flags, dsig) != 0, n_sr, counts));
+    { Scope s(h, "k_csr_merge");
+      hipLaunchKernelGGL(k_csr_merge, dim3(n_sr), dim3(64), 0, st, (const int32_t *)sr.sel_j.p, (const int32_t *)sr.sel_r.p, n_sr, (const adp_row *)p.rows2.p,
+                         sr.rows2_so, rows, counts); }
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2001,11 +2082,18 @@ static int cnn_second_run(adp_handle *h, SIG dsig, const int32_t *dlen, int n, i
 // fallback's (and once more behind a fallback merge), its count comes back in the same copy, and a call whose reads all passed
 // ends there.  Its rows' open-pore lists depend on the LLR adapter end: they may want more than the first pass did, and the
 // counter is cumulative over the call -- attempt 1 can fall short in the first pass, attempt 2 in this phase, attempt 3 holds both.
+// The re-segmentation behind the second opinion (ADP_CNN_SECOND_RESEGMENT) is a fourth phase that writes lists, behind one more
+// look at the counter; its rows' lists depend on the second opinion's "poly(A) end" and no earlier phase bounds them.  The bound in
+// general: the counter adds up what the call WANTED, every phase wants the same in every attempt, and an attempt that falls short in
+// phase p leaves an arena of twice the demand up to and including p -- so the next attempt gets past p, and a call needs at most one
+// attempt per phase that can want more than the phases in front of it, plus the one that succeeds.  The fallback cannot (above), so
+// that is first pass, second opinion, re-segmentation: FOUR attempts with the flag (cnn_attempts), three without, as before.
 // The start-peak overlay: K1 ran beside the first pass and decorated its rows; the fallback and the second opinion deliver whole
 // rows of their own validation, so the overlay is applied once more to the call's row buffer behind each (k_sp_decorate is
 // idempotent); the truncation look's merge keeps the columns (k_pt_merge).
 // The truncation look (ADP_FLAG_TRUNCATED) comes behind all of that, on every read's final row: one more synchronisation for its
 // T1 count, and T2 only where a tail window passed.
+static int cnn_attempts(int flags, const adp_row *rows) { return (flags & ADP_CNN_SECOND_RESEGMENT) && (flags & ADP_CNN_SECOND_LLR) && rows ? 4 : 3; }
 template <class SIG>
 static int cnn_after_first_pass(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int m, int minibatch, int flags, adp_row *rows,
                                 const int64_t *bounds, int bstride, const SpOut *sp, bool *changed)
@@ -2030,11 +2118,22 @@ static int cnn_after_first_pass(adp_handle *h, SIG dsig, const int32_t *dlen, in
     if (rc == 0 && n_so) {
         *changed = true;
         h->so_n_sel = n_so;
-        RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows, (int)n_so));
+        const bool sr = cnn_sr_wanted(flags, rows);
+        SrPieces srp;
+        unsigned int n_sr = 0;
+        RCCHK(cnn_second_run(h, dsig, dlen, n, m, minibatch, flags, rows, (int)n_so, sr ? &srp : nullptr));
         if (sp) cnn_sp_decorate(h, sp, rows, n); // (the second opinion's rows come bare)
         HIPCHK(hipStreamSynchronize(h->stream));
-        rc = arena_end(h);
+        rc = arena_end(h, false, nullptr, nullptr, nullptr, sr ? &n_sr : nullptr);
         if (rc < 0) return rc;
+        if (rc == 0 && n_sr) {
+            if (n_sr > n_so) { g_err = "ADP_CNN_SECOND_RESEGMENT: selection count out of range"; return ADP_ERR_HIP; }
+            RCCHK(cnn_sr_run(h, dsig, dlen, m, minibatch, flags, rows, srp, (int)n_sr));
+            if (sp) cnn_sp_decorate(h, sp, rows, n); // (the re-segmented rows come bare as well)
+            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = arena_end(h);
+            if (rc < 0) return rc;
+        }
     }
     if constexpr (std::is_same<SIG, SigF32>::value) { // (a float32-row phase: adp_detect_cnn_i16 refuses the flag)
     if (rc == 0 && trunc_wanted(flags, rows)) {
@@ -2085,7 +2184,7 @@ static int cnn_grouped(adp_handle *h, SIG dsig, const int32_t *dlen, int n, int 
         for (int i = 0; i < n_lanes; i++) HIPCHK(hipStreamSynchronize(lanes[i]->stream));
         bool changed;
         return cnn_after_first_pass(h, dsig, dlen, n, m, minibatch, flags, rows_dev, bounds_dev, 1 + kk, sp, &changed);
-    }));
+    }, cnn_attempts(flags, rows_out)));
     if (rows_out && !out_dev) HIPCHK(hipMemcpyAsync(rows_out, h->rows.p, (size_t)n * sizeof(adp_row), hipMemcpyDeviceToHost, h->stream));
     if (bounds_out) HIPCHK(hipMemcpyAsync(bounds_out, h->bounds.p, (size_t)n * (1 + kk) * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2148,7 +2247,7 @@ static int cnn_pipeline_t(adp_handle *h, SIG dsig, const int32_t *dlen, int n_re
             HIPCHK(hipStreamSynchronize(h->stream));
         }
         return rc;
-    });
+    }, cnn_attempts(flags, rows_out));
 }
 } // extern "C++"
 
@@ -2160,7 +2259,8 @@ int adp_detect_cnn(adp_handle *h, const float *signals, const int32_t *full_len,
     if (!h || !signals || !full_len || n_reads < 1 || minibatch < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (n_reads > h->max_reads || m != h->m) { g_err = "n_reads/m exceed the handle's capacity"; return ADP_ERR_CAPACITY; }
     if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr (the LLR primary)"; return ADP_ERR_UNSUPPORTED; }
-    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
+    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false; h->sr_ran = false;
+    if (flags & ADP_CNN_SECOND_RESEGMENT) RCCHK(cnn_sr_supported(h, flags, rows_out));
     if (trunc_wanted(flags, rows_out)) RCCHK(trunc_supported(h));
     RCCHK(begin_call(h));
     RCCHK(cnn_ready(h, m));
@@ -2182,7 +2282,8 @@ int adp_detect_cnn_i16(adp_handle *h, const int16_t *raw, const int32_t *full_le
     if (m & 3) { g_err = "int16 rows need m % 4 == 0 (8-byte aligned rows)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_FLAG_TRUNCATED) { g_err = "ADP_FLAG_TRUNCATED takes float32 input (adp_calibrate_i16 + adp_detect_cnn)"; return ADP_ERR_UNSUPPORTED; }
     if (flags & ADP_LLR_RESEGMENT) { g_err = "ADP_LLR_RESEGMENT goes with adp_detect_llr (the LLR primary)"; return ADP_ERR_UNSUPPORTED; }
-    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false;
+    h->fb_n_sel = h->so_n_sel = 0; h->pt_looked = false; h->sr_ran = false;
+    if (flags & ADP_CNN_SECOND_RESEGMENT) RCCHK(cnn_sr_supported(h, flags, rows_out));
     RCCHK(begin_call(h));
     RCCHK(cnn_ready(h, m));
     // (samples at or beyond min(full_len, m) read as NaN: the padding is implied)
@@ -2430,6 +2531,11 @@ int adp_debug_fetch(adp_handle *h, int what, void *host_out, uint64_t bytes)
         if (bytes < 12) return ADP_ERR_INVALID;
         int32_t c[3] = {0, 0, 0};
         if (h->rs_ran) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_RS), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+        memcpy(host_out, c, 12); return ADP_OK; }
+    case 26: { // the re-segmentation behind the last adp_detect_cnn(_i16) call's second opinion: eligible reads, reads with a second poly(A) end, rows replaced
+        if (bytes < 12) return ADP_ERR_INVALID;
+        int32_t c[3] = {0, 0, 0};
+        if (h->sr_ran) { HIPCHK(hipMemcpyAsync(c, phase_counts(h, OPW_SR), 12, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
         memcpy(host_out, c, 12); return ADP_OK; }
     case 9: src = h->have_series.p; if (bytes > h->have_series.cap) return ADP_ERR_INVALID; break; // 1: the read's moving-window series were prepared by a series kernel
     // what the kernels of phase C hand to each other (llr_stream.h, peaks.h), each copy bounded by its buffer

@@ -94,6 +94,9 @@ struct adp_handle {
     // whether the last detect call ran the phase (adp_debug_fetch 25)
     DevBuf rs_sel, rs_mbs;
     bool rs_ran = false;
+    // the same phase behind the second opinion of adp_detect_cnn (ADP_CNN_SECOND_RESEGMENT, cnn_second_resegment.h): its arrays are
+    // pieces of the second opinion's carve; whether the last adp_detect_cnn(_i16) call ran its selection (adp_debug_fetch 26)
+    bool sr_ran = false;
     unsigned int op_last_used = 0;
     bool cnn_have_w = false;
     int cnn_Lpad = 0, cnn_L1 = 0, cnn_chunk = 0, n_cu = 256;

@@ -56,8 +56,24 @@ __global__ void __launch_bounds__(SEL_THREADS) k_rs_select(const adp_row *__rest
     if (threadIdx.x == 0) { *count_out = (unsigned int)total; counts[0] = (unsigned int)total; }
 }
 
-// bounds2 [n_sel, 2]: (p1, 0 until k_rs_bounds); start_sub: pass 2's trace_start in pooled points; mbs_sub [n_sel]: the state of each
-// read's own minibatch, for kernels that take mbs[r / 1]
+// What the second segmentation of one selected read starts from, position j of the subset's arrays.  row: the failing row that holds
+// a1 and p1 (k_rs_gather: the call's row of the read; k_csr_gather, cnn_second_resegment.h: the second opinion's); mb: the state of the
+// read's own minibatch.  bounds2 [n_sel, 2]: (p1, 0 until k_rs_bounds); start_sub: pass 2's trace_start in pooled points; mbs_sub
+// [n_sel]: for kernels that take mbs[r / 1]
+static __device__ __forceinline__ void rs_gather_read(int j, const adp_row *row, int32_t len, const MbState &mb, int ds, int off,
+                                                      int32_t *__restrict__ len_sub, int64_t *__restrict__ starts, int64_t *__restrict__ bounds2,
+                                                      int8_t *__restrict__ topk_sub, int32_t *__restrict__ start_sub, MbState *__restrict__ mbs_sub)
+{
+    const int64_t a1 = (int64_t)row->col[ADP_C_PRIMARY_ADAPTER_END], p1 = (int64_t)row->col[ADP_C_PRIMARY_POLYA_END];
+    len_sub[j] = len;
+    starts[j] = a1;
+    bounds2[2 * j] = p1;
+    bounds2[2 * j + 1] = 0;
+    topk_sub[j] = 1;
+    start_sub[j] = (int32_t)((p1 - off) / ds);
+    mbs_sub[j] = mb;
+}
+
 __global__ void __launch_bounds__(256) k_rs_gather(const int32_t *__restrict__ sel, int n_sel, int mbsize, const MbState *__restrict__ mbs,
                                                    const int32_t *__restrict__ full_len, const adp_row *__restrict__ rows, int ds, int off,
                                                    int32_t *__restrict__ len_sub, int64_t *__restrict__ starts, int64_t *__restrict__ bounds2,
@@ -66,14 +82,7 @@ __global__ void __launch_bounds__(256) k_rs_gather(const int32_t *__restrict__ s
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n_sel) return;
     const int r = sel[j];
-    const int64_t a1 = (int64_t)rows[r].col[ADP_C_PRIMARY_ADAPTER_END], p1 = (int64_t)rows[r].col[ADP_C_PRIMARY_POLYA_END];
-    len_sub[j] = full_len[r];
-    starts[j] = a1;
-    bounds2[2 * j] = p1;
-    bounds2[2 * j + 1] = 0;
-    topk_sub[j] = 1;
-    start_sub[j] = (int32_t)((p1 - off) / ds);
-    mbs_sub[j] = mbs[r / mbsize];
+    rs_gather_read(j, rows + r, full_len[r], mbs[r / mbsize], ds, off, len_sub, starts, bounds2, topk_sub, start_sub, mbs_sub);
 }
 
 // as k_llr_bounds makes a poly(A) end from a pooled index (validate.h): p > 0 -> p * ds + off, and polya_end_topk is given then

@@ -247,6 +247,7 @@ def _detect_rows(eng, sig, lens, model, spc, dlen: Optional[int] = None, n: Opti
     host; or resident rows, sig and dlen (int32 [n]) pointers, n given and lens the host's copy of the lengths -- float32 rows,
     or with calibration = (dscale, doffset) pointers raw int16 rows (adp_detect_cnn_i16)."""
     resident, int16 = dlen is not None, calibration is not None
+    lib.second_opinion_flags(second_opinion)  # (a ValueError for a value it does not know, before anything else)
     _refuse_host_forms(conv, fallback, with_start_peak, host_forms, int16, flag_truncated)
     if not resident:
         n = sig.shape[0]
@@ -329,7 +330,11 @@ def detect_rows_second_opinion(eng, sig: np.ndarray, lens: np.ndarray, model, sp
     """detect_rows with the LLR second opinion (ADP_CNN_SECOND_LLR): a read whose row fails gets the row combined_detect_llr2
     returns for it on this batch, where that row passes (``reserved_`` bit 0 marks it; lib.rows_to_results names its primary
     columns ``llr_*``).  An extension: the reference runs one primary per configuration.  ONE library call.
-    with_start_peak: the overlay of detect_rows_start_peak on the rows this call delivers, the rescued ones included."""
+    with_start_peak: the overlay of detect_rows_start_peak on the rows this call delivers, the rescued ones included.
+    second_opinion: True / "llr"; or "llr_resegment" -- a read whose second opinion fails behind a first change point is segmented
+    once more from that opinion's poly(A) end and validated from its adapter end (ADP_CNN_SECOND_RESEGMENT, an extension, untuned;
+    ``reserved_`` bits 0 and 5-9, ``llr_detect_log`` says so); the resident and int16 entries below take the same values.
+    Anything else is a ValueError (lib.second_opinion_flags)."""
     return _detect_rows(eng, sig, lens, model, spc, conv=conv, fallback=fallback, second_opinion=second_opinion, flag_truncated=flag_truncated,
                         with_start_peak=with_start_peak)
 
@@ -356,10 +361,10 @@ def detect_rows_device_i16(eng, draw: int, dlen: int, dscale: int, doffset: int,
 
 
 def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc, device: int = 0,
-                            flag_truncated: bool = False, with_start_peak: bool = False) -> List[DetectResults]:
+                            flag_truncated: bool = False, with_start_peak: bool = False, second_opinion="llr") -> List[DetectResults]:
     """combined_detect_cnn, and for the reads it fails combined_detect_llr2 on the same batch where that passes (an extension;
     such results carry ``llr_adapter_end`` / ``llr_polya_end`` instead of the ``cnn_*`` pair).  Always a list.
-    with_start_peak: as combined_detect_cnn's."""
+    with_start_peak: as combined_detect_cnn's.  second_opinion: "llr", or "llr_resegment" as detect_rows_second_opinion takes it."""
     from .combined import _as_batch, get_engine
 
     sig, lens = _as_batch(batch_of_signals, full_signal_lens)
@@ -369,7 +374,7 @@ def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.n
     eng = get_engine(spc, n, m, device)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        rows = _detect_rows(eng, sig, lens, model, spc, second_opinion=True, flag_truncated=flag_truncated, with_start_peak=with_start_peak)
+        rows = _detect_rows(eng, sig, lens, model, spc, second_opinion=second_opinion, flag_truncated=flag_truncated, with_start_peak=with_start_peak)
     return lib.rows_to_results(rows, "cnn", consume=True)
 
 

@@ -188,3 +188,14 @@ def combined_detect_cnn_llr(batch_of_signals: np.ndarray, full_signal_lens: np.n
     from . import cnn as _cnn
 
     return _cnn.combined_detect_cnn_llr(batch_of_signals, full_signal_lens, model, spc, device=device)
+
+
+def combined_detect_cnn_llr_resegment(batch_of_signals: np.ndarray, full_signal_lens: np.ndarray, model, spc,
+                                      device: int = 0) -> List[DetectResults]:
+    """combined_detect_cnn_llr, and for the reads whose LLR second opinion fails behind a first change point the boundaries of one
+    more segmentation from that opinion's poly(A) end, validated from its adapter end, where they pass (ADP_CNN_SECOND_RESEGMENT,
+    include/adapted_hip_second_resegment.h: an extension, untuned, nothing validated on real data).  Such results carry the
+    ``llr_*`` pair and ``llr_detect_log`` = "resegmented: first pass failed (<reason>)".  Always a list."""
+    from . import cnn as _cnn
+
+    return _cnn.combined_detect_cnn_llr(batch_of_signals, full_signal_lens, model, spc, device=device, second_opinion="llr_resegment")

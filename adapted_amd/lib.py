@@ -29,6 +29,7 @@ ADP_CNN_SECOND_LLR = 1 << 18  # adp_detect_cnn: reads that fail get the LLR path
 ADP_FLAG_TRUNCATED = 1 << 19  # adp_detect_llr / adp_detect_cnn: flag poly(A) tails cut off by the preload window (row["reserved_"] bits 1, 2)
 ADP_POLYA_TRUNCATED = 1 << 20  # adp_validate_candidates: Boundaries.polya_truncated is True -- no RNA partition
 ADP_LLR_RESEGMENT = 1 << 21  # adp_detect_llr: re-segment failed reads behind their first change point (row["reserved_"] bits 5-9)
+ADP_CNN_SECOND_RESEGMENT = 1 << 23  # adp_detect_cnn(_i16), with ADP_CNN_SECOND_LLR: re-segment the reads the second opinion fails too
 ROW_FROM_SECOND_LLR = 1  # bits of row["reserved_"]
 ROW_POLYA_TRUNCATED = 2  # the poly(A) runs into the end of the preloaded window
 ROW_TRUNC_LOOKED = 4  # the call looked for that (every row of a call made with ADP_FLAG_TRUNCATED)
@@ -274,7 +275,8 @@ def load():
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
                             + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())
-                            + list(CLUSTER_PROTOTYPES.items()) + list(KNN_PROTOTYPES.items())):
+                            + list(CLUSTER_PROTOTYPES.items()) + list(KNN_PROTOTYPES.items())
+                            + list(SECOND_RESEGMENT_PROTOTYPES.items())):
             ret, params = proto.split(":")
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = _RETURNS[ret], [_argtype(kind) for kind in params.split()]
@@ -539,6 +541,11 @@ KNN_NR_MAX = 262144
 # tests/test_resegment_cpu.py holds this table against its header
 RESEGMENT_PROTOTYPES: dict = {}
 
+# include/adapted_hip_second_resegment.h (the header adapted_hip.h includes for the same re-segmentation behind the CNN primary's LLR
+# second opinion, an extension): a flag of adp_detect_cnn(_i16) and a selector of adp_debug_fetch -- no entry point, no row bit;
+# tests/test_cnn_second_resegment_cpu.py holds this table against its header
+SECOND_RESEGMENT_PROTOTYPES: dict = {}
+
 # include/adapted_hip_csv.h (the header adapted_hip.h includes for the CSV text of one output file's rows, an extension);
 # tests/test_native_csv_cpu.py holds this table against its header
 CSV_PROTOTYPES = {
@@ -593,8 +600,25 @@ _OPTION_FLAGS = {"with_start_peak": ADP_WITH_START_PEAK, "tails_nan": ADP_TAILS_
                  "fallback": ADP_CNN_FALLBACK, "second_opinion": ADP_CNN_SECOND_LLR, "resegment": ADP_LLR_RESEGMENT}
 
 
+# what a CNN call's ``second_opinion`` argument may say: nothing, the LLR second opinion, or that with the re-segmentation of the
+# reads it fails too (ADP_CNN_SECOND_RESEGMENT, include/adapted_hip_second_resegment.h)
+SECOND_OPINIONS = ("llr", "llr_resegment")
+
+
+def second_opinion_flags(value) -> int:
+    """a ``second_opinion`` argument -> its bits: False / None 0, True / "llr" ADP_CNN_SECOND_LLR, "llr_resegment" that and
+    ADP_CNN_SECOND_RESEGMENT; anything else is a ValueError"""
+    if value is None or value is False:
+        return 0
+    if value is True or value == "llr":
+        return ADP_CNN_SECOND_LLR
+    if value == "llr_resegment":
+        return ADP_CNN_SECOND_LLR | ADP_CNN_SECOND_RESEGMENT
+    raise ValueError("second_opinion: one of False, True, %s, not %r" % (", ".join(repr(v) for v in SECOND_OPINIONS), value))
+
+
 def _flag_word(**options) -> int:
-    return sum(_OPTION_FLAGS[name] for name, on in options.items() if on)
+    return sum(second_opinion_flags(on) if name == "second_opinion" else _OPTION_FLAGS[name] for name, on in options.items() if on)
 
 
 class MinibatchDropped(RuntimeError):
@@ -679,6 +703,18 @@ def resegment_unsupported(spc, flag_truncated: bool = False) -> Optional[str]:
     ADP_ERR_UNSUPPORTED, said without a GPU)"""
     if spc.primary_method != "llr":
         return "it belongs to the LLR primary (the configuration selects %s)" % spc.primary_method
+    if flag_truncated:
+        return "it does not go with the truncation look (which validates from start 0)"
+    if spc.mvs_polya.mvs_detect_overwrite:
+        return "it does not go with mvs_polya.mvs_detect_overwrite"
+    return None
+
+
+def second_resegment_unsupported(spc, flag_truncated: bool = False) -> Optional[str]:
+    """why the re-segmentation behind the CNN primary's second opinion (ADP_CNN_SECOND_RESEGMENT) does not go with this
+    configuration, or None (what the library refuses with ADP_ERR_UNSUPPORTED, said without a GPU)"""
+    if spc.primary_method != "cnn":
+        return "it belongs to the CNN primary's second opinion (the configuration selects %s)" % spc.primary_method
     if flag_truncated:
         return "it does not go with the truncation look (which validates from start 0)"
     if spc.mvs_polya.mvs_detect_overwrite:
@@ -1661,7 +1697,9 @@ class Engine:
         """combined_detect_cnn -> (rows or None when rows_dev is given, bounds int64 [n, 1 + k]).  fallback: with the short-read
         fallback applied on the device (ADP_CNN_FALLBACK; where the configuration has it on); without it the rows are those in
         front of the fallback.  bounds: what cnn_detect returned, either way.  second_opinion: reads whose row fails get the
-        row of the LLR path on their minibatch where that one passes (ADP_CNN_SECOND_LLR; such rows carry reserved_ bit 0).
+        row of the LLR path on their minibatch where that one passes (True / "llr": ADP_CNN_SECOND_LLR; such rows carry reserved_
+        bit 0); "llr_resegment": and where it fails behind a first change point, the row of its re-segmentation where that one
+        passes (ADP_CNN_SECOND_RESEGMENT, an extension, untuned; reserved_ bits 0 and 5-9; not with flag_truncated).
         flag_truncated: the truncation look behind all of that, as in detect_llr_rows (ADP_FLAG_TRUNCATED).
         with_start_peak: the start-peak columns of detect_rna_start_peak overlaid on the row the call delivers, whichever phase
         made it, as in detect_llr_rows (ADP_WITH_START_PEAK); nothing else of any row changes."""
@@ -1776,6 +1814,13 @@ class Engine:
         end, rows replaced); (0, 0, 0) behind a call without ``resegment``"""
         a = np.zeros(3, dtype=np.int32)
         self._check(self.lib.adp_debug_fetch(self._h, 25, a, a.nbytes))
+        return tuple(int(v) for v in a)
+
+    def debug_second_resegment(self):
+        """the re-segmentation behind the second opinion of the last detect_cnn_rows(_i16) call: (eligible reads, reads whose
+        second segmentation found a poly(A) end, rows replaced); (0, 0, 0) behind a call whose second_opinion is not "llr_resegment" """
+        a = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.adp_debug_fetch(self._h, 26, a, a.nbytes))
         return tuple(int(v) for v in a)
 
     def debug_counters(self, n: int = 8):

@@ -67,8 +67,11 @@ def build_parser() -> argparse.ArgumentParser:
     d.add_argument("-b", "--batch_size", type=int, default=4000, help="Number of reads per output file.")
     d.add_argument("-s", "--minibatch_size", type=int, default=1000, help="Number of reads per minibatch (normalisation unit).")
     d.add_argument("--start_peak", action="store_true", help="(extension) LLR and CNN primaries: also fill the start_peak_* columns and start_peak_open_pore_type of every read")
-    d.add_argument("--second_opinion", type=str, choices=["llr"], default=None,
-                   help="(extension) CNN primary: reads it fails get the LLR detector's boundaries where those pass validation")
+    d.add_argument("--second_opinion", type=str, choices=["llr", "llr_resegment"], default=None,
+                   help="(extension) CNN primary: reads it fails get the LLR detector's boundaries where those pass validation.  "
+                        "llr_resegment: and where those fail behind a first change point, the boundaries of one more segmentation from "
+                        "the LLR detector's poly(A) end, validated from its adapter end, where they pass -- such a row's llr_detect_log "
+                        "says so (untuned, nothing validated on real data).  Not with --flag_truncated or mvs_detect_overwrite")
     d.add_argument("--flag_truncated", action="store_true",
                    help="(extension) fill the polya_truncated column: True where the poly(A) runs into the end of the preloaded "
                         "signal (rerun those reads with a larger --max_obs_trace: `adapted truncated`), False on every other passing read")
@@ -305,11 +308,17 @@ def _load_spc(args):
 
 
 def _check_second_opinion(args):
-    """--second_opinion goes with the CNN primary only: said before a GPU is touched"""
-    if getattr(args, "second_opinion", None) and (args.config or args.chemistry):
-        primary = _load_spc(args).primary_method
+    """--second_opinion goes with the CNN primary only, and llr_resegment not with everything: said before a GPU is touched"""
+    choice = getattr(args, "second_opinion", None)
+    if choice and (args.config or args.chemistry):
+        spc = _load_spc(args)
+        primary = spc.primary_method
         if primary != "cnn":
-            raise SystemExit("--second_opinion llr needs the CNN primary (cnn_boundaries.cnn_detect); this configuration's primary is %s." % primary)
+            raise SystemExit("--second_opinion %s needs the CNN primary (cnn_boundaries.cnn_detect); this configuration's primary is %s." % (choice, primary))
+        if choice == "llr_resegment":
+            why = lib.second_resegment_unsupported(spc, bool(getattr(args, "flag_truncated", False)))
+            if why:
+                raise SystemExit("--second_opinion llr_resegment does not go with this run: %s." % why)
 
 
 def _check_flag_truncated(args):
@@ -326,9 +335,11 @@ def _check_flag_truncated(args):
 def _check_llr_resegment(args):
     """--llr_resegment and what it does not go with: said before a GPU is touched"""
     if getattr(args, "llr_resegment", False) and (args.config or args.chemistry):
-        why = lib.resegment_unsupported(_load_spc(args), bool(getattr(args, "flag_truncated", False)))
+        spc = _load_spc(args)
+        why = lib.resegment_unsupported(spc, bool(getattr(args, "flag_truncated", False)))
         if why:
-            raise SystemExit("--llr_resegment does not go with this run: %s." % why)
+            hint = " (with the CNN primary: --second_opinion llr_resegment)" if spc.primary_method == "cnn" else ""
+            raise SystemExit("--llr_resegment does not go with this run: %s%s." % (why, hint))
 
 
 def _check_adapter_front(args):
@@ -626,6 +637,8 @@ def run_detect(files, read_ids_incl, read_ids_excl, spc, run_dir, minibatch, bat
             logging.info("Pass: %d (%.2f%%), fail: %d", writer.n[True], 100.0 * writer.n[True] / tot, writer.n[False])
         if second_opinion:
             logging.info("Second opinion (%s): %d of the passing reads", second_opinion, n_second[0])
+        if second_opinion == "llr_resegment":
+            logging.info(lib.resegment_log(np.concatenate(reseg_marks) if reseg_marks else np.zeros(0, dtype=np.int32)))
         if flag_truncated:
             logging.info("Truncated poly(A) (polya_truncated): %d of the passing reads", n_trunc[0])
         if adapter_front is not None:

@@ -75,7 +75,10 @@ class HostPipeline:
         """with_start_peak: the start-peak columns on every row of the LLR and CNN primaries (an extension; the start-peak primary
         fills them anyway).
         second_opinion: None, or "llr" with the CNN primary -- reads the CNN path fails get the LLR path's row on their
-        minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py).
+        minibatch where that one passes, in the same library call (an extension; adapted_amd/detect/cnn.py); or "llr_resegment"
+        -- and where that one fails behind a first change point, the row of its re-segmentation where that passes
+        (ADP_CNN_SECOND_RESEGMENT, an extension, untuned; not with flag_truncated or mvs_detect_overwrite; it runs on raw int16
+        rows as well, so the native int16 plan stays).
         flag_truncated: every detect call ends with the truncation look (ADP_FLAG_TRUNCATED, an extension; LLR and CNN
         primaries).  It reads float32 rows: int16 input then takes the calibrate + float32 route, not the native int16 one.
         resegment: every LLR detect call re-segments the reads its first pass fails behind a first change point (ADP_LLR_RESEGMENT,
@@ -96,12 +99,16 @@ class HostPipeline:
         self.ragged = bool(ragged)
         if int16_input not in (False, True, "native"):
             raise ValueError('int16_input must be False, True or "native"')
-        if second_opinion not in (None, "llr"):
-            raise ValueError('second_opinion must be None or "llr"')
+        if second_opinion not in (None,) + lib.SECOND_OPINIONS:
+            raise ValueError('second_opinion must be None, "llr" or "llr_resegment"')
         if second_opinion and primary != "cnn":
             raise ValueError("second_opinion needs the CNN primary")
         self.second_opinion = second_opinion
         self.flag_truncated = bool(flag_truncated)
+        if second_opinion == "llr_resegment":
+            why = lib.second_resegment_unsupported(spc, self.flag_truncated)
+            if why:
+                raise ValueError("second_opinion llr_resegment: " + why)
         if self.flag_truncated:
             if primary not in ("llr", "cnn"):
                 raise ValueError("flag_truncated goes with the LLR and CNN primaries")
@@ -338,7 +345,7 @@ class HostPipeline:
         self.eng.copy_wait(j)  # this slot's copies only: the next slot's may still be in flight
         dsig, dlen = s["ds"], s["dl"]
         # the CNN primary's options (the reference runs find_peaks and its row compaction per minibatch: adapted/detect/cnn.py:136-160)
-        options = dict(minibatch=self.mb, second_opinion=bool(self.second_opinion), with_start_peak=bool(self.with_start_peak))
+        options = dict(minibatch=self.mb, second_opinion=self.second_opinion or False, with_start_peak=bool(self.with_start_peak))
         if self.native_i16:
             if self.ragged:
                 self.eng.expand_ragged_i16(dsig, s["do"], dlen, n, self.dsig16)

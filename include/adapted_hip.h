@@ -79,7 +79,9 @@ extern "C" {
                                       see adp_detect_llr; adp_row.reserved_ bits 1 and 2) */
 #define ADP_POLYA_TRUNCATED (1 << 20) /* adp_validate_candidates: Boundaries.polya_truncated is True for every read -- the RNA partition
                                       is all None (adapted/partition/signal_partitions.py:74-77) */
-/* (1 << 21 is ADP_LLR_RESEGMENT, a flag of adp_detect_llr with a header of its own: adapted_hip_resegment.h, included below) */
+/* (1 << 21 is ADP_LLR_RESEGMENT, a flag of adp_detect_llr with a header of its own: adapted_hip_resegment.h, included below;
+ * 1 << 22 is ADP_KNN_NO_PRUNE of adapted_hip_knn.h; 1 << 23 is ADP_CNN_SECOND_RESEGMENT, a flag of adp_detect_cnn(_i16):
+ * adapted_hip_second_resegment.h) */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -590,6 +592,11 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 /* Re-segmentation of reads the LLR primary fails -- ADP_LLR_RESEGMENT, a flag of adp_detect_llr, an extension --: its rule, its row
  * bits and its counters in a header of its own; it declares no entry point (adapted_amd/lib.py, RESEGMENT_PROTOTYPES, is empty). */
 #include "adapted_hip_resegment.h"
+
+/* The same re-segmentation behind the CNN primary's LLR second opinion -- ADP_CNN_SECOND_RESEGMENT, a flag of adp_detect_cnn(_i16), an
+ * extension --: its rule and its counters in a header of its own; no entry point (adapted_amd/lib.py, SECOND_RESEGMENT_PROTOTYPES,
+ * is empty). */
+#include "adapted_hip_second_resegment.h"
 
 /* The rows of one output file to that file's CSV text on the GPU -- adp_format_rows, an extension --: a header of its own, with its
  * prototype table in adapted_amd/lib.py, CSV_PROTOTYPES. */
