@@ -35,10 +35,33 @@
 // a segment as the kernels take it: the clipped slice's first sample (an element offset into the signals) and its size
 struct EvSeg { long long off; int32_t n, pad; };
 
+// Where the kernels' samples come from, their template parameter: src.seg(g, off)[k] is sample k of segment g, whose slice starts
+// at element `off` of the signals, widened to a double.  EvPlain<float> / EvPlain<double>: the signals as they are.  EvI16: raw
+// int16 ADC samples packed back to back and a calibration per SEGMENT, pA = scale[g] * (float32(adc) + offset[g]) as RowI16
+// states it (common.h: the bits of adp_calibrate_i16).  A packed slice starts at any element, so the samples are loaded one by
+// one (2-byte aligned; RowI16's vector forms want 8-byte rows); a calibration that is not finite makes NaN samples.
+template <class T> struct EvPlain {
+    const T *sig;
+    struct Seg {
+        const T *x;
+        __device__ __forceinline__ double operator[](long long k) const { return (double)x[k]; }
+    };
+    __device__ __forceinline__ Seg seg(int, long long off) const { return Seg{sig + off}; }
+};
+struct EvI16 {
+    const int16_t *raw;
+    const float *scale, *offset;
+    struct Seg {
+        RowI16 r;
+        __device__ __forceinline__ double operator[](long long k) const { return (double)r.cook1(r.raw1(k)); }
+    };
+    __device__ __forceinline__ Seg seg(int g, long long off) const { return Seg{RowI16{(const GLB int16_t *)raw + off, scale[g], offset[g], 0}}; }
+};
+
 // grid = (tiles of the longest segment of the batch, slots), block = EV_BLOCK.  Slot s holds segment g0 + s; score: [slots, stride].
 // nanflag[g] (zeroed by the caller) is set when the slice holds a NaN.
-template <class T>
-__global__ void __launch_bounds__(EV_BLOCK) k_ev_scores(const T *__restrict__ sig, const EvSeg *__restrict__ segs, int g0, int w,
+template <class Src>
+__global__ void __launch_bounds__(EV_BLOCK) k_ev_scores(const Src src, const EvSeg *__restrict__ segs, int g0, int w,
                                                       double var_floor, size_t stride, double *__restrict__ score,
                                                       int32_t *__restrict__ nanflag)
 {
@@ -49,13 +72,13 @@ __global__ void __launch_bounds__(EV_BLOCK) k_ev_scores(const T *__restrict__ si
     const int n = segs[g].n;
     const int t0 = blockIdx.x * EV_TILE;
     if (t0 >= n) return;
-    const T *x = sig + segs[g].off;
+    const auto x = src.seg(g, segs[g].off);
     // the samples [lo, hi) behind this tile's scores
     const int lo = t0 > w ? t0 - w : 0;
     const int hi = (long long)t0 + EV_TILE + w - 1 < (long long)n ? t0 + EV_TILE + w - 1 : n;
     bool bad = false;
     for (int k = t; k < hi - lo; k += EV_BLOCK) {
-        const double v = (double)x[lo + k];
+        const double v = x[lo + k];
         sx[k] = v;
         bad |= v != v;
     }

@@ -84,9 +84,9 @@ static __device__ double fp_median(const LDS double *v, int c, LDS double *mid)
 }
 
 // grid = slots, block = 64.  info [n_seg, 2]: what k_ev_bounds wrote (the number of boundaries, the status).  count / fpstatus
-// [n_seg], lengths / levels / fp [n_seg, E], norm [n_seg, 2].
-template <class T>
-__global__ void __launch_bounds__(64) k_ev_levels(const T *__restrict__ sig, const EvSeg *__restrict__ segs, int g0,
+// [n_seg], lengths / levels / fp [n_seg, E], norm [n_seg, 2].  Src: the samples' source (events_api.h).
+template <class Src>
+__global__ void __launch_bounds__(64) k_ev_levels(const Src src, const EvSeg *__restrict__ segs, int g0,
                                                 const double *__restrict__ score, size_t stride, const uint32_t *__restrict__ wl_all,
                                                 int half, const int64_t *__restrict__ info, int E, int32_t *__restrict__ count_out,
                                                 int32_t *__restrict__ fpstatus, int32_t *__restrict__ lengths, double *__restrict__ levels,
@@ -152,19 +152,19 @@ __global__ void __launch_bounds__(64) k_ev_levels(const T *__restrict__ sig, con
         count = kept + 1;
         __syncthreads();
         // the levels: a lane per event of one leaf, then the wave on every longer one
-        const T *x = sig + segs[g].off;
+        const auto x = src.seg(g, segs[g].off);
         for (int base = 0; base < count; base += 64) {
             const int e = base + ln;
             if (e < count) {
                 const int a = edge[e], len = edge[e + 1] - a;
-                if (len <= 128) lev[e] = (0.0 + np_pw_leaf<double>(a, len, [&](int k) { return (double)x[k]; })) / (double)len;
+                if (len <= 128) lev[e] = (0.0 + np_pw_leaf<double>(a, len, [&](int k) { return x[k]; })) / (double)len;
             }
         }
         __syncthreads();
         for (int e = 0; e < count; e++) {
             const int a = edge[e], len = edge[e + 1] - a;
             if (len > 128) {
-                const double t = np_sum_wave(len, [&](long k) { return (double)x[a + k]; }, sum);
+                const double t = np_sum_wave(len, [&](long k) { return x[a + k]; }, sum);
                 if (ln == 0) lev[e] = t / (double)len;
             }
         }

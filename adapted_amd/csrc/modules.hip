@@ -58,6 +58,16 @@ template <class S, class T> static int stage_in(adp_handle *h, int flags, const 
 template <class F> static auto by_elem(bool f64, const void *sig, F &&fn) { return f64 ? fn((const double *)sig) : fn((const float *)sig); }
 template <class P> using elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
 
+// the samples of a segmentation call: the signals (host, or device with ADP_IN_DEVICE) and their bytes; the element type --
+// float32, float64 with `f64`, raw int16 with `i16`: then a calibration per segment, float32 [n_seg] each, where `sig` is
+struct EvIn { const void *sig; size_t bytes; bool f64, i16; const float *scale, *offset; };
+// fn(the kernels' sample source, events_api.h) of the staged input
+template <class F> static auto by_source(const EvIn &in, const void *ds, const float *dscale, const float *doffset, F &&fn)
+{
+    if (in.i16) return fn(EvI16{(const int16_t *)ds, dscale, doffset});
+    return in.f64 ? fn(EvPlain<double>{(const double *)ds}) : fn(EvPlain<float>{(const float *)ds});
+}
+
 // a byte budget in MiB: `dflt`, or what the environment holds under `name` (`value`: its getenv, read per call)
 static int scratch_mib(const char *name, const char *value, long long dflt, long long *mib)
 {
@@ -795,32 +805,22 @@ int adp_sizeof_event_args(void) { return (int)sizeof(adp_event_args); }
 // table and where its pieces go -- count and fp to device memory with ADP_OUT_DEVICE, lengths / levels / norm nowhere when NULL
 struct EvLevels { int E; int32_t *count, *fpstatus, *lengths; double *levels, *fp, *norm; };
 
-// adp_segment_events and, with `lv`, adp_event_levels: the same checks, slots and batches; k_ev_levels behind k_ev_bounds
-static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
-                      const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out,
-                      const EvLevels *lv)
+static int ev_args_check(const adp_event_args *args)
 {
-    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
     if (args->window < 2 || args->window > EV_WMAX) { g_err = "window must lie in [2, 64]"; return ADP_ERR_INVALID; }
     if (args->min_distance < 1) { g_err = "min_distance must be >= 1 (scipy: `distance` must be greater or equal to 1)"; return ADP_ERR_INVALID; }
     if (!std::isfinite(args->threshold) || !(args->threshold > 0.0)) { g_err = "threshold must be finite and > 0"; return ADP_ERR_INVALID; }
     if (!std::isfinite(args->var_floor) || !(args->var_floor > 0.0)) { g_err = "var_floor must be finite and > 0"; return ADP_ERR_INVALID; }
-    if (L >= (1 << 30)) { g_err = "rows of fewer than 2^30 samples"; return ADP_ERR_INVALID; } // (positions share a word with 2 state bits)
-    // the clipped slices (sigstats_api.h's ss_slice, on the host: len and segs are host arrays) and the longest one
-    std::vector<EvSeg> es(n_seg);
-    int lmax = 0;
-    for (int g = 0; g < n_seg; g++) {
-        const adp_seg &sg = segs[g];
-        es[g] = EvSeg{0, 0, 0};
-        if (sg.start < 0 || sg.end <= sg.start) continue;
-        const long long S = len[sg.row];
-        const long long a = sg.start < S ? sg.start : S, b = sg.end < S ? sg.end : S;
-        es[g] = EvSeg{(long long)sg.row * L + a, (int32_t)(b - a), 0};
-        if (es[g].n > lmax) lmax = es[g].n;
-    }
+    return ADP_OK;
+}
+
+// the body of the four segmentation calls, checks done: es[g] is segment g's slice of in.sig (host values) and lmax the longest;
+// slots and batches; k_ev_levels behind k_ev_bounds with `lv`
+static int ev_segment(adp_handle *h, const EvIn &in, const std::vector<EvSeg> &es, int lmax, const adp_event_args *args, int flags,
+                      int cap, int64_t *pos_out, int64_t *info_out, double *stats_out, const EvLevels *lv)
+{
     RCCHK(begin_call(h));
-    const bool f64 = (flags & ADP_MVS_F64) != 0;
-    const size_t n = n_reads, ns = n_seg, esz = f64 ? 8 : 4;
+    const size_t ns = es.size();
     // a slot: the scores of one segment and its two lists of maxima; slots within a byte budget -- EV_SCRATCH_MIB, as the series
     // kernels' (mv_slots), or ADP_EVENTS_SCRATCH_MIB from the environment, read per call -- and batches of slots
     const size_t stride = ((size_t)(lmax > 0 ? lmax : 1) + 1) & ~(size_t)1, half = stride / 2 + 1;
@@ -830,13 +830,14 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
     if (slots < 1) slots = 1;
     if (slots > ns) slots = ns;
     if (slots > 32768) slots = 32768;
-    Piece<char> s_sig; Piece<EvSeg> dsegs; Piece<int32_t> dnan; Piece<double> dscore, dstats; Piece<uint32_t> pk, wl; Piece<int64_t> dpos, dinfo;
+    Piece<char> s_sig; Piece<float> s_scale, s_offset; Piece<EvSeg> dsegs; Piece<int32_t> dnan; Piece<double> dscore, dstats; Piece<uint32_t> pk, wl; Piece<int64_t> dpos, dinfo;
     // (the event tables: in the workspace, but for the two that stay on the device with ADP_OUT_DEVICE)
     const bool lv_dev = lv && (flags & ADP_OUT_DEVICE);
     const size_t E = lv ? lv->E : 0;
     Piece<int32_t> dcount, dfst, dlens; Piece<double> dlev, dfp, dnorm;
     RCCHK(ws_carve(h, [&](Carve &w) {
-        s_sig = w.take<char>((size_t)L * esz * n, !(flags & ADP_IN_DEVICE));
+        s_sig = w.take<char>(in.bytes, !(flags & ADP_IN_DEVICE));
+        s_scale = w.take<float>(ns, in.i16 && !(flags & ADP_IN_DEVICE)); s_offset = w.take<float>(ns, in.i16 && !(flags & ADP_IN_DEVICE));
         dsegs = w.take<EvSeg>(ns); dnan = w.take<int32_t>(ns);
         dpos = w.take<int64_t>(ns * cap); dinfo = w.take<int64_t>(ns * 2); dstats = w.take<double>(ns * 2);
         dscore = w.take<double>(slots * stride); pk = w.take<uint32_t>(slots * half); wl = w.take<uint32_t>(slots * half);
@@ -846,8 +847,9 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
         }
     }));
     int32_t *kcount = lv_dev ? lv->count : dcount.p; double *kfp = lv_dev ? lv->fp : dfp.p; // (what k_ev_levels writes)
-    const void *ds;
-    RCCHK(stage_in(h, flags, sig, s_sig, &ds));
+    const void *ds; const float *dscale = nullptr, *doffset = nullptr;
+    RCCHK(stage_in(h, flags, in.sig, s_sig, &ds));
+    if (in.i16) { RCCHK(stage_in(h, flags, in.scale, s_scale, &dscale)); RCCHK(stage_in(h, flags, in.offset, s_offset, &doffset)); }
     RCCHK(h2d(h, dsegs, es.data()));
     RCCHK(zero(h, dnan));
     const adp_event_args &a = *args;
@@ -858,13 +860,13 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
         const int ntile = (bmax + EV_TILE - 1) / EV_TILE;
         if (ntile > 0) {
             Scope s(h, "k_ev_scores");
-            by_elem(f64, ds, [&](auto sig) { hipLaunchKernelGGL(k_ev_scores<elem_t<decltype(sig)>>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, sig, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan); });
+            by_source(in, ds, dscale, doffset, [&](auto src) { hipLaunchKernelGGL(k_ev_scores<decltype(src)>, dim3(ntile, (unsigned)nb), dim3(EV_BLOCK), 0, h->stream, src, dsegs, (int)g0, a.window, a.var_floor, stride, dscore, dnan); });
         }
         { Scope s(h, "k_ev_bounds");
           hipLaunchKernelGGL(k_ev_bounds, dim3((unsigned)nb), dim3(64), 0, h->stream, dscore, stride, dsegs, (int)g0, a.window, a.min_distance, a.threshold, cap, pk, wl, (int)half, dnan, dpos, dinfo, dstats); }
         if (lv) {
             Scope s(h, "k_ev_levels");
-            by_elem(f64, ds, [&](auto sig) { hipLaunchKernelGGL(k_ev_levels<elem_t<decltype(sig)>>, dim3((unsigned)nb), dim3(64), 0, h->stream, sig, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, kcount, dfst, dlens, dlev, kfp, dnorm); });
+            by_source(in, ds, dscale, doffset, [&](auto src) { hipLaunchKernelGGL(k_ev_levels<decltype(src)>, dim3((unsigned)nb), dim3(64), 0, h->stream, src, dsegs, (int)g0, dscore, stride, wl, (int)half, dinfo, lv->E, kcount, dfst, dlens, dlev, kfp, dnorm); });
         }
     }
     HIPCHK(hipGetLastError());
@@ -882,11 +884,77 @@ static int ev_segment(adp_handle *h, const void *sig, const int32_t *len, int n_
     return ADP_OK;
 }
 
+// adp_segment_events and, with `lv`, adp_event_levels: the checks and the clipped slices of the signal matrix, then ev_segment
+static int ev_matrix(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
+                     const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out,
+                     const EvLevels *lv)
+{
+    RCCHK(seg_check(sig, len, n_reads, L, segs, n_seg));
+    RCCHK(ev_args_check(args));
+    if (L >= (1 << 30)) { g_err = "rows of fewer than 2^30 samples"; return ADP_ERR_INVALID; } // (positions share a word with 2 state bits)
+    // the clipped slices (sigstats_api.h's ss_slice, on the host: len and segs are host arrays) and the longest one
+    std::vector<EvSeg> es(n_seg);
+    int lmax = 0;
+    for (int g = 0; g < n_seg; g++) {
+        const adp_seg &sg = segs[g];
+        es[g] = EvSeg{0, 0, 0};
+        if (sg.start < 0 || sg.end <= sg.start) continue;
+        const long long S = len[sg.row];
+        const long long a = sg.start < S ? sg.start : S, b = sg.end < S ? sg.end : S;
+        es[g] = EvSeg{(long long)sg.row * L + a, (int32_t)(b - a), 0};
+        if (es[g].n > lmax) lmax = es[g].n;
+    }
+    const bool f64 = (flags & ADP_MVS_F64) != 0;
+    const EvIn in{sig, (size_t)L * (f64 ? 8 : 4) * n_reads, f64, false, nullptr, nullptr};
+    return ev_segment(h, in, es, lmax, args, flags, cap, pos_out, info_out, stats_out, lv);
+}
+
+// adp_segment_events_packed and, with `lv`, adp_event_levels_packed: segment g is packed[offsets[g] : offsets[g + 1]), float32 pA or,
+// with ADP_PACKED_I16, raw int16 samples with a calibration per segment; then ev_segment
+static int ev_packed(adp_handle *h, const void *packed, const int64_t *offsets, const float *scale, const float *offset, int n_seg,
+                     const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out,
+                     const EvLevels *lv)
+{
+    if (!packed || !offsets || n_seg < 1) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    const bool i16 = (flags & ADP_PACKED_I16) != 0;
+    if (i16 && (!scale || !offset)) { g_err = "ADP_PACKED_I16 needs a scale and an offset per segment"; return ADP_ERR_INVALID; }
+    if (flags & ADP_MVS_F64) { g_err = "the packed calls take float32 or int16 samples, not float64"; return ADP_ERR_INVALID; }
+    RCCHK(ev_args_check(args));
+    if (offsets[0] < 0) { g_err = "offsets[0] must be >= 0"; return ADP_ERR_INVALID; }
+    std::vector<EvSeg> es(n_seg);
+    int lmax = 0;
+    for (int g = 0; g < n_seg; g++) {
+        if (offsets[g + 1] < offsets[g]) { g_err = "offsets must not decrease"; return ADP_ERR_INVALID; }
+        const int64_t n = offsets[g + 1] - offsets[g];
+        if (n >= ((int64_t)1 << 30)) { g_err = "segments of fewer than 2^30 samples"; return ADP_ERR_INVALID; } // (as ev_matrix's rows)
+        es[g] = EvSeg{(long long)offsets[g], (int32_t)n, 0};
+        if (es[g].n > lmax) lmax = es[g].n;
+    }
+    size_t bytes = (size_t)offsets[n_seg] * (i16 ? 2 : 4);
+    if (bytes < 1) bytes = 1; // (every segment empty: nothing is read)
+    const EvIn in{packed, bytes, false, i16, scale, offset};
+    return ev_segment(h, in, es, lmax, args, flags, cap, pos_out, info_out, stats_out, lv);
+}
+
+static bool ev_levels_args(adp_handle *h, const adp_event_args *args, int64_t *info_out, double *stats_out, int32_t *count_out,
+                           int32_t *fpstatus_out, double *fp_out)
+{
+    return h && args && info_out && stats_out && count_out && fpstatus_out && fp_out;
+}
+
 int adp_segment_events(adp_handle *h, const void *sig, const int32_t *len, int n_reads, int L, const adp_seg *segs, int n_seg,
                        const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out, double *stats_out)
 {
     if (!h || !args || !info_out || !stats_out || cap < 0 || (cap > 0 && !pos_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
-    return ev_segment(h, sig, len, n_reads, L, segs, n_seg, args, flags, cap, pos_out, info_out, stats_out, nullptr);
+    return ev_matrix(h, sig, len, n_reads, L, segs, n_seg, args, flags, cap, pos_out, info_out, stats_out, nullptr);
+}
+
+int adp_segment_events_packed(adp_handle *h, const void *packed, const int64_t *offsets, const float *scale, const float *offset,
+                              int n_seg, const adp_event_args *args, int flags, int cap, int64_t *pos_out, int64_t *info_out,
+                              double *stats_out)
+{
+    if (!h || !args || !info_out || !stats_out || cap < 0 || (cap > 0 && !pos_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    return ev_packed(h, packed, offsets, scale, offset, n_seg, args, flags, cap, pos_out, info_out, stats_out, nullptr);
 }
 
 // ---- adapter event fingerprints and their DTW distances to templates (an extension; fingerprint_api.h)
@@ -895,10 +963,21 @@ int adp_event_levels(adp_handle *h, const void *sig, const int32_t *len, int n_r
                      const adp_event_args *args, int flags, int max_events, int64_t *info_out, double *stats_out, int32_t *count_out,
                      int32_t *fpstatus_out, int32_t *lengths_out, double *levels_out, double *fp_out, double *norm_out)
 {
-    if (!h || !args || !info_out || !stats_out || !count_out || !fpstatus_out || !fp_out) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (!ev_levels_args(h, args, info_out, stats_out, count_out, fpstatus_out, fp_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
     if (max_events < 2 || max_events > FP_EMAX) { g_err = "max_events must lie in [2, 512]"; return ADP_ERR_INVALID; }
     const EvLevels lv{max_events, count_out, fpstatus_out, lengths_out, levels_out, fp_out, norm_out};
-    return ev_segment(h, sig, len, n_reads, L, segs, n_seg, args, flags, 0, nullptr, info_out, stats_out, &lv);
+    return ev_matrix(h, sig, len, n_reads, L, segs, n_seg, args, flags, 0, nullptr, info_out, stats_out, &lv);
+}
+
+int adp_event_levels_packed(adp_handle *h, const void *packed, const int64_t *offsets, const float *scale, const float *offset,
+                            int n_seg, const adp_event_args *args, int flags, int max_events, int64_t *info_out, double *stats_out,
+                            int32_t *count_out, int32_t *fpstatus_out, int32_t *lengths_out, double *levels_out, double *fp_out,
+                            double *norm_out)
+{
+    if (!ev_levels_args(h, args, info_out, stats_out, count_out, fpstatus_out, fp_out)) { g_err = "bad argument"; return ADP_ERR_INVALID; }
+    if (max_events < 2 || max_events > FP_EMAX) { g_err = "max_events must lie in [2, 512]"; return ADP_ERR_INVALID; }
+    const EvLevels lv{max_events, count_out, fpstatus_out, lengths_out, levels_out, fp_out, norm_out};
+    return ev_packed(h, packed, offsets, scale, offset, n_seg, args, flags, 0, nullptr, info_out, stats_out, &lv);
 }
 
 int adp_dtw_assign(adp_handle *h, const double *q, const int32_t *q_count, int nq, int Eq, const double *t, const int32_t *t_count,

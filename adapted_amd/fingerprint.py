@@ -77,6 +77,23 @@ def event_levels_batch(signals, lens, segs, params: Optional[FingerprintParams] 
                        r["stats"][:, 1].copy())
 
 
+def event_levels_packed(packed, offsets, params: Optional[FingerprintParams] = None, scale=None, offset=None, device=0,
+                        engine=None) -> EventLevels:
+    """event_levels_batch of segments that lie back to back in one array (adp_event_levels_packed,
+    include/adapted_hip_events_packed.h); packed, offsets, scale and offset as polya_length.segment_events_packed takes them.
+    The same bytes as event_levels_batch gives for the same samples inside a padded matrix."""
+    params = params or FingerprintParams()
+    params.check()
+    E = int(params.max_events)
+    if np.asarray(offsets).size < 2:
+        return EventLevels(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, E), dtype=np.int32), np.zeros((0, E)),
+                           np.zeros((0, E)), np.zeros((0, 2)), np.zeros(0), np.zeros(0))
+    eng = engine or _engine(device)
+    r = eng.event_levels_packed(packed, offsets, params.events.args(), E, scale=scale, offset=offset)
+    return EventLevels(r["count"], r["status"], r["lengths"], r["levels"], r["fingerprints"], r["norm"], r["stats"][:, 0].copy(),
+                       r["stats"][:, 1].copy())
+
+
 def event_levels(signal, params: Optional[FingerprintParams] = None, device=0) -> EventLevels:
     """The event table and fingerprint of one signal (arrays without the leading axis; count and status are numbers)"""
     params = params or FingerprintParams()
@@ -228,5 +245,5 @@ def template_arrays(templates: Templates):
     return _templates(np.where(np.isnan(templates.levels), 0.0, templates.levels), templates.counts)
 
 
-__all__ = ["FingerprintParams", "EventLevels", "Templates", "BarcodeAssignment", "event_levels", "event_levels_batch", "dtw_distances",
+__all__ = ["FingerprintParams", "EventLevels", "Templates", "BarcodeAssignment", "event_levels", "event_levels_batch", "event_levels_packed", "dtw_distances",
            "assign_barcodes", "medoid_templates", "save_templates", "load_templates"]

@@ -273,6 +273,7 @@ def load():
     try:
         for name, proto in (list(PROTOTYPES.items()) + list(MODULE_PROTOTYPES.items()) + list(I16_PROTOTYPES.items())
                             + list(EVENT_PROTOTYPES.items()) + list(FINGERPRINT_PROTOTYPES.items())
+                            + list(EVENT_PACKED_PROTOTYPES.items())
                             + list(ADAPTER_FRONT_PROTOTYPES.items()) + list(REVALIDATE_PROTOTYPES.items())
                             + list(TEMPLATE_PROTOTYPES.items()) + list(RESEGMENT_PROTOTYPES.items()) + list(CSV_PROTOTYPES.items())
                             + list(CLUSTER_PROTOTYPES.items()) + list(KNN_PROTOTYPES.items())
@@ -488,6 +489,16 @@ FINGERPRINT_PROTOTYPES = {
                         "double* double* double*",
     "adp_dtw_assign": "int: adp_handle* double* int32* int int double* int32* int int int int double* int32* double*",
 }
+
+# include/adapted_hip_events_packed.h (the header adapted_hip.h includes for the packed forms of the two event calls -- segments back
+# to back in one array, float32 pA or raw int16 samples with a calibration per segment --, an extension);
+# tests/test_events_packed_cpu.py holds this table and the flag against its header
+EVENT_PACKED_PROTOTYPES = {
+    "adp_segment_events_packed": "int: adp_handle* void* int64* float* float* int adp_event_args* int int int64* int64* double*",
+    "adp_event_levels_packed": "int: adp_handle* void* int64* float* float* int adp_event_args* int int int64* double* int32* int32* "
+                               "int32* double* double* double*",
+}
+ADP_PACKED_I16 = 1 << 24  # the two packed event calls: raw int16 samples with a calibration per segment
 
 # include/adapted_hip_adapter_front.h (the header adapted_hip.h includes for the adapter-front post-pass over the rows of a detect
 # call, an extension); tests/test_adapter_front_cpu.py holds this table against its header
@@ -1453,6 +1464,69 @@ class Engine:
         self._check(self.lib.adp_event_levels(self._h, sig, lens, n, L, segs, ns, C.byref(args), flags | (ADP_OUT_DEVICE if on_dev else 0), E,
                                               out["info"], out["stats"], int(count_ptr) if on_dev else out["count"], out["status"],
                                               out["lengths"], out["levels"], int(fp_ptr) if on_dev else out["fingerprints"], out["norm"]))
+        return out
+
+    def _packed_in(self, packed, offsets, scale, offset):
+        """the packed calls' input: segment g is packed[offsets[g]:offsets[g + 1]] -- a host float32 or int16 array, or a device
+        pointer (int16 when ``scale`` is given); offsets int64 [n_seg + 1] on the host; with int16 samples scale / offset float32
+        [n_seg], host arrays beside a host array, device pointers beside a device pointer -> (packed, offsets, scale, offset, n_seg,
+        flags)"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1:
+            raise ValueError("offsets: int64 [n_seg + 1]")
+        ns = offsets.size - 1
+        if (scale is None) != (offset is None):
+            raise ValueError("scale and offset go together")
+        if isinstance(packed, int):
+            _check_runtime_once_torch_is_here()
+            if scale is not None and not (isinstance(scale, int) and isinstance(offset, int)):
+                raise ValueError("a device pointer to int16 samples needs device pointers to scale and offset")
+            return packed, offsets, scale, offset, ns, ADP_IN_DEVICE | (ADP_PACKED_I16 if scale is not None else 0)
+        a = np.asarray(packed)
+        if a.dtype not in (np.float32, np.int16) or not a.flags.c_contiguous or a.ndim != 1:
+            raise ValueError("packed: a C-contiguous float32 or int16 [samples] array")
+        if ns and (offsets[0] < 0 or offsets[-1] > a.size or (np.diff(offsets) < 0).any()):
+            raise ValueError("offsets must lie in [0, packed.size] and must not decrease")
+        if a.dtype == np.int16:
+            if scale is None:
+                raise ValueError("int16 samples need a scale and an offset per segment")
+            return (a if a.size else np.zeros(1, dtype=np.int16), offsets, self._per_read(scale, ns, "scale", np.float32),
+                    self._per_read(offset, ns, "offset", np.float32), ns, ADP_PACKED_I16)
+        return a if a.size else np.zeros(1, dtype=np.float32), offsets, None, None, ns, 0
+
+    def segment_events_packed(self, packed, offsets, args: "AdpEventArgs", cap: int = 0, scale=None, offset=None):
+        """adp_segment_events_packed: segment_events of the segments packed[offsets[g]:offsets[g + 1]] -- float32 pA, or raw int16
+        samples with ``scale`` / ``offset`` float32 [n_seg] (pA = scale * (float32(adc) + offset), calibrate_i16's bits); a host
+        array or a device pointer (_packed_in) -> segment_events' (pos, info, stats)"""
+        packed, offsets, scale, offset, ns, flags = self._packed_in(packed, offsets, scale, offset)
+        cap = int(cap)
+        if ns == 0:  # (the library wants a segment: an empty batch has an empty answer)
+            return np.zeros((0, cap), dtype=np.int64), np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2))
+        pos = np.zeros((ns, cap), dtype=np.int64)
+        info = np.zeros((ns, 2), dtype=np.int64)
+        stats = np.zeros((ns, 2))
+        self._check(self.lib.adp_segment_events_packed(self._h, packed, offsets, scale, offset, ns, C.byref(args), flags, cap,
+                                                       pos if cap > 0 else None, info, stats))
+        return pos, info, stats
+
+    def event_levels_packed(self, packed, offsets, args: "AdpEventArgs", max_events: int, scale=None, offset=None,
+                            fp_ptr: Optional[int] = None, count_ptr: Optional[int] = None):
+        """adp_event_levels_packed: event_levels of the segments segment_events_packed takes -> event_levels' dict; ``fp_ptr`` and
+        ``count_ptr`` as there"""
+        packed, offsets, scale, offset, ns, flags = self._packed_in(packed, offsets, scale, offset)
+        E = int(max_events)
+        if (fp_ptr is None) != (count_ptr is None):
+            raise ValueError("fp_ptr and count_ptr go together")
+        on_dev = fp_ptr is not None
+        out = {"info": np.zeros((ns, 2), dtype=np.int64), "stats": np.zeros((ns, 2)), "count": None if on_dev else np.zeros(ns, dtype=np.int32),
+               "status": np.zeros(ns, dtype=np.int32), "lengths": np.zeros((ns, max(E, 0)), dtype=np.int32), "levels": np.zeros((ns, max(E, 0))),
+               "fingerprints": None if on_dev else np.zeros((ns, max(E, 0))), "norm": np.zeros((ns, 2))}
+        if ns == 0:  # (the library wants a segment: an empty batch has an empty answer)
+            return out
+        self._check(self.lib.adp_event_levels_packed(self._h, packed, offsets, scale, offset, ns, C.byref(args),
+                                                     flags | (ADP_OUT_DEVICE if on_dev else 0), E, out["info"], out["stats"],
+                                                     int(count_ptr) if on_dev else out["count"], out["status"], out["lengths"],
+                                                     out["levels"], int(fp_ptr) if on_dev else out["fingerprints"], out["norm"]))
         return out
 
     def _fp_rows(self, q, q_count, n, E, noun: str, sizes: str, shape: Optional[str] = None):

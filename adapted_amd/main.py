@@ -56,6 +56,12 @@ def build_parser() -> argparse.ArgumentParser:
     from .knn import add_arguments as add_knn_arguments
 
     add_knn_arguments(n)
+    e = sub.add_parser("events", help="(extension) Recompute the adapter events of a finished run from its detected_boundaries_<k>.csv and "
+                                      "the input files: only the adapter slices go to the GPU; writes the polya_length / fingerprints files "
+                                      "detect --polya_length / --fingerprints would have (untuned, nothing validated on real data).")
+    from .events_command import add_arguments as add_events_arguments
+
+    add_events_arguments(e)
     d.add_argument("-i", "--input", type=str, nargs="+", required=True, help="input files / directories (.pod5 or .npz bundles)")
     d.add_argument("-o", "--output", type=str, default=None)
     d.add_argument("--config", type=str, default=None, help="config TOML (overrides --chemistry)")
@@ -176,6 +182,24 @@ def fingerprint_records(read_ids, fp, names=None) -> List[dict]:
     return out
 
 
+def write_polya_length_file(polya_dir: str, k: int, records):
+    """polya_length_<k>.csv from the polya_length_records of a file's reads, in the CSV's order"""
+    pd.DataFrame(records, columns=POLYA_LENGTH_COLUMNS).round(3).to_csv(os.path.join(polya_dir, "polya_length_%d.csv" % k), index=False)
+
+
+def write_fingerprint_files(fp_dir: str, k: int, recs, E: int, barcodes: bool):
+    """fingerprints_<k>.npz and, with ``barcodes``, barcodes_<k>.csv from the fingerprint_records of a file's reads, in the CSV's
+    order.  Distances are written in full precision."""
+    with open(os.path.join(fp_dir, "fingerprints_%d.npz" % k), "wb") as fh:
+        np.savez(fh, read_id=np.asarray([r["read_id"] for r in recs], dtype=str),
+                 count=np.asarray([r["count"] for r in recs], dtype=np.int32), status=np.asarray([r["status"] for r in recs], dtype=np.int32),
+                 lengths=np.asarray([r["lengths"] for r in recs], dtype=np.int32).reshape(len(recs), E),
+                 levels=np.asarray([r["levels"] for r in recs], dtype=np.float64).reshape(len(recs), E),
+                 fingerprints=np.asarray([r["fingerprints"] for r in recs], dtype=np.float64).reshape(len(recs), E))
+    if barcodes:
+        pd.DataFrame([r["barcode"] for r in recs], columns=BARCODE_COLUMNS).to_csv(os.path.join(fp_dir, "barcodes_%d.csv" % k), index=False)
+
+
 class _Writer:
     """Accumulates pass / fail results and flushes CSV files of `batch` reads each."""
 
@@ -247,19 +271,9 @@ class _Writer:
     def _flush_extensions(self, ok: bool, items):
         """the extension files beside a flushed CSV file, from the records its reads carry; then the file counts"""
         if ok and self.polya_dir:
-            pd.DataFrame([r.polya_length for r in items], columns=POLYA_LENGTH_COLUMNS).round(3).to_csv(
-                os.path.join(self.polya_dir, "polya_length_%d.csv" % self.bidx[ok]), index=False)
+            write_polya_length_file(self.polya_dir, self.bidx[ok], [r.polya_length for r in items])
         if ok and self.fp_dir:
-            recs, E = [r.fingerprint for r in items], self.fp_width
-            with open(os.path.join(self.fp_dir, "fingerprints_%d.npz" % self.bidx[ok]), "wb") as fh:
-                np.savez(fh, read_id=np.asarray([r["read_id"] for r in recs], dtype=str),
-                         count=np.asarray([r["count"] for r in recs], dtype=np.int32), status=np.asarray([r["status"] for r in recs], dtype=np.int32),
-                         lengths=np.asarray([r["lengths"] for r in recs], dtype=np.int32).reshape(len(recs), E),
-                         levels=np.asarray([r["levels"] for r in recs], dtype=np.float64).reshape(len(recs), E),
-                         fingerprints=np.asarray([r["fingerprints"] for r in recs], dtype=np.float64).reshape(len(recs), E))
-            if self.barcodes:
-                pd.DataFrame([r["barcode"] for r in recs], columns=BARCODE_COLUMNS).to_csv(
-                    os.path.join(self.fp_dir, "barcodes_%d.csv" % self.bidx[ok]), index=False)
+            write_fingerprint_files(self.fp_dir, self.bidx[ok], [r.fingerprint for r in items], self.fp_width, self.barcodes)
         self.bidx[ok] += 1
         self.n[ok] += len(items)
 
@@ -675,6 +689,11 @@ def main(argv=None):
         from .knn import knn_command
 
         knn_command(args)
+        return
+    if args.mode == "events":
+        from .events_command import events_command
+
+        events_command(args)
         return
     if args.mode == "continue":
         run_dir = args.continue_from

@@ -102,6 +102,26 @@ def segment_events_batch(signals, lens, segs, params: Optional[EventParams] = No
     return pos, info[:, 0].copy(), info[:, 1].copy(), stats
 
 
+def segment_events_packed(packed, offsets, params: Optional[EventParams] = None, cap: Optional[int] = None, scale=None, offset=None,
+                          device=0, engine=None):
+    """segment_events_batch of segments that lie back to back in one array (adp_segment_events_packed,
+    include/adapted_hip_events_packed.h): segment g is ``packed[offsets[g]:offsets[g + 1]]`` -- float32 pA, or raw int16 ADC
+    samples with ``scale`` / ``offset``, one calibration per segment (pA = scale * (float32(adc) + offset), rounded to float32
+    twice).  packed: a host array, or a device pointer (int; int16 when ``scale`` and ``offset`` are given, device pointers
+    too); offsets: int64 [n_seg + 1] on the host.  -> segment_events_batch's (pos, count, status, stats), the same bytes as that
+    call gives for the same samples inside a padded matrix.  The int16 form's parity with pod5's own signal_pa is unpinned."""
+    params = params or EventParams()
+    params.check()
+    if np.asarray(offsets).size < 2:
+        return np.zeros((0, int(cap or 0)), dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros((0, 2))
+    eng = engine or _engine(device)
+    a = params.args()
+    pos, info, stats = eng.segment_events_packed(packed, offsets, a, cap=0 if cap is None else int(cap), scale=scale, offset=offset)
+    if cap is None and info[:, 0].max() > 0:
+        pos, info, stats = eng.segment_events_packed(packed, offsets, a, cap=int(info[:, 0].max()), scale=scale, offset=offset)
+    return pos, info[:, 0].copy(), info[:, 1].copy(), stats
+
+
 def segment_events(signal, params: Optional[EventParams] = None, device=0) -> np.ndarray:
     """The event boundaries of one signal (int64, ascending); none for a signal with a NaN or shorter than two windows"""
     x = as_work(signal).reshape(1, -1)
@@ -148,4 +168,4 @@ def estimate_polya_length(adapter_start, adapter_end, polya_end, *, method, even
     return polya_nt, spn
 
 
-__all__ = ["EventParams", "segment_events", "segment_events_batch", "estimate_polya_length"]
+__all__ = ["EventParams", "segment_events", "segment_events_batch", "segment_events_packed", "estimate_polya_length"]

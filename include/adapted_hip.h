@@ -81,7 +81,7 @@ extern "C" {
                                       is all None (adapted/partition/signal_partitions.py:74-77) */
 /* (1 << 21 is ADP_LLR_RESEGMENT, a flag of adp_detect_llr with a header of its own: adapted_hip_resegment.h, included below;
  * 1 << 22 is ADP_KNN_NO_PRUNE of adapted_hip_knn.h; 1 << 23 is ADP_CNN_SECOND_RESEGMENT, a flag of adp_detect_cnn(_i16):
- * adapted_hip_second_resegment.h) */
+ * adapted_hip_second_resegment.h; 1 << 24 is ADP_PACKED_I16 of adapted_hip_events_packed.h) */
 
 /* SigProcConfig, flattened.  Ranges are [lo, hi] with -inf/+inf for "None". */
 typedef struct adp_cfg {
@@ -566,6 +566,11 @@ int adp_open_pores(adp_handle *h, const void *sig, const int32_t *len, int n_rea
 /* Adapter event fingerprints and their comparison by dynamic time warping -- adp_event_levels and adp_dtw_assign, an extension --:
  * a header of its own again, with its prototype table in adapted_amd/lib.py, FINGERPRINT_PROTOTYPES. */
 #include "adapted_hip_fingerprint.h"
+
+/* The packed forms of those two event calls -- segments back to back in one array, float32 pA or raw int16 samples with a
+ * calibration per segment (ADP_PACKED_I16, 1 << 24), an extension --: a header of its own, with its prototype table in
+ * adapted_amd/lib.py, EVENT_PACKED_PROTOTYPES. */
+#include "adapted_hip_events_packed.h"
 
 /* The adapter's front boundary as a post-pass over the rows of a detect call -- adp_adapter_front and adp_adapter_front_i16, an
  * extension --: a header of its own, with its prototype table in adapted_amd/lib.py, ADAPTER_FRONT_PROTOTYPES. */
